@@ -15,6 +15,10 @@ every GPU its own batch (config2: 100k pods per GPU); the workloads BASELINE quo
 shards 200k pods and config5 500k pods over the N GPUs.  The exchange (all-gather of the 20-byte per-pod decisions, and with
 `--gather table` of one uint8 table) is measured outside the timed region and reported next to the kernel-only step.
 
+A plain run sets up, warms up, times `--steps` sweeps and prints the line; everything else the benchmark measures or checks
+(every_row, full_cycle, topological_sort, gather, the config #3 / #4 / #5 legs of the default line, cpu_baseline) runs only with
+`--full`.  `--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of its result rows) as .npy files.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -101,6 +105,7 @@ WORKLOADS = {
                     desc="noderesources.Allocatable (LeastAllocated), 100 nodes x 1k pods (plumbing)"),
 }
 PID = {"alloc": 0, "tlp": 1, "lvrb": 2, "nrt": 3, "net": 4, "cap": 5, "lroc": 7, "peaks": 8}
+DUMP_TABLE_BYTES = 48 << 20  # --dump-outputs: the sampled score / status rows (float32), well inside the 64 MB the whole dump may take
 SEQ_PATH = {1: "one-workgroup chain (Filter-less profile)", 2: "per-pod single-row launches replayed from a graph", 3: "cooperative persistent kernel"}
 
 
@@ -506,6 +511,46 @@ def profile_counters(workload: str, plugins, rows_evaluated=None, n_nodes=None):
     return out
 
 
+def dump_outputs(out_dir, parts, plugins, seed: int = 0) -> dict:
+    """--dump-outputs: what the last timed step left in HBM, read the way a caller reads it — every plugin's normalized score rows
+    (spx_fetch_scores, 0..100), the Filter status rows of NRT and NetworkOverhead (spx_fetch_status), CapacityScheduling's PreFilter
+    status of every pod (spx_fetch_prefilter) — as float32 DIR/<name>.npy.  The tables hold pods x nodes bytes each, so the score and
+    status rows are a fixed sample of pod rows (seeded: the same rows every run of the same arguments); rows.npy holds their batch
+    indices.  parts: (engine, batch index of its first row) for every engine holding rows, in row order."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    names = {v: k for k, v in PID.items()}
+    parts = [(e, first) for e, first in parts if e.n_pods > 0]
+    n_nodes = parts[0][0].n_nodes
+    held = sum(e.n_pods for e, _ in parts)
+    score_p = [p for p in plugins if p != PID["cap"]]
+    status_p = [p for p in plugins if p in (PID["nrt"], PID["net"])]
+    per_row = 4 * n_nodes * max(1, len(score_p) + len(status_p))
+    k = min(held, max(1, DUMP_TABLE_BYTES // per_row))
+    local = np.sort(np.random.default_rng(seed).choice(held, k, replace=False)) if k < held else np.arange(held)
+    bounds = np.cumsum([0] + [e.n_pods for e, _ in parts])
+    arrays = {"rows": np.empty(k, np.float64)}
+    for p in score_p:
+        arrays[f"scores_{names[p]}"] = np.empty((k, n_nodes), np.float32)
+    for p in status_p:
+        arrays[f"status_{names[p]}"] = np.empty((k, n_nodes), np.float32)
+    for i, r in enumerate(local):
+        j = int(np.searchsorted(bounds, r, side="right")) - 1
+        e, first = parts[j]
+        row = int(r - bounds[j])
+        arrays["rows"][i] = first + row
+        for p in score_p:
+            arrays[f"scores_{names[p]}"][i] = e.scores(p, row)
+        for p in status_p:
+            arrays[f"status_{names[p]}"][i] = e.status(p, row)
+    if PID["cap"] in plugins:
+        arrays["prefilter_cap"] = np.concatenate([e.prefilter(PID["cap"]) for e, _ in parts]).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "files": sorted(f"{n}.npy" for n in arrays), "rows_sampled": int(k), "rows_held": int(held),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -515,7 +560,7 @@ def main() -> None:
     ap.add_argument("--plugins", default="", help="override the workload's plugin set, e.g. alloc or tlp,lvrb (experiments)")
     ap.add_argument("--round-frac", type=float, default=0.0, help="fraction of nodes with integer-valued metrics (tie stress)")
     ap.add_argument("--gather", default="best", choices=["none", "best", "table"],
-                    help="N>1 only, measured OUTSIDE the timed region: all-gather of per-pod decisions and (table) of one score slab")
+                    help="N>1 with --full, measured OUTSIDE the timed region: all-gather of per-pod decisions and (table) of one score slab")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "copy"], help="single-process multi-device exchange (spx_multi)")
     ap.add_argument("--devices", default="", help="single-process multi-device mode: explicit device list, e.g. 0,0 with --transport copy "
                                                   "runs two ranks on one GPU (plumbing check of the sharded path on a one-GPU box)")
@@ -530,11 +575,15 @@ def main() -> None:
                     "scaling run); gloo = the same code path with the collectives on host tensors, for boxes with fewer GPUs than ranks (tests)")
     ap.add_argument("--rank-devices", default="", help="ranks mode: device of each local rank, e.g. 0,0 puts two ranks on device 0 (needs --dist-backend gloo: RCCL "
                     "refuses two ranks on one device)")
-    ap.add_argument("--verify-gather", action="store_true", help="ranks mode, strong-scaling workloads: rank 0 also evaluates the whole batch in one engine and "
+    ap.add_argument("--verify-gather", action="store_true", help="ranks mode with --full, strong-scaling workloads: rank 0 also evaluates the whole batch in one engine and "
                     "compares the all-gathered decisions with it (gather.mismatches; small shapes — tests)")
     ap.add_argument("--no-config5-leg", action="store_true", help="default (config2) line only: skip the bounded full-profile leg (config5_leg)")
     ap.add_argument("--no-legs", action="store_true", help="default (config2) line only: skip the full-size config3 / config4 / config5_share legs")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-oracle work for cpu_baseline (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU-oracle work for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need, outside the timed region: every_row, "
+                    "full_cycle, topological_sort, gather (N > 1), the default line's config #3 / #4 / #5 legs, cpu_baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (a seeded sample of the result rows, "
+                    "float32) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -612,9 +661,11 @@ def main() -> None:
             from scheduler_plugins_amd import shard
             rows = shard.shard_rows(n_pods_total, world, rank)  # ceil(P/G) rows per rank: the one partition rule (= spx_multi_shard)
             load_tables(target, w, snap, rows)
+            first_row = rows[0]
         else:  # same node snapshot, an own pod batch per rank
             snap = build_snapshot(hdr, w, w["n_pods"] if not strong else n_pods_total, synth.SEED + 1000 * rank)
             load_tables(target, w, snap)
+            first_row = 0
         local_pods = target.n_pods
 
     engines = target.engines if mode == "multi" else [e0]
@@ -690,10 +741,16 @@ def main() -> None:
         # launches, sustained clocks); a plugin set evaluated by more than one kernel counts all of them as one launch
         kern_ms = ev0.elapsed_time(ev1) / args.steps
 
+    # what the last timed step computed, before anything below evaluates again (rank 0's rows in ranks mode)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        parts = [(e, target.shard(r)[0]) for r, e in enumerate(target.engines)] if mode == "multi" else [(e0, first_row)]
+        dumped = dump_outputs(args.dump_outputs, parts, plugins)
+
     # the same sweep with every pod row evaluated (no representative rows + copies), outside the timed region: how much of `value`
-    # is the synthetic queue's repetitiveness — printed next to it in every line that uses pod classes
+    # is the synthetic queue's repetitiveness — printed next to it in every line that uses pod classes (--full)
     every_row = None
-    if mode == "single" and not args.no_pod_classes and not args.no_every_row and any(v["rows_copied"] > 0 for v in pod_classes.values()):
+    if args.full and mode == "single" and not args.no_pod_classes and not args.no_every_row and any(v["rows_copied"] > 0 for v in pod_classes.values()):
         try:
             for name in pod_classes:
                 target.set_option("NRT_POD_CLASSES" if name == "nrt" else "PEAKS_POD_CLASSES", 0)
@@ -721,7 +778,7 @@ def main() -> None:
     # per-row argmax + D2H of the per-pod decisions — wall clock, once
     full_cycle = None
     score_mask = mask & ~(1 << 6)
-    if mode == "single" and not args.plugins and not args.sweep_only and args.workload in ("config2", "config2_lvrb", "config5_share", "config4", "config3"):
+    if args.full and mode == "single" and not args.plugins and not args.sweep_only and args.workload in ("config2", "config2_lvrb", "config5_share", "config4", "config3"):
         try:
             barrier()
             c0 = time.perf_counter()
@@ -781,7 +838,7 @@ def main() -> None:
 
     # config #4 names "NodeNetworkCost + TopologicalSort": the queue sort of the whole batch (one device; 16-byte keys), device time
     sort_info = None
-    if "net" in w["plugins"] and rank == 0:
+    if args.full and "net" in w["plugins"] and rank == 0:
         try:
             q_pods = snap["pods"]
             if mode == "multi":
@@ -801,7 +858,7 @@ def main() -> None:
 
     # the exchange step of the sharded path, reported separately: per-pod decisions, optionally one table
     gather_info = None
-    if world > 1 and args.gather != "none":
+    if args.full and world > 1 and args.gather != "none":
         try:
             if mode == "multi":
                 target.eval(mask)
@@ -940,19 +997,21 @@ def main() -> None:
         out["gather"] = gather_info
     if sort_info is not None:
         out["topological_sort"] = sort_info
-    if rank == 0 and world == 1 and mode == "single" and args.workload == "config2" and not args.plugins and not args.sweep_only and not args.no_config5_leg:
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if args.full and rank == 0 and world == 1 and mode == "single" and args.workload == "config2" and not args.plugins and not args.sweep_only and not args.no_config5_leg:
         try:
             out["config5_leg"] = config5_leg(hdr, local_rank)
         except Exception as ex:
             out["config5_leg"] = {"error": repr(ex)[:300]}
-    if rank == 0 and world == 1 and mode == "single" and args.workload == "config2" and not args.plugins and not args.sweep_only and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and mode == "single" and args.workload == "config2" and not args.plugins and not args.sweep_only and not args.no_legs:
         # BASELINE's other single-device workloads at full size, a few steps each (the driver's default run times them too)
         for leg, name, n in (("config3_leg", "config3", 10), ("config4_leg", "config4", 5), ("config5_share_leg", "config5_share", 5)):
             try:
                 out[leg] = workload_leg(hdr, local_rank, name, n)
             except Exception as ex:
                 out[leg] = {"error": repr(ex)[:300]}
-    if rank == 0 and args.cpu_budget > 0 and world == 1:
+    if args.full and rank == 0 and args.cpu_budget > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(spx, snap, e0, plugins, args.cpu_budget)
     target.close()
     if dist is not None:

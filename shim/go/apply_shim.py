@@ -7,7 +7,8 @@ Writes the edited copies of the six files under <output dir> (same relative path
 maintainer adds: the field `spx *spx.Engine` to Allocatable / TargetLoadPacking / LoadVariationRiskBalancing / TopologyMatch /
 NetworkOverhead / CapacityScheduling (set in their New functions from the profile's engine), `order map[string]int32` to TopologicalSort, the import of pkg/spx (shim/go/pkg/spx),
 and renames the reference's TopologyMatch.Filter body to filterWithVictims for the preemption dry run.  UNCOMPILED: no Go
-toolchain in this image; tests/test_go_shim_apply.py checks that every edit still finds its method in /root/reference.
+toolchain in this image; tests/golden/gen_shim_verified.py checks that every edit finds its method in a reference checkout and
+records the edits it verified, which tests/test_go_shim_apply.py holds this list to.
 
 Reference methods replaced (file:line in the surveyed checkout; twelve bodies in eight files):
   pkg/noderesources/allocatable.go:63 Score, :143 NormalizeScore

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Checks hand-typed golden tables against the reference's Go test tables, read with goparse (no Go toolchain here, nothing is
-executed).  Runs only where /root/reference is mounted; tests/test_golden_hand_typed.py calls it and is skipped elsewhere.
+executed).  Runs where a checkout of the reference is at hand (`python verify_hand_typed.py REFERENCE_CHECKOUT --record`); with
+`--record` it writes what it verified to hand_typed_verified.json, which tests/test_golden_hand_typed.py holds the tables to.
 Covered: allocatable.py (pkg/noderesources/allocatable_test.go:114-238) — every case's pod, node sizes, resource weights, mode,
 expected list and line; trimaran.py's COMPUTE_SCORE and MU_SIGMA; lroc.py's three Beta-distribution tables and the tolerance;
 peaks.py's power model and NormalizeScore cases.  README.md lists what is still hand-typed only."""
@@ -1001,7 +1002,55 @@ def check_integration() -> int:
     return checked
 
 
+HAND_TYPED = ("allocatable", "trimaran", "lroc", "network", "nrt_helpers", "peaks", "nrt_preemption", "nrt_preemption_flow", "integration")
+CHECKS = (check_allocatable, check_trimaran, check_trimaran_score_cases, check_lroc, check_lroc_compute_risk, check_network, check_nrt_helpers,
+          check_nrt_helpers_pods, check_nrt_helpers_numa_lists, check_peaks, check_lroc_resource_tables, check_trimaran_stats,
+          check_nrt_helpers_zones_and_over_reserve, check_nrt_preemption, check_nrt_preemption_flow, check_integration)
+RECORD = HERE / "hand_typed_verified.json"
+
+
+def _canonical(v):
+    """a JSON form of a hand-typed value that keeps what Python tells apart (1 / 1.0 / True, tuple / list) and ignores set order"""
+    if isinstance(v, dict):
+        return ["dict", sorted(([_canonical(k), _canonical(x)] for k, x in v.items()), key=repr)]
+    if isinstance(v, (list, tuple)):
+        return [type(v).__name__, [_canonical(x) for x in v]]
+    if isinstance(v, (set, frozenset)):
+        return ["set", sorted((_canonical(x) for x in v), key=repr)]
+    if v is None or isinstance(v, (bool, int, float, str)):
+        return repr(v)
+    raise TypeError(f"not a table value: {type(v).__name__}")
+
+
+def table_digest(name: str) -> str:
+    """sha256 of a hand-typed module: every value it defines in canonical form and the source of its helper functions"""
+    import __future__
+    import hashlib
+    import importlib
+    import inspect
+    import json
+    import types
+    items = []
+    for k, v in sorted(vars(importlib.import_module(name)).items()):
+        if k.startswith("__") or isinstance(v, (types.ModuleType, type, __future__._Feature)):
+            continue
+        items.append([k, inspect.getsource(v) if isinstance(v, types.FunctionType) else _canonical(v)])
+    return hashlib.sha256(json.dumps(items).encode()).hexdigest()
+
+
+def record() -> dict:
+    """every check's count and every hand-typed module's digest, written to hand_typed_verified.json (after all checks passed)"""
+    import json
+    rec = {"what": "hand-typed tables verified field by field against the reference's Go test sources by verify_hand_typed.py: "
+                   "the number of items each check compared, and the digest (table_digest) of each module as it was verified",
+           "checks": {fn.__name__: fn() for fn in CHECKS}, "tables": {name: table_digest(name) for name in HAND_TYPED}}
+    RECORD.write_text(json.dumps(rec, indent=1, sort_keys=True) + "\n")
+    return rec
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and not sys.argv[1].startswith("-"):
+        REF = Path(sys.argv[1])
     print("allocatable.py:", check_allocatable(), "cases agree with allocatable_test.go")
     print("trimaran.py:", check_trimaran(), "rows of COMPUTE_SCORE / MU_SIGMA agree with analysis_test.go / resourcestats_test.go")
     print("trimaran.py:", check_trimaran_score_cases(), "TLP / LVRB Score cases agree with targetloadpacking_test.go / loadvariationriskbalancing_test.go")
@@ -1018,3 +1067,5 @@ if __name__ == "__main__":
     print("nrt_preemption.py:", check_nrt_preemption(), "items (two fixtures, every TestGetNRTPostPodsEviction case, the error texts) agree with preemption_test.go / preemption.go")
     print("nrt_preemption_flow.py:", check_nrt_preemption_flow(), "items (NRT, node, pods, the seven sub-tests) agree with filter_preemption_test.go")
     print("integration.py:", check_integration(), "items (TLP, LVRB, Allocatable Least / Most, LROC, Peaks) agree with test/integration/*_test.go")
+    if "--record" in sys.argv:
+        print("recorded", RECORD.name, record()["tables"])

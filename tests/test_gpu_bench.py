@@ -50,7 +50,7 @@ def check_line(d, n_gpus_want, scaling):
 
 def test_single_device_line_config1(gpu_required):
     """BASELINE.json configs[0]: Allocatable (LeastAllocated), 100 nodes x 1k pods, through the C ABI"""
-    d = run_bench("--workload", "config1", "--steps", "5", "--warmup", "2", "--cpu-budget", "1")
+    d = run_bench("--workload", "config1", "--steps", "5", "--warmup", "2", "--cpu-budget", "1", "--full")
     check_line(d, 1, "weak")
     assert d["config"]["n_nodes"] == 100 and d["config"]["n_pods_per_step"] == 1000 and d["config"]["plugins"] == ["alloc"]
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] == "port"
@@ -63,7 +63,7 @@ def test_single_device_line_config1(gpu_required):
     ("small_full", "strong", []),
 ])
 def test_multi_device_mode(gpu_required, workload, scaling, extra):
-    d = run_bench("--workload", workload, "--devices", "0,0", "--transport", "copy", "--steps", "3", "--warmup", "1", "--cpu-budget", "0", *extra)
+    d = run_bench("--workload", workload, "--devices", "0,0", "--transport", "copy", "--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--full", *extra)
     check_line(d, 2, scaling)
     assert d["config"]["host"].startswith("one process driving 2 devices")
     g = d["gather"]
@@ -82,7 +82,7 @@ def test_multi_device_mode_eight_ranks(gpu_required, workload, gather):
     """`--gpus 8` as one process sees it — eight ranks' engines, host threads, shards of 1 000 (the ragged batch: seven of 1 024 and one of
     1 023) and the exchange — with all eight on device 0 over peer copies: config #4's and config #5's plugin sets at plumbing size, so
     that the first run on eight devices is not the first run of this code with eight ranks"""
-    d = run_bench("--workload", workload, "--devices", "0,0,0,0,0,0,0,0", "--transport", "copy", "--steps", "2", "--warmup", "1", "--cpu-budget", "0", "--gather", gather)
+    d = run_bench("--workload", workload, "--devices", "0,0,0,0,0,0,0,0", "--transport", "copy", "--steps", "2", "--warmup", "1", "--cpu-budget", "0", "--gather", gather, "--full")
     check_line(d, 8, "strong")
     assert d["config"]["host"].startswith("one process driving 8 devices")
     total = 8191 if workload == "small_full_ragged" else 8000
@@ -95,7 +95,7 @@ def test_multi_device_mode_eight_ranks(gpu_required, workload, gather):
 @pytest.mark.skipif(n_gpus() < 2, reason="needs two GPUs")
 @pytest.mark.parametrize("workload", ["small", "small_full"])
 def test_multi_device_mode_rccl(gpu_required, workload):
-    d = run_bench("--workload", workload, "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--gather", "table")
+    d = run_bench("--workload", workload, "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--gather", "table", "--full")
     check_line(d, 2, "weak" if workload == "small" else "strong")
     assert d["gather"]["transport"] == "rccl"
 
@@ -137,7 +137,7 @@ def test_ranks_mode_two_processes(gpu_required, workload, scaling, gather):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29613",
-           str(ROOT / "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--gather", gather, *extra]
+           str(ROOT / "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--gather", gather, "--full", *extra]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -162,10 +162,44 @@ def test_ranks_mode_ragged_strong_shards_assemble(gpu_required, ranks, port):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(port),
            str(ROOT / "bench.py"), "--gpus", str(ranks), "--workload", "small_full_ragged", "--steps", "2", "--warmup", "1", "--cpu-budget", "0", "--gather", "best",
-           "--verify-gather", *extra]
+           "--verify-gather", "--full", *extra]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][0])
     check_line(d, ranks, "strong")
     assert d["config"]["n_pods_per_step"] == 8191 and d["config"]["n_pods_slowest_rank"] == -(-8191 // ranks)
     assert d["gather"]["verified_rows"] == 8191 and d["gather"]["mismatches"] == 0, d["gather"]
+
+
+@pytest.mark.parametrize("workload,scaling", [("small", "weak"), ("small_full", "strong")])
+def test_plain_line_and_dumped_outputs(gpu_required, hdr, tmp_path, workload, scaling):
+    """a plain line (no --full) carries none of the sections --full adds; --dump-outputs writes what the last timed step computed:
+    the sampled rows of every table equal what a fresh engine computes for the same seeded batch"""
+    import bench
+    from scheduler_plugins_amd.engine import Engine
+    d = run_bench("--workload", workload, "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    check_line(d, 1, scaling)
+    assert d["steps"] == 4 and d["warmup"] == 1
+    for key in ("every_row", "full_cycle", "topological_sort", "gather", "config5_leg", "config3_leg", "cpu_baseline"):
+        assert key not in d, key
+    files = sorted(tmp_path.glob("*.npy"))
+    assert [f.name for f in files] == d["dump_outputs"]["files"]
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    got = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    w = bench.WORKLOADS[workload]
+    rows = got["rows"].astype(np.int64)
+    assert len(rows) == d["dump_outputs"]["rows_sampled"] > 0 and np.all(np.diff(rows) > 0)
+    snap = bench.build_snapshot(hdr, w, w["n_pods"], synth.SEED)
+    with Engine(0) as e:
+        bench.load_tables(e, w, snap)
+        e.eval(mask_of(*[bench.PID[p] for p in w["plugins"]]))
+        e.sync()
+        for p in w["plugins"]:
+            pid = bench.PID[p]
+            if p == "cap":
+                assert np.array_equal(got["prefilter_cap"], e.prefilter(pid).astype(np.float32))
+                continue
+            assert np.array_equal(got[f"scores_{p}"], np.stack([e.scores(pid, int(r)) for r in rows]).astype(np.float32)), p
+            if p in ("nrt", "net"):
+                assert np.array_equal(got[f"status_{p}"], np.stack([e.status(pid, int(r)) for r in rows]).astype(np.float32)), p

@@ -8,6 +8,8 @@ for batch in "config2 config2_lvrb config2_peaks" "config3 config3_most config3_
   python tools/collect_profiles.py r06 $batch 2>&1 | tail -4
 done
 rm -rf gpurun_out/prof_*
-/usr/local/graft/bin/gpurun --timeout 2400 -- 'mkdir -p gpurun_out/r6; timeout 1800 python bench.py --workload config5 --gpus 1 --steps 3 --warmup 1 --sweep-only --cpu-budget 0 > gpurun_out/r6/config5_full_bench_line.json 2> gpurun_out/r6/config5_full.err; python -c "
-import json;d=json.loads(open(\"gpurun_out/r6/config5_full_bench_line.json\").read().strip().splitlines()[-1]);print(\"config5 whole\", d[\"roofline\"][\"kernel_ms\"], d.get(\"every_row\",{}).get(\"kernel_ms\"))"' 2>&1 | tail -2
-cp gpurun_out/r6/config5_full_bench_line.json profiles/r06/
+OUT=${OUT:-bench_out}/r6
+mkdir -p "$OUT"
+timeout 1800 python bench.py --workload config5 --gpus 1 --steps 3 --warmup 1 --sweep-only --cpu-budget 0 --full > "$OUT/config5_full_bench_line.json" 2> "$OUT/config5_full.err"
+python -c "import json, sys; d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('config5 whole', d['roofline']['kernel_ms'], d.get('every_row', {}).get('kernel_ms'))" "$OUT/config5_full_bench_line.json"
+cp "$OUT/config5_full_bench_line.json" profiles/r06/

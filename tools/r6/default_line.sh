@@ -1,11 +1,12 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out/r6
-python bench.py > gpurun_out/r6/default_line.json 2> gpurun_out/r6/default_line.err
-tail -c 300 gpurun_out/r6/default_line.err
+export OUT=${OUT:-bench_out}/r6
+mkdir -p "$OUT"
+python bench.py --full > "$OUT/default_line.json" 2> "$OUT/default_line.err"
+tail -c 300 "$OUT/default_line.err"
 python - <<'PY'
-import json
-d=json.loads(open("gpurun_out/r6/default_line.json").read().strip().splitlines()[-1])
+import json, os
+d=json.loads(open(os.environ["OUT"] + "/default_line.json").read().strip().splitlines()[-1])
 print({k:d[k] for k in ("metric","value","unit","ms_per_step","n_gpus","steps","warmup","dtype","vs_baseline")})
 print("roofline", d["roofline"])
 for k in ("config3_leg","config4_leg","config5_share_leg"):
