@@ -820,7 +820,8 @@ int spx_load_quota(spx_engine* e, const spx_pod_objects* pods, const spx_resourc
 /* The whole profile in one call: the loaders above run side by side on host threads of the library (they fill disjoint tables and share
  * the engine's stream; spx_load_nrt itself runs its node half and its pod half on two threads).  nodes and pods are required; a loader
  * whose members are NULL is skipped: metrics (+ rc, assigned) = spx_load_trimaran, nrt + nrt_params = spx_load_nrt, appgroups + nettopo =
- * spx_load_network, quota = spx_load_quota.  Returns the first failing loader's code.  No other call on the engine may run meanwhile. */
+ * spx_load_network, quota = spx_load_quota; nrt without nrt_params is SPX_ERR_ARG.  Returns the first failing loader's code, and
+ * spx_last_error on the calling thread names that loader's failure.  No other call on the engine may run meanwhile. */
 typedef struct spx_profile_objects {
   const spx_node_objects* nodes;
   const spx_resource_classes* rc;

@@ -373,6 +373,7 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       if ((rc = nrt_rank_stream(e, classes ? 1 : 2))) return rc;
     }
     const bool stream = e->nrt_rk_max_dwords && e->nrt_rk_kind == (classes ? 1 : 2) && e->option[SPX_OPT_NRT_RANK_FILTER];
+    spx_engine::FzKey fz_key;  // what d_nrt_fz holds once the fused launch has run (gen 0: matches no later sweep)
     if (classes) {
       na.row_list = static_cast<const int32_t*>(e->d_nrt_uniq.p);
       na.n_list = e->nrt_n_uniq;
@@ -389,9 +390,8 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       if (fused) {
         if ((rc = ensure(e, e->d_nrt_fz, spx::nrt_fused_item_words(e->nrt_n_res, na.n_list) * sizeof(uint32_t)))) return rc;
         na.fz_items = static_cast<uint32_t*>(e->d_nrt_fz.p);
-        const spx_engine::FzKey key{e->nrt_items_gen, classes ? 1 : 2, na.pk_tab_slot, e->d_nrt_fz.p};
-        na.fz_pack = !(key == e->nrt_fz_key);
-        e->nrt_fz_key = key;
+        fz_key = spx_engine::FzKey{e->nrt_items_gen, classes ? 1 : 2, na.pk_tab_slot, e->d_nrt_fz.p};
+        na.fz_pack = !(fz_key == e->nrt_fz_key);
       }
     }
     if (na.strategy == SPX_NRT_LEAST_NUMA_NODES && na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect) {
@@ -440,6 +440,9 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       na.wrank = static_cast<const uint16_t*>(e->d_nrt_wrank.p);
     }
     const bool ran_fused = spx::launch_nrt(na, e->stream);
+    // the fused launch may decline (BalancedAllocation's cpu slot not exact in float32, a chunk block too large for LDS): then the
+    // pack did not run either, and the key must not claim d_nrt_fz holds this pod generation's items
+    if (na.fz_items) e->nrt_fz_key = ran_fused ? fz_key : spx_engine::FzKey{};
     e->last_nrt_filter = ran_fused ? 3 : (na.rk_stream ? 2 : 1);
     if (classes)
       spx::launch_rows_expand(static_cast<const int32_t*>(e->d_nrt_dups.p), static_cast<const int32_t*>(e->d_nrt_dups.p) + 2 * e->nrt_n_dups, e->nrt_n_tasks, na.out_status, na.out_score,

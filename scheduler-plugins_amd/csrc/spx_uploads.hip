@@ -1257,17 +1257,25 @@ int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_obj
 // NetworkOverhead tables, quota tables), share one stream, and each takes a worker pool of its own.  Members left NULL skip their loader.
 int spx_load_profile(spx_engine* e, const spx_profile_objects* o) {
   if (!e || !o || !o->nodes || !o->pods) return SPX_ERR_ARG;
+  if (o->nrt && !o->nrt_params) return fail(e, SPX_ERR_ARG, "spx_load_profile: nrt without nrt_params");
   int rc_;
   if ((rc_ = set_nodes(e, o->nodes->n_nodes)) || (rc_ = set_pods(e, o->pods->n_pods))) return rc_;
   int rcs[4] = {SPX_OK, SPX_OK, SPX_OK, SPX_OK};
+  std::string msgs[4];  // a failing loader's message, taken on the thread it failed on (fail() records it in that thread's tl_err)
+  const auto run = [&](int i, const auto& load) {
+    tl_err_engine = nullptr;
+    rcs[i] = load();
+    if (rcs[i] && tl_err_engine == e) msgs[i] = tl_err;
+  };
   std::vector<std::thread> th;
-  if (o->nrt && o->nrt_params) th.emplace_back([&] { rcs[1] = spx_load_nrt(e, o->nodes, o->nrt, o->rc, o->pods, o->nrt_params); });  // the longest first
-  if (o->appgroups && o->nettopo) th.emplace_back([&] { rcs[2] = spx_load_network(e, o->nodes, o->pods, o->appgroups, o->nettopo); });
-  if (o->quota) th.emplace_back([&] { rcs[3] = spx_load_quota(e, o->pods, o->rc, o->quota); });
-  if (o->metrics) rcs[0] = spx_load_trimaran(e, o->nodes, o->rc, o->pods, o->metrics, o->assigned);
+  if (o->nrt) th.emplace_back([&] { run(1, [&] { return spx_load_nrt(e, o->nodes, o->nrt, o->rc, o->pods, o->nrt_params); }); });  // the longest first
+  if (o->appgroups && o->nettopo) th.emplace_back([&] { run(2, [&] { return spx_load_network(e, o->nodes, o->pods, o->appgroups, o->nettopo); }); });
+  if (o->quota) th.emplace_back([&] { run(3, [&] { return spx_load_quota(e, o->pods, o->rc, o->quota); }); });
+  if (o->metrics) run(0, [&] { return spx_load_trimaran(e, o->nodes, o->rc, o->pods, o->metrics, o->assigned); });
   for (std::thread& t : th) t.join();
-  for (int r : rcs)
-    if (r) return r;
+  // the caller's spx_last_error must name the failure returned here, not an older one of this thread on this engine
+  for (int i = 0; i < 4; ++i)
+    if (rcs[i]) return fail(e, rcs[i], msgs[i].empty() ? std::string("spx_load_profile: a loader failed") : msgs[i]);
   return SPX_OK;
 }
 

@@ -373,6 +373,18 @@ class Engine:
         self._ck(fn(pods.ref(), rc.ref() if rc else None, slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(pc.values(), fn.argtypes[3:])]))
         return pc
 
+    def set_nrt_params(self, params: Table) -> None:
+        """the scoring strategy alone (spx_set_nrt_params): slot weights travel with the slot table, the tables stay in place"""
+        self._ck(self._lib.spx_set_nrt_params(self._h, params.ref()))
+
+    def upload_nrt_nodes(self, nc: Dict[str, np.ndarray], n_res: int) -> None:
+        """the node zone tables alone, for the pod batch in place (spx_upload_nrt_nodes: the preemption dry run's re-upload)"""
+        n = len(nc["flags"])
+        self._ck(self._lib.spx_upload_nrt_nodes(self._h, Table(self._hdr, "spx_nrt_nodes_soa", n_nodes=n, n_res=n_res, **nc).ref()))
+        self.n_nodes = n
+        if getattr(self, "nrt_soa", None) is not None:
+            self.nrt_soa["nodes"] = nc
+
     def upload_nrt_pods(self, pc: Dict[str, np.ndarray], n_res: int) -> None:
         P = len(pc["qos"])
         self._ck(self._lib.spx_upload_nrt_pods(self._h, Table(self._hdr, "spx_nrt_pods_soa", n_pods=P, n_res=n_res, **pc).ref()))
