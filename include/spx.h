@@ -395,10 +395,14 @@ typedef struct spx_peaks_pods_soa {
 
 /* NodeResourceTopologyMatch.  Resources are renumbered into dense "slots" 0..n_res-1 (the union of
  * what pods request and zones report; slot_res gives the canonical id).  Limits of this build:
- * n_res <= 8, NUMA zones per node <= 8, containers per pod <= 8 (flatten fails beyond them). */
+ * n_res <= 8 and NUMA zones per node <= 8 (flatten fails beyond them).  Containers per pod are unbounded:
+ * a pod with up to SPX_NRT_MAX_CTRS containers keeps them in the dense pod table; a pod with more is a
+ * "long row" — n_ctr = SPX_NRT_CTRS_LONG, per-container columns zero, pod-level columns (qos, non_native,
+ * pod_present, pod_req) filled as for any row — whose containers travel in spx_nrt_long_pods. */
 #define SPX_NRT_MAX_RES 8
 #define SPX_NRT_MAX_ZONES 8
 #define SPX_NRT_MAX_CTRS 8
+#define SPX_NRT_CTRS_LONG 255
 #define SPX_NRT_F_HAS_NRT 1
 #define SPX_NRT_F_FRESH 2
 #define SPX_NRT_F_SINGLE_NUMA 4
@@ -450,6 +454,19 @@ typedef struct spx_nrt_pods_soa {
   const uint8_t* pod_present;
   const int64_t* pod_req;
 } spx_nrt_pods_soa;
+
+/* The containers of the long rows of an spx_nrt_pods_soa batch, CSR: long row k is batch row pod_row[k] (ascending), its containers
+ * ctr_ptr[k] .. ctr_ptr[k+1]-1 in document order (init and sidecar containers first, then app containers, as in spx_pod_objects);
+ * ctr_kind / ctr_present / ctr_req [n_ctr][n_res] as the dense table's per-container columns. */
+typedef struct spx_nrt_long_pods {
+  int64_t n_long;
+  int32_t n_res;
+  const int32_t* pod_row;
+  const int32_t* ctr_ptr;
+  const uint8_t* ctr_kind;
+  const uint8_t* ctr_present;
+  const int64_t* ctr_req;
+} spx_nrt_long_pods;
 
 /* NetworkOverhead.  A pod's PreFilter state depends only on its (AppGroup, workload selector) "workload
  * key"; the matched (placed pod, dependency) pairs are flattened once per key. */
@@ -614,6 +631,12 @@ int spx_update_quota_used(spx_engine* e, int64_t n_rows, const int32_t* ns, cons
 int spx_upload_nrt_slots(spx_engine* e, const spx_nrt_slots* t);
 int spx_upload_nrt_nodes(spx_engine* e, const spx_nrt_nodes_soa* t);
 int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t);
+/* the containers of the batch's long rows (after spx_upload_nrt_pods; t->pod_row must list exactly the rows whose n_ctr is
+ * SPX_NRT_CTRS_LONG, else SPX_ERR_ARG).  An NRT spx_eval / spx_decide / spx_commit_sequential of a batch with long rows and no table
+ * fails with SPX_ERR_STATE; a table with n_long = 0 for a batch without long rows is accepted (and clears the table). */
+int spx_upload_nrt_long_pods(spx_engine* e, const spx_nrt_long_pods* t);
+/* *n_out = long rows the last NodeResourceTopologyMatch sweep of spx_eval evaluated (those inside its row range; 0 = none / no sweep yet) */
+int spx_nrt_long_rows(const spx_engine* e, int64_t* n_out);
 int spx_upload_net_nodes(spx_engine* e, const spx_net_nodes_soa* t);
 int spx_upload_net_topo(spx_engine* e, const spx_net_topo_soa* t);
 int spx_upload_net_pods(spx_engine* e, const spx_net_pods_soa* t);
@@ -932,6 +955,11 @@ int spx_flatten_nrt_nodes(const spx_node_objects* nodes, const spx_nrt_objects* 
 int spx_flatten_nrt_node_rows(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, const int64_t* idx, int64_t n_rows, uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id, uint8_t* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist, uint8_t* node_present);
 /* pod arrays sized: qos[P], non_native[P], n_ctr[P], ctr_kind[P*8], ctr_present[P*8], ctr_req[P*8*n_res], pod_present[P], pod_req[P*n_res] */
 int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, uint8_t* qos, uint8_t* non_native, uint8_t* n_ctr, uint8_t* ctr_kind, uint8_t* ctr_present, int64_t* ctr_req, uint8_t* pod_present, int64_t* pod_req);
+/* the containers of the pods with more than SPX_NRT_MAX_CTRS containers (the long rows spx_flatten_nrt_pods marks), CSR as
+ * spx_nrt_long_pods.  *n_long_out / *n_ctr_out receive the counts; with every output array NULL the call only counts.  Otherwise
+ * pod_row / ctr_ptr must hold long_cap / long_cap + 1 entries and ctr_kind / ctr_present / ctr_req ctr_cap / ctr_cap / ctr_cap x n_res,
+ * and a table larger than that is SPX_ERR_ARG (the counts are written first, so the caller can resize and call again). */
+int spx_flatten_nrt_long_pods(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, int64_t long_cap, int64_t ctr_cap, int64_t* n_long_out, int64_t* n_ctr_out, int32_t* pod_row, int32_t* ctr_ptr, uint8_t* ctr_kind, uint8_t* ctr_present, int64_t* ctr_req);
 
 /* NetworkOverhead / TopologicalSort.  region_cost[n_regions*n_regions] and zone_cost[n_zones*n_zones]: -1 = no entry.
  * spx_flatten_net_keys sizes: *n_keys_out and *n_pairs_out first (pass NULL arrays), then fill

@@ -133,6 +133,12 @@ struct spx_engine {
   void* h_items = nullptr;       // pinned staging of the NRT pod record stream, built in place (its own buffer: spx_load_nrt's node and pod halves run side by side)
   size_t h_items_bytes = 0;
   DevBuf d_delta;                // staged rows of a node-table delta (spx_update_*_nodes)
+  // long rows (pods with more than SPX_NRT_MAX_CTRS containers): their containers in CSR (spx_upload_nrt_long_pods), evaluated by
+  // kernels_nrt_long.hip after the dense sweep
+  std::vector<int32_t> h_nrt_long_rows;  // rows of the uploaded batch whose n_ctr is SPX_NRT_CTRS_LONG, ascending
+  bool nrt_long_ok = true;               // the long table describes those rows (trivially true without any)
+  int64_t nrt_long_last = 0;             // spx_nrt_long_rows
+  DevBuf d_nrtl_row, d_nrtl_ptr, d_nrtl_kind, d_nrtl_pres, d_nrtl_req, d_nrtl_map;
   DevBuf d_nrt_uniq, d_nrt_dups;  // int32 [n_uniq] representative rows, ascending; int32 [n_dups][2] (row, its representative)
   int64_t nrt_n_uniq = 0, nrt_n_dups = 0, nrt_n_tasks = 0;  // (d_nrt_dups: the pairs sorted by representative, then the copy tasks — expand_tasks)
   DevBuf d_nrt_rk, d_nrt_rk_off;  // rank-space Filter: the chunk stream of the listed rows (nrt_build_rank_stream) and its chunk offsets
@@ -568,6 +574,48 @@ void fill_nrt(const spx_engine* e, spx::NrtArgs& na) {
   na.redo_cap = e->nrt_redo_cap;
   na.ln_tab = (e->nrt_ln_ok && e->nrt_ln_built) ? static_cast<const uint32_t*>(e->d_nrt_ln.p) : nullptr;
   na.ln_const = na.ln_tab ? na.ln_tab + static_cast<size_t>(spx::make_ln_layout().rows) * static_cast<size_t>(e->n_nodes) : nullptr;
+}
+
+// the long rows of [row_begin, row_end) (kernels_nrt_long.hip) after the dense sweep `na` wrote their cells as those of an empty pod
+// (no containers, no request): their status and score rows are overwritten (or, with na.out_raw, the raw row).  Inside the sequential commit loop
+// (row_indirect) the launch reads the row from the device and leaves at once when it is not long.  No launch without long rows.
+int launch_nrt_long_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begin, int64_t row_end) {
+  e->nrt_long_last = 0;
+  const std::vector<int32_t>& rows = e->h_nrt_long_rows;
+  if (rows.empty()) return SPX_OK;
+  if (!e->nrt_long_ok) return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
+  const int64_t k0 = std::lower_bound(rows.begin(), rows.end(), row_begin) - rows.begin();
+  const int64_t k1 = std::lower_bound(rows.begin(), rows.end(), row_end) - rows.begin();
+  if (k1 <= k0 && !e->row_indirect) return SPX_OK;
+  spx::NrtLongArgs l{};
+  l.n_nodes = na.n_nodes;
+  l.n_pods = na.n_pods;
+  l.row_stride = na.row_stride;
+  l.n_res = na.n_res;
+  l.strategy = na.strategy;
+  std::memcpy(l.slot_flags, na.slot_flags, sizeof l.slot_flags);
+  std::memcpy(l.slot_weight, na.slot_weight, sizeof l.slot_weight);
+  l.flags = na.flags, l.max_numa = na.max_numa, l.n_zones = na.n_zones, l.zone_id = na.zone_id, l.zone_present = na.zone_present;
+  l.zone_avail = na.zone_avail, l.zone_cost = na.zone_cost, l.min_avg = na.min_avg, l.node_present = na.node_present;
+  l.qos = na.qos, l.non_native = na.non_native, l.pod_present = na.pod_present, l.pod_req = na.pod_req;
+  l.pod_row = static_cast<const int32_t*>(e->d_nrtl_row.p);
+  l.ctr_ptr = static_cast<const int32_t*>(e->d_nrtl_ptr.p);
+  l.ctr_kind = static_cast<const uint8_t*>(e->d_nrtl_kind.p);
+  l.ctr_present = static_cast<const uint8_t*>(e->d_nrtl_pres.p);
+  l.ctr_req = static_cast<const int64_t*>(e->d_nrtl_req.p);
+  l.long_begin = k0;
+  l.long_end = k1;
+  if (e->row_indirect) {
+    l.row_ptr = e->row_indirect;
+    l.long_of_row = static_cast<const int32_t*>(e->d_nrtl_map.p);
+  }
+  l.out_status = na.out_status;
+  l.out_score = na.out_score;
+  l.out_raw = na.out_raw;
+  spx::launch_nrt_long(l, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  e->nrt_long_last = k1 - k0;
+  return SPX_OK;
 }
 
 // the reference-arithmetic NRT kernel's request column, when the coming launch may take that kernel and the batch did not ship it

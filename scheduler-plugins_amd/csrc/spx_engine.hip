@@ -74,7 +74,8 @@ int spx_destroy(spx_engine* e) {
                     &e->d_best, &e->d_stats, &e->d_decide, &e->d_lroc_nreq_c, &e->d_lroc_nreq_m, &e->d_lroc_nlim_c, &e->d_lroc_nlim_m,
                     &e->d_lroc_preq_c, &e->d_lroc_preq_m, &e->d_lroc_plim_c, &e->d_lroc_plim_m, &e->d_lroc_tab, &e->d_lroc_podf,
                     &e->d_pk_cap, &e->d_pk_util, &e->d_pk_valid, &e->d_pk_k1, &e->d_pk_k2, &e->d_pk_pod, &e->d_pk_min, &e->d_pk_max, &e->d_pk_rowc, &e->d_pk_tab, &e->d_pk_seg, &e->d_pk_segn,
-                    &e->d_nrt_uniq, &e->d_nrt_dups, &e->d_pk_uniq, &e->d_pk_dups, &e->d_delta, &e->d_nrt_lnrec, &e->d_net_pair_node2, &e->d_net_pair_max2, &e->d_nrt_rk, &e->d_nrt_rk_off, &e->d_nrt_rk_first, &e->d_nrt_fz, &e->d_nrt_wsort, &e->d_nrt_wrank};
+                    &e->d_nrt_uniq, &e->d_nrt_dups, &e->d_pk_uniq, &e->d_pk_dups, &e->d_delta, &e->d_nrt_lnrec, &e->d_net_pair_node2, &e->d_net_pair_max2, &e->d_nrt_rk, &e->d_nrt_rk_off, &e->d_nrt_rk_first, &e->d_nrt_fz, &e->d_nrt_wsort, &e->d_nrt_wrank,
+                    &e->d_nrtl_row, &e->d_nrtl_ptr, &e->d_nrtl_kind, &e->d_nrtl_pres, &e->d_nrtl_req, &e->d_nrtl_map};
   for (DevBuf* b : bufs)
     if (b->p && !b->external) (void)hipFree(b->p);
   for (int i = 0; i < SPX_NUM_PLUGINS; ++i) {
@@ -232,6 +233,8 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   int rc;
   const bool N = plugin_mask & (1u << SPX_PLUGIN_NRT);
   if (N && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
+  if (N && !e->nrt_long_ok)
+    return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
   if (A && (rc = prepare_alloc(e))) return rc;
   const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD);
   if (W && !(e->net_nodes && e->net_topo && e->net_pods)) return fail(e, SPX_ERR_STATE, "NetworkOverhead node/topology/pod tables not uploaded");
@@ -448,6 +451,9 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       spx::launch_rows_expand(static_cast<const int32_t*>(e->d_nrt_dups.p), static_cast<const int32_t*>(e->d_nrt_dups.p) + 2 * e->nrt_n_dups, e->nrt_n_tasks, na.out_status, na.out_score,
                               e->row_stride, e->stream);
     SPX_HIP(e, hipGetLastError());
+    // the long rows overwrite what the sweep above wrote from their pod-level request, before NetworkOverhead and Allocatable's
+    // masked normalisation read the NRT status table (a long row is a class of its own: no copy of it was made above)
+    if ((rc = launch_nrt_long_rows(e, na, row_begin, row_end))) return rc;
   }
   if (W) {
     if (e->score_stride[SPX_PLUGIN_NETOVERHEAD] != e->row_stride)
@@ -567,6 +573,12 @@ int spx_sync(spx_engine* e) {
 }
 
 int spx_nrt_filter_path(const spx_engine* e) { return e ? e->last_nrt_filter : 0; }
+
+int spx_nrt_long_rows(const spx_engine* e, int64_t* n_out) {
+  if (!e || !n_out) return SPX_ERR_ARG;
+  *n_out = e->nrt_long_last;
+  return SPX_OK;
+}
 
 int spx_nrt_packed_score_slots(const spx_engine* e) {
   if (!e) return SPX_ERR_ARG;
@@ -688,6 +700,10 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
     na.row_end = pod_row + 1;
     na.out_raw = static_cast<int64_t*>(e->d_raw_row.p);
     spx::launch_nrt(na, e->stream);
+    const int64_t swept = e->nrt_long_last;  // (spx_nrt_long_rows reports spx_eval's sweeps, not this row)
+    rc = launch_nrt_long_rows(e, na, pod_row, pod_row + 1);
+    e->nrt_long_last = swept;
+    if (rc) return rc;
     SPX_HIP(e, hipGetLastError());
     SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
     SPX_HIP(e, hipStreamSynchronize(e->stream));

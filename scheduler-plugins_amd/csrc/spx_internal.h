@@ -404,6 +404,43 @@ constexpr LnLayout make_ln_layout() {
   return l;
 }
 bool launch_nrt(const NrtArgs& a, hipStream_t s);  // true = ran as the fused Filter + Score launch
+
+// NodeResourceTopologyMatch's long rows (pods with more than SPX_NRT_MAX_CTRS containers; kernels_nrt_long.hip): the node columns and
+// pod-level columns of NrtArgs, and the containers of the long rows in CSR (spx_upload_nrt_long_pods)
+struct NrtLongArgs {
+  int64_t n_nodes;
+  int64_t n_pods;
+  int64_t row_stride;
+  int32_t n_res;
+  int32_t strategy;
+  uint8_t slot_flags[SPX_NRT_MAX_RES];
+  int64_t slot_weight[SPX_NRT_MAX_RES];
+  const uint8_t* flags;          // [N]
+  const int32_t* max_numa;       // [N]
+  const uint8_t* n_zones;        // [N]
+  const uint8_t* zone_id;        // [Z][N]
+  const uint8_t* zone_present;   // [Z][N]
+  const int64_t* zone_avail;     // [Z][n_res][N]
+  const int32_t* zone_cost;      // [Z][Z][N]
+  const float* min_avg;          // [Z][N]
+  const uint8_t* node_present;   // [N]
+  const uint8_t* qos;            // [P]
+  const uint8_t* non_native;     // [P]
+  const uint8_t* pod_present;    // [P]
+  const int64_t* pod_req;        // [P][n_res]
+  const int32_t* pod_row;        // [n_long] batch row of each long row, ascending
+  const int32_t* ctr_ptr;        // [n_long + 1]
+  const uint8_t* ctr_kind;       // [n_ctr]
+  const uint8_t* ctr_present;    // [n_ctr]
+  const int64_t* ctr_req;        // [n_ctr][n_res]
+  int64_t long_begin, long_end;  // the long rows evaluated: [long_begin, long_end) of the table
+  const int64_t* row_ptr;        // when set: only the batch row *row_ptr (sequential commit), long_of_row[row] its long row or -1
+  const int32_t* long_of_row;    // [P]
+  uint8_t* out_status;           // [P][row_stride]
+  uint8_t* out_score;            // [P][row_stride]
+  int64_t* out_raw;              // when set: raw int64 scores of the one long row long_begin, no table writes
+};
+void launch_nrt_long(const NrtLongArgs& a, hipStream_t s);
 // the reference-arithmetic kernel's per-container request column [P][8][n_res] int64, rebuilt from the pod record stream (whose
 // quantities are exact doubles whenever the stream is valid): the engine does not ship that column — 256 bytes per pod — with every
 // pod batch, only when a launch is going to read it

@@ -844,7 +844,21 @@ int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t) {
   constexpr size_t Cm = SPX_NRT_MAX_CTRS;
   if ((rc = upload(e, e->d_nrt_qos, t->qos, p))) return rc;
   if ((rc = upload(e, e->d_nrt_nn, t->non_native, p))) return rc;
-  if ((rc = upload(e, e->d_nrt_nctr, t->n_ctr, p))) return rc;
+  // long rows (n_ctr = SPX_NRT_CTRS_LONG): their containers come with spx_upload_nrt_long_pods; the dense sweeps see them as pods without
+  // containers (the device column holds 0), and kernels_nrt_long.hip overwrites their cells afterwards
+  e->h_nrt_long_rows.clear();
+  for (size_t i = 0; i < p; ++i)
+    if (t->n_ctr && t->n_ctr[i] == SPX_NRT_CTRS_LONG) e->h_nrt_long_rows.push_back(static_cast<int32_t>(i));
+  e->nrt_long_ok = e->h_nrt_long_rows.empty();
+  e->nrt_long_last = 0;
+  if (e->h_nrt_long_rows.empty()) {
+    if ((rc = upload(e, e->d_nrt_nctr, t->n_ctr, p))) return rc;
+  } else {
+    std::vector<uint8_t> nctr(t->n_ctr, t->n_ctr + p);
+    for (const int32_t r : e->h_nrt_long_rows) nctr[static_cast<size_t>(r)] = 0;
+    if ((rc = upload(e, e->d_nrt_nctr, nctr.data(), p))) return rc;
+    SPX_HIP(e, hipStreamSynchronize(e->stream));  // (a local vector)
+  }
   if ((rc = upload(e, e->d_nrt_ckind, t->ctr_kind, p * Cm))) return rc;
   if ((rc = upload(e, e->d_nrt_cpres, t->ctr_present, p * Cm))) return rc;
   if (!t->ctr_req && p * R) return fail(e, SPX_ERR_ARG, "NULL column in table");
@@ -904,6 +918,40 @@ int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t) {
   }
   e->nrt_pods = true;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
+  return SPX_OK;
+}
+
+int spx_upload_nrt_long_pods(spx_engine* e, const spx_nrt_long_pods* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (!e->nrt_pods) return fail(e, SPX_ERR_STATE, "NRT: upload the pod table (spx_upload_nrt_pods) before its long rows");
+  if (t->n_long < 0 || t->n_res != e->nrt_n_res) return fail(e, SPX_ERR_ARG, "NRT long rows: n_long < 0 or n_res differs from the slot table");
+  const std::vector<int32_t>& rows = e->h_nrt_long_rows;
+  if (static_cast<size_t>(t->n_long) != rows.size())
+    return fail(e, SPX_ERR_ARG, "NRT long rows: the table must list exactly the batch rows whose n_ctr is SPX_NRT_CTRS_LONG");
+  if (t->n_long == 0) {
+    e->nrt_long_ok = true;
+    return SPX_OK;
+  }
+  if (!t->pod_row || !t->ctr_ptr) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  const size_t L = static_cast<size_t>(t->n_long), R = static_cast<size_t>(t->n_res);
+  for (size_t k = 0; k < L; ++k)
+    if (t->pod_row[k] != rows[k]) return fail(e, SPX_ERR_ARG, "NRT long rows: the table must list exactly the batch rows whose n_ctr is SPX_NRT_CTRS_LONG");
+  if (t->ctr_ptr[0] != 0) return fail(e, SPX_ERR_ARG, "NRT long rows: ctr_ptr[0] must be 0");
+  for (size_t k = 0; k < L; ++k)
+    if (t->ctr_ptr[k + 1] - t->ctr_ptr[k] <= SPX_NRT_MAX_CTRS) return fail(e, SPX_ERR_ARG, "NRT long rows: a long row holds more than 8 containers");
+  const size_t n_ctr = static_cast<size_t>(t->ctr_ptr[L]);
+  e->nrt_long_ok = false;
+  int rc;
+  if ((rc = upload(e, e->d_nrtl_row, t->pod_row, L * 4)) || (rc = upload(e, e->d_nrtl_ptr, t->ctr_ptr, (L + 1) * 4)) ||
+      (rc = upload(e, e->d_nrtl_kind, t->ctr_kind, n_ctr)) || (rc = upload(e, e->d_nrtl_pres, t->ctr_present, n_ctr)) ||
+      (rc = upload(e, e->d_nrtl_req, t->ctr_req, n_ctr * R * 8)))
+    return rc;
+  std::vector<int32_t> map(static_cast<size_t>(e->n_pods), -1);  // batch row -> long row (the commit loop's row_indirect launches)
+  for (size_t k = 0; k < L; ++k) map[static_cast<size_t>(rows[k])] = static_cast<int32_t>(k);
+  if ((rc = upload(e, e->d_nrtl_map, map.data(), map.size() * 4))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->nrt_long_ok = true;
   return SPX_OK;
 }
 
@@ -1229,6 +1277,20 @@ int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_obj
     const auto t2 = clk::now();
     const spx_nrt_pods_soa ps{pods->n_pods, n_res, qos.data(), nn.data(), nctr.data(), ckind.data(), cpres.data(), creq.data(), ppres.data(), preq.data()};
     rc_pods = spx_upload_nrt_pods(e, &ps);
+    if (rc_pods == SPX_OK && !e->nrt_long_ok) {  // pods with more than 8 containers: their CSR table
+      int64_t n_long = 0, n_lc = 0;
+      spx_flatten_nrt_long_pods(pods, rc, &slots, 0, 0, &n_long, &n_lc, nullptr, nullptr, nullptr, nullptr, nullptr);
+      const size_t Ls = static_cast<size_t>(n_long), Cs = static_cast<size_t>(n_lc);
+      std::vector<int32_t> lrow(Ls), lptr(Ls + 1);
+      std::vector<uint8_t> lkind(Cs), lpres(Cs);
+      std::vector<int64_t> lreq(Cs * R);
+      if (spx_flatten_nrt_long_pods(pods, rc, &slots, n_long, n_lc, &n_long, &n_lc, lrow.data(), lptr.data(), lkind.data(), lpres.data(), lreq.data()) != SPX_OK) {
+        rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_long_pods failed");
+        return;
+      }
+      const spx_nrt_long_pods lt{n_long, n_res, lrow.data(), lptr.data(), lkind.data(), lpres.data(), lreq.data()};
+      rc_pods = spx_upload_nrt_long_pods(e, &lt);
+    }
     e->load_nrt_ms[5] = since(t2);  // 5: spx_upload_nrt_pods (item stream, pod classes, rank stream)
   });
   int rc_nodes = SPX_OK;

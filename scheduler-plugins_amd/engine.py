@@ -29,6 +29,27 @@ def mask_of(*plugins: int) -> int:
     return m
 
 
+class NrtPods(dict):
+    """the dense NRT pod columns (spx_nrt_pods_soa, one entry per column) with `.long`: the containers of the batch's long rows — pods with
+    more than SPX_NRT_MAX_CTRS containers, n_ctr == SPX_NRT_CTRS_LONG — as spx_flatten_nrt_long_pods returns them (dict: n_long,
+    pod_row, ctr_ptr, ctr_kind, ctr_present, ctr_req)"""
+    long: Optional[dict] = None
+
+
+def long_rows_slice(lt: Optional[dict], rows, R: int) -> Optional[dict]:
+    """the long-row table of batch rows [rows[0], rows[1]) with pod_row rebased to the slice (rows None: lt itself)"""
+    if lt is None or rows is None:
+        return lt
+    b, e = rows
+    pr = lt["pod_row"]
+    k0, k1 = int(np.searchsorted(pr, b)), int(np.searchsorted(pr, e))
+    ptr = lt["ctr_ptr"]
+    c0, c1 = int(ptr[k0]), int(ptr[k1])
+    return dict(n_long=k1 - k0, pod_row=(pr[k0:k1] - b).astype(np.int32), ctr_ptr=(ptr[k0:k1 + 1] - c0).astype(np.int32),
+                ctr_kind=lt["ctr_kind"][c0:c1].copy(), ctr_present=lt["ctr_present"][c0:c1].copy(),
+                ctr_req=lt["ctr_req"][c0 * max(R, 1):c1 * max(R, 1)].copy())
+
+
 def _rows(cols: Dict[str, np.ndarray], n_total: int, rows) -> Dict[str, np.ndarray]:
     """slice of per-pod SoA columns: every column holds a fixed number of entries per pod, pod-major"""
     if rows is None:
@@ -340,7 +361,39 @@ class Engine:
                   pod_req=np.zeros(P * max(R, 1), np.int64))
         fn = L.spx_flatten_nrt_pods
         self._ck(fn(pods.ref(), rc.ref() if rc else None, slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(pc.values(), fn.argtypes[3:])]))
-        return {"params": params, "slots": slots, "nodes": nc, "pods": pc, "N": N, "P": P, "R": R}
+        pc = NrtPods(pc)
+        pc.long = self.flatten_nrt_long_pods(pods, rc, slots)
+        return {"params": params, "slots": slots, "nodes": nc, "pods": pc, "long": pc.long, "N": N, "P": P, "R": R}
+
+    def flatten_nrt_long_pods(self, pods: Table, rc: Optional[Table], slots: Table) -> dict:
+        """the containers of the pods with more than 8 containers, CSR (spx_flatten_nrt_long_pods): n_long, pod_row, ctr_ptr,
+        ctr_kind, ctr_present, ctr_req [n_ctr * n_res]"""
+        L = self._lib
+        R = int(slots.struct.n_res)
+        n_long, n_ctr = C.c_int64(), C.c_int64()
+        args = (pods.ref(), rc.ref() if rc else None, slots.ref())
+        self._ck_static(L.spx_flatten_nrt_long_pods(*args, 0, 0, C.byref(n_long), C.byref(n_ctr), None, None, None, None, None))
+        nl, nc = n_long.value, n_ctr.value
+        lt = dict(n_long=nl, pod_row=np.zeros(nl, np.int32), ctr_ptr=np.zeros(nl + 1, np.int32), ctr_kind=np.zeros(nc, np.uint8),
+                  ctr_present=np.zeros(nc, np.uint8), ctr_req=np.zeros(nc * max(R, 1), np.int64))
+        if nl:
+            self._ck_static(L.spx_flatten_nrt_long_pods(*args, nl, nc, C.byref(n_long), C.byref(n_ctr),
+                                                        *[lt[k].ctypes.data_as(t) for k, t in zip(("pod_row", "ctr_ptr", "ctr_kind", "ctr_present", "ctr_req"),
+                                                                                                  L.spx_flatten_nrt_long_pods.argtypes[7:])]))
+        return lt
+
+    def upload_nrt_long_pods(self, lt: Optional[dict], n_res: int) -> None:
+        """the long rows' containers (spx_upload_nrt_long_pods), after the pod table they belong to; None = an empty table"""
+        if lt is None:
+            lt = dict(n_long=0)
+        cols = {k: lt[k] for k in ("pod_row", "ctr_ptr", "ctr_kind", "ctr_present", "ctr_req") if k in lt and len(lt[k])}
+        self._ck(self._lib.spx_upload_nrt_long_pods(self._h, Table(self._hdr, "spx_nrt_long_pods", n_long=int(lt["n_long"]), n_res=n_res, **cols).ref()))
+
+    def nrt_long_rows(self) -> int:
+        """long rows (pods with more than 8 containers) the last NRT sweep of eval evaluated (spx_nrt_long_rows)"""
+        n = C.c_int64()
+        self._ck(self._lib.spx_nrt_long_rows(self._h, C.byref(n)))
+        return n.value
 
     def flatten_nrt_node_rows(self, nodes: Table, nrt: Table, slots: Table, idx) -> Dict[str, np.ndarray]:
         """the SoA rows of the listed nodes only (spx_flatten_nrt_node_rows): what a delta encoder produces for the changed nodes"""
@@ -371,6 +424,8 @@ class Engine:
                   pod_req=np.zeros(P * max(R, 1), np.int64))
         fn = self._lib.spx_flatten_nrt_pods
         self._ck(fn(pods.ref(), rc.ref() if rc else None, slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(pc.values(), fn.argtypes[3:])]))
+        pc = NrtPods(pc)
+        pc.long = self.flatten_nrt_long_pods(pods, rc, slots)
         return pc
 
     def set_nrt_params(self, params: Table) -> None:
@@ -388,6 +443,8 @@ class Engine:
     def upload_nrt_pods(self, pc: Dict[str, np.ndarray], n_res: int) -> None:
         P = len(pc["qos"])
         self._ck(self._lib.spx_upload_nrt_pods(self._h, Table(self._hdr, "spx_nrt_pods_soa", n_pods=P, n_res=n_res, **pc).ref()))
+        if getattr(pc, "long", None) is not None:
+            self.upload_nrt_long_pods(pc.long, n_res)
         self.n_pods = P
         self.nrt_soa["pods"] = pc
 
@@ -450,6 +507,9 @@ class Engine:
         P = f["P"] if rows is None else rows[1] - rows[0]
         if P > 0:
             self._ck(L.spx_upload_nrt_pods(self._h, Table(H, "spx_nrt_pods_soa", n_pods=P, n_res=f["R"], **pc).ref()))
+            lt = f.get("long", getattr(f["pods"], "long", None))
+            if lt is not None:
+                self.upload_nrt_long_pods(long_rows_slice(lt, rows, f["R"]), f["R"])
         self.n_nodes, self.n_pods = f["N"], P
         self.nrt_soa = {"slots": f["slots"], "nodes": f["nodes"], "pods": pc}
 

@@ -328,16 +328,14 @@ extern "C" int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resou
     std::memset(ctr_req + i * CM * R, 0, static_cast<size_t>(CM) * R * sizeof(int64_t));
     std::memset(pod_req + i * R, 0, static_cast<size_t>(R) * sizeof(int64_t));
     const int32_t c0 = pods->ctr_ptr[i], c1 = pods->ctr_ptr[i + 1];
-    if (c1 - c0 > CM) {
-      err = SPX_ERR_ARG;
-      return;
-    }
+    // more containers than the dense columns hold: a long row (its containers go to spx_flatten_nrt_long_pods' table)
+    const bool is_long = c1 - c0 > CM;
     qos[i] = static_cast<uint8_t>(pod_qos(pods, i));
     bool nn = false;
-    n_ctr[i] = static_cast<uint8_t>(c1 - c0);
+    n_ctr[i] = static_cast<uint8_t>(is_long ? SPX_NRT_CTRS_LONG : c1 - c0);
     for (int32_t c = c0; c < c1; ++c) {
       const int64_t slot_base = (i * CM + (c - c0));
-      ctr_kind[slot_base] = pods->ctr_kind[c];
+      if (!is_long) ctr_kind[slot_base] = pods->ctr_kind[c];
       uint8_t present = 0;
       for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) {
         const int s = slot_of(slots, pods->req_res[k]);
@@ -346,10 +344,10 @@ extern "C" int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resou
           return;
         }
         present |= static_cast<uint8_t>(1u << s);
-        ctr_req[slot_base * R + s] = pods->req_qty[k];
+        if (!is_long) ctr_req[slot_base * R + s] = pods->req_qty[k];
         if (!rc_has(rc, pods->req_res[k], SPX_RC_NATIVE)) nn = true;
       }
-      ctr_present[slot_base] = present;
+      if (!is_long) ctr_present[slot_base] = present;
     }
     non_native[i] = nn ? 1 : 0;
     // GetPodEffectiveRequest (pkg/util/resource.go:51-85) with map key presence
@@ -398,4 +396,44 @@ extern "C" int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resou
   }
   }, 4096);
   return err.load();
+}
+
+extern "C" int spx_flatten_nrt_long_pods(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, int64_t long_cap,
+                                         int64_t ctr_cap, int64_t* n_long_out, int64_t* n_ctr_out, int32_t* pod_row, int32_t* ctr_ptr,
+                                         uint8_t* ctr_kind, uint8_t* ctr_present, int64_t* ctr_req) {
+  (void)rc;  // (the dense table carries the pod-level columns; the containers' own need no resource classes)
+  if (!pods || !slots || !n_long_out || !n_ctr_out) return SPX_ERR_ARG;
+  const bool count_only = !pod_row && !ctr_ptr && !ctr_kind && !ctr_present && !ctr_req;
+  if (!count_only && (!pod_row || !ctr_ptr || !ctr_kind || !ctr_present || !ctr_req || long_cap < 0 || ctr_cap < 0)) return SPX_ERR_ARG;
+  const int R = slots->n_res;
+  int64_t n_long = 0, n_ctr = 0;
+  for (int64_t i = 0; i < pods->n_pods; ++i) {
+    const int64_t n = pods->ctr_ptr[i + 1] - pods->ctr_ptr[i];
+    if (n > CM) ++n_long, n_ctr += n;
+  }
+  *n_long_out = n_long;
+  *n_ctr_out = n_ctr;
+  if (count_only) return SPX_OK;
+  if (n_long > long_cap || n_ctr > ctr_cap || n_ctr > INT32_MAX) return SPX_ERR_ARG;
+  int64_t k = 0, at = 0;
+  ctr_ptr[0] = 0;
+  for (int64_t i = 0; i < pods->n_pods; ++i) {
+    const int32_t c0 = pods->ctr_ptr[i], c1 = pods->ctr_ptr[i + 1];
+    if (c1 - c0 <= CM) continue;
+    pod_row[k] = static_cast<int32_t>(i);
+    for (int32_t c = c0; c < c1; ++c, ++at) {
+      ctr_kind[at] = pods->ctr_kind[c];
+      std::memset(ctr_req + at * R, 0, static_cast<size_t>(R) * sizeof(int64_t));
+      uint8_t present = 0;
+      for (int32_t q = pods->req_ptr[c]; q < pods->req_ptr[c + 1]; ++q) {
+        const int s = slot_of(slots, pods->req_res[q]);
+        if (s < 0) return SPX_ERR_ARG;
+        present |= static_cast<uint8_t>(1u << s);
+        ctr_req[at * R + s] = pods->req_qty[q];
+      }
+      ctr_present[at] = present;
+    }
+    ctr_ptr[++k] = static_cast<int32_t>(at);
+  }
+  return SPX_OK;
 }

@@ -135,7 +135,12 @@ void nrt_build_items(const spx_nrt_pods_soa* t, const uint8_t* slot_flags, int c
       uint32_t* w = &items[i * 10 * IW];
       std::memset(w, 0, 10 * IW * sizeof(uint32_t));  // the record ends with the last container: zeros after it
       const bool non_g = t->qos[i] != SPX_QOS_GUARANTEED;
-      const uint32_t n_ctr = t->n_ctr[i];
+      // a long row (more containers than the record holds): kernels_nrt_long.hip overwrites its cells after the sweep, so its record is
+      // that of an empty pod — QoS and non-native flag only.  Neither its containers nor its pod-level request (the sum over all of
+      // them) take part in the record, the batch's preconditions or its quantities: a single long pod would otherwise widen NrtQty
+      // past the packed Score's bounds and send the whole batch off the fused sweep
+      const bool is_long = t->n_ctr[i] == SPX_NRT_CTRS_LONG;
+      const uint32_t n_ctr = is_long ? 0u : t->n_ctr[i];
       uint32_t last_app = 0xffu;
       bool seen_app = false;
       for (size_t c = 0; c < Cm && c < n_ctr; ++c) {
@@ -148,10 +153,22 @@ void nrt_build_items(const spx_nrt_pods_soa* t, const uint8_t* slot_flags, int c
         }
         fill(w + (2 + c) * IW, t->ctr_present[i * Cm + c], t->ctr_req + (i * Cm + c) * R, non_g, kind, bad, big, qty);
       }
-      fill(w + IW, t->pod_present[i], t->pod_req + i * R, non_g, 0, bad, big, qty);
+      if (is_long) {
+        const int64_t none[SPX_NRT_MAX_RES] = {0};
+        bool bad_l = false;
+        uint32_t big_l = 0;
+        NrtQty qty_l;
+        fill(w + IW, 0u, none, non_g, 0, bad_l, big_l, qty_l);
+      } else {
+        fill(w + IW, t->pod_present[i], t->pod_req + i * R, non_g, 0, bad, big, qty);
+      }
       w[0] = t->qos[i] | (static_cast<uint32_t>(t->non_native[i] != 0) << 8) | (n_ctr << 16) | (last_app << 24);
       w[1] = n_ctr ? (65536u + n_ctr - 1u) / n_ctr : 0u;
-      if (hash_out) hash_out[i] = canon.hash(w);
+      // A long row's record is that of an empty pod; salted by its row, its hash meets no other row's, so it forms a class of its own
+      // (never a copy, never a representative of others).  A 64-bit collision would also need equal canonical records (NrtCanon):
+      // n_ctr is part of them except for BestEffort pods without non-native requests, so both rows would be such pods — they pass
+      // Filter and score 100 whatever their containers (filter.go:183-186, score.go:69-72), and the copied cells are right.
+      if (hash_out) hash_out[i] = is_long ? canon.hash(w) ^ (0x9e3779b97f4a7c15ull * (static_cast<uint64_t>(i) + 1)) : canon.hash(w);
     }
     if (bad) ok = false;
     if (big) big_pods.fetch_or(big, std::memory_order_relaxed);

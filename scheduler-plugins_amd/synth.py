@@ -125,6 +125,48 @@ def take_pods(hdr: Header, pods: Table, idx) -> Table:
     )
 
 
+def lengthen_pods(hdr: Header, pods: Table, frac: float = 0.0, seed: int = SEED, lo: int = 9, hi: int = 40, rows=None) -> Table:
+    """The pod table with a share `frac` of its pods (or the pods `rows`) made "long" for NodeResourceTopologyMatch: lo..hi containers
+    each (more than the dense NRT table's 8), copies of the pod's own containers taken in turn with every quantity divided by a third of
+    the count (so that some still fit a zone); up to three init containers lead, a third of them sidecars.  Requests equal limits
+    wherever they did, so each pod keeps its QoS class.  Other pods and columns are unchanged."""
+    rng = np.random.default_rng(seed + 303)
+    P = int(pods.struct.n_pods)
+    if rows is None:
+        rows = np.flatnonzero(rng.random(P) < frac)
+    chosen = np.zeros(P, bool)
+    chosen[np.asarray(rows, dtype=np.int64)] = True
+    ptr, kind = pods.array("ctr_ptr"), pods.array("ctr_kind")
+    src, kinds, div = [], [], []
+    counts = np.zeros(P, np.int64)
+    for i in range(P):
+        own = np.arange(ptr[i], ptr[i + 1])
+        if not chosen[i] or len(own) == 0:
+            src.extend(own), kinds.extend(kind[own]), div.extend([1] * len(own))
+            counts[i] = len(own)
+            continue
+        n = int(rng.integers(lo, hi + 1))
+        n_init = int(rng.integers(0, 4))
+        k = np.zeros(n, np.uint8)
+        k[:n_init] = np.where(rng.random(n_init) < 1 / 3, 2, 1)
+        src.extend(own[np.arange(n) % len(own)]), kinds.extend(k), div.extend([max(1, n // 3)] * n)
+        counts[i] = n
+    src, div = np.asarray(src, np.int64), np.asarray(div, np.int64)
+    ctr_ptr = np.zeros(P + 1, np.int32)
+    np.cumsum(counts, out=ctr_ptr[1:])
+    req_ptr, rpos = _gather_csr(pods.array("req_ptr"), src)
+    lim_ptr, lpos = _gather_csr(pods.array("lim_ptr"), src)
+    rdiv, ldiv = np.repeat(div, np.diff(req_ptr)), np.repeat(div, np.diff(lim_ptr))
+    return Table(
+        hdr, "spx_pod_objects", n_pods=P, ctr_ptr=ctr_ptr, ctr_kind=np.asarray(kinds, np.uint8),
+        req_ptr=req_ptr, req_res=pods.array("req_res")[rpos], req_qty=pods.array("req_qty")[rpos] // rdiv,
+        lim_ptr=lim_ptr, lim_res=pods.array("lim_res")[lpos], lim_qty=pods.array("lim_qty")[lpos] // ldiv,
+        ovh_ptr=pods.array("ovh_ptr"), ovh_res=pods.array("ovh_res"), ovh_qty=pods.array("ovh_qty"),
+        priority=pods.array("priority"), queue_ts=pods.array("queue_ts"), appgroup=pods.array("appgroup"), selector=pods.array("selector"),
+        ns=pods.array("ns"),
+    )
+
+
 def synth_nodes(hdr: Header, n_nodes: int, seed: int = SEED, device_res: int = -1, n_regions: int = 8,
                 zones_per_region: int = 8) -> Table:
     rng = np.random.default_rng(seed + 2)
@@ -340,9 +382,11 @@ def synth_nrt(hdr: Header, nodes: Table, seed: int = SEED, n_zones: int = 8, var
     )
 
 
-def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary: bool = True, wide: bool = False) -> Dict[str, Table]:
+def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary: bool = True, wide: bool = False,
+                 long_frac: float = 0.0, long_ctrs=(9, 40)) -> Dict[str, Table]:
     """Object tables for BASELINE.json config #3 (NRT Filter+Score, 8 NUMA zones).  `wide`: six resource slots (cpu, memory,
-    hugepages-2Mi, hugepages-1Gi, two extended resources) instead of four — the kernels' 8-slot instantiations."""
+    hugepages-2Mi, hugepages-1Gi, two extended resources) instead of four — the kernels' 8-slot instantiations.  `long_frac`: that
+    share of the pods gets long_ctrs[0]..long_ctrs[1] containers (lengthen_pods); 0 leaves the snapshot as it always was."""
     nodes = synth_nodes(hdr, n_nodes, seed, device_res=RES_DEVICE)
     # node-level allocatable must list hugepages too (util.ResourceList key check, filter.go:110-116)
     rng = np.random.default_rng(seed + 6)
@@ -358,14 +402,17 @@ def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary:
         res = np.tile(np.array([RES_HUGEPAGES_2MI, RES_DEVICE, RES_HUGEPAGES_1GI, RES_DEVICE2], dtype=np.int32), (N, 1))
         qty = np.concatenate([qty, np.stack([np.full(N, 64 * GiB, dtype=np.int64), rng_w.integers(1, 9, N)], axis=1)], axis=1)
     ptr, sel = _csr_from_mask(mask)
+    pods = synth_pods(hdr, n_pods, seed, device_res=RES_DEVICE, hugepage_res=RES_HUGEPAGES_2MI,
+                      device2_res=RES_DEVICE2 if wide else -1, hugepage2_res=RES_HUGEPAGES_1GI if wide else -1)
+    if long_frac > 0:
+        pods = lengthen_pods(hdr, pods, long_frac, seed, *long_ctrs)
     nodes = Table(hdr, "spx_node_objects", n_nodes=N, alloc_cpu_milli=nodes.array("alloc_cpu_milli"),
                   alloc_mem=nodes.array("alloc_mem"), alloc_eph=nodes.array("alloc_eph"), alloc_pods=nodes.array("alloc_pods"),
                   scalar_ptr=ptr, scalar_res=res.reshape(-1)[sel], scalar_qty=qty.reshape(-1)[sel],
                   cap_cpu_milli=nodes.array("cap_cpu_milli"), region=nodes.array("region"), zone=nodes.array("zone"))
     return {
         "nodes": nodes,
-        "pods": synth_pods(hdr, n_pods, seed, device_res=RES_DEVICE, hugepage_res=RES_HUGEPAGES_2MI,
-                           device2_res=RES_DEVICE2 if wide else -1, hugepage2_res=RES_HUGEPAGES_1GI if wide else -1),
+        "pods": pods,
         "nrt": synth_nrt(hdr, nodes, seed, vary=vary, wide=wide),
         "rc": nrt_resource_classes(hdr, wide),
     }
