@@ -395,11 +395,18 @@ typedef struct spx_peaks_pods_soa {
 
 /* NodeResourceTopologyMatch.  Resources are renumbered into dense "slots" 0..n_res-1 (the union of
  * what pods request and zones report; slot_res gives the canonical id).  Limits of this build:
- * n_res <= 8 and NUMA zones per node <= 8 (flatten fails beyond them).  Containers per pod are unbounded:
- * a pod with up to SPX_NRT_MAX_CTRS containers keeps them in the dense pod table; a pod with more is a
- * "long row" — n_ctr = SPX_NRT_CTRS_LONG, per-container columns zero, pod-level columns (qos, non_native,
- * pod_present, pod_req) filled as for any row — whose containers travel in spx_nrt_long_pods. */
+ * NUMA zones per node <= 8 (flatten fails beyond them).  The dense tables below (spx_nrt_nodes_soa,
+ * spx_nrt_pods_soa) hold n_res <= SPX_NRT_MAX_RES = 8 slots, and spx_flatten_nrt_slots fails beyond 8.
+ * A snapshot with up to SPX_NRT_MAX_RES_WIDE = 32 slots travels in the wide tables (spx_nrt_nodes_wide,
+ * spx_nrt_pods_wide; spx_flatten_nrt_slots_wide), which spx_load_nrt takes by itself above 8 slots; a wide
+ * snapshot's pods may hold up to SPX_NRT_WIDE_MAX_CTRS containers each.  In the dense tables containers
+ * per pod are unbounded: a pod with up to SPX_NRT_MAX_CTRS containers keeps them in the dense pod table; a
+ * pod with more is a "long row" — n_ctr = SPX_NRT_CTRS_LONG, per-container columns zero, pod-level columns
+ * (qos, non_native, pod_present, pod_req) filled as for any row — whose containers travel in
+ * spx_nrt_long_pods. */
 #define SPX_NRT_MAX_RES 8
+#define SPX_NRT_MAX_RES_WIDE 32
+#define SPX_NRT_WIDE_MAX_CTRS 64
 #define SPX_NRT_MAX_ZONES 8
 #define SPX_NRT_MAX_CTRS 8
 #define SPX_NRT_CTRS_LONG 255
@@ -467,6 +474,41 @@ typedef struct spx_nrt_long_pods {
   const uint8_t* ctr_present;
   const int64_t* ctr_req;
 } spx_nrt_long_pods;
+
+/* The wide NRT node table (up to SPX_NRT_MAX_RES_WIDE slots): the columns of spx_nrt_nodes_soa, host row-major, with uint32 presence
+ * masks (bit s = slot s).  zone_id / zone_present / min_avg_dist [N*8], zone_avail [N*8*n_res], zone_cost [N*64], node_present [N]. */
+typedef struct spx_nrt_nodes_wide {
+  int64_t n_nodes;
+  int32_t n_res;
+  const uint8_t* flags;
+  const int32_t* max_numa;
+  const uint8_t* n_zones;
+  const uint8_t* zone_id;
+  const uint32_t* zone_present;
+  const int64_t* zone_avail;
+  const int32_t* zone_cost;
+  const float* min_avg_dist;
+  const uint32_t* node_present;
+} spx_nrt_nodes_wide;
+
+/* The wide NRT pod table, CSR throughout.  Pod p's effective request (GetPodEffectiveRequest with key presence) is the list
+ * req_ptr[p] .. req_ptr[p+1]-1 of (req_slot, req_qty); its containers are ctr_ptr[p] .. ctr_ptr[p+1]-1 (document order: init and
+ * sidecar containers first, then app containers), container c with kind ctr_kind[c] and request list ent_ptr[c] .. ent_ptr[c+1]-1
+ * of (ent_slot, ent_qty).  Every list is in ascending slot order (= ascending resource id) and keeps zero quantities. */
+typedef struct spx_nrt_pods_wide {
+  int64_t n_pods;
+  int32_t n_res;
+  const uint8_t* qos;
+  const uint8_t* non_native;
+  const int32_t* req_ptr;
+  const uint8_t* req_slot;
+  const int64_t* req_qty;
+  const int32_t* ctr_ptr;
+  const uint8_t* ctr_kind;
+  const int32_t* ent_ptr;
+  const uint8_t* ent_slot;
+  const int64_t* ent_qty;
+} spx_nrt_pods_wide;
 
 /* NetworkOverhead.  A pod's PreFilter state depends only on its (AppGroup, workload selector) "workload
  * key"; the matched (placed pod, dependency) pairs are flattened once per key. */
@@ -637,6 +679,14 @@ int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t);
 int spx_upload_nrt_long_pods(spx_engine* e, const spx_nrt_long_pods* t);
 /* *n_out = long rows the last NodeResourceTopologyMatch sweep of spx_eval evaluated (those inside its row range; 0 = none / no sweep yet) */
 int spx_nrt_long_rows(const spx_engine* e, int64_t* n_out);
+/* The wide NRT tables (up to SPX_NRT_MAX_RES_WIDE slots), evaluated by kernels_nrt_wide.hip; order: slots, nodes, pods.  The wide
+ * slot table replaces the dense NRT tables (and a later spx_upload_nrt_slots the wide ones): an engine holds one form at a time.
+ * On a wide engine spx_commit_sequential with NodeResourceTopologyMatch and spx_update_nrt_nodes fail with SPX_ERR_STATE. */
+int spx_upload_nrt_slots_wide(spx_engine* e, const spx_nrt_slots* t);
+int spx_upload_nrt_nodes_wide(spx_engine* e, const spx_nrt_nodes_wide* t);
+int spx_upload_nrt_pods_wide(spx_engine* e, const spx_nrt_pods_wide* t);
+/* 1 = the NRT tables in place are the wide form, 0 = dense (or none) */
+int spx_nrt_wide(const spx_engine* e);
 int spx_upload_net_nodes(spx_engine* e, const spx_net_nodes_soa* t);
 int spx_upload_net_topo(spx_engine* e, const spx_net_topo_soa* t);
 int spx_upload_net_pods(spx_engine* e, const spx_net_pods_soa* t);
@@ -792,6 +842,8 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
  *                              MostAllocated strategies with unit weights under the preconditions of SPX_OPT_NRT_RANK_FILTER and
  *                              SPX_OPT_NRT_PACKED_SCORE, and for BalancedAllocation with up to four resource slots (its undecided cells are
  *                              recomputed in float64 by a second launch); 0 = the Filter launch and the Score launch.  Same tables either way
+ *   SPX_OPT_NRT_WIDE           1 = spx_load_nrt / spx_load_profile take the wide NRT tables (kernels_nrt_wide.hip) for a snapshot of 8 or
+ *                              fewer resource slots too; 0 (default) = only above 8 slots.  Read at the load, not at the launch
  */
 #define SPX_OPT_ROW_ALIGN 0
 #define SPX_OPT_REFERENCE_KERNELS 1
@@ -812,7 +864,8 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
 #define SPX_OPT_NRT_RANK_NARROW 16
 #define SPX_OPT_PEAKS_ESTIMATE 17
 #define SPX_OPT_NRT_FUSED 18
-#define SPX_NUM_OPTIONS 19
+#define SPX_OPT_NRT_WIDE 19
+#define SPX_NUM_OPTIONS 20
 int spx_set_option(spx_engine* e, int option, int64_t value);
 int spx_get_option(const spx_engine* e, int option, int64_t* value);
 
@@ -864,7 +917,7 @@ int spx_load_profile(spx_engine* e, const spx_profile_objects* o);
 int spx_commit_path(const spx_engine* e);
 /* Which Filter launch the last NodeResourceTopologyMatch sweep ran: 1 = float64 compares (k_nrt_fast / the reference-arithmetic
  * kernel), 2 = rank space (SPX_OPT_NRT_RANK_FILTER: whole-batch sweeps), 3 = rank space inside the fused Filter + Score launch
- * (SPX_OPT_NRT_FUSED); 0 = none yet */
+ * (SPX_OPT_NRT_FUSED), 4 = the wide tables' sweep (kernels_nrt_wide.hip); 0 = none yet */
 int spx_nrt_filter_path(const spx_engine* e);
 /* SPX_OPT_NRT_PACKED_SCORE with the uploaded tables and parameters: 0 = the LeastAllocated Score launch keeps float64 (other strategy,
  * large weights, a slot that qualifies neither way, option off); else bit 24 set, bits 0..15 = the weighted slots (positions of the
@@ -960,6 +1013,16 @@ int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resource_classes
  * pod_row / ctr_ptr must hold long_cap / long_cap + 1 entries and ctr_kind / ctr_present / ctr_req ctr_cap / ctr_cap / ctr_cap x n_res,
  * and a table larger than that is SPX_ERR_ARG (the counts are written first, so the caller can resize and call again). */
 int spx_flatten_nrt_long_pods(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, int64_t long_cap, int64_t ctr_cap, int64_t* n_long_out, int64_t* n_ctr_out, int32_t* pod_row, int32_t* ctr_ptr, uint8_t* ctr_kind, uint8_t* ctr_present, int64_t* ctr_req);
+/* The wide forms (up to SPX_NRT_MAX_RES_WIDE slots).  spx_flatten_nrt_slots_wide: the numbering of spx_flatten_nrt_slots (ascending
+ * resource id) for up to cap <= SPX_NRT_MAX_RES_WIDE slots; *n_res_out receives the count even when it exceeds cap (SPX_ERR_ARG). */
+int spx_flatten_nrt_slots_wide(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_nrt_params* p, int32_t cap, int32_t* n_res_out, int32_t* slot_res, uint8_t* slot_flags, int64_t* slot_weight);
+/* node arrays sized as spx_flatten_nrt_nodes', zone_present [N*8] and node_present [N] as uint32 masks */
+int spx_flatten_nrt_nodes_wide(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id, uint32_t* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist, uint32_t* node_present);
+/* the pod table of spx_nrt_pods_wide.  *n_req_out / *n_ent_out receive the entry counts of the pod-level and container lists; with
+ * every output array NULL the call only counts.  Otherwise qos / non_native [P], req_ptr / ctr_ptr [P+1], ctr_kind [C], ent_ptr [C+1]
+ * (C = pods->ctr_ptr[P] - pods->ctr_ptr[0]: the outputs start at 0), req_slot / req_qty [req_cap], ent_slot / ent_qty [ent_cap]; larger
+ * lists than that are SPX_ERR_ARG. */
+int spx_flatten_nrt_pods_wide(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, int64_t req_cap, int64_t ent_cap, int64_t* n_req_out, int64_t* n_ent_out, uint8_t* qos, uint8_t* non_native, int32_t* req_ptr, uint8_t* req_slot, int64_t* req_qty, int32_t* ctr_ptr, uint8_t* ctr_kind, int32_t* ent_ptr, uint8_t* ent_slot, int64_t* ent_qty);
 
 /* NetworkOverhead / TopologicalSort.  region_cost[n_regions*n_regions] and zone_cost[n_zones*n_zones]: -1 = no entry.
  * spx_flatten_net_keys sizes: *n_keys_out and *n_pairs_out first (pass NULL arrays), then fill

@@ -180,6 +180,8 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
   const bool T = plugin_mask & (1u << SPX_PLUGIN_TLP), N = plugin_mask & (1u << SPX_PLUGIN_NRT);
   const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD), Q = plugin_mask & (1u << SPX_PLUGIN_CAPACITY);
   if ((T || (plugin_mask & (1u << SPX_PLUGIN_LVRB))) && !(e->tri_nodes && e->tri_pods)) return fail(e, SPX_ERR_STATE, "trimaran node/pod tables not uploaded");
+  if (N && e->nrt_wide)
+    return fail(e, SPX_ERR_STATE, "NRT: spx_commit_sequential does not take a wide snapshot (more than 8 resource slots, or SPX_OPT_NRT_WIDE)");
   if (N && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
   if (N && !e->nrt_long_ok)
     return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");

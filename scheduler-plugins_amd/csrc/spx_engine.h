@@ -60,7 +60,7 @@ struct spx_engine {
   int64_t row_stride = 0;
 
   // spx_set_option state (per engine; nothing is read from the environment)
-  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1};
+  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0};
 
   // params
   int32_t alloc_mode = SPX_MODE_LEAST;
@@ -139,6 +139,14 @@ struct spx_engine {
   bool nrt_long_ok = true;               // the long table describes those rows (trivially true without any)
   int64_t nrt_long_last = 0;             // spx_nrt_long_rows
   DevBuf d_nrtl_row, d_nrtl_ptr, d_nrtl_kind, d_nrtl_pres, d_nrtl_req, d_nrtl_map;
+  // the wide NRT tables (more than SPX_NRT_MAX_RES slots, or SPX_OPT_NRT_WIDE; kernels_nrt_wide.hip).  nrt_wide: they, not the dense
+  // tables above, are the engine's NRT state (spx_upload_nrt_slots_wide sets it, spx_upload_nrt_slots clears it)
+  bool nrt_wide = false;
+  bool nrtw_slots = false, nrtw_nodes = false, nrtw_pods = false;
+  int32_t nrtw_n_res = 0;
+  DevBuf d_nrtw_sflags, d_nrtw_sweight;
+  DevBuf d_nrtw_flags, d_nrtw_max_numa, d_nrtw_nz, d_nrtw_zid, d_nrtw_zp, d_nrtw_avail, d_nrtw_cost, d_nrtw_minavg, d_nrtw_np;
+  DevBuf d_nrtw_qos, d_nrtw_nn, d_nrtw_rptr, d_nrtw_rslot, d_nrtw_rqty, d_nrtw_cptr, d_nrtw_ckind, d_nrtw_eptr, d_nrtw_eslot, d_nrtw_eqty;
   DevBuf d_nrt_uniq, d_nrt_dups;  // int32 [n_uniq] representative rows, ascending; int32 [n_dups][2] (row, its representative)
   int64_t nrt_n_uniq = 0, nrt_n_dups = 0, nrt_n_tasks = 0;  // (d_nrt_dups: the pairs sorted by representative, then the copy tasks — expand_tasks)
   DevBuf d_nrt_rk, d_nrt_rk_off;  // rank-space Filter: the chunk stream of the listed rows (nrt_build_rank_stream) and its chunk offsets
@@ -615,6 +623,47 @@ int launch_nrt_long_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begi
   spx::launch_nrt_long(l, e->stream);
   SPX_HIP(e, hipGetLastError());
   e->nrt_long_last = k1 - k0;
+  return SPX_OK;
+}
+
+// NodeResourceTopologyMatch over the wide tables, rows [row_begin, row_end) into the status / score tables (or, with out_raw, the one
+// row's raw scores).  Replaces the whole dense machinery: no pod classes, rank stream, fused walk, redo lists or long rows.
+int launch_nrt_wide_rows(spx_engine* e, int64_t row_begin, int64_t row_end, int64_t* out_raw) {
+  if (!(e->nrtw_slots && e->nrtw_nodes && e->nrtw_pods)) return fail(e, SPX_ERR_STATE, "NRT wide slot/node/pod tables not uploaded");
+  spx::NrtWideArgs w{};
+  w.n_nodes = e->n_nodes;
+  w.n_pods = e->n_pods;
+  w.row_stride = e->row_stride;
+  w.n_res = e->nrtw_n_res;
+  w.strategy = e->nrt_params.strategy;
+  w.slot_flags = static_cast<const uint8_t*>(e->d_nrtw_sflags.p);
+  w.slot_weight = static_cast<const int64_t*>(e->d_nrtw_sweight.p);
+  w.flags = static_cast<const uint8_t*>(e->d_nrtw_flags.p);
+  w.max_numa = static_cast<const int32_t*>(e->d_nrtw_max_numa.p);
+  w.n_zones = static_cast<const uint8_t*>(e->d_nrtw_nz.p);
+  w.zone_id = static_cast<const uint8_t*>(e->d_nrtw_zid.p);
+  w.zone_present = static_cast<const uint32_t*>(e->d_nrtw_zp.p);
+  w.zone_avail = static_cast<const int64_t*>(e->d_nrtw_avail.p);
+  w.zone_cost = static_cast<const int32_t*>(e->d_nrtw_cost.p);
+  w.min_avg = static_cast<const float*>(e->d_nrtw_minavg.p);
+  w.node_present = static_cast<const uint32_t*>(e->d_nrtw_np.p);
+  w.qos = static_cast<const uint8_t*>(e->d_nrtw_qos.p);
+  w.non_native = static_cast<const uint8_t*>(e->d_nrtw_nn.p);
+  w.req_ptr = static_cast<const int32_t*>(e->d_nrtw_rptr.p);
+  w.req_slot = static_cast<const uint8_t*>(e->d_nrtw_rslot.p);
+  w.req_qty = static_cast<const int64_t*>(e->d_nrtw_rqty.p);
+  w.ctr_ptr = static_cast<const int32_t*>(e->d_nrtw_cptr.p);
+  w.ctr_kind = static_cast<const uint8_t*>(e->d_nrtw_ckind.p);
+  w.ent_ptr = static_cast<const int32_t*>(e->d_nrtw_eptr.p);
+  w.ent_slot = static_cast<const uint8_t*>(e->d_nrtw_eslot.p);
+  w.ent_qty = static_cast<const int64_t*>(e->d_nrtw_eqty.p);
+  w.row_begin = row_begin;
+  w.row_end = row_end;
+  w.out_status = static_cast<uint8_t*>(e->status[SPX_PLUGIN_NRT].p);
+  w.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_NRT].p);
+  w.out_raw = out_raw;
+  spx::launch_nrt_wide(w, e->stream);
+  SPX_HIP(e, hipGetLastError());
   return SPX_OK;
 }
 

@@ -75,7 +75,10 @@ int spx_destroy(spx_engine* e) {
                     &e->d_lroc_preq_c, &e->d_lroc_preq_m, &e->d_lroc_plim_c, &e->d_lroc_plim_m, &e->d_lroc_tab, &e->d_lroc_podf,
                     &e->d_pk_cap, &e->d_pk_util, &e->d_pk_valid, &e->d_pk_k1, &e->d_pk_k2, &e->d_pk_pod, &e->d_pk_min, &e->d_pk_max, &e->d_pk_rowc, &e->d_pk_tab, &e->d_pk_seg, &e->d_pk_segn,
                     &e->d_nrt_uniq, &e->d_nrt_dups, &e->d_pk_uniq, &e->d_pk_dups, &e->d_delta, &e->d_nrt_lnrec, &e->d_net_pair_node2, &e->d_net_pair_max2, &e->d_nrt_rk, &e->d_nrt_rk_off, &e->d_nrt_rk_first, &e->d_nrt_fz, &e->d_nrt_wsort, &e->d_nrt_wrank,
-                    &e->d_nrtl_row, &e->d_nrtl_ptr, &e->d_nrtl_kind, &e->d_nrtl_pres, &e->d_nrtl_req, &e->d_nrtl_map};
+                    &e->d_nrtl_row, &e->d_nrtl_ptr, &e->d_nrtl_kind, &e->d_nrtl_pres, &e->d_nrtl_req, &e->d_nrtl_map,
+                    &e->d_nrtw_sflags, &e->d_nrtw_sweight, &e->d_nrtw_flags, &e->d_nrtw_max_numa, &e->d_nrtw_nz, &e->d_nrtw_zid, &e->d_nrtw_zp,
+                    &e->d_nrtw_avail, &e->d_nrtw_cost, &e->d_nrtw_minavg, &e->d_nrtw_np, &e->d_nrtw_qos, &e->d_nrtw_nn, &e->d_nrtw_rptr,
+                    &e->d_nrtw_rslot, &e->d_nrtw_rqty, &e->d_nrtw_cptr, &e->d_nrtw_ckind, &e->d_nrtw_eptr, &e->d_nrtw_eslot, &e->d_nrtw_eqty};
   for (DevBuf* b : bufs)
     if (b->p && !b->external) (void)hipFree(b->p);
   for (int i = 0; i < SPX_NUM_PLUGINS; ++i) {
@@ -131,6 +134,7 @@ int spx_set_option(spx_engine* e, int option, int64_t value) {
     case SPX_OPT_NET_ALLOC_FUSED:
     case SPX_OPT_NRT_RANK_NARROW:
     case SPX_OPT_NRT_FUSED:
+    case SPX_OPT_NRT_WIDE:
       if (value != 0 && value != 1) return fail(e, SPX_ERR_ARG, "option takes 0 or 1");
       break;
     case SPX_OPT_NRT_LN_LIST_PERMILLE:
@@ -232,8 +236,9 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   if (row_begin < 0 || row_end > e->n_pods || row_begin > row_end) return fail(e, SPX_ERR_ARG, "row range out of bounds");
   int rc;
   const bool N = plugin_mask & (1u << SPX_PLUGIN_NRT);
-  if (N && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
-  if (N && !e->nrt_long_ok)
+  if (N && e->nrt_wide && !(e->nrtw_slots && e->nrtw_nodes && e->nrtw_pods)) return fail(e, SPX_ERR_STATE, "NRT wide slot/node/pod tables not uploaded");
+  if (N && !e->nrt_wide && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
+  if (N && !e->nrt_wide && !e->nrt_long_ok)
     return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
   if (A && (rc = prepare_alloc(e))) return rc;
   const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD);
@@ -324,7 +329,14 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     spx::launch_quota(qa, e->stream);
     SPX_HIP(e, hipGetLastError());
   }
-  if (N) {
+  if (N && e->nrt_wide) {  // the wide tables: one sparse launch over the row range (kernels_nrt_wide.hip)
+    if (e->score_stride[SPX_PLUGIN_NRT] != e->row_stride)
+      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
+    if (e->row_indirect) return fail(e, SPX_ERR_STATE, "NRT: the sequential commit loop does not take a wide snapshot (more than 8 resource slots)");
+    if ((rc = launch_nrt_wide_rows(e, row_begin, row_end, nullptr))) return rc;
+    e->last_nrt_filter = 4;
+    e->nrt_long_last = 0;
+  } else if (N) {
     if (e->score_stride[SPX_PLUGIN_NRT] != e->row_stride)
       return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
     if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && (rc = build_ln_tab(e))) return rc;
@@ -574,6 +586,8 @@ int spx_sync(spx_engine* e) {
 
 int spx_nrt_filter_path(const spx_engine* e) { return e ? e->last_nrt_filter : 0; }
 
+int spx_nrt_wide(const spx_engine* e) { return e && e->nrt_wide ? 1 : 0; }
+
 int spx_nrt_long_rows(const spx_engine* e, int64_t* n_out) {
   if (!e || !n_out) return SPX_ERR_ARG;
   *n_out = e->nrt_long_last;
@@ -685,6 +699,14 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
   if (plugin == SPX_PLUGIN_ALLOCATABLE) {
     if ((rc = prepare_alloc(e))) return rc;
     SPX_HIP(e, hipMemcpyAsync(out, e->d_alloc_raw.p, bytes, hipMemcpyDeviceToHost, e->stream));
+    SPX_HIP(e, hipStreamSynchronize(e->stream));
+    return SPX_OK;
+  }
+  if (plugin == SPX_PLUGIN_NRT && e->nrt_wide) {
+    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
+    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
+    if ((rc = launch_nrt_wide_rows(e, pod_row, pod_row + 1, static_cast<int64_t*>(e->d_raw_row.p)))) return rc;
+    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
     SPX_HIP(e, hipStreamSynchronize(e->stream));
     return SPX_OK;
   }

@@ -441,6 +441,42 @@ struct NrtLongArgs {
   int64_t* out_raw;              // when set: raw int64 scores of the one long row long_begin, no table writes
 };
 void launch_nrt_long(const NrtLongArgs& a, hipStream_t s);
+
+// NodeResourceTopologyMatch over the wide tables (up to SPX_NRT_MAX_RES_WIDE slots; kernels_nrt_wide.hip): node-major columns as
+// NrtArgs' with uint32 presence masks, the pod table in CSR (spx_nrt_pods_wide)
+struct NrtWideArgs {
+  int64_t n_nodes;
+  int64_t n_pods;
+  int64_t row_stride;
+  int32_t n_res;
+  int32_t strategy;
+  const uint8_t* slot_flags;     // [n_res]
+  const int64_t* slot_weight;    // [n_res]
+  const uint8_t* flags;          // [N]
+  const int32_t* max_numa;       // [N]
+  const uint8_t* n_zones;        // [N]
+  const uint8_t* zone_id;        // [Z][N]
+  const uint32_t* zone_present;  // [Z][N]
+  const int64_t* zone_avail;     // [Z][n_res][N]
+  const int32_t* zone_cost;      // [Z][Z][N]
+  const float* min_avg;          // [Z][N]
+  const uint32_t* node_present;  // [N]
+  const uint8_t* qos;            // [P]
+  const uint8_t* non_native;     // [P]
+  const int32_t* req_ptr;        // [P + 1]
+  const uint8_t* req_slot;
+  const int64_t* req_qty;
+  const int32_t* ctr_ptr;        // [P + 1]
+  const uint8_t* ctr_kind;       // [C]
+  const int32_t* ent_ptr;        // [C + 1]
+  const uint8_t* ent_slot;
+  const int64_t* ent_qty;
+  int64_t row_begin, row_end;
+  uint8_t* out_status;           // [P][row_stride]
+  uint8_t* out_score;            // [P][row_stride]
+  int64_t* out_raw;              // when set: raw int64 scores of the one row row_begin, no table writes
+};
+void launch_nrt_wide(const NrtWideArgs& a, hipStream_t s);
 // the reference-arithmetic kernel's per-container request column [P][8][n_res] int64, rebuilt from the pod record stream (whose
 // quantities are exact doubles whenever the stream is valid): the engine does not ship that column — 256 bytes per pod — with every
 // pod batch, only when a launch is going to read it

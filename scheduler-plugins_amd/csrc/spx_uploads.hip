@@ -236,6 +236,8 @@ int spx_update_quota_used(spx_engine* e, int64_t n_rows, const int32_t* ns, cons
 int spx_update_nrt_nodes(spx_engine* e, const int64_t* idx, const spx_nrt_nodes_soa* t) {
   if (!e || !t) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
+  if (e->nrt_wide)
+    return fail(e, SPX_ERR_STATE, "NRT node delta: the engine holds a wide snapshot (more than 8 resource slots, or SPX_OPT_NRT_WIDE): load it again instead");
   if (!e->nrt_nodes || !e->nrt_slots) return fail(e, SPX_ERR_STATE, "NRT node delta: upload the slot and node tables first");
   if (t->n_res != e->nrt_n_res) return fail(e, SPX_ERR_ARG, "NRT node delta: n_res differs from the slot table");
   const int64_t n = t->n_nodes;
@@ -476,6 +478,12 @@ int spx_set_nrt_params(spx_engine* e, const spx_nrt_params* p) {
 int spx_upload_nrt_slots(spx_engine* e, const spx_nrt_slots* t) {
   if (!e || !t) return SPX_ERR_ARG;
   if (t->n_res < 0 || t->n_res > SPX_NRT_MAX_RES) return fail(e, SPX_ERR_ARG, "NRT: more resource slots than this build supports");
+  if (e->nrt_wide) {  // back from the wide tables: nothing of the dense state survives them (spx_upload_nrt_slots_wide)
+    e->nrt_wide = false;
+    e->nrtw_slots = e->nrtw_nodes = e->nrtw_pods = false;
+    e->nrt_fz_key = spx_engine::FzKey{};
+    e->nrt_pk_tab_built = e->nrt_wsort_built = false;
+  }
   e->nrt_n_res = t->n_res;
   for (int i = 0; i < t->n_res; ++i) {
     e->nrt_slot_flags[i] = t->slot_flags[i];
@@ -955,6 +963,106 @@ int spx_upload_nrt_long_pods(spx_engine* e, const spx_nrt_long_pods* t) {
   return SPX_OK;
 }
 
+// The wide form replaces the dense NRT state: its tables and every cache keyed on them (the fused walk's items, the packed Score's
+// table, the windows' sorted quantities, the long rows) are invalidated; spx_upload_nrt_slots does the same the other way round.
+int spx_upload_nrt_slots_wide(spx_engine* e, const spx_nrt_slots* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  if (t->n_res < 0 || t->n_res > SPX_NRT_MAX_RES_WIDE) return fail(e, SPX_ERR_ARG, "NRT: more resource slots than the wide tables hold (32)");
+  if (t->n_res && (!t->slot_flags || !t->slot_weight)) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  SPX_HIP(e, hipSetDevice(e->device));
+  e->nrt_slots = e->nrt_nodes = e->nrt_pods = false;
+  ++e->nrt_items_gen;
+  e->nrt_fz_key = spx_engine::FzKey{};
+  e->nrt_pk_tab_built = e->nrt_wsort_built = false;
+  e->h_nrt_long_rows.clear();
+  e->nrt_long_ok = true;
+  e->nrt_long_last = 0;
+  e->nrt_wide = true;
+  e->nrtw_slots = e->nrtw_nodes = e->nrtw_pods = false;
+  const size_t R = static_cast<size_t>(t->n_res);
+  int rc;
+  if ((rc = upload(e, e->d_nrtw_sflags, t->slot_flags, R)) || (rc = upload(e, e->d_nrtw_sweight, t->slot_weight, R * 8))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->nrtw_n_res = t->n_res;
+  e->nrtw_slots = true;
+  return SPX_OK;
+}
+
+int spx_upload_nrt_nodes_wide(spx_engine* e, const spx_nrt_nodes_wide* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (!e->nrt_wide || !e->nrtw_slots || t->n_res != e->nrtw_n_res) return fail(e, SPX_ERR_STATE, "NRT: upload the wide slot table first (n_res mismatch)");
+  int rc = set_nodes(e, t->n_nodes);
+  if (rc) return rc;
+  e->nrtw_nodes = false;
+  const int64_t n = t->n_nodes, R = t->n_res;
+  constexpr int64_t Zm = SPX_NRT_MAX_ZONES;
+  if (!t->flags || !t->max_numa || !t->n_zones || !t->zone_id || !t->zone_present || !t->zone_cost || !t->min_avg_dist || !t->node_present ||
+      (!t->zone_avail && R))
+    return fail(e, SPX_ERR_ARG, "NULL column in table");
+  const size_t m = static_cast<size_t>(n);
+  for (size_t i = 0; i < m; ++i) {  // the kernel indexes its subset table by the zone count and shifts by the NUMA ids
+    if (t->n_zones[i] > Zm) return fail(e, SPX_ERR_ARG, "NRT wide nodes: more than 8 NUMA zones on a node");
+    for (int64_t z = 0; z < Zm; ++z)
+      if (t->zone_id[i * Zm + z] > 63) return fail(e, SPX_ERR_ARG, "NRT wide nodes: a NUMA id above 63");
+  }
+  if ((rc = upload(e, e->d_nrtw_flags, t->flags, m)) || (rc = upload(e, e->d_nrtw_max_numa, t->max_numa, m * 4)) || (rc = upload(e, e->d_nrtw_nz, t->n_zones, m)) ||
+      (rc = upload(e, e->d_nrtw_np, t->node_present, m * 4)))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  if ((rc = upload_transposed(e, e->d_nrtw_zid, t->zone_id, n, Zm)) || (rc = upload_transposed(e, e->d_nrtw_zp, t->zone_present, n, Zm)) ||
+      (rc = upload_transposed(e, e->d_nrtw_cost, t->zone_cost, n, Zm * Zm)) || (rc = upload_transposed(e, e->d_nrtw_minavg, t->min_avg_dist, n, Zm)))
+    return rc;
+  if (R && (rc = upload_transposed(e, e->d_nrtw_avail, t->zone_avail, n, Zm * R))) return rc;
+  if (!R && (rc = ensure(e, e->d_nrtw_avail, 8))) return rc;
+  e->nrtw_nodes = true;
+  return SPX_OK;
+}
+
+int spx_upload_nrt_pods_wide(spx_engine* e, const spx_nrt_pods_wide* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (!e->nrt_wide || !e->nrtw_slots || t->n_res != e->nrtw_n_res) return fail(e, SPX_ERR_STATE, "NRT: upload the wide slot table first (n_res mismatch)");
+  if (!t->qos || !t->non_native || !t->req_ptr || !t->ctr_ptr || !t->ent_ptr) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  int rc = set_pods(e, t->n_pods);
+  if (rc) return rc;
+  e->nrtw_pods = false;
+  const size_t P = static_cast<size_t>(t->n_pods);
+  if (t->req_ptr[0] != 0 || t->ctr_ptr[0] != 0 || t->ent_ptr[0] != 0) return fail(e, SPX_ERR_ARG, "NRT wide pods: req_ptr / ctr_ptr / ent_ptr must start at 0");
+  for (size_t i = 0; i < P; ++i) {
+    const int32_t nc = t->ctr_ptr[i + 1] - t->ctr_ptr[i];
+    if (nc < 0 || t->req_ptr[i + 1] < t->req_ptr[i]) return fail(e, SPX_ERR_ARG, "NRT wide pods: req_ptr / ctr_ptr must not decrease");
+    if (nc > SPX_NRT_WIDE_MAX_CTRS) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "NRT wide pods: pod row %zu has %d containers; a wide snapshot takes up to %d per pod", i, nc, SPX_NRT_WIDE_MAX_CTRS);
+      return fail(e, SPX_ERR_ARG, buf);
+    }
+  }
+  const size_t C = static_cast<size_t>(t->ctr_ptr[P]), Er = static_cast<size_t>(t->req_ptr[P]);
+  for (size_t c = 0; c < C; ++c)
+    if (t->ent_ptr[c + 1] < t->ent_ptr[c]) return fail(e, SPX_ERR_ARG, "NRT wide pods: ent_ptr must not decrease");
+  const size_t Ec = static_cast<size_t>(t->ent_ptr[C]);
+  // slots in range and every list ascending: the kernel indexes the slot columns by them and stops a search at the first larger slot
+  auto lists_ok = [&](const int32_t* ptr, size_t n_lists, const uint8_t* slot) {
+    for (size_t l = 0; l < n_lists; ++l)
+      for (int32_t k = ptr[l]; k < ptr[l + 1]; ++k)
+        if (slot[k] >= t->n_res || (k > ptr[l] && slot[k] <= slot[k - 1])) return false;
+    return true;
+  };
+  if ((Er && (!t->req_slot || !t->req_qty)) || (Ec && (!t->ent_slot || !t->ent_qty)) || (C && !t->ctr_kind)) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  if (!lists_ok(t->req_ptr, P, t->req_slot) || !lists_ok(t->ent_ptr, C, t->ent_slot))
+    return fail(e, SPX_ERR_ARG, "NRT wide pods: every list must name slots below n_res in ascending order");
+  if ((rc = upload(e, e->d_nrtw_qos, t->qos, P)) || (rc = upload(e, e->d_nrtw_nn, t->non_native, P)) ||
+      (rc = upload(e, e->d_nrtw_rptr, t->req_ptr, (P + 1) * 4)) || (rc = upload(e, e->d_nrtw_rslot, t->req_slot, Er)) ||
+      (rc = upload(e, e->d_nrtw_rqty, t->req_qty, Er * 8)) || (rc = upload(e, e->d_nrtw_cptr, t->ctr_ptr, (P + 1) * 4)) ||
+      (rc = upload(e, e->d_nrtw_ckind, t->ctr_kind, C)) || (rc = upload(e, e->d_nrtw_eptr, t->ent_ptr, (C + 1) * 4)) ||
+      (rc = upload(e, e->d_nrtw_eslot, t->ent_slot, Ec)) || (rc = upload(e, e->d_nrtw_eqty, t->ent_qty, Ec * 8)))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->nrtw_pods = true;
+  return SPX_OK;
+}
+
 int spx_upload_net_nodes(spx_engine* e, const spx_net_nodes_soa* t) {
   if (!e || !t) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
@@ -1240,6 +1348,60 @@ int spx_load_trimaran_pods(spx_engine* e, const spx_pod_objects* pods) {
   return SPX_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// spx_load_nrt's wide route: slot numbering done, the node and pod halves flattened and uploaded side by side as in the dense route
+int load_nrt_wide(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_pod_objects* pods,
+                  const spx_nrt_params* params, const spx_nrt_slots& slots) {
+  int rc_;
+  if ((rc_ = spx_set_nrt_params(e, params)) || (rc_ = spx_upload_nrt_slots_wide(e, &slots))) return rc_;
+  if ((rc_ = set_nodes(e, nodes->n_nodes)) || (rc_ = set_pods(e, pods->n_pods))) return rc_;
+  const size_t N = static_cast<size_t>(nodes->n_nodes), P = static_cast<size_t>(pods->n_pods), R = static_cast<size_t>(slots.n_res > 0 ? slots.n_res : 1),
+               Z = SPX_NRT_MAX_ZONES, C = static_cast<size_t>(pods->ctr_ptr[pods->n_pods] - pods->ctr_ptr[0]);
+  int rc_pods = SPX_OK;
+  std::thread pod_half([&] {
+    int64_t n_req = 0, n_ent = 0;
+    if (spx_flatten_nrt_pods_wide(pods, rc, &slots, 0, 0, &n_req, &n_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr) != SPX_OK) {
+      rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_pods_wide failed");
+      return;
+    }
+    std::vector<uint8_t> qos(P), nn(P), rslot(static_cast<size_t>(n_req)), ckind(C), eslot(static_cast<size_t>(n_ent));
+    std::vector<int32_t> rptr(P + 1), cptr(P + 1), eptr(C + 1);
+    std::vector<int64_t> rqty(static_cast<size_t>(n_req)), eqty(static_cast<size_t>(n_ent));
+    if (spx_flatten_nrt_pods_wide(pods, rc, &slots, n_req, n_ent, &n_req, &n_ent, qos.data(), nn.data(), rptr.data(), rslot.data(), rqty.data(), cptr.data(),
+                                  ckind.data(), eptr.data(), eslot.data(), eqty.data()) != SPX_OK) {
+      rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_pods_wide failed");
+      return;
+    }
+    const spx_nrt_pods_wide ps{pods->n_pods, slots.n_res, qos.data(), nn.data(), rptr.data(), rslot.data(), rqty.data(), cptr.data(), ckind.data(),
+                               eptr.data(), eslot.data(), eqty.data()};
+    rc_pods = spx_upload_nrt_pods_wide(e, &ps);
+  });
+  int rc_nodes = SPX_OK;
+  {
+    std::vector<uint8_t> nflags(N), nz(N), zid(N * Z);
+    std::vector<uint32_t> zp(N * Z), np(N);
+    std::vector<int32_t> max_numa(N), zcost(N * Z * Z);
+    std::vector<int64_t> zavail(N * Z * R);
+    std::vector<float> minavg(N * Z);
+    if (spx_flatten_nrt_nodes_wide(nodes, nrt, &slots, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(),
+                                   minavg.data(), np.data()) != SPX_OK) {
+      rc_nodes = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_nodes_wide failed");
+    } else {
+      const spx_nrt_nodes_wide ns{nodes->n_nodes, slots.n_res, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(),
+                                  minavg.data(), np.data()};
+      rc_nodes = spx_upload_nrt_nodes_wide(e, &ns);
+    }
+  }
+  pod_half.join();
+  return rc_nodes ? rc_nodes : rc_pods;
+}
+}  // namespace
+
+extern "C" {
+
 int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_pod_objects* pods,
                  const spx_nrt_params* params) {
   if (!e || !nodes || !nrt || !pods || !params) return SPX_ERR_ARG;
@@ -1247,12 +1409,19 @@ int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_obj
   auto since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
   for (double& x : e->load_nrt_ms) x = 0.0;
   auto t0 = clk::now();
-  int32_t n_res = 0, slot_res[SPX_NRT_MAX_RES] = {0};
-  uint8_t slot_flags[SPX_NRT_MAX_RES] = {0};
-  int64_t slot_weight[SPX_NRT_MAX_RES] = {0};
-  if (spx_flatten_nrt_slots(pods, nrt, rc, params, &n_res, slot_res, slot_flags, slot_weight) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_nrt_slots failed");
+  // the slot numbering once, wide enough for either form: up to 8 slots it is spx_flatten_nrt_slots' own
+  int32_t n_res = 0, slot_res[SPX_NRT_MAX_RES_WIDE] = {0};
+  uint8_t slot_flags[SPX_NRT_MAX_RES_WIDE] = {0};
+  int64_t slot_weight[SPX_NRT_MAX_RES_WIDE] = {0};
+  if (spx_flatten_nrt_slots_wide(pods, nrt, rc, params, SPX_NRT_MAX_RES_WIDE, &n_res, slot_res, slot_flags, slot_weight) != SPX_OK) {
+    if (n_res <= SPX_NRT_MAX_RES_WIDE) return fail(e, SPX_ERR_ARG, "spx_flatten_nrt_slots failed");
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "NRT: the snapshot names %d distinct resources; this build takes up to %d", n_res, SPX_NRT_MAX_RES_WIDE);
+    return fail(e, SPX_ERR_ARG, buf);
+  }
   const spx_nrt_slots slots{n_res, slot_res, slot_flags, slot_weight};
   e->load_nrt_ms[0] = since(t0);  // 0: spx_flatten_nrt_slots
+  if (n_res > SPX_NRT_MAX_RES || e->option[SPX_OPT_NRT_WIDE]) return load_nrt_wide(e, nodes, nrt, rc, pods, params, slots);
   t0 = clk::now();
   int rc_;
   if ((rc_ = spx_set_nrt_params(e, params)) || (rc_ = spx_upload_nrt_slots(e, &slots))) return rc_;

@@ -50,6 +50,23 @@ def long_rows_slice(lt: Optional[dict], rows, R: int) -> Optional[dict]:
                 ctr_req=lt["ctr_req"][c0 * max(R, 1):c1 * max(R, 1)].copy())
 
 
+WIDE_POD_COLS = ("qos", "non_native", "req_ptr", "req_slot", "req_qty", "ctr_ptr", "ctr_kind", "ent_ptr", "ent_slot", "ent_qty")
+
+
+def wide_rows_slice(pw: dict, rows) -> dict:
+    """the wide NRT pod table (spx_nrt_pods_wide columns) of batch rows [rows[0], rows[1]), its offsets rebased (rows None: pw itself)"""
+    if rows is None:
+        return pw
+    b, e = rows
+    rp, cp, ep = pw["req_ptr"], pw["ctr_ptr"], pw["ent_ptr"]
+    r0, r1, c0, c1 = int(rp[b]), int(rp[e]), int(cp[b]), int(cp[e])
+    e0, e1 = int(ep[c0]), int(ep[c1])
+    return dict(qos=pw["qos"][b:e].copy(), non_native=pw["non_native"][b:e].copy(),
+                req_ptr=(rp[b:e + 1] - r0).astype(np.int32), req_slot=pw["req_slot"][r0:r1].copy(), req_qty=pw["req_qty"][r0:r1].copy(),
+                ctr_ptr=(cp[b:e + 1] - c0).astype(np.int32), ctr_kind=pw["ctr_kind"][c0:c1].copy(),
+                ent_ptr=(ep[c0:c1 + 1] - e0).astype(np.int32), ent_slot=pw["ent_slot"][e0:e1].copy(), ent_qty=pw["ent_qty"][e0:e1].copy())
+
+
 def _rows(cols: Dict[str, np.ndarray], n_total: int, rows) -> Dict[str, np.ndarray]:
     """slice of per-pod SoA columns: every column holds a fixed number of entries per pod, pod-major"""
     if rows is None:
@@ -337,15 +354,21 @@ class Engine:
         self.upload_nrt(self.flatten_nrt(nodes, nrt, rc, pods, params))
 
     def flatten_nrt(self, nodes: Table, nrt: Table, rc: Optional[Table], pods: Table, params: Table) -> dict:
+        """the NRT tables of a snapshot: the dense form up to 8 resource slots, the wide one (flatten_nrt_wide, "wide" in the dict)
+        above 8 or with the NRT_WIDE option set — the choice spx_load_nrt makes"""
         L, H = self._lib, self._hdr
+        if self._h and self.get_option("NRT_WIDE"):  # (a host-only wrapper has no engine, hence no options)
+            return self.flatten_nrt_wide(nodes, nrt, rc, pods, params)
         u8p, i32p, i64p, f32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
         n_res = C.c_int32()
         slot_res = np.zeros(8, np.int32)
         slot_flags = np.zeros(8, np.uint8)
         slot_weight = np.zeros(8, np.int64)
-        self._ck(L.spx_flatten_nrt_slots(pods.ref(), nrt.ref(), rc.ref() if rc else None, params.ref(), C.byref(n_res),
-                                         slot_res.ctypes.data_as(i32p), slot_flags.ctypes.data_as(u8p),
-                                         slot_weight.ctypes.data_as(i64p)))
+        rc_ = L.spx_flatten_nrt_slots(pods.ref(), nrt.ref(), rc.ref() if rc else None, params.ref(), C.byref(n_res),
+                                      slot_res.ctypes.data_as(i32p), slot_flags.ctypes.data_as(u8p), slot_weight.ctypes.data_as(i64p))
+        if rc_ == H.consts["SPX_ERR_ARG"] and self.nrt_slots_wide(nrt, rc, pods, params)[0] > 8:
+            return self.flatten_nrt_wide(nodes, nrt, rc, pods, params)
+        self._ck(rc_)
         R = n_res.value
         slots = Table(H, "spx_nrt_slots", n_res=R, slot_res=slot_res, slot_flags=slot_flags, slot_weight=slot_weight)
         N, P = nodes.struct.n_nodes, pods.struct.n_pods
@@ -364,6 +387,56 @@ class Engine:
         pc = NrtPods(pc)
         pc.long = self.flatten_nrt_long_pods(pods, rc, slots)
         return {"params": params, "slots": slots, "nodes": nc, "pods": pc, "long": pc.long, "N": N, "P": P, "R": R}
+
+    def nrt_slots_wide(self, nrt: Table, rc: Optional[Table], pods: Table, params: Table, cap: int = 32):
+        """(count, status, slot_res, slot_flags, slot_weight) of spx_flatten_nrt_slots_wide with `cap` slots; the count is the snapshot's
+        even when it exceeds cap (status SPX_ERR_ARG, arrays untouched)"""
+        n_res = C.c_int32()
+        slot_res, slot_flags, slot_weight = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.int64)
+        st = self._lib.spx_flatten_nrt_slots_wide(pods.ref(), nrt.ref(), rc.ref() if rc else None, params.ref(), cap, C.byref(n_res),
+                                                  slot_res.ctypes.data_as(C.POINTER(C.c_int32)), slot_flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  slot_weight.ctypes.data_as(C.POINTER(C.c_int64)))
+        return n_res.value, st, slot_res, slot_flags, slot_weight
+
+    def flatten_nrt_wide(self, nodes: Table, nrt: Table, rc: Optional[Table], pods: Table, params: Table) -> dict:
+        """the wide NRT tables (up to 32 resource slots): slots, nodes (spx_nrt_nodes_wide columns) and pods (spx_nrt_pods_wide columns)"""
+        L, H = self._lib, self._hdr
+        R, st, slot_res, slot_flags, slot_weight = self.nrt_slots_wide(nrt, rc, pods, params)
+        if st != 0:
+            from . import SpxError
+            raise SpxError(st,f"NRT: the snapshot names {R} distinct resources; this build takes up to 32" if R > 32 else "spx_flatten_nrt_slots_wide failed")
+        slots = Table(H, "spx_nrt_slots", n_res=R, slot_res=slot_res, slot_flags=slot_flags, slot_weight=slot_weight)
+        N, P = nodes.struct.n_nodes, pods.struct.n_pods
+        nc = dict(flags=np.zeros(N, np.uint8), max_numa=np.zeros(N, np.int32), n_zones=np.zeros(N, np.uint8),
+                  zone_id=np.zeros(N * 8, np.uint8), zone_present=np.zeros(N * 8, np.uint32),
+                  zone_avail=np.zeros(N * 8 * max(R, 1), np.int64), zone_cost=np.zeros(N * 64, np.int32),
+                  min_avg_dist=np.zeros(N * 8, np.float32), node_present=np.zeros(N, np.uint32))
+        fn = L.spx_flatten_nrt_nodes_wide
+        self._ck_static(fn(nodes.ref(), nrt.ref(), slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(nc.values(), fn.argtypes[3:])]))
+        return {"wide": True, "params": params, "slots": slots, "nodes": nc, "pods": self.flatten_nrt_pods_wide(pods, rc, slots),
+                "N": N, "P": P, "R": R}
+
+    def flatten_nrt_pods_wide(self, pods: Table, rc: Optional[Table], slots: Table) -> Dict[str, np.ndarray]:
+        """the wide pod table (spx_flatten_nrt_pods_wide): CSR lists of (slot, quantity), pod-level and per container"""
+        L = self._lib
+        P = pods.struct.n_pods
+        cptr = pods.array("ctr_ptr")
+        n_ctr = int(cptr[P]) - int(cptr[0])  # (a pod view may start inside a larger table)
+        args = (pods.ref(), rc.ref() if rc else None, slots.ref())
+        n_req, n_ent = C.c_int64(), C.c_int64()
+        self._ck_static(L.spx_flatten_nrt_pods_wide(*args, 0, 0, C.byref(n_req), C.byref(n_ent), *([None] * 10)))
+        nr, ne = n_req.value, n_ent.value
+        pw = dict(qos=np.zeros(P, np.uint8), non_native=np.zeros(P, np.uint8), req_ptr=np.zeros(P + 1, np.int32), req_slot=np.zeros(nr, np.uint8),
+                  req_qty=np.zeros(nr, np.int64), ctr_ptr=np.zeros(P + 1, np.int32), ctr_kind=np.zeros(n_ctr, np.uint8),
+                  ent_ptr=np.zeros(n_ctr + 1, np.int32), ent_slot=np.zeros(ne, np.uint8), ent_qty=np.zeros(ne, np.int64))
+        fn = L.spx_flatten_nrt_pods_wide
+        self._ck_static(fn(*args, nr, ne, C.byref(n_req), C.byref(n_ent),
+                           *[pw[k].ctypes.data_as(t) for k, t in zip(WIDE_POD_COLS, fn.argtypes[7:])]))
+        return pw
+
+    def nrt_wide(self) -> bool:
+        """whether the NRT tables in place are the wide form (spx_nrt_wide)"""
+        return bool(self._lib.spx_nrt_wide(self._h))
 
     def flatten_nrt_long_pods(self, pods: Table, rc: Optional[Table], slots: Table) -> dict:
         """the containers of the pods with more than 8 containers, CSR (spx_flatten_nrt_long_pods): n_long, pod_row, ctr_ptr,
@@ -500,6 +573,18 @@ class Engine:
     def upload_nrt(self, f: dict, rows=None) -> None:
         """rows = (begin, end): this engine holds only that slice of the pod batch (MultiEngine)"""
         L, H = self._lib, self._hdr
+        if f.get("wide"):
+            self._ck(L.spx_set_nrt_params(self._h, f["params"].ref()))
+            self._ck(L.spx_upload_nrt_slots_wide(self._h, f["slots"].ref()))
+            self._ck(L.spx_upload_nrt_nodes_wide(self._h, Table(H, "spx_nrt_nodes_wide", n_nodes=f["N"], n_res=f["R"], **f["nodes"]).ref()))
+            pw = wide_rows_slice(f["pods"], rows)
+            P = f["P"] if rows is None else rows[1] - rows[0]
+            if P > 0:
+                cols = {k: v for k, v in pw.items() if len(v)}  # (an empty list column travels as NULL)
+                self._ck(L.spx_upload_nrt_pods_wide(self._h, Table(H, "spx_nrt_pods_wide", n_pods=P, n_res=f["R"], **cols).ref()))
+            self.n_nodes, self.n_pods = f["N"], P
+            self.nrt_soa = {"slots": f["slots"], "nodes": f["nodes"], "pods": pw, "wide": True}
+            return
         self._ck(L.spx_set_nrt_params(self._h, f["params"].ref()))
         self._ck(L.spx_upload_nrt_slots(self._h, f["slots"].ref()))
         self._ck(L.spx_upload_nrt_nodes(self._h, Table(H, "spx_nrt_nodes_soa", n_nodes=f["N"], n_res=f["R"], **f["nodes"]).ref()))

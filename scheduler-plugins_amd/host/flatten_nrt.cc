@@ -81,11 +81,64 @@ inline KV* kv_find(std::vector<KV>& v, int32_t res) {
   return nullptr;
 }
 
+// GetPodEffectiveRequest (pkg/util/resource.go:51-85) with map key presence: pod i's request into `res` (init_res: scratch)
+void pod_effective_request(const spx_pod_objects* pods, int64_t i, std::vector<KV>& init_res, std::vector<KV>& res) {
+  const int32_t c0 = pods->ctr_ptr[i], c1 = pods->ctr_ptr[i + 1];
+  init_res.clear();
+  res.clear();
+  for (int32_t c = c0; c < c1; ++c) {
+    if (pods->ctr_kind[c] == SPX_CTR_APP) continue;
+    for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) {
+      KV* e = kv_find(init_res, pods->req_res[k]);
+      if (e && pods->req_qty[k] <= e->qty) continue;
+      if (e) e->qty = pods->req_qty[k];
+      else init_res.push_back({pods->req_res[k], pods->req_qty[k]});
+    }
+  }
+  for (int32_t c = c0; c < c1; ++c) {
+    if (pods->ctr_kind[c] != SPX_CTR_APP) continue;
+    for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) {
+      KV* e = kv_find(res, pods->req_res[k]);
+      if (e) e->qty += pods->req_qty[k];
+      else res.push_back({pods->req_res[k], pods->req_qty[k]});
+    }
+  }
+  for (const KV& in : init_res) {
+    KV* e = kv_find(res, in.res);
+    if (e && in.qty <= e->qty) continue;
+    if (e) e->qty = in.qty;
+    else res.push_back(in);
+  }
+  if (pods->ovh_ptr)
+    for (int32_t k = pods->ovh_ptr[i]; k < pods->ovh_ptr[i + 1]; ++k) {
+      KV* e = kv_find(res, pods->ovh_res[k]);
+      if (e) e->qty += pods->ovh_qty[k];
+      else res.push_back({pods->ovh_res[k], pods->ovh_qty[k]});
+    }
+}
+
+// the slot numbering for up to `cap` slots; *n_res_out is written first when `count_first` (the wide form reports the count it refuses)
+int flatten_slots(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_nrt_params* p, int cap,
+                  bool count_first, int32_t* n_res_out, int32_t* slot_res, uint8_t* slot_flags, int64_t* slot_weight);
+
 }  // namespace
 
 extern "C" int spx_flatten_nrt_slots(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const spx_resource_classes* rc,
                                      const spx_nrt_params* p, int32_t* n_res_out, int32_t* slot_res, uint8_t* slot_flags,
                                      int64_t* slot_weight) {
+  return flatten_slots(pods, nrt, rc, p, RM, false, n_res_out, slot_res, slot_flags, slot_weight);
+}
+
+extern "C" int spx_flatten_nrt_slots_wide(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const spx_resource_classes* rc,
+                                          const spx_nrt_params* p, int32_t cap, int32_t* n_res_out, int32_t* slot_res, uint8_t* slot_flags,
+                                          int64_t* slot_weight) {
+  if (cap < 0 || cap > SPX_NRT_MAX_RES_WIDE) return SPX_ERR_ARG;
+  return flatten_slots(pods, nrt, rc, p, cap, true, n_res_out, slot_res, slot_flags, slot_weight);
+}
+
+namespace {
+int flatten_slots(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_nrt_params* p, int cap,
+                  bool count_first, int32_t* n_res_out, int32_t* slot_res, uint8_t* slot_flags, int64_t* slot_weight) {
   if (!pods || !nrt || !n_res_out || !slot_res || !slot_flags || !slot_weight) return SPX_ERR_ARG;
   // the distinct resource ids of three long arrays (every container request, every overhead entry, every zone resource: ~0.8 M entries
   // at config #5's share): scanned in pieces on the host threads, each piece's handful of ids merged under a lock
@@ -120,7 +173,8 @@ extern "C" int spx_flatten_nrt_slots(const spx_pod_objects* pods, const spx_nrt_
   const int32_t n_zones = nrt->zone_ptr[nrt->n_nodes];
   scan(nrt->zres_res, nrt->zres_ptr[n_zones]);
   std::sort(ids.begin(), ids.end());
-  if (ids.size() > static_cast<size_t>(RM)) return SPX_ERR_ARG;  // more distinct resources than this build supports
+  if (count_first) *n_res_out = static_cast<int32_t>(ids.size());
+  if (ids.size() > static_cast<size_t>(cap)) return SPX_ERR_ARG;  // more distinct resources than the caller's table holds
   *n_res_out = static_cast<int32_t>(ids.size());
   for (size_t s = 0; s < ids.size(); ++s) {
     const int32_t r = ids[s];
@@ -139,11 +193,11 @@ extern "C" int spx_flatten_nrt_slots(const spx_pod_objects* pods, const spx_nrt_
   return SPX_OK;
 }
 
-namespace {
-// node i of the object tables -> row j of the SoA columns
+// node i of the object tables -> row j of the SoA columns; PM is the presence mask type (uint8_t: dense, uint32_t: wide)
+template <typename PM>
 int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, int64_t i, int64_t j,
-                     uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id, uint8_t* zone_present, int64_t* zone_avail,
-                     int32_t* zone_cost, float* min_avg_dist, uint8_t* node_present) {
+                     uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id, PM* zone_present, int64_t* zone_avail,
+                     int32_t* zone_cost, float* min_avg_dist, PM* node_present) {
   const int R = slots->n_res;
     // ---- TopologyManager config
     int scope = 0, policy = 0, mx = 8;
@@ -159,12 +213,12 @@ int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, 
                                     (policy == 3 ? SPX_NRT_F_SINGLE_NUMA : 0) | (scope == 1 ? SPX_NRT_F_POD_SCOPE : 0));
     max_numa[j] = mx;
     // ---- node-level key set of util.ResourceList(allocatable)
-    uint8_t np = 0;
+    PM np = 0;
     for (int s = 0; s < R; ++s) {
       const int32_t r = slots->slot_res[s];
       bool has = r == SPX_RES_CPU || r == SPX_RES_MEMORY || r == SPX_RES_PODS || r == SPX_RES_EPHEMERAL;
       for (int32_t k = nodes->scalar_ptr[i]; !has && k < nodes->scalar_ptr[i + 1]; ++k) has = nodes->scalar_res[k] == r;
-      if (has) np |= static_cast<uint8_t>(1u << s);
+      if (has) np |= static_cast<PM>(1u << s);
     }
     node_present[j] = np;
     // ---- NUMA node list (list order = zone order), with assumed pods subtracted from every zone
@@ -180,7 +234,7 @@ int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, 
         }  // beyond this build's limits (8 zones, ids 0..63)
         zsrc[nz] = z;
         zone_id[j * Z + nz] = static_cast<uint8_t>(id);
-        uint8_t present = 0;
+        PM present = 0;
         for (int32_t k = nrt->zres_ptr[z]; k < nrt->zres_ptr[z + 1]; ++k) {
           const int s = slot_of(slots, nrt->zres_res[k]);
           if (s < 0) {
@@ -191,7 +245,7 @@ int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, 
             for (int32_t a = nrt->assumed_ptr[i]; a < nrt->assumed_ptr[i + 1]; ++a)
               for (int32_t q = nrt->arl_ptr[a]; q < nrt->arl_ptr[a + 1]; ++q)
                 if (nrt->arl_res[q] == nrt->zres_res[k]) avail = avail < nrt->arl_qty[q] ? 0 : avail - nrt->arl_qty[q];
-          present |= static_cast<uint8_t>(1u << s);
+          present |= static_cast<PM>(1u << s);
           zone_avail[(j * Z + nz) * R + s] = avail;
         }
         zone_present[j * Z + nz] = present;
@@ -260,12 +314,11 @@ int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, 
     for (int k = 0; k < Z; ++k) min_avg_dist[j * Z + k] = best[k];
   return SPX_OK;
 }
-}  // namespace
 
-extern "C" int spx_flatten_nrt_nodes(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots,
-                                     uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id,
-                                     uint8_t* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist,
-                                     uint8_t* node_present) {
+template <typename PM>
+int flatten_nodes(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, uint8_t* flags, int32_t* max_numa,
+                  uint8_t* n_zones, uint8_t* zone_id, PM* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist,
+                  PM* node_present) {
   if (!nodes || !nrt || !slots || !flags || !max_numa || !n_zones || !zone_id || !zone_present || !zone_avail || !zone_cost ||
       !min_avg_dist || !node_present)
     return SPX_ERR_ARG;
@@ -273,7 +326,7 @@ extern "C" int spx_flatten_nrt_nodes(const spx_node_objects* nodes, const spx_nr
   if (nrt->n_nodes != n) return SPX_ERR_ARG;
   const int R = slots->n_res;
   std::memset(zone_id, 0, static_cast<size_t>(n) * Z);
-  std::memset(zone_present, 0, static_cast<size_t>(n) * Z);
+  std::memset(zone_present, 0, static_cast<size_t>(n) * Z * sizeof(PM));
   std::memset(zone_avail, 0, static_cast<size_t>(n) * Z * R * sizeof(int64_t));
   std::atomic<int> err{SPX_OK};
   // nodes are independent: split across host threads (20k nodes x 255 zone subsets for the distance minima alone)
@@ -287,6 +340,22 @@ extern "C" int spx_flatten_nrt_nodes(const spx_node_objects* nodes, const spx_nr
     }
   }, 256);
   return err.load();
+}
+}  // namespace
+
+extern "C" int spx_flatten_nrt_nodes(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots,
+                                     uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id,
+                                     uint8_t* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist,
+                                     uint8_t* node_present) {
+  return flatten_nodes(nodes, nrt, slots, flags, max_numa, n_zones, zone_id, zone_present, zone_avail, zone_cost, min_avg_dist, node_present);
+}
+
+extern "C" int spx_flatten_nrt_nodes_wide(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots,
+                                          uint8_t* flags, int32_t* max_numa, uint8_t* n_zones, uint8_t* zone_id,
+                                          uint32_t* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist,
+                                          uint32_t* node_present) {
+  if (slots && (slots->n_res < 0 || slots->n_res > SPX_NRT_MAX_RES_WIDE)) return SPX_ERR_ARG;
+  return flatten_nodes(nodes, nrt, slots, flags, max_numa, n_zones, zone_id, zone_present, zone_avail, zone_cost, min_avg_dist, node_present);
 }
 
 // the same columns for the listed nodes only (a snapshot delta: spx_update_nrt_nodes takes these rows): row j describes node idx[j]
@@ -350,38 +419,7 @@ extern "C" int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resou
       if (!is_long) ctr_present[slot_base] = present;
     }
     non_native[i] = nn ? 1 : 0;
-    // GetPodEffectiveRequest (pkg/util/resource.go:51-85) with map key presence
-    init_res.clear();
-    res.clear();
-    for (int32_t c = c0; c < c1; ++c) {
-      if (pods->ctr_kind[c] == SPX_CTR_APP) continue;
-      for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) {
-        KV* e = kv_find(init_res, pods->req_res[k]);
-        if (e && pods->req_qty[k] <= e->qty) continue;
-        if (e) e->qty = pods->req_qty[k];
-        else init_res.push_back({pods->req_res[k], pods->req_qty[k]});
-      }
-    }
-    for (int32_t c = c0; c < c1; ++c) {
-      if (pods->ctr_kind[c] != SPX_CTR_APP) continue;
-      for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) {
-        KV* e = kv_find(res, pods->req_res[k]);
-        if (e) e->qty += pods->req_qty[k];
-        else res.push_back({pods->req_res[k], pods->req_qty[k]});
-      }
-    }
-    for (const KV& in : init_res) {
-      KV* e = kv_find(res, in.res);
-      if (e && in.qty <= e->qty) continue;
-      if (e) e->qty = in.qty;
-      else res.push_back(in);
-    }
-    if (pods->ovh_ptr)
-      for (int32_t k = pods->ovh_ptr[i]; k < pods->ovh_ptr[i + 1]; ++k) {
-        KV* e = kv_find(res, pods->ovh_res[k]);
-        if (e) e->qty += pods->ovh_qty[k];
-        else res.push_back({pods->ovh_res[k], pods->ovh_qty[k]});
-      }
+    pod_effective_request(pods, i, init_res, res);
     uint8_t pp = 0;
     for (const KV& e : res) {
       const int s = slot_of(slots, e.res);
@@ -435,5 +473,96 @@ extern "C" int spx_flatten_nrt_long_pods(const spx_pod_objects* pods, const spx_
     }
     ctr_ptr[++k] = static_cast<int32_t>(at);
   }
+  return SPX_OK;
+}
+
+// Wide pod table: every list in ascending slot order.  Pass 1 takes each container's and each pod's presence mask (uint32: up to 32
+// slots) on the host threads, the list offsets follow from their popcounts, pass 2 fills the lists.
+extern "C" int spx_flatten_nrt_pods_wide(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, int64_t req_cap,
+                                         int64_t ent_cap, int64_t* n_req_out, int64_t* n_ent_out, uint8_t* qos, uint8_t* non_native,
+                                         int32_t* req_ptr, uint8_t* req_slot, int64_t* req_qty, int32_t* ctr_ptr, uint8_t* ctr_kind,
+                                         int32_t* ent_ptr, uint8_t* ent_slot, int64_t* ent_qty) {
+  if (!pods || !slots || !n_req_out || !n_ent_out || slots->n_res < 0 || slots->n_res > SPX_NRT_MAX_RES_WIDE) return SPX_ERR_ARG;
+  const bool count_only = !qos && !non_native && !req_ptr && !req_slot && !req_qty && !ctr_ptr && !ctr_kind && !ent_ptr && !ent_slot && !ent_qty;
+  if (!count_only && (!qos || !non_native || !req_ptr || !req_slot || !req_qty || !ctr_ptr || !ctr_kind || !ent_ptr || !ent_slot || !ent_qty))
+    return SPX_ERR_ARG;
+  // (a pod table may be a view into a larger one: its container offsets need not start at 0; the outputs are rebased)
+  const int64_t P = pods->n_pods, cb = pods->ctr_ptr[0], C = pods->ctr_ptr[P] - cb;
+  std::vector<uint32_t> cmask(static_cast<size_t>(C)), pmask(static_cast<size_t>(P));
+  std::atomic<int> err{SPX_OK};
+  spx_host::parallel_rows(P, [&](int64_t row0, int64_t row1) {
+    std::vector<KV> init_res, res;
+    for (int64_t i = row0; i < row1; ++i) {
+      bool nn = false;
+      for (int32_t c = pods->ctr_ptr[i]; c < pods->ctr_ptr[i + 1]; ++c) {
+        uint32_t m = 0;
+        for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) {
+          const int s = slot_of(slots, pods->req_res[k]);
+          if (s < 0) {
+            err = SPX_ERR_ARG;
+            return;
+          }
+          m |= 1u << s;
+          if (!rc_has(rc, pods->req_res[k], SPX_RC_NATIVE)) nn = true;
+        }
+        cmask[static_cast<size_t>(c - cb)] = m;
+      }
+      pod_effective_request(pods, i, init_res, res);
+      uint32_t m = 0;
+      for (const KV& e : res) {
+        const int s = slot_of(slots, e.res);
+        if (s < 0) {
+          err = SPX_ERR_ARG;
+          return;
+        }
+        m |= 1u << s;
+      }
+      pmask[static_cast<size_t>(i)] = m;
+      if (!count_only) {
+        qos[i] = static_cast<uint8_t>(pod_qos(pods, i));
+        non_native[i] = nn ? 1 : 0;
+      }
+    }
+  }, 4096);
+  if (err.load() != SPX_OK) return err.load();
+  int64_t n_req = 0, n_ent = 0;
+  for (int64_t i = 0; i < P; ++i) n_req += __builtin_popcount(pmask[static_cast<size_t>(i)]);
+  for (int64_t c = 0; c < C; ++c) n_ent += __builtin_popcount(cmask[static_cast<size_t>(c)]);
+  *n_req_out = n_req;
+  *n_ent_out = n_ent;
+  if (count_only) return SPX_OK;
+  if (n_req > req_cap || n_ent > ent_cap || n_req > INT32_MAX || n_ent > INT32_MAX) return SPX_ERR_ARG;
+  req_ptr[0] = 0;
+  for (int64_t i = 0; i < P; ++i) {
+    req_ptr[i + 1] = req_ptr[i] + __builtin_popcount(pmask[static_cast<size_t>(i)]);
+    ctr_ptr[i] = static_cast<int32_t>(pods->ctr_ptr[i] - cb);
+  }
+  ctr_ptr[P] = static_cast<int32_t>(C);
+  ent_ptr[0] = 0;
+  for (int64_t c = 0; c < C; ++c) ent_ptr[c + 1] = ent_ptr[c] + __builtin_popcount(cmask[static_cast<size_t>(c)]);
+  spx_host::parallel_rows(P, [&](int64_t row0, int64_t row1) {
+    std::vector<KV> init_res, res;
+    int64_t qty[SPX_NRT_MAX_RES_WIDE];
+    for (int64_t i = row0; i < row1; ++i) {
+      for (int32_t c = pods->ctr_ptr[i]; c < pods->ctr_ptr[i + 1]; ++c) {
+        ctr_kind[c - cb] = pods->ctr_kind[c];
+        for (int32_t k = pods->req_ptr[c]; k < pods->req_ptr[c + 1]; ++k) qty[slot_of(slots, pods->req_res[k])] = pods->req_qty[k];  // (the last entry of a name wins, as in the dense table)
+        int32_t at = ent_ptr[c - cb];
+        for (uint32_t m = cmask[static_cast<size_t>(c - cb)]; m; m &= m - 1) {
+          const int s = __builtin_ctz(m);
+          ent_slot[at] = static_cast<uint8_t>(s);
+          ent_qty[at++] = qty[s];
+        }
+      }
+      pod_effective_request(pods, i, init_res, res);
+      for (const KV& e : res) qty[slot_of(slots, e.res)] = e.qty;
+      int32_t at = req_ptr[i];
+      for (uint32_t m = pmask[static_cast<size_t>(i)]; m; m &= m - 1) {
+        const int s = __builtin_ctz(m);
+        req_slot[at] = static_cast<uint8_t>(s);
+        req_qty[at++] = qty[s];
+      }
+    }
+  }, 4096);
   return SPX_OK;
 }

@@ -26,6 +26,96 @@ def _csr_from_mask(mask: np.ndarray):
     return ptr, mask.reshape(-1)
 
 
+def _csr_append(ptr: np.ndarray, cols, mask: np.ndarray, add):
+    """a CSR structure with entries appended to each row: row r keeps its entries, then gains add[j][r, k] for every k with mask[r, k]
+    (in k order).  cols / add: parallel value arrays.  Returns (new ptr, new value arrays)."""
+    n = len(ptr) - 1
+    old_cnt, new_cnt = np.diff(ptr).astype(np.int64), mask.sum(axis=1).astype(np.int64)
+    nptr = np.zeros(n + 1, dtype=np.int32)
+    np.cumsum(old_cnt + new_cnt, out=nptr[1:])
+    row_old = np.repeat(np.arange(n), old_cnt)
+    pos_old = nptr[:-1][row_old] + (np.arange(len(row_old)) - ptr[:-1][row_old])
+    row_new = np.repeat(np.arange(n), new_cnt)
+    new_start = np.concatenate([[0], np.cumsum(new_cnt)[:-1]]).astype(np.int64)
+    pos_new = nptr[:-1][row_new] + old_cnt[row_new] + (np.arange(len(row_new)) - new_start[row_new])
+    sel = mask.reshape(-1)
+    out = []
+    for c, a in zip(cols, add):
+        v = np.zeros(int(nptr[-1]), dtype=c.dtype)
+        v[pos_old] = c
+        v[pos_new] = a.reshape(-1)[sel]
+        out.append(v)
+    return nptr, out
+
+
+RES_EXTRA0 = 12  # first id of nrt_snapshot(extra_res=...)'s resources
+
+
+def extra_resource_is_hugepage(k: int) -> bool:
+    """extra resource k (id RES_EXTRA0 + k): every third one a hugepage size, the others extended (SR-IOV / RDMA style) device pools"""
+    return k % 3 == 1
+
+
+def _widen_nrt(hdr: Header, nodes_scalar, nrt: Table, pods: Table, extra_res: int, seed: int, req_frac: float):
+    """nrt_snapshot's extra resources, from their own random stream: reported by a random subset of node allocatables and zones,
+    requested (request == limit, zero quantities included) by the first app container of a share req_frac of the pods"""
+    rng = np.random.default_rng(seed + 207)
+    ptr, res, qty = nodes_scalar
+    N, K = len(ptr) - 1, extra_res
+    ids = np.arange(RES_EXTRA0, RES_EXTRA0 + K, dtype=np.int32)
+    hp = np.array([extra_resource_is_hugepage(k) for k in range(K)])
+    node_has = rng.random((N, K)) < 0.8
+    node_qty = np.where(hp[None, :], 64 * GiB, 8).astype(np.int64) * np.ones((N, 1), np.int64)
+    sptr, (sres, sqty) = _csr_append(ptr, [res, qty], node_has, [np.tile(ids, (N, 1)), node_qty])
+    # zones: a node that lists the resource reports it in most of its zones
+    zone_ptr = nrt.array("zone_ptr")
+    nzt = int(zone_ptr[-1])
+    node_of = np.repeat(np.arange(N), np.diff(zone_ptr))
+    z_has = (node_has & (rng.random((N, K)) < 0.75))[node_of] & (rng.random((nzt, K)) < 0.85)
+    z_qty = np.where(hp[None, :], rng.integers(0, 9, (nzt, K)) * GiB, rng.integers(0, 5, (nzt, K))).astype(np.int64)
+    zptr, (zres, zavail) = _csr_append(nrt.array("zres_ptr"), [nrt.array("zres_res"), nrt.array("zres_avail")], z_has, [np.tile(ids, (nzt, 1)), z_qty])
+    fields = ("has_nrt", "fresh", "legacy_policy", "attr_scope", "attr_policy", "attr_max_numa", "zone_ptr", "zone_is_node", "zone_numa_id",
+              "zcost_ptr", "zcost_numa_id", "zcost_value", "assumed_ptr", "arl_ptr", "arl_res", "arl_qty")
+    nrt = Table(hdr, "spx_nrt_objects", n_nodes=N, zres_ptr=zptr, zres_res=zres, zres_avail=zavail, **{f: nrt.array(f) for f in fields})
+    # pods: one to three extra resources in the first app container
+    P = int(pods.struct.n_pods)
+    cptr, kind = pods.array("ctr_ptr"), pods.array("ctr_kind")
+    n_ctr = int(cptr[-1])
+    first_app = np.full(P, -1, np.int64)
+    for i in np.flatnonzero(rng.random(P) < req_frac):
+        app = np.flatnonzero(kind[cptr[i]:cptr[i + 1]] == 0)
+        if len(app):
+            first_app[i] = cptr[i] + app[0]
+    pick = np.zeros((P, K), bool)
+    n_pick = rng.integers(1, 4, P)
+    for i in np.flatnonzero(first_app >= 0):
+        pick[i, rng.choice(K, min(K, int(n_pick[i])), replace=False)] = True
+    c_has = np.zeros((n_ctr, K), bool)
+    c_has[first_app[first_app >= 0]] = pick[first_app >= 0]
+    c_qty = np.where(hp[None, :], rng.integers(0, 3, (n_ctr, K)) * GiB, rng.integers(0, 3, (n_ctr, K))).astype(np.int64)
+    rptr, (rres, rqty) = _csr_append(pods.array("req_ptr"), [pods.array("req_res"), pods.array("req_qty")], c_has, [np.tile(ids, (n_ctr, 1)), c_qty])
+    lptr, (lres, lqty) = _csr_append(pods.array("lim_ptr"), [pods.array("lim_res"), pods.array("lim_qty")], c_has, [np.tile(ids, (n_ctr, 1)), c_qty])
+    pfields = ("ctr_ptr", "ctr_kind", "ovh_ptr", "ovh_res", "ovh_qty", "priority", "queue_ts", "appgroup", "selector", "ns")
+    pods = Table(hdr, "spx_pod_objects", n_pods=P, req_ptr=rptr, req_res=rres, req_qty=rqty, lim_ptr=lptr, lim_res=lres, lim_qty=lqty,
+                 **{f: pods.array(f) for f in pfields})
+    return (sptr, sres, sqty), nrt, pods
+
+
+def widen_snapshot(hdr: Header, snap: Dict[str, Table], extra_res: int, seed: int = SEED, req_frac: float = 0.15) -> Dict[str, Table]:
+    """a snapshot (nrt_snapshot / full_snapshot keys) with nrt_snapshot(extra_res=...)'s extra resources added to its nodes, NRT objects,
+    pods and resource classes; the other tables are shared"""
+    nodes = snap["nodes"]
+    scalar = (nodes.array("scalar_ptr"), nodes.array("scalar_res"), nodes.array("scalar_qty"))
+    scalar, nrt, pods = _widen_nrt(hdr, scalar, snap["nrt"], snap["pods"], extra_res, seed, req_frac)
+    nf = ("alloc_cpu_milli", "alloc_mem", "alloc_eph", "alloc_pods", "cap_cpu_milli", "region", "zone")
+    out = dict(snap)
+    out["nodes"] = Table(hdr, "spx_node_objects", n_nodes=int(nodes.struct.n_nodes), scalar_ptr=scalar[0], scalar_res=scalar[1],
+                         scalar_qty=scalar[2], **{f: nodes.array(f) for f in nf})
+    out["nrt"], out["pods"] = nrt, pods
+    out["rc"] = nrt_resource_classes(hdr, False, extra_res)
+    return out
+
+
 def synth_pods(hdr: Header, n_pods: int, seed: int = SEED, device_res: int = -1, n_appgroups: int = 0,
                n_namespaces: int = 100, hugepage_res: int = -1, qos_p=(0.5, 0.4, 0.1), device2_res: int = -1, hugepage2_res: int = -1) -> Table:
     """`qos_p`: shares of Guaranteed / Burstable / BestEffort pods (50 / 40 / 10 %; experiments vary it).
@@ -284,14 +374,16 @@ RES_HUGEPAGES_1GI = 10  # "hugepages-1Gi"      (the six-slot workload: a cluster
 RES_DEVICE2 = 11        # a second extended resource
 
 
-def nrt_resource_classes(hdr: Header, wide: bool = False) -> Table:
-    flags = np.zeros(12 if wide else 10, dtype=np.uint8)
+def nrt_resource_classes(hdr: Header, wide: bool = False, extra_res: int = 0) -> Table:
+    flags = np.zeros(RES_EXTRA0 + extra_res if extra_res else (12 if wide else 10), dtype=np.uint8)
     flags[[0, 1, 2, 3, 4]] = 2              # native
     flags[RES_HUGEPAGES_2MI] = 1 | 2 | 4    # hugepage, native, scalar
     flags[RES_DEVICE] = 4                   # extended: not native, scalar
     if wide:
         flags[RES_HUGEPAGES_1GI] = 1 | 2 | 4
         flags[RES_DEVICE2] = 4
+    for k in range(extra_res):
+        flags[RES_EXTRA0 + k] = (1 | 2 | 4) if extra_resource_is_hugepage(k) else 4
     return Table(hdr, "spx_resource_classes", n_res=len(flags), flags=flags)
 
 
@@ -383,10 +475,12 @@ def synth_nrt(hdr: Header, nodes: Table, seed: int = SEED, n_zones: int = 8, var
 
 
 def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary: bool = True, wide: bool = False,
-                 long_frac: float = 0.0, long_ctrs=(9, 40)) -> Dict[str, Table]:
+                 long_frac: float = 0.0, long_ctrs=(9, 40), extra_res: int = 0, extra_req_frac: float = 0.15) -> Dict[str, Table]:
     """Object tables for BASELINE.json config #3 (NRT Filter+Score, 8 NUMA zones).  `wide`: six resource slots (cpu, memory,
     hugepages-2Mi, hugepages-1Gi, two extended resources) instead of four — the kernels' 8-slot instantiations.  `long_frac`: that
-    share of the pods gets long_ctrs[0]..long_ctrs[1] containers (lengthen_pods); 0 leaves the snapshot as it always was."""
+    share of the pods gets long_ctrs[0]..long_ctrs[1] containers (lengthen_pods); 0 leaves the snapshot as it always was.
+    `extra_res`: that many more resources (ids RES_EXTRA0.., hugepage sizes and extended device pools) reported by a random subset of
+    node allocatables and zones and requested by a share extra_req_frac of the pods (_widen_nrt); 0 leaves the snapshot unchanged."""
     nodes = synth_nodes(hdr, n_nodes, seed, device_res=RES_DEVICE)
     # node-level allocatable must list hugepages too (util.ResourceList key check, filter.go:110-116)
     rng = np.random.default_rng(seed + 6)
@@ -406,15 +500,19 @@ def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary:
                       device2_res=RES_DEVICE2 if wide else -1, hugepage2_res=RES_HUGEPAGES_1GI if wide else -1)
     if long_frac > 0:
         pods = lengthen_pods(hdr, pods, long_frac, seed, *long_ctrs)
+    scalar = (ptr, res.reshape(-1)[sel], qty.reshape(-1)[sel])
+    nrt = synth_nrt(hdr, nodes, seed, vary=vary, wide=wide)
+    if extra_res > 0:
+        scalar, nrt, pods = _widen_nrt(hdr, scalar, nrt, pods, extra_res, seed, extra_req_frac)
     nodes = Table(hdr, "spx_node_objects", n_nodes=N, alloc_cpu_milli=nodes.array("alloc_cpu_milli"),
                   alloc_mem=nodes.array("alloc_mem"), alloc_eph=nodes.array("alloc_eph"), alloc_pods=nodes.array("alloc_pods"),
-                  scalar_ptr=ptr, scalar_res=res.reshape(-1)[sel], scalar_qty=qty.reshape(-1)[sel],
+                  scalar_ptr=scalar[0], scalar_res=scalar[1], scalar_qty=scalar[2],
                   cap_cpu_milli=nodes.array("cap_cpu_milli"), region=nodes.array("region"), zone=nodes.array("zone"))
     return {
         "nodes": nodes,
         "pods": pods,
-        "nrt": synth_nrt(hdr, nodes, seed, vary=vary, wide=wide),
-        "rc": nrt_resource_classes(hdr, wide),
+        "nrt": nrt,
+        "rc": nrt_resource_classes(hdr, wide, extra_res),
     }
 
 
