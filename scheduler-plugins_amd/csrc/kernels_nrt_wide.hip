@@ -10,60 +10,28 @@
 // Container scope charges each app container to the NUMA id it fits (subtractResourcesFromNUMANodeList) and LeastNUMANodes charges each
 // container to its chosen subset (subtractFromNUMAs).  A lane records each container's choice as one byte in LDS (rec[c][lane]: the
 // chosen id | 0x80, or the subset's position mask); the quantity of slot s a later container sees is the table's, replayed through the
-// earlier containers' records that name s.  Every slot evolves on its own, so the replay is exact.  Integer arithmetic as
-// kernels_nrt_long.hip (int64; container scope divides the sum over all containers by their count).
+// earlier containers' records that name s.  Every slot evolves on its own, so the replay is exact.  Integer arithmetic in int64;
+// container scope divides the sum over all containers by their count.
+//
+// A different algorithm from the dense kernels' (lists, not a table per lane), so fits_any / zone_score / numa_nodes_required here are its
+// own.  What is the same — the subset table, div_le100, value_of, normalize_score, the packed NUMA ids, the strategy groups and the write
+// of a cell — comes from nrt_ref_device.h.
 //
 // Reference: pkg/noderesourcetopology/filter.go:42-258, score.go:62-191, least_numa.go:35-233, least_allocated.go,
 // most_allocated.go, balanced_allocation.go, numaresources.go:105-215.
-#include "spx_internal.h"
+#include "nrt_ref_device.h"
 
 namespace spx {
 
 namespace {
 
-constexpr int kZ = SPX_NRT_MAX_ZONES;
 constexpr int kMaxCtrs = SPX_NRT_WIDE_MAX_CTRS;
 constexpr int kBlock = 256;
 constexpr int kCache = 4;        // LeastNUMANodes: requested slots whose zone quantities a lane holds during the subset search
-constexpr int kSgAlloc = 0;      // LeastAllocated / MostAllocated
-constexpr int kSgBalanced = 1;   // BalancedAllocation
-constexpr int kSgLeastNuma = 2;  // LeastNUMANodes
 constexpr int kNoReplay = 0;     // the table's quantities
 constexpr int kFilterReplay = 1; // less the app containers charged before (Filter, container scope)
 constexpr int kGreedyReplay = 2; // less the subsets the containers before took (LeastNUMANodes, container scope)
 constexpr uint32_t kApplied = 0x80u;
-
-// combin.Combinations(n, k) for n <= 8 as bitmasks over list positions, size-major then lexicographic (as kernels_nrt_long.hip)
-struct WideCombo {
-  uint8_t mask[kZ][256];
-  uint8_t start[kZ][kZ + 2];  // start[n-1][k-1] .. start[n-1][k]: subsets of size k
-};
-
-constexpr WideCombo make_wide_combos() {
-  WideCombo t{};
-  for (int n = 1; n <= kZ; ++n) {
-    int idx = 0;
-    for (int k = 1; k <= n; ++k) {
-      t.start[n - 1][k - 1] = static_cast<uint8_t>(idx);
-      int c[kZ] = {};
-      for (int i = 0; i < k; ++i) c[i] = i;
-      while (true) {
-        int m = 0;
-        for (int i = 0; i < k; ++i) m |= 1 << c[i];
-        t.mask[n - 1][idx++] = static_cast<uint8_t>(m);
-        int i = k - 1;
-        while (i >= 0 && c[i] == n - k + i) --i;
-        if (i < 0) break;
-        ++c[i];
-        for (int j = i + 1; j < k; ++j) c[j] = c[j - 1] + 1;
-      }
-    }
-    t.start[n - 1][n] = static_cast<uint8_t>(idx);
-  }
-  return t;
-}
-
-__constant__ WideCombo kWideCombo = make_wide_combos();
 
 // a wave-uniform request list: entries in ascending slot order
 struct WList {
@@ -81,11 +49,11 @@ __device__ __forceinline__ uint32_t list_mask(const WList& l) {
 // the lane's node: NUMA ids and per-zone presence masks (the zone quantities stay in memory)
 struct WideNode {
   int64_t n;
-  uint32_t id_lo, id_hi;  // NUMA id per list position, 8 bits each
-  uint32_t zp[kZ];        // per-zone resource-presence mask
+  ZoneIds ids;
+  uint32_t zp[kZ];  // per-zone resource-presence mask
   int nz;
   uint32_t node_present;
-  __device__ __forceinline__ uint32_t id(int z) const { return ((z < 4 ? id_lo >> (8 * z) : id_hi >> (8 * (z - 4))) & 0xffu); }
+  __device__ __forceinline__ uint32_t id(int z) const { return ids.id(z); }
   __device__ __forceinline__ bool reports(int z, int s) const { return z < nz && ((zp[z] >> s) & 1u); }
 };
 
@@ -178,20 +146,6 @@ __device__ __forceinline__ bool fits_any(const WideNode& ns, const NrtWideArgs& 
   }
   *numa_id = bitmask ? static_cast<uint32_t>(__builtin_ctzll(bitmask)) : 0u;
   return ok && bitmask != 0;
-}
-
-// floor(num / den) for 0 <= num <= 101 * den: float estimate + exact fix-up (as kernels_nrt_long.hip)
-__device__ __forceinline__ int64_t div_le100(uint64_t num, uint64_t den) {
-  const float qf = static_cast<float>(num) * __frcp_rn(static_cast<float>(den));
-  uint64_t q = static_cast<uint64_t>(static_cast<uint32_t>(qf));
-  const uint64_t prod = q * den;
-  if (prod > num) --q;
-  else if (num - prod >= den) ++q;
-  return static_cast<int64_t>(q);
-}
-
-__device__ __forceinline__ int64_t value_of(bool is_cpu, int64_t q) {  // Quantity.Value(): cpu is in millicores
-  return is_cpu ? (q + 999) / 1000 : q;
 }
 
 __device__ __forceinline__ double balanced_fraction(const WideNode& ns, const NrtWideArgs& a, int z, int s, int64_t q) {
@@ -293,8 +247,8 @@ __device__ uint32_t numa_nodes_required(const WideNode& ns, const NrtWideArgs& a
     }
   }
   const int e_rest = e;
-  const uint8_t* masks = kWideCombo.mask[ns.nz - 1];
-  const uint8_t* start = kWideCombo.start[ns.nz - 1];
+  const uint8_t* masks = kCombo.mask[ns.nz - 1];
+  const uint8_t* start = kCombo.start[ns.nz - 1];
   for (int k = 1; k <= ns.nz; ++k) {
     const float min_avg = a.min_avg[static_cast<int64_t>(k - 1) * a.n_nodes + ns.n];
     uint32_t best = 0;
@@ -347,12 +301,6 @@ __device__ uint32_t numa_nodes_required(const WideNode& ns, const NrtWideArgs& a
   return 0;
 }
 
-__device__ __forceinline__ int64_t normalize_score(int count, bool is_min, int max_numa) {  // least_numa.go:90-100
-  const int64_t numa_node_score = 100 / static_cast<int64_t>(max_numa);
-  const int64_t score = 100 - static_cast<int64_t>(count) * numa_node_score;
-  return is_min ? score + numa_node_score / 2 : score;
-}
-
 __device__ __forceinline__ uint32_t ids_of(const WideNode& ns, uint32_t pos_mask) {  // the low 8 bits: list positions < 8
   uint32_t bits = 0;
 #pragma unroll
@@ -387,13 +335,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_nrt_wide(NrtWideArgs a, int group
   ns.nz = in ? a.n_zones[n] : 0;
   ns.node_present = in ? a.node_present[n] : 0u;
   const int max_numa = in ? a.max_numa[n] : 8;
-  ns.id_lo = ns.id_hi = 0;
+  ns.ids.lo = ns.ids.hi = 0;
 #pragma unroll
   for (int z = 0; z < kZ; ++z) {
     const uint32_t idv = in ? a.zone_id[static_cast<int64_t>(z) * a.n_nodes + n] : 0u;
     ns.zp[z] = in ? a.zone_present[static_cast<int64_t>(z) * a.n_nodes + n] : 0u;
-    if (z < 4) ns.id_lo |= idv << (8 * z);
-    else ns.id_hi |= idv << (8 * (z - 4));
+    ns.ids.set(z, idv);
   }
   const bool fresh = nflags & SPX_NRT_F_FRESH;
   const bool has_nrt = nflags & SPX_NRT_F_HAS_NRT;
@@ -486,15 +433,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_nrt_wide(NrtWideArgs a, int group
     score = n_ctr > 0 ? sum / n_ctr : 0;
   }
 
-  if (!in) return;
-  if (a.out_raw != nullptr) {  // parity harness: the int64 Score() value, one row
-    a.out_raw[n] = score;
-  } else {
-    const int64_t cell = pod * a.row_stride + n;
-    a.out_status[cell] = static_cast<uint8_t>(status);
-    score = score < 0 ? 0 : (score > 255 ? 255 : score);
-    a.out_score[cell] = static_cast<uint8_t>(score);
-  }
+  write_cell(a, in, pod, n, status, score);
 }
 
 }  // namespace

@@ -337,9 +337,27 @@ size_t nrt_window_sort_bytes(int64_t n_nodes, size_t* rank_bytes);
 void launch_nrt_window_sort(const NrtArgs& a, double* wsort, uint16_t* wrank, hipStream_t s);
 void launch_nrt_pk_tab_build(const NrtArgs& a, int n_tiles, hipStream_t s);  // kernels_nrt_fast.hip: the packed Score's table of exceptions
 
-// combin.Combinations(8, k) for k = 1..8 as bitmasks over list positions, size-major then lexicographic — the order
-// least_numa.go:167-208 walks.  Subsets of a node with fewer zones are the entries without high positions, in the same
-// relative order.  Shared by the engine (per-node distance table) and the float64 LeastNUMANodes kernel.
+// combin.Combinations(n, k), n <= 8, as bitmasks over list positions in lexicographic order — the order least_numa.go:167-208
+// walks — written to out; returns their number.  The one subset generator: Combo8 below and the reference-arithmetic kernels'
+// table (nrt_ref_device.h) are filled by it.
+constexpr int nrt_combinations(int n, int k, uint8_t* out) {
+  int cnt = 0;
+  int c[8] = {};
+  for (int i = 0; i < k; ++i) c[i] = i;
+  while (true) {
+    int m = 0;
+    for (int i = 0; i < k; ++i) m |= 1 << c[i];
+    out[cnt++] = static_cast<uint8_t>(m);
+    int i = k - 1;
+    while (i >= 0 && c[i] == n - k + i) --i;
+    if (i < 0) break;
+    ++c[i];
+    for (int j = i + 1; j < k; ++j) c[j] = c[j - 1] + 1;
+  }
+  return cnt;
+}
+// The subsets of 8 positions for k = 1..8, size-major.  Subsets of a node with fewer zones are the entries without high
+// positions, in the same relative order.  Shared by the engine (per-node distance table) and the float64 LeastNUMANodes kernel.
 struct Combo8 {
   uint8_t mask[256];
   uint8_t start[10];  // start[k-1] .. start[k]: subsets of size k
@@ -349,18 +367,7 @@ constexpr Combo8 make_combo8() {
   int idx = 0;
   for (int k = 1; k <= 8; ++k) {
     t.start[k - 1] = static_cast<uint8_t>(idx);
-    int c[8] = {};
-    for (int i = 0; i < k; ++i) c[i] = i;
-    while (true) {
-      int m = 0;
-      for (int i = 0; i < k; ++i) m |= 1 << c[i];
-      t.mask[idx++] = static_cast<uint8_t>(m);
-      int i = k - 1;
-      while (i >= 0 && c[i] == 8 - k + i) --i;
-      if (i < 0) break;
-      ++c[i];
-      for (int j = i + 1; j < k; ++j) c[j] = c[j - 1] + 1;
-    }
+    idx += nrt_combinations(8, k, t.mask + idx);
   }
   t.start[8] = static_cast<uint8_t>(idx);  // 255
   return t;
