@@ -844,6 +844,17 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
  *                              recomputed in float64 by a second launch); 0 = the Filter launch and the Score launch.  Same tables either way
  *   SPX_OPT_NRT_WIDE           1 = spx_load_nrt / spx_load_profile take the wide NRT tables (kernels_nrt_wide.hip) for a snapshot of 8 or
  *                              fewer resource slots too; 0 (default) = only above 8 slots.  Read at the load, not at the launch
+ *   SPX_OPT_ALLOC_TABLE_KEEP   1 (default) = an spx_eval with no Filter plugin and no feasibility mask in play does not write rows of
+ *                              NodeResourcesAllocatable's engine-owned score table that already hold what it would write: without a Filter the
+ *                              table is one normalised row repeated for every pod (allocatable.go:118-126 never reads the pod), so it changes
+ *                              only when the node allocatable columns or spx_set_allocatable_params change that row — not with a new pod
+ *                              batch, a load-watcher delta, or a node re-list that leaves the row as it was.  The engine records which rows
+ *                              hold the row in place; the masked normalisations, spx_bind_score_table and a reallocation reset the record, and
+ *                              a bound (caller-owned) table is always written.  A caller that writes into the engine-owned table through the
+ *                              pointer of spx_score_table sets the option to 0.  The record is made when the writing launch is issued and
+ *                              assumes that issued launches execute: a caller that captures spx_eval into a graph of its own and does not
+ *                              replay it sets the option to 0 as well.  0 = every spx_eval writes the rows.  Same tables either
+ *                              way; spx_alloc_table_path reports what the last spx_eval did
  */
 #define SPX_OPT_ROW_ALIGN 0
 #define SPX_OPT_REFERENCE_KERNELS 1
@@ -865,7 +876,8 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
 #define SPX_OPT_PEAKS_ESTIMATE 17
 #define SPX_OPT_NRT_FUSED 18
 #define SPX_OPT_NRT_WIDE 19
-#define SPX_NUM_OPTIONS 20
+#define SPX_OPT_ALLOC_TABLE_KEEP 20
+#define SPX_NUM_OPTIONS 21
 int spx_set_option(spx_engine* e, int option, int64_t value);
 int spx_get_option(const spx_engine* e, int option, int64_t* value);
 
@@ -919,6 +931,11 @@ int spx_commit_path(const spx_engine* e);
  * kernel), 2 = rank space (SPX_OPT_NRT_RANK_FILTER: whole-batch sweeps), 3 = rank space inside the fused Filter + Score launch
  * (SPX_OPT_NRT_FUSED), 4 = the wide tables' sweep (kernels_nrt_wide.hip); 0 = none yet */
 int spx_nrt_filter_path(const spx_engine* e);
+/* What the last spx_eval on this engine (those spx_decide and spx_commit_sequential issue included) did with NodeResourcesAllocatable's
+ * score table: 1 = wrote the rows (the broadcast row, or the feasibility-aware normalisation with Filter plugins in play), 2 = kept
+ * them (SPX_OPT_ALLOC_TABLE_KEEP: they already held the row in place, no Allocatable store was issued); 0 = Allocatable was not in
+ * the mask, its normalisation was folded into spx_decide's argmax, or no spx_eval has run */
+int spx_alloc_table_path(const spx_engine* e);
 /* SPX_OPT_NRT_PACKED_SCORE with the uploaded tables and parameters: 0 = the LeastAllocated Score launch keeps float64 (other strategy,
  * large weights, a slot that qualifies neither way, option off); else bit 24 set, bits 0..15 = the weighted slots (positions of the
  * uploaded slot table) that are packed unconditionally, bits 16..23 = 1 + the slot that goes through the per-launch table, 0 = none */

@@ -41,6 +41,15 @@ __global__ __launch_bounds__(256) void k_net_append(int64_t n, const int32_t* __
   dst_max[pos[i]] = cost[i];
 }
 
+// Allocatable's normalised row after a re-upload against the row before it (prepare_alloc): a node re-list that leaves the row as it
+// was keeps the score table that broadcasts it.  One workgroup: the row is O(10^4) bytes.
+__global__ __launch_bounds__(1024) void k_rows_equal(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, int64_t words, uint32_t* __restrict__ flag) {
+  int differs = 0;
+  for (int64_t i = threadIdx.x; i < words; i += 1024) differs |= a[i] != b[i];
+  differs = __syncthreads_or(differs);
+  if (threadIdx.x == 0) *flag = differs ? 0u : 1u;
+}
+
 __global__ __launch_bounds__(256) void k_nrt_derive_rows(NrtDeltaArgs a) {
   constexpr int Z = SPX_NRT_MAX_ZONES;
   const int R = a.n_res;
@@ -95,6 +104,10 @@ void launch_scatter_rows_rowmajor(void* dst, int inner, const int32_t* idx, cons
   const dim3 grid(static_cast<unsigned>((n + 255) / 256)), block(256);
   if (elem_bytes == 1) hipLaunchKernelGGL(k_scatter_rows_rm<uint8_t>, grid, block, 0, s, static_cast<uint8_t*>(dst), inner, idx, static_cast<const uint8_t*>(src), n_rows);
   else hipLaunchKernelGGL(k_scatter_rows_rm<uint64_t>, grid, block, 0, s, static_cast<uint64_t*>(dst), inner, idx, static_cast<const uint64_t*>(src), n_rows);
+}
+
+void launch_rows_equal(const uint8_t* a, const uint8_t* b, int64_t bytes, uint32_t* flag, hipStream_t s) {
+  hipLaunchKernelGGL(k_rows_equal, dim3(1), dim3(1024), 0, s, reinterpret_cast<const uint32_t*>(a), reinterpret_cast<const uint32_t*>(b), bytes / 4, flag);
 }
 
 void launch_net_append(int64_t n, const int32_t* pos, const int32_t* node, const int64_t* cost, int32_t* dst_node, int64_t* dst_max, hipStream_t s) {

@@ -60,7 +60,7 @@ struct spx_engine {
   int64_t row_stride = 0;
 
   // spx_set_option state (per engine; nothing is read from the environment)
-  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0};
+  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0, 1};
 
   // params
   int32_t alloc_mode = SPX_MODE_LEAST;
@@ -74,6 +74,8 @@ struct spx_engine {
   DevBuf d_alloc, d_alloc_w, d_alloc_raw, d_alloc_norm, d_alloc_rel;
   int32_t alloc_n_res = 0;
   bool alloc_ready = false;  // raw/norm computed for the current table + params
+  DevBuf d_alloc_prev;       // the d_alloc_norm before the last recomputation (prepare_alloc compares the two)
+  uint64_t alloc_epoch = 0;  // generation of d_alloc_norm's content: prepare_alloc bumps it when the row it computes differs from the one before
   DevBuf d_cap_cpu, d_tlp_util, d_tlp_missing, d_tlp_valid;
   DevBuf d_lv_acpu, d_lv_amem, d_lv_cavg, d_lv_cstd, d_lv_mavg, d_lv_mstd, d_lv_flags;
   bool tri_nodes = false;
@@ -241,6 +243,18 @@ struct spx_engine {
     uint64_t ext_gen = 0;
   } eval_info[SPX_NUM_PLUGINS];
   uint64_t ext_gen = 0;
+  // SPX_OPT_ALLOC_TABLE_KEEP: the rows of Allocatable's engine-owned score table that hold the unmasked broadcast of d_alloc_norm —
+  // which buffer and stride they were written to and from which generation of the row (alloc_epoch).  Recorded by spx_eval once the
+  // launch that writes them has been issued; an spx_eval whose rows lie inside, with the same buffer, stride and epoch, leaves
+  // Allocatable's stores out of the sweep.  Buffer, stride and epoch are compared at use; everything else that writes into the
+  // table (the masked normalisations, a bound table, a reallocation) resets the record: alloc_table_dirty.
+  struct AllocKept {
+    int64_t begin = 0, end = 0;
+    const void* buf = nullptr;
+    int64_t stride = 0;
+    uint64_t epoch = 0;
+  } alloc_kept;
+  int last_alloc_table = 0;  // spx_alloc_table_path
 };
 
 
@@ -323,6 +337,9 @@ int set_pods(spx_engine* e, int64_t p) {
   return SPX_OK;
 }
 
+// something other than the unmasked broadcast wrote (or may have written) into Allocatable's score table, or the buffer changed
+void alloc_table_dirty(spx_engine* e) { e->alloc_kept = spx_engine::AllocKept{}; }
+
 int ensure_score_table(spx_engine* e, int plugin) {
   DevBuf& b = e->score[plugin];
   if (b.external) {
@@ -330,7 +347,9 @@ int ensure_score_table(spx_engine* e, int plugin) {
       return fail(e, SPX_ERR_STATE, "bound score table is smaller than n_pods x row_stride");
     return SPX_OK;
   }
+  const size_t had = b.p ? b.bytes : 0;
   int rc = ensure(e, b, static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride));
+  if (plugin == SPX_PLUGIN_ALLOCATABLE && (rc || b.bytes != had)) alloc_table_dirty(e);  // (a new allocation may come back at the old address)
   if (rc) return rc;
   e->score_rows[plugin] = e->n_pods;
   e->score_stride[plugin] = e->row_stride;
@@ -369,7 +388,18 @@ int prepare_alloc(spx_engine* e) {
   if (rc) return rc;
   if ((rc = ensure(e, e->d_alloc_raw, static_cast<size_t>(e->n_nodes) * sizeof(int64_t)))) return rc;
   if ((rc = ensure(e, e->d_alloc_rel, static_cast<size_t>(e->row_stride + 4) * sizeof(uint32_t)))) return rc;
+  // (The comparison is a launch of its own, kernels_delta.hip's k_rows_equal, on a copy of the old row — not a few lines inside
+  // k_alloc_prepare, which has both rows in hand: that kernel lives in kernels_trimaran.hip, whose machine code stamps the counter
+  // profiles of every trimaran workload, and this runs once per node table, off the sweep.)
+  // the row in place (if one was ever computed) is set aside: a recomputation that ends with the same row — a node re-list with
+  // unchanged allocatable — keeps alloc_epoch, and with it the score table that broadcasts the row (SPX_OPT_ALLOC_TABLE_KEEP)
+  const bool had_norm = e->alloc_epoch != 0 && e->d_alloc_norm.p && e->d_alloc_norm.bytes >= static_cast<size_t>(e->row_stride);
   if ((rc = ensure(e, e->d_alloc_norm, static_cast<size_t>(e->row_stride)))) return rc;
+  if (had_norm) {
+    if ((rc = ensure(e, e->d_alloc_prev, static_cast<size_t>(e->row_stride)))) return rc;
+    SPX_HIP(e, hipMemcpyAsync(e->d_alloc_prev.p, e->d_alloc_norm.p, static_cast<size_t>(e->row_stride), hipMemcpyDeviceToDevice, e->stream));
+  }
+  const uint64_t epoch_before = e->alloc_epoch++;  // a failure below leaves the row unknown: the old epoch comes back only once the rows are known to agree
   spx::AllocPrepArgs a{};
   a.n_nodes = e->n_nodes;
   a.row_stride = e->row_stride;
@@ -382,10 +412,17 @@ int prepare_alloc(spx_engine* e) {
   a.norm = static_cast<uint8_t*>(e->d_alloc_norm.p);
   spx::launch_alloc_prepare(a, e->stream);
   SPX_HIP(e, hipGetLastError());
-  uint32_t compact = 0;  // once per node table: the flag the kernel leaves behind the offsets
-  SPX_HIP(e, hipMemcpyAsync(&compact, static_cast<const uint32_t*>(e->d_alloc_rel.p) + e->row_stride, sizeof compact, hipMemcpyDeviceToHost, e->stream));
+  uint32_t* const flags = static_cast<uint32_t*>(e->d_alloc_rel.p) + e->row_stride;
+  if (had_norm) {
+    spx::launch_rows_equal(a.norm, static_cast<const uint8_t*>(e->d_alloc_prev.p), e->row_stride, flags + 1, e->stream);
+    SPX_HIP(e, hipGetLastError());
+  }
+  // once per node table, in one copy: the flag the kernel leaves behind the offsets, and behind it "the row is the one before"
+  uint32_t back[2] = {0, 0};
+  SPX_HIP(e, hipMemcpyAsync(back, flags, had_norm ? sizeof back : sizeof back[0], hipMemcpyDeviceToHost, e->stream));
   SPX_HIP(e, hipStreamSynchronize(e->stream));
-  e->alloc_compact = compact != 0;
+  e->alloc_compact = back[0] != 0;
+  if (had_norm && back[1] != 0) e->alloc_epoch = epoch_before;
   e->alloc_ready = true;
   return SPX_OK;
 }

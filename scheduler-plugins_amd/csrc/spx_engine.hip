@@ -56,7 +56,7 @@ int spx_destroy(spx_engine* e) {
   if (!e) return SPX_OK;
   (void)hipSetDevice(e->device);
   (void)hipStreamSynchronize(e->stream);
-  DevBuf* bufs[] = {&e->d_alloc,   &e->d_alloc_w,  &e->d_alloc_raw, &e->d_alloc_norm, &e->d_alloc_rel, &e->d_cap_cpu, &e->d_tlp_util,
+  DevBuf* bufs[] = {&e->d_alloc,   &e->d_alloc_w,  &e->d_alloc_raw, &e->d_alloc_norm, &e->d_alloc_rel, &e->d_alloc_prev, &e->d_cap_cpu, &e->d_tlp_util,
                     &e->d_tlp_missing, &e->d_tlp_valid, &e->d_lv_acpu, &e->d_lv_amem, &e->d_lv_cavg, &e->d_lv_cstd,
                     &e->d_lv_mavg, &e->d_lv_mstd,  &e->d_lv_flags,  &e->d_tlp_pod,    &e->d_lv_rcpu, &e->d_lv_rmem,
                     &e->d_raw_row,   &e->d_lv_exact, &e->d_lv_fast, &e->d_tlp_fast, &e->d_tlp_amb, &e->d_lv_amb, &e->d_nrt_pk_tab, &e->d_commit, &e->d_nrt_flags, &e->d_nrt_max_numa, &e->d_nrt_nz, &e->d_nrt_zid, &e->d_nrt_zp,
@@ -135,6 +135,7 @@ int spx_set_option(spx_engine* e, int option, int64_t value) {
     case SPX_OPT_NRT_RANK_NARROW:
     case SPX_OPT_NRT_FUSED:
     case SPX_OPT_NRT_WIDE:
+    case SPX_OPT_ALLOC_TABLE_KEEP:
       if (value != 0 && value != 1) return fail(e, SPX_ERR_ARG, "option takes 0 or 1");
       break;
     case SPX_OPT_NRT_LN_LIST_PERMILLE:
@@ -274,6 +275,19 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   const bool masked = N || W || e->ext_mask;
   bool alloc_by_net = false;  // Allocatable's masked table written by the NetworkOverhead sweep (SPX_OPT_NET_ALLOC_FUSED)
   a.out_alloc = (A && !masked) ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p) : nullptr;
+  // the unmasked table is the broadcast of d_alloc_norm, whatever the pod batch: rows that already hold the broadcast of the row in
+  // place are not written again (SPX_OPT_ALLOC_TABLE_KEEP) — the sweeps run their instantiations without Allocatable's stores.
+  // Only in an engine-owned table (a bound one is the caller's memory), and not for the commit loop's device-side row.
+  const DevBuf& alloc_table = e->score[SPX_PLUGIN_ALLOCATABLE];
+  const bool alloc_keepable = a.out_alloc && !alloc_table.external && !e->row_indirect;
+  bool alloc_kept_now = false;
+  if (alloc_keepable && e->option[SPX_OPT_ALLOC_TABLE_KEEP] && row_end > row_begin) {
+    const spx_engine::AllocKept& k = e->alloc_kept;
+    alloc_kept_now = k.buf == alloc_table.p && k.stride == e->score_stride[SPX_PLUGIN_ALLOCATABLE] && k.epoch == e->alloc_epoch && k.end > k.begin &&
+                     row_begin >= k.begin && row_end <= k.end;
+    if (alloc_kept_now) a.out_alloc = nullptr;
+  }
+  if (A && masked && !e->skip_alloc_masked) alloc_table_dirty(e);  // a masked normalisation is about to write these rows (launch_net or launch_alloc_masked)
   a.out_tlp = T ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_TLP].p) : nullptr;
   a.out_lvrb = L ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_LVRB].p) : nullptr;
   if (L) {
@@ -490,6 +504,19 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   }
   spx::launch_trimaran(a, e->stream);
   SPX_HIP(e, hipGetLastError());
+  e->last_alloc_table = !A ? 0 : masked ? (e->skip_alloc_masked ? 0 : 1) : (alloc_kept_now ? 2 : 1);
+  if (alloc_keepable && a.out_alloc && row_end > row_begin) {
+    // the launch that broadcasts the row into [row_begin, row_end) is on the stream: these rows join the record when they touch
+    // rows written to the same buffer from the same row (eval_info's rule), and replace it otherwise
+    spx_engine::AllocKept& k = e->alloc_kept;
+    const bool same = k.buf == alloc_table.p && k.stride == e->score_stride[SPX_PLUGIN_ALLOCATABLE] && k.epoch == e->alloc_epoch && k.end > k.begin;
+    if (same && row_begin <= k.end && row_end >= k.begin) {
+      k.begin = std::min(k.begin, row_begin);
+      k.end = std::max(k.end, row_end);
+    } else {
+      k = spx_engine::AllocKept{row_begin, row_end, alloc_table.p, e->score_stride[SPX_PLUGIN_ALLOCATABLE], e->alloc_epoch};
+    }
+  }
   if (R) {
     spx::LrocArgs la{};
     fill_lroc(e, la);
@@ -585,6 +612,8 @@ int spx_sync(spx_engine* e) {
 }
 
 int spx_nrt_filter_path(const spx_engine* e) { return e ? e->last_nrt_filter : 0; }
+
+int spx_alloc_table_path(const spx_engine* e) { return e ? e->last_alloc_table : 0; }
 
 int spx_nrt_wide(const spx_engine* e) { return e && e->nrt_wide ? 1 : 0; }
 
@@ -836,6 +865,7 @@ int spx_score_table(spx_engine* e, int plugin, void** dptr, int64_t* row_stride,
 int spx_bind_score_table(spx_engine* e, int plugin, void* dptr, int64_t row_stride, int64_t n_rows) {
   if (!e || plugin < 0 || plugin >= SPX_NUM_PLUGINS) return SPX_ERR_ARG;
   DevBuf& b = e->score[plugin];
+  if (plugin == SPX_PLUGIN_ALLOCATABLE) alloc_table_dirty(e);  // another buffer from here on (a bound one is never kept: the caller owns it)
   if (!dptr) {  // unbind
     if (b.external) b = DevBuf{};
     e->score_rows[plugin] = e->score_stride[plugin] = 0;
