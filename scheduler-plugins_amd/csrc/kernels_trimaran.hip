@@ -455,10 +455,11 @@ __device__ __forceinline__ uint32_t tlp_cell_exact(const TrimaranArgs& a, int64_
 // AMB (round 5): the ambiguity bookkeeping leaves the cell.  Which (node, pod value) pairs can be ambiguous is a property of the
 // node alone — the score is piecewise linear in the pod's integer millicores, so it comes within the tolerance of a rounding tie
 // only at isolated integers (k_tlp_amb_build lists them, per launch, as a bit per (pod value, node tile)).  A row whose pod value
-// has no such node in this wave's tile runs the streamlined cell: add, add, compare, fma, select, v_cvt_pk_u8_f32 (which rounds to
-// nearest even and clamps by itself: tools/micro/cvt_pk_u8.hip) — 5 instructions instead of ~9.5; the other rows (~8 % of the
-// (row, tile) pairs on continuous inputs), rows of pods outside the table and waves holding an always-exact node take the
-// checked cell exactly as before.
+// has no such node in this wave's tile runs the streamlined cell: add, add, sign mask, fma, bit select, v_cvt_pk_u8_f32 (which rounds
+// to nearest even and clamps by itself: tools/micro/cvt_pk_u8.hip) — 5 instructions instead of ~9.5, issued stage by stage over four
+// pairs of cells (round 8, see the row loop); the other rows (~8 % of the (row, tile) pairs on continuous inputs), rows of pods
+// outside the table and waves holding an always-exact node take the checked cell exactly as before.  Which rows those are is one
+// 64-bit mask per chunk, tested with scalar instructions.
 template <int NPL, bool A, bool D = false, bool AMB = false>
 __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(TrimaranArgs a, int n_tiles, double c1, double c2, DecideArgs dec) {
   SPX_RESOLVE_ROWS(a);
@@ -524,6 +525,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
       b2l[j >> 1][j & 1] = v.y;
       kc[j] = F32x2{v.z, v.w};
     }
+    // one copy of the pairs: opaque, so that the streamlined row, the checked row and the exact path all read these registers (left
+    // alone the compiler kept the loaded records AND up to two differently ordered sets of pairs alive through the row loop)
+#pragma unroll
+    for (int k = 0; k < NPL / 2; ++k) asm("" : "+v"(b2h[k]), "+v"(b2l[k]));
   }
   // no early exit for lanes past the row: every lane stays live so that the v_readlane broadcasts below always read
   // registers that were written under a full exec mask (stores are guarded by `active` instead)
@@ -532,37 +537,76 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
   unsigned reevaluated = 0;  // cells this lane sent through the exact path (spx_fetch_stats), flushed once per wave
   const bool wave_nan = AMB ? __ballot(lane_nan) != 0 : true;  // a node that always takes the exact path: every row of the wave is checked
 
+  // the chunk's rows classified once (wave-uniform, scalar): bit r set = row r takes the checked cell in this tile.  The ballot's
+  // sources are written by every lane (no early exit above), so the rule for v_readlane holds for it as well.
+  const uint64_t bad_rows = __ballot(pod_bad != 0);
+  const uint64_t slow_rows = (!AMB || wave_nan) ? ~0ull : __ballot((pod_slow | pod_bad) != 0);
+
   for (int r = 0; r < n_rows; ++r) {
     const int64_t row = (pod0 + r) * a.row_stride + node0;
     if constexpr (A && !D) {
       if (active) store_bytes<NPL>(a.out_alloc + row, alloc_w);
     }
     const float pod_f = __int_as_float(__builtin_amdgcn_readlane(pod_bits, r));
-    const bool row_bad = __builtin_amdgcn_readlane(pod_bad, r) != 0;
-    bool any = row_bad;
     uint32_t w[NPL / 4];
     uint32_t tb[D ? NPL : 1];  // decisions-only mode: the byte of each cell on its own (the table mode packs four per dword)
     const F32x2 pod2{pod_f, pod_f};
     const F32x2 off2{tf, 100.0f};
-    const bool row_slow = !AMB || wave_nan || __builtin_amdgcn_readlane(pod_slow, r) != 0;  // wave-uniform
+    const bool row_slow = ((slow_rows >> r) & 1ull) != 0;
     if (!row_slow) {
       // streamlined: no cell of this row in this tile can be ambiguous (k_tlp_amb_build), so the float32 value rounds to the
-      // reference's integer — nothing to track
+      // reference's integer — nothing to track.  Evaluated in groups of kStage pairs, stage by stage (first adds, second adds,
+      // sign masks, multiply-adds, selects, conversions): consecutive instructions belong to different pairs, so none waits on
+      // the one before it and the packed-float32 forwarding hazard costs no s_nop; sched_barrier keeps the stages apart (left to
+      // itself the scheduler re-serialises each pair to save registers).
+      //   The branch is picked by u's sign bit, m = u_bits >> 31 (arithmetic), x = (m & x12.y) | (~m & x12.x): v_ashrrev_i32 +
+      // v_bfi_b32, full rate, no vcc.  It picks what `__float_as_int(u) > 0` picks for every u except +0.0, which cannot reach this
+      // path: u = fl((p + b2h) + b2l) with the first add exact and the second rounding once is zero only if p + b2h + b2l is
+      // exactly zero, i.e. p = -b; k_tlp_amb_build lists every integer within 2e-6 of -b for the node's tile and a listed row is
+      // row_slow; a node with NaN constants makes wave_nan (every row slow); padding slots have b = 1e30.  The checked cell below
+      // keeps the compare.
+      constexpr int kStage = 4;  // pairs per group (8 pairs: 28 more registers live, past the 3-wave limit)
+      static_assert((NPL / 2) % kStage == 0 && kStage % 2 == 0, "whole groups of whole dwords");
 #pragma unroll
-      for (int j = 0; j < NPL / 4; ++j) {
-        uint32_t acc = 0;
+      for (int g = 0; g < NPL / 2; g += kStage) {
+        F32x2 u2[kStage], x12[2 * kStage];
+        int m[2 * kStage], xs[2 * kStage];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int i = j * 4 + q;
-          const F32x2 u2 = (pod2 + b2h[i >> 1]) + b2l[i >> 1];
-          const float u = u2[i & 1];
-          const bool gt = __float_as_int(u) > 0;
-          const F32x2 x12 = __builtin_elementwise_fma(kc[i], F32x2{u, u}, off2);
-          const float x = gt ? x12.x : x12.y;
-          if constexpr (D) tb[i] = __builtin_amdgcn_cvt_pk_u8_f32(x, 0, 0u);
-          else acc = __builtin_amdgcn_cvt_pk_u8_f32(x, q, acc);
+        for (int k = 0; k < kStage; ++k) u2[k] = pod2 + b2h[g + k];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < kStage; ++k) u2[k] = u2[k] + b2l[g + k];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 2 * kStage; ++c) {
+          m[c] = __float_as_int(u2[c >> 1][c & 1]) >> 31;
+          asm("" : "+v"(m[c]));  // opaque: otherwise the mask is folded back into compare + select
         }
-        w[j] = acc;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 2 * kStage; ++c) {
+          const float u = u2[c >> 1][c & 1];
+          x12[c] = __builtin_elementwise_fma(kc[2 * g + c], F32x2{u, u}, off2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 2 * kStage; ++c) xs[c] = (m[c] & __float_as_int(x12[c].y)) | (~m[c] & __float_as_int(x12[c].x));
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (D) {
+#pragma unroll
+          for (int c = 0; c < 2 * kStage; ++c) tb[2 * g + c] = __builtin_amdgcn_cvt_pk_u8_f32(__int_as_float(xs[c]), 0, 0u);
+        } else {
+          // byte q of every dword of the group before byte q + 1 of any: kStage / 2 independent chains
+          uint32_t acc[kStage / 2];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int d = 0; d < kStage / 2; ++d) acc[d] = __builtin_amdgcn_cvt_pk_u8_f32(__int_as_float(xs[4 * d + q]), q, q ? acc[d] : 0u);
+          }
+#pragma unroll
+          for (int d = 0; d < kStage / 2; ++d) w[g / 2 + d] = acc[d];
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
     } else {
     // one cell: rounded float32 score and whether it is provably the reference's result
@@ -578,6 +622,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
     // the row's worst rounding margin and smallest |u| as running float max/min (v_max3/v_min3: half an instruction per
     // cell) instead of 32 compares and a chain of lane-mask ORs; NaN cells (nodes outside the float32 range) are
     // invisible to max/min and are flagged per lane by lane_nan
+    const bool row_bad = ((bad_rows >> r) & 1ull) != 0;
+    bool any = row_bad;
     float worst = 0.0f, minu = 1e30f;
 #pragma unroll
     for (int j = 0; j < NPL / 4; ++j) {

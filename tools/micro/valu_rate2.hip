@@ -47,12 +47,20 @@
   X(37, "v_cvt_u32_f32", "v_cvt_u32_f32 %1, %5\n\t")                     \
   X(38, "v_rndne_f32", "v_rndne_f32 %1, %5\n\t")                         \
   X(39, "v_fract_f32", "v_fract_f32 %1, %5\n\t")                         \
-  X(40, "v_cmp_le_f32 + v_addc", "v_cmp_le_f32 vcc, %5, %6\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc\n\t") \
-  X(41, "v_cmp_le_u32 + v_addc", "v_cmp_le_u32 vcc, %5, %6\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc\n\t") \
-  X(42, "v_sub_u32 + v_alignbit", "v_sub_u32 %2, %5, %6\n\tv_alignbit_b32 %1, %1, %2, 31\n\t") \
-  X(43, "v_sub_f32 + v_min_f32 (pair)", "v_sub_f32 %2, %5, %6\n\tv_min_f32 %1, %1, %2\n\t")
+  X(40, "v_ashrrev_i32", "v_ashrrev_i32 %1, 31, %5\n\t")                  \
+  X(41, "v_bfi_b32", "v_bfi_b32 %1, %5, %6, %6\n\t")                      \
+  X(42, "v_bitop3_b32", "v_bitop3_b32 %1, %5, %6, %6 bitop3:0xe4\n\t")    \
+  X(43, "v_cmp_lt_i32", "v_cmp_lt_i32 vcc, 0, %5\n\t")                    \
+  X(44, "v_cmp_le_f32 + v_addc", "v_cmp_le_f32 vcc, %5, %6\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc\n\t") \
+  X(45, "v_cmp_le_u32 + v_addc", "v_cmp_le_u32 vcc, %5, %6\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc\n\t") \
+  X(46, "v_sub_u32 + v_alignbit", "v_sub_u32 %2, %5, %6\n\tv_alignbit_b32 %1, %1, %2, 31\n\t") \
+  X(47, "v_sub_f32 + v_min_f32 (pair)", "v_sub_f32 %2, %5, %6\n\tv_min_f32 %1, %1, %2\n\t") \
+  X(48, "v_cmp_lt_i32 vcc, s_nop 1, v_cndmask", "v_cmp_lt_i32 vcc, 0, %5\n\ts_nop 1\n\tv_cndmask_b32 %1, %5, %6, vcc\n\t") \
+  X(49, "v_cmp_lt_i32 sgpr, s_nop 1, v_cndmask", "v_cmp_lt_i32 s[20:21], 0, %5\n\ts_nop 1\n\tv_cndmask_b32 %1, %5, %6, s[20:21]\n\t") \
+  X(50, "v_ashrrev_i32 + v_bitop3_b32", "v_ashrrev_i32 %2, 31, %5\n\tv_bitop3_b32 %1, %5, %6, %2 bitop3:0xe4\n\t") \
+  X(51, "v_ashrrev_i32 + v_bfi_b32", "v_ashrrev_i32 %2, 31, %5\n\tv_bfi_b32 %1, %2, %5, %6\n\t")
 
-constexpr int kPairFrom = 40;
+constexpr int kPairFrom = 44;  // from here on each entry is two VALU instructions (the select forms of k_tlp_fast2's streamlined cell: 48-51)
 
 template <int KIND>
 __global__ __launch_bounds__(256) void k_rate(double* out, int reps, double seed) {
