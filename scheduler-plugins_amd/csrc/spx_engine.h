@@ -1,6 +1,6 @@
 // spx_engine.h — the engine's state and the helpers its translation units share (round 6: csrc/spx_engine.hip, one file of 3 900 lines
-// in round 5, is now spx_engine.hip (lifecycle, options, parameters, evaluation, fetch), spx_uploads.hip (tables and deltas into HBM, the
-// one-call loaders) and spx_commit.hip (the one-pod-at-a-time loops)).  Not part of the ABI.  The helpers sit in an anonymous namespace:
+// in round 5, is now spx_engine.hip (lifecycle, options, parameters, evaluation, fetch), spx_uploads.hip (tables and deltas into HBM),
+// spx_loads.hip (the one-call loaders) and spx_commit.hip (the one-pod-at-a-time loops)).  Not part of the ABI.  The helpers sit in an anonymous namespace:
 // every translation unit gets its own copy of the small ones it uses; the three thread-local error slots exist once (spx_engine.hip).
 #pragma once
 
@@ -299,6 +299,16 @@ int upload(spx_engine* e, DevBuf& b, const void* src, size_t bytes) {
   int rc = ensure(e, b, bytes);
   if (rc) return rc;
   if (bytes) SPX_HIP(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream));
+  return SPX_OK;
+}
+
+// a pinned host buffer of at least `want` bytes; a buffer that has to grow is allocated with `slack` bytes to spare
+int ensure_pinned(spx_engine* e, void*& p, size_t& bytes, size_t want, size_t slack) {
+  if (bytes >= want) return SPX_OK;
+  if (p) SPX_HIP(e, hipHostFree(p));
+  p = nullptr, bytes = 0;
+  SPX_HIP(e, hipHostMalloc(&p, want + slack, hipHostMallocDefault));
+  bytes = want + slack;
   return SPX_OK;
 }
 

@@ -1,6 +1,6 @@
 // spx_engine.hip — the C-ABI engine of libspx.so: lifecycle, options and parameters, the evaluation (spx_eval, spx_decide, spx_eval_best)
-// and the fetch calls.  Tables and deltas into HBM: spx_uploads.hip; the one-pod-at-a-time loops: spx_commit.hip; shared state and
-// helpers: spx_engine.h.  See include/spx.h for the contract.
+// and the fetch calls.  Tables and deltas into HBM: spx_uploads.hip; the one-call loaders: spx_loads.hip; the one-pod-at-a-time loops:
+// spx_commit.hip; shared state and helpers: spx_engine.h.  See include/spx.h for the contract.
 //
 // There is deliberately no CPU fallback: spx_create() fails with SPX_ERR_NOGPU when no HIP device
 // is usable, and every compute entry point needs an engine.

@@ -1,7 +1,193 @@
-// spx_uploads.hip — tables into HBM: spx_upload_* (SoA columns), spx_update_* (snapshot deltas), the derived host-built streams of the
-// NRT sweeps (host/nrt_streams.cc), and spx_load_* / spx_load_profile (object tables -> SoA -> device inside the library).
-// Engine state and shared helpers: spx_engine.h.
+// spx_uploads.hip — tables into HBM: spx_upload_* (SoA columns), spx_update_* (snapshot deltas) and the derived host-built streams of the
+// NRT sweeps (host/nrt_streams.cc).  A full node table and a delta of its rows take one road: the helpers of the first namespace below.
+// The one-call loaders (object tables -> SoA -> these functions): spx_loads.hip.  Engine state and shared helpers: spx_engine.h.
 #include "spx_engine.h"
+
+#include <array>
+
+namespace {
+// one pinned blob for a delta's columns: [idx int32 n] then each column, 16-byte aligned; uploaded with one DMA
+struct DeltaBlob {
+  spx_engine* e;
+  size_t bytes = 0;
+  std::vector<std::pair<const void*, size_t>> parts;  // (source, bytes)
+  std::vector<size_t> offset;
+  size_t add(const void* src, size_t n) {
+    const size_t at = bytes;
+    parts.emplace_back(src, n);
+    offset.push_back(at);
+    bytes = (bytes + n + 15) & ~static_cast<size_t>(15);
+    return at;
+  }
+  int ship() {
+    if (int rc = ensure_pinned(e, e->h_stage, e->h_stage_bytes, bytes, 65536)) return rc;
+    for (size_t k = 0; k < parts.size(); ++k) {
+      char* dst = static_cast<char*>(e->h_stage) + offset[k];
+      const char* src = static_cast<const char*>(parts[k].first);
+      const int64_t blocks = static_cast<int64_t>((parts[k].second + 65535) / 65536);  // (a full node table: megabytes per column)
+      const size_t len = parts[k].second;
+      spx_host::parallel_rows(blocks, [&](int64_t b0, int64_t b1) {
+        const size_t at = static_cast<size_t>(b0) * 65536, end = std::min(len, static_cast<size_t>(b1) * 65536);
+        if (end > at) std::memcpy(dst + at, src + at, end - at);
+      }, 16);
+    }
+    return upload(e, e->d_delta, e->h_stage, bytes);
+  }
+  const char* dev(size_t at) const { return static_cast<const char*>(e->d_delta.p) + at; }
+};
+
+// an index listed twice would be scattered twice in no particular order — and the columns that travel with the rows (the float64
+// images, the host copies, a presence column) could end up describing different rows of the delta: refused
+int refuse_duplicates(spx_engine* e, const int32_t* idx, int64_t n, const char* msg) {
+  std::vector<int32_t> sorted(idx, idx + n);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(e, SPX_ERR_ARG, msg);
+  return SPX_OK;
+}
+
+int delta_indices(spx_engine* e, const int64_t* idx, int64_t n_rows, std::vector<int32_t>& out) {
+  if (n_rows < 0 || (n_rows && !idx)) return fail(e, SPX_ERR_ARG, "delta: NULL index column");
+  out.resize(static_cast<size_t>(n_rows));
+  for (int64_t i = 0; i < n_rows; ++i) {
+    if (idx[i] < 0 || idx[i] >= e->n_nodes) return fail(e, SPX_ERR_ARG, "delta: node index out of range");
+    out[static_cast<size_t>(i)] = static_cast<int32_t>(idx[i]);
+  }
+  return refuse_duplicates(e, out.data(), n_rows, "delta: a node index is listed twice");
+}
+
+// the trimaran node table's columns, in the order they are shipped
+struct TriCol {
+  DevBuf* dst;
+  const void* src;
+  int bytes;  // per node
+};
+std::array<TriCol, 11> trimaran_cols(spx_engine* e, const spx_trimaran_nodes_soa* t) {
+  return {{{&e->d_cap_cpu, t->cap_cpu_milli, 8}, {&e->d_tlp_util, t->tlp_cpu_util, 8}, {&e->d_tlp_missing, t->tlp_missing_milli, 8}, {&e->d_tlp_valid, t->tlp_valid, 1},
+           {&e->d_lv_acpu, t->lv_alloc_cpu_milli, 8}, {&e->d_lv_amem, t->lv_alloc_mem, 8}, {&e->d_lv_cavg, t->lv_cpu_avg, 8}, {&e->d_lv_cstd, t->lv_cpu_std, 8},
+           {&e->d_lv_mavg, t->lv_mem_avg, 8}, {&e->d_lv_mstd, t->lv_mem_std, 8}, {&e->d_lv_flags, t->lv_flags, 1}}};
+}
+// the exactness of LVRB's allocatable columns, an aggregate over all nodes: a full table establishes it (replace), a delta's rows
+// may only take it away
+void trimaran_alloc_exactness(spx_engine* e, const spx_trimaran_nodes_soa* t, bool replace) {
+  const size_t n = static_cast<size_t>(t->n_nodes);
+  e->lv_alloc_exact = (replace || e->lv_alloc_exact) && all_below_2p52(t->lv_alloc_cpu_milli, n) && all_below_2p52(t->lv_alloc_mem, n);
+  e->lv_alloc_f32 = (replace || e->lv_alloc_f32) && all_below_2p47(t->lv_alloc_cpu_milli, n) && all_below_2p47(t->lv_alloc_mem, n);
+}
+
+// What rows [row0, row1) of an NRT node table say about the float64 formulation's preconditions.  A full upload scans the table in
+// chunks and merges; a delta scans its rows and merges into what the engine holds.
+struct NrtRowScan {
+  bool ok = true;     // NUMA ids are list positions, every present capacity is in the formulation's range (nrt_fast_qty)
+  bool ln_ok = true;  // every zone cost lies within [0, 255]: LeastNUMANodes' tables can be built (findSuitableCombination's 256 sentinel)
+  uint32_t big = 0;   // slots with a capacity (Value() form) that float32 does not hold exactly
+  spx_engine::NrtQty qty;
+  void merge(const NrtRowScan& o) { ok = ok && o.ok, ln_ok = ln_ok && o.ln_ok, big |= o.big, qty.merge(o.qty); }
+};
+NrtRowScan nrt_scan_rows(const spx_nrt_nodes_soa* t, int cpu_slot, int64_t row0, int64_t row1) {
+  constexpr int64_t Zm = SPX_NRT_MAX_ZONES;
+  const int64_t R = t->n_res;
+  NrtRowScan s;
+  for (int64_t i = row0; i < row1; ++i) {
+    const int nz = t->n_zones[i];
+    for (int z = 0; z < nz && z < Zm; ++z) {
+      if (t->zone_id[i * Zm + z] != z) s.ok = false;  // "lowest NUMA id" must be "lowest list position"
+      for (int64_t r = 0; r < R; ++r) {
+        if (!((t->zone_present[i * Zm + z] >> r) & 1u)) continue;
+        const int64_t cap = t->zone_avail[(i * Zm + z) * R + r];
+        if (!nrt_fast_qty(cap)) s.ok = false;
+        if (!nrt_exact_f32(static_cast<double>(nrt_value_of(r == cpu_slot, cap)))) s.big |= 1u << r;
+        if (cap >= 0) s.qty.add(static_cast<int>(r), nrt_value_of(r == cpu_slot, cap));
+      }
+      for (int zb = 0; zb < nz && zb < Zm; ++zb) {
+        const int64_t c = t->zone_cost[(i * Zm + z) * Zm + zb];
+        if (c < 0 || c > 255) s.ln_ok = false;
+      }
+    }
+  }
+  return s;
+}
+
+// Rows of an NRT node table to the device: row i of `t` describes node ix[i] (`whole`: every node, in order — a full upload).  The
+// rows as they are join `b` (which may hold parts of the caller's already) and leave with one DMA; the device turns them into the
+// node-major columns (k_scatter_rows) and the float64 formulation's derived columns (k_nrt_derive_rows).  The caller waits for the stream.
+int ship_nrt_rows(spx_engine* e, const spx_nrt_nodes_soa* t, const std::vector<int32_t>& ix, bool whole, DeltaBlob& b) {
+  constexpr size_t Zm = SPX_NRT_MAX_ZONES;
+  const int64_t n = t->n_nodes, N = e->n_nodes;
+  const size_t m = static_cast<size_t>(n), R = static_cast<size_t>(t->n_res);
+  const size_t o_idx = b.add(ix.data(), m * 4);
+  const size_t o_flags = b.add(t->flags, m), o_max = b.add(t->max_numa, m * 4), o_nz = b.add(t->n_zones, m), o_np = b.add(t->node_present, m);
+  const size_t o_zid = b.add(t->zone_id, m * Zm), o_zp = b.add(t->zone_present, m * Zm);
+  const size_t o_av = b.add(t->zone_avail, m * Zm * R * 8), o_cost = b.add(t->zone_cost, m * Zm * Zm * 4);
+  const size_t o_min = b.add(t->min_avg_dist, m * Zm * 4);
+  if (int rc = b.ship()) return rc;
+  const int32_t* d_idx = reinterpret_cast<const int32_t*>(b.dev(o_idx));
+  hipStream_t s = e->stream;
+  // the one-wide columns of a whole table are the staged columns as they are: copied (scattered with the identity index, the four
+  // took stage 4 of spx_load_nrt from 2.61 to 2.80 ms at 20 000 nodes, outside its run-to-run spread)
+  const struct { DevBuf& dst; size_t at; int bytes; } narrow[] = {{e->d_nrt_flags, o_flags, 1}, {e->d_nrt_max_numa, o_max, 4}, {e->d_nrt_nz, o_nz, 1}, {e->d_nrt_np, o_np, 1}};
+  for (const auto& c : narrow) {
+    if (whole) SPX_HIP(e, hipMemcpyAsync(c.dst.p, b.dev(c.at), m * static_cast<size_t>(c.bytes), hipMemcpyDeviceToDevice, s));
+    else spx::launch_scatter_rows(c.dst.p, N, 1, d_idx, b.dev(c.at), n, c.bytes, s);
+  }
+  spx::launch_scatter_rows(e->d_nrt_zid.p, N, static_cast<int>(Zm), d_idx, b.dev(o_zid), n, 1, s);
+  spx::launch_scatter_rows(e->d_nrt_zp.p, N, static_cast<int>(Zm), d_idx, b.dev(o_zp), n, 1, s);
+  if (R) spx::launch_scatter_rows(e->d_nrt_avail.p, N, static_cast<int>(Zm * R), d_idx, b.dev(o_av), n, 8, s);
+  spx::launch_scatter_rows(e->d_nrt_cost.p, N, static_cast<int>(Zm * Zm), d_idx, b.dev(o_cost), n, 4, s);
+  spx::launch_scatter_rows(e->d_nrt_minavg.p, N, static_cast<int>(Zm), d_idx, b.dev(o_min), n, 4, s);
+  spx::NrtDeltaArgs da{};
+  da.n_rows = n, da.n_nodes = N, da.n_res = t->n_res, da.cpu_slot = e->nrt_cpu_slot;
+  da.idx = d_idx, da.n_zones = reinterpret_cast<const uint8_t*>(b.dev(o_nz)), da.zone_present = reinterpret_cast<const uint8_t*>(b.dev(o_zp));
+  da.zone_avail = reinterpret_cast<const int64_t*>(b.dev(o_av));
+  da.f_av = static_cast<double*>(e->d_nrt_fav.p), da.f_rc = static_cast<double*>(e->d_nrt_frc.p), da.f_rcv = static_cast<double*>(e->d_nrt_frcv.p);
+  da.f_cpu = static_cast<double*>(e->d_nrt_fcpu.p), da.f_braw = static_cast<double*>(e->d_nrt_fbraw.p), da.f_rep = static_cast<uint8_t*>(e->d_nrt_frep.p);
+  spx::launch_nrt_derive_rows(da, s);
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+// The float64 formulation's view of an NRT slot table: the cpu slot, whether the weights are in its range, and per slot subset the sum
+// of the weights with its biased reciprocal ([2^n_res][2]; zeros when they are not in range).
+struct NrtSlotWeights {
+  int32_t cpu_slot = -1;
+  bool fast = true;
+  std::vector<double> wtab;
+};
+NrtSlotWeights nrt_slot_weights(const spx_nrt_slots* t) {
+  NrtSlotWeights w;
+  int64_t wtotal = 0;
+  for (int i = 0; i < t->n_res; ++i) {
+    if (t->slot_flags[i] & SPX_NRT_SLOT_CPU) w.cpu_slot = i;
+    // the Least/MostAllocated Score accumulates integer zone totals (v_mad_u32_u24: weights below 2^24) whose high bit marks a
+    // zero zone score: 100 * sum(weights) must stay below 2^31 — with room, sum(weights) < 2^20 (upstream weights are 1..100)
+    if (t->slot_weight[i] < 0 || t->slot_weight[i] >= kNrtWeightLimit) w.fast = false;
+    else wtotal += t->slot_weight[i];
+  }
+  if (wtotal >= kNrtWeightLimit) w.fast = false;
+  w.wtab.assign(static_cast<size_t>(2) << t->n_res, 0.0);
+  if (w.fast)
+    for (unsigned m = 0; m < (1u << t->n_res); ++m) {
+      int64_t sum = 0;
+      for (int i = 0; i < t->n_res; ++i)
+        if ((m >> i) & 1u) sum += t->slot_weight[i];
+      w.wtab[2 * m] = static_cast<double>(sum);
+      w.wtab[2 * m + 1] = nrt_biased_rcp(static_cast<double>(sum));
+    }
+  return w;
+}
+
+// Pod classes to the device: `uniq` the representative rows, `dups` the (row, representative) pairs, which leave as [pairs | copy
+// tasks] (expand_tasks).  The three counters are set once both columns are on their way and the vectors may go out of scope.
+int ship_classes(spx_engine* e, DevBuf& d_uniq, DevBuf& d_dups, const std::vector<int32_t>& uniq, std::vector<int32_t>& dups, int64_t n_rows, int64_t& n_uniq,
+                 int64_t& n_dups, int64_t& n_tasks) {
+  const int64_t pairs = static_cast<int64_t>(dups.size() / 2), tasks = expand_tasks(dups, n_rows);
+  int rc;
+  if ((rc = upload(e, d_uniq, uniq.data(), uniq.size() * sizeof(int32_t)))) return rc;
+  if ((rc = upload(e, d_dups, dups.data(), dups.size() * sizeof(int32_t)))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  n_uniq = static_cast<int64_t>(uniq.size()), n_dups = pairs, n_tasks = tasks;
+  return SPX_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -26,19 +212,9 @@ int spx_upload_trimaran_nodes(spx_engine* e, const spx_trimaran_nodes_soa* t) {
   if (rc) return rc;
   const size_t n = static_cast<size_t>(t->n_nodes);
   e->tlp_amb_built = e->lv_amb_built = false;  // (before the first column changes: a failed upload must not leave tables that describe the old ones)
-  if ((rc = upload(e, e->d_cap_cpu, t->cap_cpu_milli, n * 8))) return rc;
-  if ((rc = upload(e, e->d_tlp_util, t->tlp_cpu_util, n * 8))) return rc;
-  if ((rc = upload(e, e->d_tlp_missing, t->tlp_missing_milli, n * 8))) return rc;
-  if ((rc = upload(e, e->d_tlp_valid, t->tlp_valid, n))) return rc;
-  if ((rc = upload(e, e->d_lv_acpu, t->lv_alloc_cpu_milli, n * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_amem, t->lv_alloc_mem, n * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_cavg, t->lv_cpu_avg, n * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_cstd, t->lv_cpu_std, n * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_mavg, t->lv_mem_avg, n * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_mstd, t->lv_mem_std, n * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_flags, t->lv_flags, n))) return rc;
-  e->lv_alloc_exact = all_below_2p52(t->lv_alloc_cpu_milli, n) && all_below_2p52(t->lv_alloc_mem, n);
-  e->lv_alloc_f32 = all_below_2p47(t->lv_alloc_cpu_milli, n) && all_below_2p47(t->lv_alloc_mem, n);
+  for (const TriCol& c : trimaran_cols(e, t))
+    if ((rc = upload(e, *c.dst, c.src, n * static_cast<size_t>(c.bytes)))) return rc;
+  trimaran_alloc_exactness(e, t, true);
   e->lroc_tab_ready = false;
   e->tri_nodes = true;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
@@ -46,67 +222,15 @@ int spx_upload_trimaran_nodes(spx_engine* e, const spx_trimaran_nodes_soa* t) {
 }
 
 
-namespace {
-// one pinned blob for a delta's columns: [idx int32 n] then each column, 16-byte aligned; uploaded with one DMA
-struct DeltaBlob {
-  spx_engine* e;
-  size_t bytes = 0;
-  std::vector<std::pair<const void*, size_t>> parts;  // (source, bytes)
-  std::vector<size_t> offset;
-  size_t add(const void* src, size_t n) {
-    const size_t at = bytes;
-    parts.emplace_back(src, n);
-    offset.push_back(at);
-    bytes = (bytes + n + 15) & ~static_cast<size_t>(15);
-    return at;
-  }
-  int ship() {
-    if (e->h_stage_bytes < bytes) {
-      if (e->h_stage) SPX_HIP(e, hipHostFree(e->h_stage));
-      e->h_stage = nullptr, e->h_stage_bytes = 0;
-      SPX_HIP(e, hipHostMalloc(&e->h_stage, bytes + 65536, hipHostMallocDefault));
-      e->h_stage_bytes = bytes + 65536;
-    }
-    for (size_t k = 0; k < parts.size(); ++k) {
-      char* dst = static_cast<char*>(e->h_stage) + offset[k];
-      const char* src = static_cast<const char*>(parts[k].first);
-      const int64_t blocks = static_cast<int64_t>((parts[k].second + 65535) / 65536);  // (a full node table: megabytes per column)
-      const size_t len = parts[k].second;
-      spx_host::parallel_rows(blocks, [&](int64_t b0, int64_t b1) {
-        const size_t at = static_cast<size_t>(b0) * 65536, end = std::min(len, static_cast<size_t>(b1) * 65536);
-        if (end > at) std::memcpy(dst + at, src + at, end - at);
-      }, 16);
-    }
-    return upload(e, e->d_delta, e->h_stage, bytes);
-  }
-  const char* dev(size_t at) const { return static_cast<const char*>(e->d_delta.p) + at; }
-};
-
-int delta_indices(spx_engine* e, const int64_t* idx, int64_t n_rows, std::vector<int32_t>& out) {
-  if (n_rows < 0 || (n_rows && !idx)) return fail(e, SPX_ERR_ARG, "delta: NULL index column");
-  out.resize(static_cast<size_t>(n_rows));
-  for (int64_t i = 0; i < n_rows; ++i) {
-    if (idx[i] < 0 || idx[i] >= e->n_nodes) return fail(e, SPX_ERR_ARG, "delta: node index out of range");
-    out[static_cast<size_t>(i)] = static_cast<int32_t>(idx[i]);
-  }
-  // a node listed twice would be scattered twice in no particular order — and the columns derived from the rows (the float64 images,
-  // the host copies) could end up describing different rows of the delta: refused
-  std::vector<int32_t> sorted(out);
-  std::sort(sorted.begin(), sorted.end());
-  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(e, SPX_ERR_ARG, "delta: a node index is listed twice");
-  return SPX_OK;
-}
-}  // namespace
-
 int spx_update_trimaran_nodes(spx_engine* e, const int64_t* idx, const spx_trimaran_nodes_soa* t) {
   if (!e || !t) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
   if (!e->tri_nodes) return fail(e, SPX_ERR_STATE, "trimaran node delta: upload the full table first");
   const int64_t n = t->n_nodes;
   if (n == 0) return SPX_OK;
-  if (!t->cap_cpu_milli || !t->tlp_cpu_util || !t->tlp_missing_milli || !t->tlp_valid || !t->lv_alloc_cpu_milli || !t->lv_alloc_mem ||
-      !t->lv_cpu_avg || !t->lv_cpu_std || !t->lv_mem_avg || !t->lv_mem_std || !t->lv_flags)
-    return fail(e, SPX_ERR_ARG, "NULL column in table");
+  const std::array<TriCol, 11> cols = trimaran_cols(e, t);
+  for (const TriCol& c : cols)
+    if (!c.src) return fail(e, SPX_ERR_ARG, "NULL column in table");
   std::vector<int32_t> ix;
   int rc = delta_indices(e, idx, n, ix);
   if (rc) return rc;
@@ -114,19 +238,13 @@ int spx_update_trimaran_nodes(spx_engine* e, const int64_t* idx, const spx_trima
   const size_t m = static_cast<size_t>(n);
   DeltaBlob b{e};
   const size_t o_idx = b.add(ix.data(), m * 4);
-  struct Col { DevBuf* dst; const void* src; int bytes; } cols[] = {
-      {&e->d_cap_cpu, t->cap_cpu_milli, 8}, {&e->d_tlp_util, t->tlp_cpu_util, 8}, {&e->d_tlp_missing, t->tlp_missing_milli, 8}, {&e->d_tlp_valid, t->tlp_valid, 1},
-      {&e->d_lv_acpu, t->lv_alloc_cpu_milli, 8}, {&e->d_lv_amem, t->lv_alloc_mem, 8}, {&e->d_lv_cavg, t->lv_cpu_avg, 8}, {&e->d_lv_cstd, t->lv_cpu_std, 8},
-      {&e->d_lv_mavg, t->lv_mem_avg, 8}, {&e->d_lv_mstd, t->lv_mem_std, 8}, {&e->d_lv_flags, t->lv_flags, 1}};
   size_t at[11];
-  for (int k = 0; k < 11; ++k) at[k] = b.add(cols[k].src, m * static_cast<size_t>(cols[k].bytes));
+  for (size_t k = 0; k < cols.size(); ++k) at[k] = b.add(cols[k].src, m * static_cast<size_t>(cols[k].bytes));
   if ((rc = b.ship())) return rc;
-  for (int k = 0; k < 11; ++k)
+  for (size_t k = 0; k < cols.size(); ++k)
     spx::launch_scatter_rows(cols[k].dst->p, e->n_nodes, 1, reinterpret_cast<const int32_t*>(b.dev(o_idx)), b.dev(at[k]), n, cols[k].bytes, e->stream);
   SPX_HIP(e, hipGetLastError());
-  // the aggregate property stays conservative: rows may only take it away (a full upload re-establishes it)
-  e->lv_alloc_exact = e->lv_alloc_exact && all_below_2p52(t->lv_alloc_cpu_milli, m) && all_below_2p52(t->lv_alloc_mem, m);
-  e->lv_alloc_f32 = e->lv_alloc_f32 && all_below_2p47(t->lv_alloc_cpu_milli, m) && all_below_2p47(t->lv_alloc_mem, m);
+  trimaran_alloc_exactness(e, t, false);
   e->lroc_tab_ready = false;
   e->evaluated = 0;  // every table computed from the old rows is stale
   e->best_valid = false;
@@ -207,12 +325,7 @@ int spx_update_quota_used(spx_engine* e, int64_t n_rows, const int32_t* ns, cons
   constexpr size_t S = SPX_QUOTA_SLOTS;
   for (int64_t i = 0; i < n_rows; ++i)
     if (ns[i] < 0 || ns[i] >= e->q_n_namespaces) return fail(e, SPX_ERR_ARG, "quota delta: namespace index out of range");
-  {
-    // two rows for one namespace would be scattered in unspecified order (d_q_used and d_q_usedp could end up from different rows)
-    std::vector<int32_t> seen(ns, ns + n_rows);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(e, SPX_ERR_ARG, "quota delta: a namespace is listed twice");
-  }
+  if (int rc = refuse_duplicates(e, ns, n_rows, "quota delta: a namespace is listed twice")) return rc;  // (d_q_used and d_q_usedp from different rows)
   const size_t m = static_cast<size_t>(n_rows);
   int64_t agg[SPX_QUOTA_SLOTS + 1];
   std::memcpy(agg, agg_used, sizeof e->q_agg_used);
@@ -248,75 +361,30 @@ int spx_update_nrt_nodes(spx_engine* e, const int64_t* idx, const spx_nrt_nodes_
   std::vector<int32_t> ix;
   int rc = delta_indices(e, idx, n, ix);
   if (rc) return rc;
-  constexpr int64_t Zm = SPX_NRT_MAX_ZONES;
-  const int64_t R = t->n_res, N = e->n_nodes;
-  const size_t m = static_cast<size_t>(n);
-  // the float64 formulation's preconditions for the new rows (the same tests as spx_upload_nrt_nodes); a row that breaks them
-  // sends the whole table to the reference-arithmetic kernel until the next full upload
-  bool ok = true, cost_changed = false, ln_ok = true;
-  uint32_t big = 0;
-  spx_engine::NrtQty qty;
-  for (int64_t i = 0; i < n; ++i) {
-    const int nz = t->n_zones[i];
-    for (int z = 0; z < nz && z < Zm; ++z) {
-      if (t->zone_id[i * Zm + z] != z) ok = false;
-      for (int64_t r = 0; r < R; ++r) {
-        if (!((t->zone_present[i * Zm + z] >> r) & 1u)) continue;
-        const int64_t cap = t->zone_avail[(i * Zm + z) * R + r];
-        if (!nrt_fast_qty(cap)) ok = false;
-        if (!nrt_exact_f32(static_cast<double>(nrt_value_of(r == e->nrt_cpu_slot, cap)))) big |= 1u << r;
-        if (cap >= 0) qty.add(static_cast<int>(r), nrt_value_of(r == e->nrt_cpu_slot, cap));
-      }
-    }
-    const int32_t* hc = &e->h_nrt_cost[static_cast<size_t>(ix[static_cast<size_t>(i)]) * Zm * Zm];
-    if (std::memcmp(hc, t->zone_cost + i * Zm * Zm, sizeof(int32_t) * Zm * Zm) != 0 || e->h_nrt_nz[static_cast<size_t>(ix[static_cast<size_t>(i)])] != t->n_zones[i]) {
-      cost_changed = true;  // (the host copies follow once the rows have shipped: a failed delta leaves them describing the device)
-      for (int za = 0; za < nz && za < Zm; ++za)
-        for (int zb = 0; zb < nz && zb < Zm; ++zb) {
-          const int64_t c = t->zone_cost[(i * Zm + za) * Zm + zb];
-          if (c < 0 || c > 255) ln_ok = false;
-        }
-    }
+  constexpr size_t Zm = SPX_NRT_MAX_ZONES;
+  // a row that breaks the float64 formulation's preconditions sends the whole table to the reference-arithmetic kernel until the next full upload
+  const NrtRowScan scan = nrt_scan_rows(t, e->nrt_cpu_slot, 0, n);
+  bool cost_changed = false;  // zone costs or zone counts differ from what LeastNUMANodes' tables were built from
+  for (int64_t i = 0; i < n && !cost_changed; ++i) {
+    const size_t node = static_cast<size_t>(ix[static_cast<size_t>(i)]);
+    cost_changed = std::memcmp(&e->h_nrt_cost[node * Zm * Zm], t->zone_cost + i * Zm * Zm, sizeof(int32_t) * Zm * Zm) != 0 || e->h_nrt_nz[node] != t->n_zones[i];
   }
   DeltaBlob b{e};
-  const size_t o_idx = b.add(ix.data(), m * 4);
-  const size_t o_flags = b.add(t->flags, m), o_max = b.add(t->max_numa, m * 4), o_nz = b.add(t->n_zones, m), o_np = b.add(t->node_present, m);
-  const size_t o_zid = b.add(t->zone_id, m * Zm), o_zp = b.add(t->zone_present, m * Zm);
-  const size_t o_av = b.add(t->zone_avail, m * Zm * static_cast<size_t>(R) * 8), o_cost = b.add(t->zone_cost, m * Zm * Zm * 4);
-  const size_t o_min = b.add(t->min_avg_dist, m * Zm * 4);
-  if ((rc = b.ship())) return rc;
-  const int32_t* d_idx = reinterpret_cast<const int32_t*>(b.dev(o_idx));
-  hipStream_t s = e->stream;
-  spx::launch_scatter_rows(e->d_nrt_flags.p, N, 1, d_idx, b.dev(o_flags), n, 1, s);
-  spx::launch_scatter_rows(e->d_nrt_max_numa.p, N, 1, d_idx, b.dev(o_max), n, 4, s);
-  spx::launch_scatter_rows(e->d_nrt_nz.p, N, 1, d_idx, b.dev(o_nz), n, 1, s);
-  spx::launch_scatter_rows(e->d_nrt_np.p, N, 1, d_idx, b.dev(o_np), n, 1, s);
-  spx::launch_scatter_rows(e->d_nrt_zid.p, N, static_cast<int>(Zm), d_idx, b.dev(o_zid), n, 1, s);
-  spx::launch_scatter_rows(e->d_nrt_zp.p, N, static_cast<int>(Zm), d_idx, b.dev(o_zp), n, 1, s);
-  if (R) spx::launch_scatter_rows(e->d_nrt_avail.p, N, static_cast<int>(Zm * R), d_idx, b.dev(o_av), n, 8, s);
-  spx::launch_scatter_rows(e->d_nrt_cost.p, N, static_cast<int>(Zm * Zm), d_idx, b.dev(o_cost), n, 4, s);
-  spx::launch_scatter_rows(e->d_nrt_minavg.p, N, static_cast<int>(Zm), d_idx, b.dev(o_min), n, 4, s);
-  spx::NrtDeltaArgs da{};
-  da.n_rows = n, da.n_nodes = N, da.n_res = static_cast<int32_t>(R), da.cpu_slot = e->nrt_cpu_slot;
-  da.idx = d_idx, da.n_zones = reinterpret_cast<const uint8_t*>(b.dev(o_nz)), da.zone_present = reinterpret_cast<const uint8_t*>(b.dev(o_zp)), da.zone_avail = reinterpret_cast<const int64_t*>(b.dev(o_av));
-  da.f_av = static_cast<double*>(e->d_nrt_fav.p), da.f_rc = static_cast<double*>(e->d_nrt_frc.p), da.f_rcv = static_cast<double*>(e->d_nrt_frcv.p);
-  da.f_cpu = static_cast<double*>(e->d_nrt_fcpu.p), da.f_braw = static_cast<double*>(e->d_nrt_fbraw.p), da.f_rep = static_cast<uint8_t*>(e->d_nrt_frep.p);
-  spx::launch_nrt_derive_rows(da, s);
-  SPX_HIP(e, hipGetLastError());
-  if (cost_changed)
+  if ((rc = ship_nrt_rows(e, t, ix, false, b))) return rc;
+  if (cost_changed)  // (the host copies follow once the rows have shipped: a failed delta leaves them describing the device)
     for (int64_t i = 0; i < n; ++i) {
       const size_t node = static_cast<size_t>(ix[static_cast<size_t>(i)]);
       std::memcpy(&e->h_nrt_cost[node * Zm * Zm], t->zone_cost + i * Zm * Zm, sizeof(int32_t) * Zm * Zm);
       e->h_nrt_nz[node] = t->n_zones[i];
     }
-  e->nrt_fast_nodes = e->nrt_fast_nodes && ok;
-  e->nrt_big_nodes |= big;
-  e->nrt_qty_nodes.merge(qty);
+  e->nrt_fast_nodes = e->nrt_fast_nodes && scan.ok;
+  e->nrt_big_nodes |= scan.big;
+  e->nrt_qty_nodes.merge(scan.qty);
+  // (an unchanged row's costs are the host copy's, which an earlier scan vouched for unless nrt_ln_ok is false already — and it stays
+  // false until the next full upload: scanning every row of the delta decides as scanning the changed ones would)
+  e->nrt_ln_ok = e->nrt_ln_ok && scan.ln_ok;
   e->nrt_pk_tab_built = e->nrt_wsort_built = false;  // zone capacities changed
-  if (cost_changed) {  // LeastNUMANodes' per-node tables are rebuilt when that strategy is next evaluated
-    e->nrt_ln_built = false;
-    e->nrt_ln_ok = e->nrt_ln_ok && ln_ok;
-  }
+  if (cost_changed) e->nrt_ln_built = false;  // LeastNUMANodes' per-node tables are rebuilt when that strategy is next evaluated
   // (the window-local node order — perm — is a grouping hint for the sweep, not a correctness input: left as it is)
   e->evaluated = 0;  // NRT's tables, and every table normalised over the feasible nodes its status named (Allocatable, NetworkOverhead, Peaks)
   e->best_valid = false;
@@ -435,13 +503,7 @@ int spx_upload_peaks_pods(spx_engine* e, const spx_peaks_pods_soa* t) {
       else dups.push_back(static_cast<int32_t>(i)), dups.push_back(tab[k]);
     }
     if (!dups.empty()) {
-      const int64_t n_dups = static_cast<int64_t>(dups.size() / 2), n_tasks = expand_tasks(dups, static_cast<int64_t>(p));
-      if ((rc = upload(e, e->d_pk_uniq, uniq.data(), uniq.size() * sizeof(int32_t)))) return rc;
-      if ((rc = upload(e, e->d_pk_dups, dups.data(), dups.size() * sizeof(int32_t)))) return rc;
-      SPX_HIP(e, hipStreamSynchronize(e->stream));  // the vectors go out of scope
-      e->pk_n_uniq = static_cast<int64_t>(uniq.size());
-      e->pk_n_dups = n_dups;
-      e->pk_n_tasks = n_tasks;
+      if ((rc = ship_classes(e, e->d_pk_uniq, e->d_pk_dups, uniq, dups, t->n_pods, e->pk_n_uniq, e->pk_n_dups, e->pk_n_tasks))) return rc;
     }
   }
   e->peaks_pods = true;
@@ -495,27 +557,10 @@ int spx_upload_nrt_slots(spx_engine* e, const spx_nrt_slots* t) {
   e->nrt_nodes = e->nrt_pods = false;  // tables are laid out by slot count
   // float64 formulation: weight-subset table, cpu slot, weight range
   SPX_HIP(e, hipSetDevice(e->device));
-  e->nrt_cpu_slot = -1;
-  e->nrt_fast_slots = true;
-  int64_t wtotal = 0;
-  for (int i = 0; i < t->n_res; ++i) {
-    if (t->slot_flags[i] & SPX_NRT_SLOT_CPU) e->nrt_cpu_slot = i;
-    // the Least/MostAllocated Score accumulates integer zone totals (v_mad_u32_u24: weights below 2^24) whose high bit marks a
-    // zero zone score: 100 * sum(weights) must stay below 2^31 — with room, sum(weights) < 2^20 (upstream weights are 1..100)
-    if (t->slot_weight[i] < 0 || t->slot_weight[i] >= kNrtWeightLimit) e->nrt_fast_slots = false;
-    else wtotal += t->slot_weight[i];
-  }
-  if (wtotal >= kNrtWeightLimit) e->nrt_fast_slots = false;
-  std::vector<double> wtab(static_cast<size_t>(2) << t->n_res, 0.0);
-  if (e->nrt_fast_slots)
-    for (unsigned m = 0; m < (1u << t->n_res); ++m) {
-      int64_t w = 0;
-      for (int i = 0; i < t->n_res; ++i)
-        if ((m >> i) & 1u) w += t->slot_weight[i];
-      wtab[2 * m] = static_cast<double>(w);
-      wtab[2 * m + 1] = nrt_biased_rcp(static_cast<double>(w));
-    }
-  e->nrt_wtab = std::move(wtab);
+  NrtSlotWeights w = nrt_slot_weights(t);
+  e->nrt_cpu_slot = w.cpu_slot;
+  e->nrt_fast_slots = w.fast;
+  e->nrt_wtab = std::move(w.wtab);
   return SPX_OK;
 }
 
@@ -532,11 +577,11 @@ int spx_upload_nrt_nodes(spx_engine* e, const spx_nrt_nodes_soa* t) {
   if (!t->flags || !t->max_numa || !t->n_zones || !t->zone_id || !t->zone_present || !t->zone_cost || !t->min_avg_dist || !t->node_present ||
       (!t->zone_avail && R))
     return fail(e, SPX_ERR_ARG, "NULL column in table");
-  // Round 4: the full upload takes the delta's road (spx_update_nrt_nodes) with every node listed — the rows as they are into ONE
-  // pinned blob, one DMA, and the device turns them into the node-major columns (k_scatter_rows) and the float64 formulation's
-  // derived columns (k_nrt_derive_rows: the expressions below used to run here, on the host, into five freshly allocated vectors
-  // that were then copied from pageable memory: 12.6 of the 24 ms a full snapshot load took at 20 000 nodes).  What stays on the host:
-  // the preconditions of the float64 formulation, the window-local node order, the host copy LeastNUMANodes' tables are built from.
+  // Round 4: the full upload takes the delta's road (ship_nrt_rows) with every node listed — the rows as they are into ONE pinned
+  // blob, one DMA, and the device derives the rest (the derived columns used to be computed here, on the host, into five freshly
+  // allocated vectors that were then copied from pageable memory: 12.6 of the 24 ms a full snapshot load took at 20 000 nodes).
+  // What is this call's own: the buffers, the preconditions of the float64 formulation as a fresh start, the window-local node order,
+  // the host copy LeastNUMANodes' tables are built from.
   const size_t m = static_cast<size_t>(n), cells = static_cast<size_t>(Zm * R) * m;
   if ((rc = ensure(e, e->d_nrt_flags, m)) || (rc = ensure(e, e->d_nrt_max_numa, m * 4)) || (rc = ensure(e, e->d_nrt_nz, m)) || (rc = ensure(e, e->d_nrt_np, m)) ||
       (rc = ensure(e, e->d_nrt_zid, m * Zm)) || (rc = ensure(e, e->d_nrt_zp, m * Zm)) || (rc = ensure(e, e->d_nrt_avail, cells * 8)) ||
@@ -545,45 +590,18 @@ int spx_upload_nrt_nodes(spx_engine* e, const spx_nrt_nodes_soa* t) {
       (rc = ensure(e, e->d_nrt_fbraw, m * Zm * 8)) || (rc = ensure(e, e->d_nrt_frep, static_cast<size_t>(R > 0 ? R : 1) * m)))
     return rc;
   {
-    std::atomic<bool> ok{true}, ln_ok{true};
-    std::atomic<uint32_t> big_nodes{0};
-    spx_engine::NrtQty qty_all;
-    std::mutex qty_mu;
+    NrtRowScan scan;
+    std::mutex scan_mu;
     spx_host::parallel_rows(n, [&](int64_t row0, int64_t row1) {
-    bool my_ok = true, my_ln = true;
-    uint32_t my_big = 0;
-    spx_engine::NrtQty my_qty;
-    for (int64_t i = row0; i < row1; ++i) {
-      const int nz = t->n_zones[i];
-      for (int z = 0; z < nz && z < Zm; ++z) {
-        if (t->zone_id[i * Zm + z] != z) my_ok = false;  // "lowest NUMA id" must be "lowest list position"
-        for (int64_t r = 0; r < R; ++r) {
-          if (!((t->zone_present[i * Zm + z] >> r) & 1u)) continue;
-          const int64_t cap = t->zone_avail[(i * Zm + z) * R + r];
-          if (!nrt_fast_qty(cap)) my_ok = false;
-          if (!nrt_exact_f32(static_cast<double>(nrt_value_of(r == e->nrt_cpu_slot, cap)))) my_big |= 1u << r;
-          if (cap >= 0) my_qty.add(static_cast<int>(r), nrt_value_of(r == e->nrt_cpu_slot, cap));
-        }
-        // LeastNUMANodes' tables can be built when every zone cost lies within [0, 255] (findSuitableCombination's 256 sentinel)
-        for (int zb = 0; zb < nz && zb < Zm; ++zb) {
-          const int64_t c = t->zone_cost[(i * Zm + z) * Zm + zb];
-          if (c < 0 || c > 255) my_ln = false;
-        }
-      }
-    }
-    if (!my_ok) ok = false;
-    if (!my_ln) ln_ok = false;
-    if (my_big) big_nodes.fetch_or(my_big, std::memory_order_relaxed);
-    {
-      std::lock_guard<std::mutex> g(qty_mu);
-      qty_all.merge(my_qty);
-    }
+      const NrtRowScan part = nrt_scan_rows(t, e->nrt_cpu_slot, row0, row1);
+      std::lock_guard<std::mutex> g(scan_mu);
+      scan.merge(part);
     }, 1024);
-    e->nrt_fast_nodes = ok.load();
-    e->nrt_big_nodes = big_nodes.load();
-    e->nrt_qty_nodes = qty_all;
+    e->nrt_fast_nodes = scan.ok;
+    e->nrt_big_nodes = scan.big;
+    e->nrt_qty_nodes = scan.qty;
     e->nrt_pk_tab_built = e->nrt_wsort_built = false;
-    e->nrt_ln_ok = ln_ok.load();
+    e->nrt_ln_ok = scan.ln_ok;
     e->nrt_ln_built = false;  // built when that strategy is first evaluated (build_ln_tab): more host time than everything else in this call
     // window-local node order: inside each run of 256 nodes, group the nodes by the code path their flags select
     // (not aligned / pod scope / container scope) so that wavefronts are mostly homogeneous; inside a group, by how tight the
@@ -631,36 +649,13 @@ int spx_upload_nrt_nodes(spx_engine* e, const spx_nrt_nodes_soa* t) {
     std::vector<int32_t> all(m);
     for (size_t i = 0; i < m; ++i) all[i] = static_cast<int32_t>(i);
     DeltaBlob b{e};
-    const size_t o_idx = b.add(all.data(), m * 4), o_perm = b.add(perm.data(), perm.size() * sizeof(int32_t));
-    const size_t o_flags = b.add(t->flags, m), o_max = b.add(t->max_numa, m * 4), o_nz = b.add(t->n_zones, m), o_np = b.add(t->node_present, m);
-    const size_t o_zid = b.add(t->zone_id, m * Zm), o_zp = b.add(t->zone_present, m * Zm);
-    const size_t o_av = b.add(t->zone_avail, cells * 8), o_cost = b.add(t->zone_cost, m * Zm * Zm * 4);
-    const size_t o_min = b.add(t->min_avg_dist, m * Zm * 4);
+    const size_t o_perm = b.add(perm.data(), perm.size() * sizeof(int32_t));
     if ((rc = ensure(e, e->d_nrt_perm, perm.size() * sizeof(int32_t)))) return rc;
-    if ((rc = b.ship())) return rc;
+    if ((rc = ship_nrt_rows(e, t, all, true, b))) return rc;
     e->h_nrt_cost.assign(t->zone_cost, t->zone_cost + m * Zm * Zm);  // (the host copies follow the shipped rows)
     e->h_nrt_nz.assign(t->n_zones, t->n_zones + m);
-    const int32_t* d_idx = reinterpret_cast<const int32_t*>(b.dev(o_idx));
-    hipStream_t st = e->stream;
-    SPX_HIP(e, hipMemcpyAsync(e->d_nrt_perm.p, b.dev(o_perm), perm.size() * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    SPX_HIP(e, hipMemcpyAsync(e->d_nrt_flags.p, b.dev(o_flags), m, hipMemcpyDeviceToDevice, st));
-    SPX_HIP(e, hipMemcpyAsync(e->d_nrt_max_numa.p, b.dev(o_max), m * 4, hipMemcpyDeviceToDevice, st));
-    SPX_HIP(e, hipMemcpyAsync(e->d_nrt_nz.p, b.dev(o_nz), m, hipMemcpyDeviceToDevice, st));
-    SPX_HIP(e, hipMemcpyAsync(e->d_nrt_np.p, b.dev(o_np), m, hipMemcpyDeviceToDevice, st));
-    spx::launch_scatter_rows(e->d_nrt_zid.p, n, static_cast<int>(Zm), d_idx, b.dev(o_zid), n, 1, st);
-    spx::launch_scatter_rows(e->d_nrt_zp.p, n, static_cast<int>(Zm), d_idx, b.dev(o_zp), n, 1, st);
-    if (R) spx::launch_scatter_rows(e->d_nrt_avail.p, n, static_cast<int>(Zm * R), d_idx, b.dev(o_av), n, 8, st);
-    spx::launch_scatter_rows(e->d_nrt_cost.p, n, static_cast<int>(Zm * Zm), d_idx, b.dev(o_cost), n, 4, st);
-    spx::launch_scatter_rows(e->d_nrt_minavg.p, n, static_cast<int>(Zm), d_idx, b.dev(o_min), n, 4, st);
-    spx::NrtDeltaArgs da{};
-    da.n_rows = n, da.n_nodes = n, da.n_res = static_cast<int32_t>(R), da.cpu_slot = e->nrt_cpu_slot;
-    da.idx = d_idx, da.n_zones = reinterpret_cast<const uint8_t*>(b.dev(o_nz)), da.zone_present = reinterpret_cast<const uint8_t*>(b.dev(o_zp));
-    da.zone_avail = reinterpret_cast<const int64_t*>(b.dev(o_av));
-    da.f_av = static_cast<double*>(e->d_nrt_fav.p), da.f_rc = static_cast<double*>(e->d_nrt_frc.p), da.f_rcv = static_cast<double*>(e->d_nrt_frcv.p);
-    da.f_cpu = static_cast<double*>(e->d_nrt_fcpu.p), da.f_braw = static_cast<double*>(e->d_nrt_fbraw.p), da.f_rep = static_cast<uint8_t*>(e->d_nrt_frep.p);
-    spx::launch_nrt_derive_rows(da, st);
-    SPX_HIP(e, hipGetLastError());
-    SPX_HIP(e, hipStreamSynchronize(st));  // the blob is reused by the next staged call
+    SPX_HIP(e, hipMemcpyAsync(e->d_nrt_perm.p, b.dev(o_perm), perm.size() * sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
+    SPX_HIP(e, hipStreamSynchronize(e->stream));  // the blob is reused by the next staged call
   }
   e->nrt_nodes = true;
   return SPX_OK;
@@ -812,32 +807,16 @@ int nrt_rank_stream(spx_engine* e, int kind) {
 int spx_internal_nrt_pod_classes(const spx_nrt_slots* slots, const spx_nrt_pods_soa* t, int32_t* rep_out, int32_t* fast_ok_out) {
   if (!slots || !t || !rep_out || !fast_ok_out || t->n_res != slots->n_res || t->n_pods <= 0) return SPX_ERR_ARG;
   const int R = t->n_res;
-  int cpu_slot = -1;
-  int64_t wtotal = 0;
-  bool slots_ok = true;
-  for (int i = 0; i < R; ++i) {
-    if (slots->slot_flags[i] & SPX_NRT_SLOT_CPU) cpu_slot = i;
-    if (slots->slot_weight[i] < 0 || slots->slot_weight[i] >= kNrtWeightLimit) slots_ok = false;
-    else wtotal += slots->slot_weight[i];
-  }
-  if (wtotal >= kNrtWeightLimit) slots_ok = false;
-  std::vector<double> wtab(static_cast<size_t>(2) << R, 0.0);
-  for (unsigned m = 0; m < (1u << R); ++m) {
-    int64_t w = 0;
-    for (int i = 0; i < R; ++i)
-      if ((m >> i) & 1u) w += slots->slot_weight[i];
-    wtab[2 * m] = static_cast<double>(w);
-    wtab[2 * m + 1] = nrt_biased_rcp(static_cast<double>(w));
-  }
+  const NrtSlotWeights w = nrt_slot_weights(slots);  // (the weights only decide *fast_ok_out: out of range, no classes are built)
   const size_t p = static_cast<size_t>(t->n_pods), IW = R <= 4 ? 16 : 32;
   std::vector<uint32_t> items(p * 10 * IW);
   std::vector<uint64_t> hash(p);
   bool ok = false;
   uint32_t big = 0;
-  nrt_build_items(t, slots->slot_flags, cpu_slot, wtab, items.data(), &ok, &big, hash.data());
-  *fast_ok_out = (ok && slots_ok) ? 1 : 0;
+  nrt_build_items(t, slots->slot_flags, w.cpu_slot, w.wtab, items.data(), &ok, &big, hash.data());
+  *fast_ok_out = (ok && w.fast) ? 1 : 0;
   for (size_t i = 0; i < p; ++i) rep_out[i] = static_cast<int32_t>(i);
-  if (ok && slots_ok) nrt_build_classes(items.data(), hash.data(), p, static_cast<size_t>(R), rep_out);
+  if (ok && w.fast) nrt_build_classes(items.data(), hash.data(), p, static_cast<size_t>(R), rep_out);
   return SPX_OK;
 }
 
@@ -875,12 +854,7 @@ int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t) {
   {  // float64 formulation: the pod record stream (nrt_build_items) + its preconditions, then the pod equivalence classes
     const size_t IW = R <= 4 ? 16 : 32;
     const size_t items_bytes = p * 10 * IW * sizeof(uint32_t);
-    if (e->h_items_bytes < items_bytes) {
-      if (e->h_items) SPX_HIP(e, hipHostFree(e->h_items));
-      e->h_items = nullptr, e->h_items_bytes = 0;
-      SPX_HIP(e, hipHostMalloc(&e->h_items, items_bytes + (items_bytes >> 3), hipHostMallocDefault));
-      e->h_items_bytes = items_bytes + (items_bytes >> 3);
-    }
+    if ((rc = ensure_pinned(e, e->h_items, e->h_items_bytes, items_bytes, items_bytes >> 3))) return rc;
     uint32_t* const items = static_cast<uint32_t*>(e->h_items);  // pinned: built in place (rows zeroed by the thread that fills them)
     bool ok = false;
     uint32_t big = 0;
@@ -912,13 +886,7 @@ int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t) {
         else dups.push_back(static_cast<int32_t>(i)), dups.push_back(rep[i]);
       }
       if (!dups.empty()) {
-        const int64_t n_dups = static_cast<int64_t>(dups.size() / 2), n_tasks = expand_tasks(dups, static_cast<int64_t>(p));
-        if ((rc = upload(e, e->d_nrt_uniq, uniq.data(), uniq.size() * sizeof(int32_t)))) return rc;
-        if ((rc = upload(e, e->d_nrt_dups, dups.data(), dups.size() * sizeof(int32_t)))) return rc;
-        SPX_HIP(e, hipStreamSynchronize(e->stream));
-        e->nrt_n_uniq = static_cast<int64_t>(uniq.size());
-        e->nrt_n_dups = n_dups;
-        e->nrt_n_tasks = n_tasks;
+        if ((rc = ship_classes(e, e->d_nrt_uniq, e->d_nrt_dups, uniq, dups, t->n_pods, e->nrt_n_uniq, e->nrt_n_dups, e->nrt_n_tasks))) return rc;
         // the representatives' requests as ranks, per chunk of up to 32 (kernels_nrt_rank.hip, kernels_nrt_fused.hip)
         if ((rc = nrt_rank_stream_upload(e, items, uniq.data(), uniq.size(), 1))) return rc;
       }
@@ -1289,283 +1257,4 @@ int spx_upload_feasible_mask(spx_engine* e, const uint8_t* mask, int64_t n_pods,
   e->ext_mask = true;
   return SPX_OK;
 }
-
-// ---------------------------------------------------------------- object tables -> SoA -> device in one call
-// What a cgo (or any FFI) caller wants: it holds object tables (marshalled itself, or decoded by spx_ingest_*) and should not have to
-// size and own two dozen intermediate arrays per plugin.  Each function runs the host flatteners with the engine's current plugin
-// parameters and uploads the result, exactly the sequence of scheduler-plugins_amd/engine.py's load_*_objects.
-int spx_load_trimaran(spx_engine* e, const spx_node_objects* nodes, const spx_resource_classes* rc, const spx_pod_objects* pods, const spx_metrics_objects* metrics,
-                      const spx_assigned_objects* assigned) {
-  if (!e || !nodes || !pods || !metrics) return SPX_ERR_ARG;
-  const size_t N = static_cast<size_t>(nodes->n_nodes), P = static_cast<size_t>(pods->n_pods), R = e->alloc_res.size();
-  spx_allocatable_params ap{e->alloc_mode, static_cast<int32_t>(R), e->alloc_res.data(), e->alloc_weight.data()};
-  std::vector<int64_t> alloc(R * N);
-  if (spx_flatten_alloc_nodes(nodes, rc, &ap, alloc.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_alloc_nodes failed");
-  spx_alloc_nodes_soa an{nodes->n_nodes, static_cast<int32_t>(R), alloc.data()};
-  int rc_;
-  if ((rc_ = spx_upload_alloc_nodes(e, &an))) return rc_;
-  std::vector<int64_t> cap(N), missing(N), acpu(N), amem(N), tpod(P), rcpu(P), rmem(P);
-  std::vector<double> util(N), cavg(N), cstd(N), mavg(N), mstd(N);
-  std::vector<uint8_t> valid(N), flags(N);
-  if (spx_flatten_trimaran_nodes(nodes, metrics, assigned, &e->tlp, cap.data(), util.data(), missing.data(), valid.data(), acpu.data(), amem.data(), cavg.data(),
-                                 cstd.data(), mavg.data(), mstd.data(), flags.data()) != SPX_OK)
-    return fail(e, SPX_ERR_ARG, "spx_flatten_trimaran_nodes failed");
-  spx_trimaran_nodes_soa tn{nodes->n_nodes, cap.data(), util.data(), missing.data(), valid.data(), acpu.data(), amem.data(), cavg.data(), cstd.data(), mavg.data(),
-                            mstd.data(), flags.data()};
-  if ((rc_ = spx_upload_trimaran_nodes(e, &tn))) return rc_;
-  if (spx_flatten_trimaran_pods(pods, &e->tlp, tpod.data(), rcpu.data(), rmem.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_trimaran_pods failed");
-  spx_trimaran_pods_soa tp{pods->n_pods, tpod.data(), rcpu.data(), rmem.data()};
-  return spx_upload_trimaran_pods(e, &tp);
-}
-
-// A new pending batch for the trimaran plugins (and Allocatable): the three pod columns are flattened by all host threads straight
-// into the engine's pinned staging buffer and leave with asynchronous DMAs at link speed — through pageable memory (flatten into
-// the caller's arrays, then spx_upload_trimaran_pods) the runtime copies each column a second time into its own staging first:
-// 1.04 ms for 100 000 pods against the sweep's 0.42.
-int spx_load_trimaran_pods(spx_engine* e, const spx_pod_objects* pods) {
-  if (!e || !pods) return SPX_ERR_ARG;
-  SPX_HIP(e, hipSetDevice(e->device));
-  int rc = set_pods(e, pods->n_pods);
-  if (rc) return rc;
-  const size_t p = static_cast<size_t>(pods->n_pods), col = (p * 8 + 255) & ~static_cast<size_t>(255), bytes = 3 * col;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));  // an earlier upload may still be reading the staging buffer
-  if (e->h_stage_bytes < bytes) {
-    if (e->h_stage) SPX_HIP(e, hipHostFree(e->h_stage));
-    e->h_stage = nullptr, e->h_stage_bytes = 0;
-    SPX_HIP(e, hipHostMalloc(&e->h_stage, bytes + 65536, hipHostMallocDefault));
-    e->h_stage_bytes = bytes + 65536;
-  }
-  char* h = static_cast<char*>(e->h_stage);
-  int64_t* tpod = reinterpret_cast<int64_t*>(h);
-  int64_t* rcpu = reinterpret_cast<int64_t*>(h + col);
-  int64_t* rmem = reinterpret_cast<int64_t*>(h + 2 * col);
-  if (spx_flatten_trimaran_pods(pods, &e->tlp, tpod, rcpu, rmem) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_trimaran_pods failed");
-  if ((rc = upload(e, e->d_tlp_pod, tpod, p * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_rcpu, rcpu, p * 8))) return rc;
-  if ((rc = upload(e, e->d_lv_rmem, rmem, p * 8))) return rc;
-  e->tri_pods = true;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));
-  return SPX_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// spx_load_nrt's wide route: slot numbering done, the node and pod halves flattened and uploaded side by side as in the dense route
-int load_nrt_wide(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_pod_objects* pods,
-                  const spx_nrt_params* params, const spx_nrt_slots& slots) {
-  int rc_;
-  if ((rc_ = spx_set_nrt_params(e, params)) || (rc_ = spx_upload_nrt_slots_wide(e, &slots))) return rc_;
-  if ((rc_ = set_nodes(e, nodes->n_nodes)) || (rc_ = set_pods(e, pods->n_pods))) return rc_;
-  const size_t N = static_cast<size_t>(nodes->n_nodes), P = static_cast<size_t>(pods->n_pods), R = static_cast<size_t>(slots.n_res > 0 ? slots.n_res : 1),
-               Z = SPX_NRT_MAX_ZONES, C = static_cast<size_t>(pods->ctr_ptr[pods->n_pods] - pods->ctr_ptr[0]);
-  int rc_pods = SPX_OK;
-  std::thread pod_half([&] {
-    int64_t n_req = 0, n_ent = 0;
-    if (spx_flatten_nrt_pods_wide(pods, rc, &slots, 0, 0, &n_req, &n_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr) != SPX_OK) {
-      rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_pods_wide failed");
-      return;
-    }
-    std::vector<uint8_t> qos(P), nn(P), rslot(static_cast<size_t>(n_req)), ckind(C), eslot(static_cast<size_t>(n_ent));
-    std::vector<int32_t> rptr(P + 1), cptr(P + 1), eptr(C + 1);
-    std::vector<int64_t> rqty(static_cast<size_t>(n_req)), eqty(static_cast<size_t>(n_ent));
-    if (spx_flatten_nrt_pods_wide(pods, rc, &slots, n_req, n_ent, &n_req, &n_ent, qos.data(), nn.data(), rptr.data(), rslot.data(), rqty.data(), cptr.data(),
-                                  ckind.data(), eptr.data(), eslot.data(), eqty.data()) != SPX_OK) {
-      rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_pods_wide failed");
-      return;
-    }
-    const spx_nrt_pods_wide ps{pods->n_pods, slots.n_res, qos.data(), nn.data(), rptr.data(), rslot.data(), rqty.data(), cptr.data(), ckind.data(),
-                               eptr.data(), eslot.data(), eqty.data()};
-    rc_pods = spx_upload_nrt_pods_wide(e, &ps);
-  });
-  int rc_nodes = SPX_OK;
-  {
-    std::vector<uint8_t> nflags(N), nz(N), zid(N * Z);
-    std::vector<uint32_t> zp(N * Z), np(N);
-    std::vector<int32_t> max_numa(N), zcost(N * Z * Z);
-    std::vector<int64_t> zavail(N * Z * R);
-    std::vector<float> minavg(N * Z);
-    if (spx_flatten_nrt_nodes_wide(nodes, nrt, &slots, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(),
-                                   minavg.data(), np.data()) != SPX_OK) {
-      rc_nodes = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_nodes_wide failed");
-    } else {
-      const spx_nrt_nodes_wide ns{nodes->n_nodes, slots.n_res, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(),
-                                  minavg.data(), np.data()};
-      rc_nodes = spx_upload_nrt_nodes_wide(e, &ns);
-    }
-  }
-  pod_half.join();
-  return rc_nodes ? rc_nodes : rc_pods;
-}
-}  // namespace
-
-extern "C" {
-
-int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_pod_objects* pods,
-                 const spx_nrt_params* params) {
-  if (!e || !nodes || !nrt || !pods || !params) return SPX_ERR_ARG;
-  using clk = std::chrono::steady_clock;
-  auto since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-  for (double& x : e->load_nrt_ms) x = 0.0;
-  auto t0 = clk::now();
-  // the slot numbering once, wide enough for either form: up to 8 slots it is spx_flatten_nrt_slots' own
-  int32_t n_res = 0, slot_res[SPX_NRT_MAX_RES_WIDE] = {0};
-  uint8_t slot_flags[SPX_NRT_MAX_RES_WIDE] = {0};
-  int64_t slot_weight[SPX_NRT_MAX_RES_WIDE] = {0};
-  if (spx_flatten_nrt_slots_wide(pods, nrt, rc, params, SPX_NRT_MAX_RES_WIDE, &n_res, slot_res, slot_flags, slot_weight) != SPX_OK) {
-    if (n_res <= SPX_NRT_MAX_RES_WIDE) return fail(e, SPX_ERR_ARG, "spx_flatten_nrt_slots failed");
-    char buf[160];
-    std::snprintf(buf, sizeof buf, "NRT: the snapshot names %d distinct resources; this build takes up to %d", n_res, SPX_NRT_MAX_RES_WIDE);
-    return fail(e, SPX_ERR_ARG, buf);
-  }
-  const spx_nrt_slots slots{n_res, slot_res, slot_flags, slot_weight};
-  e->load_nrt_ms[0] = since(t0);  // 0: spx_flatten_nrt_slots
-  if (n_res > SPX_NRT_MAX_RES || e->option[SPX_OPT_NRT_WIDE]) return load_nrt_wide(e, nodes, nrt, rc, pods, params, slots);
-  t0 = clk::now();
-  int rc_;
-  if ((rc_ = spx_set_nrt_params(e, params)) || (rc_ = spx_upload_nrt_slots(e, &slots))) return rc_;
-  // (both halves below check the batch / node count against what the engine holds: settled here, before they run side by side)
-  if ((rc_ = set_nodes(e, nodes->n_nodes)) || (rc_ = set_pods(e, pods->n_pods))) return rc_;
-  e->load_nrt_ms[3] = since(t0);  // 3: params + slot table
-  const size_t N = static_cast<size_t>(nodes->n_nodes), P = static_cast<size_t>(pods->n_pods), R = static_cast<size_t>(n_res > 0 ? n_res : 1), Z = SPX_NRT_MAX_ZONES,
-               Cn = SPX_NRT_MAX_CTRS;
-  // Round 6: the node half (flatten 1.8 ms + upload 2.7 ms at 20 000 nodes) and the pod half (0.4 + 2.7 ms at 8 192 pods) touch disjoint
-  // engine state — node tables / the blob staging, pod tables / the record stream's staging — and one stream; they run on two host
-  // threads (each with its own worker pool, parallel.hpp).  Stages 1 / 4 and 2 / 5 therefore overlap in time.
-  int rc_pods = SPX_OK;
-  std::thread pod_half([&] {
-    const auto t1 = clk::now();
-    std::vector<uint8_t> qos(P), nn(P), nctr(P), ckind(P * Cn), cpres(P * Cn), ppres(P);
-    std::vector<int64_t> creq(P * Cn * R), preq(P * R);
-    if (spx_flatten_nrt_pods(pods, rc, &slots, qos.data(), nn.data(), nctr.data(), ckind.data(), cpres.data(), creq.data(), ppres.data(), preq.data()) != SPX_OK) {
-      rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_pods failed");
-      return;
-    }
-    e->load_nrt_ms[2] = since(t1);  // 2: pod columns allocated + spx_flatten_nrt_pods
-    const auto t2 = clk::now();
-    const spx_nrt_pods_soa ps{pods->n_pods, n_res, qos.data(), nn.data(), nctr.data(), ckind.data(), cpres.data(), creq.data(), ppres.data(), preq.data()};
-    rc_pods = spx_upload_nrt_pods(e, &ps);
-    if (rc_pods == SPX_OK && !e->nrt_long_ok) {  // pods with more than 8 containers: their CSR table
-      int64_t n_long = 0, n_lc = 0;
-      spx_flatten_nrt_long_pods(pods, rc, &slots, 0, 0, &n_long, &n_lc, nullptr, nullptr, nullptr, nullptr, nullptr);
-      const size_t Ls = static_cast<size_t>(n_long), Cs = static_cast<size_t>(n_lc);
-      std::vector<int32_t> lrow(Ls), lptr(Ls + 1);
-      std::vector<uint8_t> lkind(Cs), lpres(Cs);
-      std::vector<int64_t> lreq(Cs * R);
-      if (spx_flatten_nrt_long_pods(pods, rc, &slots, n_long, n_lc, &n_long, &n_lc, lrow.data(), lptr.data(), lkind.data(), lpres.data(), lreq.data()) != SPX_OK) {
-        rc_pods = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_long_pods failed");
-        return;
-      }
-      const spx_nrt_long_pods lt{n_long, n_res, lrow.data(), lptr.data(), lkind.data(), lpres.data(), lreq.data()};
-      rc_pods = spx_upload_nrt_long_pods(e, &lt);
-    }
-    e->load_nrt_ms[5] = since(t2);  // 5: spx_upload_nrt_pods (item stream, pod classes, rank stream)
-  });
-  int rc_nodes = SPX_OK;
-  {
-    const auto t1 = clk::now();
-    std::vector<uint8_t> nflags(N), nz(N), zid(N * Z), zp(N * Z), np(N);
-    std::vector<int32_t> max_numa(N), zcost(N * Z * Z);
-    std::vector<int64_t> zavail(N * Z * R);
-    std::vector<float> minavg(N * Z);
-    if (spx_flatten_nrt_nodes(nodes, nrt, &slots, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(), minavg.data(), np.data()) !=
-        SPX_OK) {
-      rc_nodes = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_nodes failed");
-    } else {
-      e->load_nrt_ms[1] = since(t1);  // 1: node columns allocated + spx_flatten_nrt_nodes
-      const auto t2 = clk::now();
-      const spx_nrt_nodes_soa ns{nodes->n_nodes, n_res, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(), minavg.data(), np.data()};
-      rc_nodes = spx_upload_nrt_nodes(e, &ns);
-      e->load_nrt_ms[4] = since(t2);  // 4: spx_upload_nrt_nodes (precondition checks, window-local node order, one blob, derived columns on the device)
-    }
-  }
-  pod_half.join();
-  return rc_nodes ? rc_nodes : rc_pods;
-}
-
-// The four loaders of a full profile side by side: they fill disjoint tables of the engine (trimaran + Allocatable columns, NRT tables,
-// NetworkOverhead tables, quota tables), share one stream, and each takes a worker pool of its own.  Members left NULL skip their loader.
-int spx_load_profile(spx_engine* e, const spx_profile_objects* o) {
-  if (!e || !o || !o->nodes || !o->pods) return SPX_ERR_ARG;
-  if (o->nrt && !o->nrt_params) return fail(e, SPX_ERR_ARG, "spx_load_profile: nrt without nrt_params");
-  int rc_;
-  if ((rc_ = set_nodes(e, o->nodes->n_nodes)) || (rc_ = set_pods(e, o->pods->n_pods))) return rc_;
-  int rcs[4] = {SPX_OK, SPX_OK, SPX_OK, SPX_OK};
-  std::string msgs[4];  // a failing loader's message, taken on the thread it failed on (fail() records it in that thread's tl_err)
-  const auto run = [&](int i, const auto& load) {
-    tl_err_engine = nullptr;
-    rcs[i] = load();
-    if (rcs[i] && tl_err_engine == e) msgs[i] = tl_err;
-  };
-  std::vector<std::thread> th;
-  if (o->nrt) th.emplace_back([&] { run(1, [&] { return spx_load_nrt(e, o->nodes, o->nrt, o->rc, o->pods, o->nrt_params); }); });  // the longest first
-  if (o->appgroups && o->nettopo) th.emplace_back([&] { run(2, [&] { return spx_load_network(e, o->nodes, o->pods, o->appgroups, o->nettopo); }); });
-  if (o->quota) th.emplace_back([&] { run(3, [&] { return spx_load_quota(e, o->pods, o->rc, o->quota); }); });
-  if (o->metrics) run(0, [&] { return spx_load_trimaran(e, o->nodes, o->rc, o->pods, o->metrics, o->assigned); });
-  for (std::thread& t : th) t.join();
-  // the caller's spx_last_error must name the failure returned here, not an older one of this thread on this engine
-  for (int i = 0; i < 4; ++i)
-    if (rcs[i]) return fail(e, rcs[i], msgs[i].empty() ? std::string("spx_load_profile: a loader failed") : msgs[i]);
-  return SPX_OK;
-}
-
-int spx_last_load_nrt_ms(const spx_engine* e, double* ms6) {
-  if (!e || !ms6) return SPX_ERR_ARG;
-  std::memcpy(ms6, e->load_nrt_ms, sizeof e->load_nrt_ms);
-  return SPX_OK;
-}
-
-int spx_load_network(spx_engine* e, const spx_node_objects* nodes, const spx_pod_objects* pods, const spx_appgroup_objects* appgroups, const spx_nettopo_objects* nettopo) {
-  if (!e || !nodes || !pods || !appgroups || !nettopo) return SPX_ERR_ARG;
-  const size_t P = static_cast<size_t>(pods->n_pods);
-  const size_t rg = static_cast<size_t>(nettopo->n_regions), zc = static_cast<size_t>(nettopo->n_zones);
-  std::vector<int32_t> rcost(rg * rg ? rg * rg : 1, -1), zcost(zc * zc ? zc * zc : 1, -1);
-  if (spx_flatten_net_topo(nettopo, rcost.data(), zcost.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_net_topo failed");
-  int32_t n_keys = 0;
-  int64_t n_pairs = 0, n_eff = 0;
-  if (spx_flatten_net_keys(pods, appgroups, &n_keys, &n_pairs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != SPX_OK)
-    return fail(e, SPX_ERR_ARG, "spx_flatten_net_keys failed");
-  std::vector<int32_t> pod_key(P), topo(P), pair_ptr(static_cast<size_t>(n_keys) + 1), pair_node(n_pairs > 0 ? static_cast<size_t>(n_pairs) : 1);
-  std::vector<uint8_t> eq(n_keys > 0 ? static_cast<size_t>(n_keys) : 1);
-  std::vector<int64_t> pair_max(n_pairs > 0 ? static_cast<size_t>(n_pairs) : 1);
-  if (spx_flatten_net_keys(pods, appgroups, &n_keys, &n_pairs, pod_key.data(), topo.data(), eq.data(), pair_ptr.data(), pair_node.data(), pair_max.data()) != SPX_OK)
-    return fail(e, SPX_ERR_ARG, "spx_flatten_net_keys failed");
-  if (spx_flatten_net_commit(pods, appgroups, &n_eff, nullptr, nullptr, nullptr) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_net_commit failed");
-  std::vector<int32_t> eff_ptr(P + 1), eff_key(n_eff > 0 ? static_cast<size_t>(n_eff) : 1);
-  std::vector<int64_t> eff_cost(n_eff > 0 ? static_cast<size_t>(n_eff) : 1);
-  if (spx_flatten_net_commit(pods, appgroups, &n_eff, eff_ptr.data(), eff_key.data(), eff_cost.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_net_commit failed");
-  int rc_;
-  const spx_net_nodes_soa nn{nodes->n_nodes, nodes->region, nodes->zone};
-  if ((rc_ = spx_upload_net_nodes(e, &nn))) return rc_;
-  const spx_net_topo_soa nt{nettopo->n_regions, nettopo->n_zones, rcost.data(), zcost.data()};
-  if ((rc_ = spx_upload_net_topo(e, &nt))) return rc_;
-  const spx_net_pods_soa np{pods->n_pods, n_keys, pod_key.data(), eq.data(), pair_ptr.data(), pair_node.data(), pair_max.data(), topo.data()};
-  if ((rc_ = spx_upload_net_pods(e, &np))) return rc_;
-  const spx_net_commit_soa nc{pods->n_pods, eff_ptr.data(), eff_key.data(), eff_cost.data()};
-  return spx_upload_net_commit(e, &nc);
-}
-
-int spx_load_quota(spx_engine* e, const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_quota_objects* quota) {
-  if (!e || !pods || !quota) return SPX_ERR_ARG;
-  constexpr size_t S = SPX_QUOTA_SLOTS;
-  const size_t P = static_cast<size_t>(pods->n_pods), NS = static_cast<size_t>(quota->n_namespaces), NN = quota->n_nominated > 0 ? static_cast<size_t>(quota->n_nominated) : 1;
-  std::vector<int32_t> pod_ns(P), pod_prio(P), nom_ptr(NS + 1), nom_prio(NN);
-  std::vector<int64_t> pod_req(P * S), agg_used(S), agg_min(S), other((NS ? NS : 1) * S), nom_pending(NN), nom_req(NN * S);
-  std::vector<uint8_t> pod_reqp(P), other_p(NS ? NS : 1), nom_reqp(NN);
-  uint8_t agg_used_p = 0, agg_min_p = 0;
-  if (spx_flatten_quota(pods, rc, quota, pod_ns.data(), pod_prio.data(), pod_req.data(), pod_reqp.data(), agg_used.data(), &agg_used_p, agg_min.data(), &agg_min_p, other.data(),
-                        other_p.data(), nom_ptr.data(), nom_prio.data(), nom_pending.data(), nom_req.data(), nom_reqp.data()) != SPX_OK)
-    return fail(e, SPX_ERR_ARG, "spx_flatten_quota failed");
-  spx_quota_soa q{};
-  q.n_pods = pods->n_pods, q.n_namespaces = quota->n_namespaces;
-  q.pod_ns = pod_ns.data(), q.pod_priority = pod_prio.data(), q.pod_req = pod_req.data(), q.pod_req_present = pod_reqp.data();
-  q.has_quota = quota->has_quota, q.used = quota->used, q.used_present = quota->used_present, q.max = quota->max, q.max_present = quota->max_present;
-  q.agg_used = agg_used.data(), q.agg_used_present = &agg_used_p, q.agg_min = agg_min.data(), q.agg_min_present = &agg_min_p;
-  q.other_nominated = other.data(), q.other_nominated_present = other_p.data();
-  q.nom_ptr = nom_ptr.data(), q.nom_priority = nom_prio.data(), q.nom_pending_index = nom_pending.data(), q.nom_req = nom_req.data(), q.nom_req_present = nom_reqp.data();
-  q.min = quota->min, q.min_present = quota->min_present;
-  return spx_upload_quota(e, &q);
-}
-
 }  // extern "C"
