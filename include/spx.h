@@ -61,7 +61,8 @@ extern "C" {
 #define SPX_PLUGIN_TOPOSORT 6
 #define SPX_PLUGIN_LROC 7  /* trimaran LowRiskOverCommitment */
 #define SPX_PLUGIN_PEAKS 8 /* trimaran Peaks */
-#define SPX_NUM_PLUGINS 9
+#define SPX_PLUGIN_SYSCHED 9 /* SySched (pkg/sysched) */
+#define SPX_NUM_PLUGINS 10
 
 /* fwk.Status codes (k8s.io/kube-scheduler/framework) */
 #define SPX_STATUS_SUCCESS 0
@@ -184,6 +185,30 @@ typedef struct spx_power_model_objects {
   const double* k1;
   const double* k2;
 } spx_power_model_objects;
+
+/* SySched (pkg/sysched/sysched.go): everything Score reads, with syscall names interned to ids 0..n_names-1 (at most
+ * SPX_SYSCHED_MAX_NAMES).  The distinct syscall sets getSyscalls resolves (:124-210) are a CSR: set s holds the name ids
+ * set_name[set_ptr[s] .. set_ptr[s+1]) (any order, repeats allowed; an empty set is legal: Score answers math.MaxInt64 for such
+ * a pod, :249-251).  pod_set[p] is pending pod p's set.  Per node: host_present = HostSyscalls has an entry (:253-259), the
+ * cached set itself as the CSR host_ptr / host_name, and the resident pods HostToPods lists (:267) as set ids res_set[res_ptr[n]
+ * .. res_ptr[n+1]) — Score recomputes getSyscalls for each of them, so a resident's set may hold names the cached host set lacks
+ * (a SeccompProfile that changed after addPod). */
+#define SPX_SYSCHED_MAX_NAMES 1024
+#define SPX_SYSCHED_MAX_WORDS 16 /* 64-bit words of a bitset over the names */
+typedef struct spx_sysched_objects {
+  int32_t n_names;
+  int32_t n_sets;
+  const int32_t* set_ptr;
+  const int32_t* set_name;
+  int64_t n_pods;
+  const int32_t* pod_set;
+  int64_t n_nodes;
+  const uint8_t* host_present;
+  const int32_t* host_ptr;
+  const int32_t* host_name;
+  const int32_t* res_ptr;
+  const int32_t* res_set;
+} spx_sysched_objects;
 
 /* NodeResourceTopology CR image per node plus the NRT cache's verdict for it
  * (pkg/noderesourcetopology/cache: GetCachedNRTCopy -> (nrt, CachedNRTInfo{Fresh})).
@@ -392,6 +417,35 @@ typedef struct spx_peaks_pods_soa {
   int64_t n_pods;
   const int64_t* cpu_milli;
 } spx_peaks_pods_soa;
+
+/* SySched.  With H the node's cached host set, Q_q its resident pods' sets, k = n_resident and P the pending pod's set,
+ * Score (sysched.go:261-278) is |H \ P| + sum_q |(H u P) \ Q_q| = popc(H & ~P) + a + k popc(P & ~H) - sum over b in P \ H of c[b],
+ * a = resident_missing = sum_q |H \ Q_q| and c[b] = the residents whose set holds b.  The last term exists only on nodes with a
+ * resident set that is not inside H; those carry the (b, c[b]) pairs with b outside H and c[b] > 0 in the CSR stale_ptr [N+1] /
+ * stale_bit / stale_count.  host_bits is word-major [n_words][n_nodes] (bit b of the set = bit b % 64 of word b / 64), zero for
+ * a node that is not present; n_words = ceil(n_names / 64) <= SPX_SYSCHED_MAX_WORDS.  Every score must stay below
+ * SPX_SYSCHED_MAX_SCORE (100 x score is formed in 32 bits): a + (k + 1) n_names of every node is checked at the upload. */
+#define SPX_SYSCHED_MAX_SCORE 21474836
+typedef struct spx_sysched_nodes_soa {
+  int64_t n_nodes;
+  int32_t n_words;
+  const uint64_t* host_bits;
+  const uint8_t* present;
+  const int32_t* n_resident;
+  const int32_t* resident_missing;
+  const int32_t* stale_ptr;
+  const int32_t* stale_bit;
+  const int32_t* stale_count;
+} spx_sysched_nodes_soa;
+
+/* the distinct sets as bitsets, set_bits [n_sets][n_words], and each pending pod's set */
+typedef struct spx_sysched_pods_soa {
+  int64_t n_pods;
+  int32_t n_words;
+  int32_t n_sets;
+  const uint64_t* set_bits;
+  const int32_t* pod_set;
+} spx_sysched_pods_soa;
 
 /* NodeResourceTopologyMatch.  Resources are renumbered into dense "slots" 0..n_res-1 (the union of
  * what pods request and zones report; slot_res gives the canonical id).  Limits of this build:
@@ -605,6 +659,8 @@ typedef struct spx_net_commit_soa {
  *   spx_eval + spx_fetch_scores(LROC)          LowRiskOverCommitment.PreScore + Score  pkg/trimaran/lowriskovercommitment/lowriskovercommitment.go:96-141, :158-255, beta.go:85-191
  *   spx_eval + spx_fetch_scores(PEAKS)         Peaks.Score + NormalizeScore            pkg/trimaran/peaks/peaks.go:103-144, :150-166, :186-188
  *   spx_fetch_raw(PEAKS)                       Peaks.Score (raw int64: power jump x 1e15)
+ *   spx_eval + spx_fetch_scores(SYSCHED)       SySched.Score + NormalizeScore          pkg/sysched/sysched.go:234-279, :281-288
+ *   spx_fetch_raw(SYSCHED)                     SySched.Score (raw int64; math.MaxInt64 for a pod with the empty set, :249-251)
  *   spx_eval + spx_fetch_status(NRT)           TopologyMatch.Filter                    pkg/noderesourcetopology/filter.go:179-245
  *   spx_eval + spx_fetch_scores(NRT)           TopologyMatch.Score                     pkg/noderesourcetopology/score.go:62-102
  *   spx_eval + spx_fetch_status(NETOVERHEAD)   NetworkOverhead.PreFilter + Filter      pkg/networkaware/networkoverhead/networkoverhead.go:174-298, :326-359
@@ -655,6 +711,10 @@ int spx_upload_lroc_nodes(spx_engine* e, const spx_lroc_nodes_soa* t);
 int spx_upload_lroc_pods(spx_engine* e, const spx_lroc_pods_soa* t);
 int spx_upload_peaks_nodes(spx_engine* e, const spx_peaks_nodes_soa* t);
 int spx_upload_peaks_pods(spx_engine* e, const spx_peaks_pods_soa* t);
+/* SySched tables (spx_flatten_sysched_*).  SPX_ERR_ARG: n_words outside [1, SPX_SYSCHED_MAX_WORDS], a set id out of range, a node
+ * whose largest possible score reaches SPX_SYSCHED_MAX_SCORE, a stale bit outside the names */
+int spx_upload_sysched_nodes(spx_engine* e, const spx_sysched_nodes_soa* t);
+int spx_upload_sysched_pods(spx_engine* e, const spx_sysched_pods_soa* t);
 /* Snapshot deltas (SURVEY 8d "upload deltas"): `t` holds t->n_nodes ROWS in the layout of the full upload; row i replaces node
  * idx[i] of the table already on the device (spx_upload_* must have run once: it fixes the shape).  The changed rows travel as one
  * staged blob and are scattered into the device columns; for NRT the float64 formulation's derived columns are recomputed on the
@@ -663,6 +723,9 @@ int spx_upload_peaks_pods(spx_engine* e, const spx_peaks_pods_soa* t);
  *   NRT: a republished NodeResourceTopology (pluginhelpers.go:105-161), an assumed pod charged to a node (overreserve.go:170-203) */
 int spx_update_trimaran_nodes(spx_engine* e, const int64_t* idx, const spx_trimaran_nodes_soa* t);
 int spx_update_nrt_nodes(spx_engine* e, const int64_t* idx, const spx_nrt_nodes_soa* t);
+/* SySched: a bind or a delete changes one node's cached host set, resident count, a and stale list (sysched.go:310-366 addPod /
+ * removePod); `t` holds t->n_nodes rows in the layout of the full upload (host_bits [n_words][t->n_nodes], stale_ptr over the rows) */
+int spx_update_sysched_nodes(spx_engine* e, const int64_t* idx, const spx_sysched_nodes_soa* t);
 /* NetworkOverhead: pairs appended to the workload keys' lists (AppGroup scheduled lists grow between cycles, networkoverhead.go:654-694).
  * Entry i: key[i] gains (node[i], max_cost[i]); max_cost[i] == -1: the key merely stops scoring equally.  Built by spx_flatten_net_placed.
  * Equal to re-uploading spx_flatten_net_keys' tables of the grown AppGroups (tests/test_gpu_delta.py). */
@@ -751,6 +814,7 @@ int spx_fetch_best(spx_engine* e, int64_t row_begin, int64_t row_end, int32_t* n
  * writes a score table (the per-row argmax is folded into the sweep: no 1 B/cell/plugin to HBM and back).  Fused for the
  * Filter-less profiles made of TLP, optionally ALLOCATABLE, and any of the Score-only plugins LVRB / LROC / PEAKS, with
  * non-negative plugin weights and no caller feasibility mask.  ALLOCATABLE's and TLP's tables are never written; the
+ * (a mask that holds SYSCHED is served by the unfused route: spx_eval + spx_eval_best)
  * Score-only plugins' tables ARE evaluated (spx_eval on those plugins, so they can be fetched afterwards) and read once by
  * the fused sweep in place of spx_eval_best's pass over every table.  Any other request is served by running spx_eval and
  * spx_eval_best.  Asynchronous on the engine stream like spx_eval. */
@@ -765,7 +829,8 @@ int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t r
  *   CAPACITY           Reserve: the namespace's Used grows by the pod's request, a nominated pod that gets bound stops counting as
  *                      nominated (capacity_scheduling.go:350-364, elasticquota.go:89-98) — needs spx_quota_soa.min;
  *   NETOVERHEAD        the pod joins its AppGroup's scheduled list (networkoverhead.go:205-224) — needs spx_upload_net_commit.
- * plugin_mask is a subset of {ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY}.  Without a Filter plugin the whole chain runs in one
+ * plugin_mask is a subset of {ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY}: LROC, PEAKS and SYSCHED are rejected (SySched's
+ * bind-time bookkeeping — addPod's union into the host set, sysched.go:310-333 — is not carried by the loop).  Without a Filter plugin the whole chain runs in one
  * workgroup (about 3 us per pod); with one, every pod is one single-row spx_eval + spx_eval_best + a bookkeeping launch on the engine
  * stream (tens of us per pod), score / status tables end up holding each row as its pod saw it (except Allocatable's when Filter
  * plugins are in the mask: its feasibility-aware normalisation then happens inside the argmax kernel, as in spx_decide).  A pod that fails PreFilter or has no
@@ -891,6 +956,10 @@ int spx_nrt_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_copie
  * or feasibility mask narrows a pod's node list, the same NormalizeScore (peaks.go:150-166). */
 int spx_peaks_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_copies);
 
+/* The same for the uploaded SySched pod batch (spx_upload_sysched_pods): a pod enters SySched.Score through its syscall set alone, so
+ * n_unique = pods that are the first of the batch with their set, n_copies = the rest. */
+int spx_sysched_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_copies);
+
 /* Object tables -> SoA columns -> device in one call per plugin family: the host flatteners (spx_flatten_*, below) run with the
  * engine's current plugin parameters and their result is uploaded.  For callers that hold object tables — marshalled by the shim or
  * decoded by spx_ingest_* — and would rather not size and own the intermediate arrays (the cgo shim: shim/go/pkg/spx/snapshot.go).
@@ -905,6 +974,8 @@ int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_obj
 int spx_last_load_nrt_ms(const spx_engine* e, double* ms6);
 int spx_load_network(spx_engine* e, const spx_node_objects* nodes, const spx_pod_objects* pods, const spx_appgroup_objects* appgroups, const spx_nettopo_objects* nettopo);
 int spx_load_quota(spx_engine* e, const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_quota_objects* quota);
+/* SySched: flatten + upload of both tables (spx_flatten_sysched_nodes / _pods) */
+int spx_load_sysched(spx_engine* e, const spx_sysched_objects* o);
 /* The whole profile in one call: the loaders above run side by side on host threads of the library (they fill disjoint tables and share
  * the engine's stream; spx_load_nrt itself runs its node half and its pod half on two threads).  nodes and pods are required; a loader
  * whose members are NULL is skipped: metrics (+ rc, assigned) = spx_load_trimaran, nrt + nrt_params = spx_load_nrt, appgroups + nettopo =
@@ -943,7 +1014,9 @@ int spx_nrt_packed_score_slots(const spx_engine* e);
 
 /* which formulation of a plugin's sweep the uploaded tables select: 0 = generic (reference arithmetic, operation for
  * operation), 1 = fast formulation (same results; see DESIGN.md for each kernel's preconditions); <0 on error.
- * Tests use it to make sure both formulations are exercised. */
+ * Tests use it to make sure both formulations are exercised.
+ * SPX_PLUGIN_SYSCHED has one formulation; for it the call reports how many chunks of distinct sets the last SySched sweep of
+ * spx_eval built its raw table in (the table is scratch bounded at 256 MiB, kernels_sysched.hip), 0 before the first sweep. */
 int spx_kernel_path(const spx_engine* e, int plugin);
 
 /* make the engine write a Filter plugin's status table (NRT, NETOVERHEAD) into caller-owned device memory; row_stride must be
@@ -966,7 +1039,8 @@ int spx_bind_status_table(spx_engine* e, int plugin, void* dptr, int64_t row_str
  * transport: SPX_MULTI_TRANSPORT_RCCL = ncclAllGather on each engine's stream (librccl.so.1 is dlopen'ed here, so a
  * single-GPU scheduler never maps it; needs distinct devices); SPX_MULTI_TRANSPORT_PEER_COPY = the same bytes with
  * hipMemcpyPeerAsync (also works with several ranks on one device: how the sharding logic is tested on a one-GPU box).
- * Calls on one spx_multi must come from one thread at a time. */
+ * Calls on one spx_multi must come from one thread at a time.  The layer's loaders carry no LROC, Peaks or SySched tables: those
+ * plugins are uploaded per rank through spx_multi_engine. */
 #define SPX_MULTI_TRANSPORT_RCCL 0
 #define SPX_MULTI_TRANSPORT_PEER_COPY 1
 typedef struct spx_multi spx_multi;
@@ -1015,6 +1089,15 @@ int spx_flatten_lroc_pods(const spx_pod_objects* pods, int64_t* req_cpu_milli, i
 /* Peaks: node arrays sized [N], pod array [P] */
 int spx_flatten_peaks_nodes(const spx_node_objects* nodes, const spx_metrics_objects* metrics, const spx_power_model_objects* models, int64_t* cap_cpu_milli, double* cpu_util, uint8_t* valid, double* k1, double* k2);
 int spx_flatten_peaks_pods(const spx_pod_objects* pods, int64_t* cpu_milli);
+
+/* SySched.  spx_flatten_sysched_nodes: *n_words_out and *n_stale_out (entries of the stale CSR) are written first; with every
+ * output array NULL the call only counts.  Otherwise host_bits [n_words][N], present / n_resident / resident_missing [N],
+ * stale_ptr [N+1], stale_bit / stale_count [stale_cap] (stale entries of a node in ascending bit order); more entries than
+ * stale_cap, more than SPX_SYSCHED_MAX_NAMES names, or a name / set id out of range are SPX_ERR_ARG.  A node that is not
+ * present gets zero bits, k = a = 0 and no stale entries (Score returns 0 there whatever HostToPods holds, sysched.go:253-259).
+ * spx_flatten_sysched_pods: set_bits [n_sets][n_words], pod_set [P]. */
+int spx_flatten_sysched_nodes(const spx_sysched_objects* o, int64_t stale_cap, int32_t* n_words_out, int64_t* n_stale_out, uint64_t* host_bits, uint8_t* present, int32_t* n_resident, int32_t* resident_missing, int32_t* stale_ptr, int32_t* stale_bit, int32_t* stale_count);
+int spx_flatten_sysched_pods(const spx_sysched_objects* o, uint64_t* set_bits, int32_t* pod_set);
 
 /* NRT: builds the dense slot numbering from every resource id pods request or zones report
  * (slot_res/slot_flags/slot_weight sized SPX_NRT_MAX_RES; *n_res_out receives the count) */

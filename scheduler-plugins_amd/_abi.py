@@ -32,6 +32,7 @@ _NP = {
     C.c_int64: np.int64,
     C.c_uint8: np.uint8,
     C.c_uint32: np.uint32,
+    C.c_uint64: np.uint64,
     C.c_double: np.float64,
     C.c_float: np.float32,
     C.c_int: np.int32,

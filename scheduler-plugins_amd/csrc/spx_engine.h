@@ -68,7 +68,7 @@ struct spx_engine {
   std::vector<int64_t> alloc_weight{1, 1 << 20};  // defaultResourcesToWeightMap resource_allocation.go:36
   spx_tlp_params tlp{40, 1000, 1.5};             // apis/config/v1/defaults.go:51-55
   spx_lvrb_params lvrb{1.0, 1.0};                // defaults.go:65-67
-  int64_t plugin_weight[SPX_NUM_PLUGINS] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
+  int64_t plugin_weight[SPX_NUM_PLUGINS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 
   // device tables
   DevBuf d_alloc, d_alloc_w, d_alloc_raw, d_alloc_norm, d_alloc_rel;
@@ -104,6 +104,16 @@ struct spx_engine {
   // Peaks
   DevBuf d_pk_cap, d_pk_util, d_pk_valid, d_pk_k1, d_pk_k2, d_pk_pod, d_pk_min, d_pk_max, d_pk_rowc, d_pk_tab, d_pk_seg, d_pk_segn;
   bool peaks_nodes = false, peaks_pods = false;
+
+  // SySched: node columns, the stale CSR (host copy: a delta rebuilds it whole — the lists are short and rare), the distinct sets,
+  // the pods ordered by set (classes = sets), the chunked raw table and the sets' maxima
+  DevBuf d_sy_host, d_sy_present, d_sy_k, d_sy_a, d_sy_sptr, d_sy_sbit, d_sy_scnt;
+  DevBuf d_sy_sets, d_sy_empty, d_sy_pod_set, d_sy_order, d_sy_first, d_sy_dups, d_sy_raw, d_sy_max;
+  bool sy_nodes = false, sy_pods = false;
+  int32_t sy_node_words = 0, sy_pod_words = 0, sy_n_sets = 0;
+  std::vector<int32_t> h_sy_sptr, h_sy_sbit, h_sy_scnt, h_sy_pod_set, h_sy_first;
+  int64_t sy_n_dups = 0, sy_n_tasks = 0;
+  int sy_last_chunks = 0;  // spx_kernel_path(SYSCHED)
 
   // NodeResourceTopologyMatch
   spx_nrt_params nrt_params{SPX_NRT_LEAST_ALLOCATED, 0, nullptr, nullptr};  // defaults.go:87-90
@@ -368,7 +378,10 @@ int ensure_score_table(spx_engine* e, int plugin) {
 
 constexpr uint32_t kFilterPlugins = (1u << SPX_PLUGIN_NRT) | (1u << SPX_PLUGIN_NETOVERHEAD);
 // plugins whose NormalizeScore depends on the feasible set of the cycle
-constexpr uint32_t kNormalizingPlugins = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_PEAKS);
+constexpr uint32_t kNormalizingPlugins =
+    (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_PEAKS) | (1u << SPX_PLUGIN_SYSCHED);
+// plugins that own a uint8 score table
+constexpr bool plugin_has_score(int k) { return k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS || k == SPX_PLUGIN_SYSCHED; }
 
 // rows [b, e) of `plugin` hold results of an spx_eval
 int rows_evaluated(const spx_engine* e, int plugin, int64_t b, int64_t en) {
@@ -505,6 +518,26 @@ void fill_peaks(const spx_engine* e, spx::PeaksArgs& a) {
   a.row_max = static_cast<int64_t*>(e->d_pk_max.p);
   a.row_c = static_cast<float*>(e->d_pk_rowc.p);
   a.node_tab = static_cast<double*>(e->d_pk_tab.p);
+}
+
+void fill_sysched(const spx_engine* e, spx::SyschedArgs& a) {
+  a.n_nodes = e->n_nodes;
+  a.row_stride = e->row_stride;
+  a.n_words = e->sy_node_words;
+  a.host_bits = static_cast<const uint64_t*>(e->d_sy_host.p);
+  a.present = static_cast<const uint8_t*>(e->d_sy_present.p);
+  a.n_resident = static_cast<const int32_t*>(e->d_sy_k.p);
+  a.resident_missing = static_cast<const int32_t*>(e->d_sy_a.p);
+  a.stale_ptr = static_cast<const int32_t*>(e->d_sy_sptr.p);
+  a.stale_bit = static_cast<const int32_t*>(e->d_sy_sbit.p);
+  a.stale_count = static_cast<const int32_t*>(e->d_sy_scnt.p);
+  a.set_bits = static_cast<const uint64_t*>(e->d_sy_sets.p);
+  a.set_empty = static_cast<const uint8_t*>(e->d_sy_empty.p);
+  a.pod_set = static_cast<const int32_t*>(e->d_sy_pod_set.p);
+  a.order = static_cast<const int32_t*>(e->d_sy_order.p);
+  a.set_first = static_cast<const int32_t*>(e->d_sy_first.p);
+  a.raw = static_cast<int32_t*>(e->d_sy_raw.p);
+  a.set_max = static_cast<int32_t*>(e->d_sy_max.p);
 }
 
 void fill_trimaran(const spx_engine* e, spx::TrimaranArgs& a) {

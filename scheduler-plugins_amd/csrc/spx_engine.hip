@@ -78,7 +78,9 @@ int spx_destroy(spx_engine* e) {
                     &e->d_nrtl_row, &e->d_nrtl_ptr, &e->d_nrtl_kind, &e->d_nrtl_pres, &e->d_nrtl_req, &e->d_nrtl_map,
                     &e->d_nrtw_sflags, &e->d_nrtw_sweight, &e->d_nrtw_flags, &e->d_nrtw_max_numa, &e->d_nrtw_nz, &e->d_nrtw_zid, &e->d_nrtw_zp,
                     &e->d_nrtw_avail, &e->d_nrtw_cost, &e->d_nrtw_minavg, &e->d_nrtw_np, &e->d_nrtw_qos, &e->d_nrtw_nn, &e->d_nrtw_rptr,
-                    &e->d_nrtw_rslot, &e->d_nrtw_rqty, &e->d_nrtw_cptr, &e->d_nrtw_ckind, &e->d_nrtw_eptr, &e->d_nrtw_eslot, &e->d_nrtw_eqty};
+                    &e->d_nrtw_rslot, &e->d_nrtw_rqty, &e->d_nrtw_cptr, &e->d_nrtw_ckind, &e->d_nrtw_eptr, &e->d_nrtw_eslot, &e->d_nrtw_eqty,
+                    &e->d_sy_host, &e->d_sy_present, &e->d_sy_k, &e->d_sy_a, &e->d_sy_sptr, &e->d_sy_sbit, &e->d_sy_scnt, &e->d_sy_sets, &e->d_sy_empty,
+                    &e->d_sy_pod_set, &e->d_sy_order, &e->d_sy_first, &e->d_sy_dups, &e->d_sy_raw, &e->d_sy_max};
   for (DevBuf* b : bufs)
     if (b->p && !b->external) (void)hipFree(b->p);
   for (int i = 0; i < SPX_NUM_PLUGINS; ++i) {
@@ -168,6 +170,13 @@ int spx_peaks_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_cop
   return SPX_OK;
 }
 
+int spx_sysched_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_copies) {
+  if (!e || !n_unique || !n_copies) return SPX_ERR_ARG;
+  *n_copies = e->sy_pods ? e->sy_n_dups : 0;
+  *n_unique = e->sy_pods ? e->n_pods - *n_copies : 0;
+  return SPX_OK;
+}
+
 int spx_get_option(const spx_engine* e, int option, int64_t* value) {
   if (!e || !value || option < 0 || option >= SPX_NUM_OPTIONS) return SPX_ERR_ARG;
   *value = e->option[option];
@@ -217,12 +226,17 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   if (!e) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
   const uint32_t known = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_TLP) | (1u << SPX_PLUGIN_LVRB) | (1u << SPX_PLUGIN_NRT) |
-                         (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY) | (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS);
+                         (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY) | (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS) |
+                         (1u << SPX_PLUGIN_SYSCHED);
   if (plugin_mask == 0 || (plugin_mask & ~known)) return fail(e, SPX_ERR_ARG, "plugin mask has unsupported bits");
   const bool R = plugin_mask & (1u << SPX_PLUGIN_LROC);
   if (R && !(e->tri_nodes && e->lroc_nodes && e->lroc_pods)) return fail(e, SPX_ERR_STATE, "LowRiskOverCommitment node/pod tables not uploaded");
   const bool K = plugin_mask & (1u << SPX_PLUGIN_PEAKS);
   if (K && !(e->peaks_nodes && e->peaks_pods)) return fail(e, SPX_ERR_STATE, "Peaks node/pod tables not uploaded");
+  const bool Y = plugin_mask & (1u << SPX_PLUGIN_SYSCHED);
+  if (Y && !(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
+  if (Y && e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
+  if (Y && e->row_indirect) return fail(e, SPX_ERR_STATE, "SySched is not part of the sequential commit loop");
   const bool Q = plugin_mask & (1u << SPX_PLUGIN_CAPACITY);
   if (Q && !e->quota) return fail(e, SPX_ERR_STATE, "CapacityScheduling quota tables not uploaded");
   if (e->n_nodes <= 0 && plugin_mask != (1u << SPX_PLUGIN_CAPACITY)) return fail(e, SPX_ERR_STATE, "no node table uploaded");
@@ -262,6 +276,18 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     return rc;
   if (N && (rc = ensure_status_table(e, SPX_PLUGIN_NRT))) return rc;
   if (W && (rc = ensure_status_table(e, SPX_PLUGIN_NETOVERHEAD))) return rc;
+  // SySched's raw table: as many distinct sets per chunk as the scratch budget holds (and a launch's grid takes)
+  int64_t sy_per_chunk = 0;
+  if (Y) {
+    if ((rc = ensure_score_table(e, SPX_PLUGIN_SYSCHED))) return rc;
+    if (e->score_stride[SPX_PLUGIN_SYSCHED] != e->row_stride)
+      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
+    const size_t row_bytes = static_cast<size_t>(e->row_stride) * sizeof(int32_t);
+    sy_per_chunk = std::min<int64_t>(std::max<int64_t>(1, static_cast<int64_t>(spx::kSyschedRawBudget / row_bytes)), spx::kSyschedMaxChunkSets);
+    if ((rc = ensure(e, e->d_sy_raw, static_cast<size_t>(std::min<int64_t>(sy_per_chunk, e->sy_n_sets)) * row_bytes)) ||
+        (rc = ensure(e, e->d_sy_max, static_cast<size_t>(e->sy_n_sets) * sizeof(int32_t))))
+      return rc;
+  }
 
   spx::TrimaranArgs a{};
   fill_trimaran(e, a);
@@ -562,6 +588,35 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
                               e->row_stride, e->stream);
     SPX_HIP(e, hipGetLastError());
   }
+  if (Y && row_end > row_begin) {  // after the Filter plugins, as Peaks: NormalizeScore runs over each pod's feasible nodes
+    spx::SyschedArgs ya{};
+    fill_sysched(e, ya);
+    ya.other_status[0] = N ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
+    ya.other_status[1] = W ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
+    ya.other_status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
+    ya.row_begin = row_begin;
+    ya.row_end = row_end;
+    ya.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_SYSCHED].p);
+    // nothing narrows a pod's node list and the whole batch is swept: every distinct set's row is normalised once and copied
+    const bool classes = !masked && row_begin == 0 && row_end == e->n_pods;
+    // a single row needs its own set's raw row only
+    int32_t s_lo = 0, s_hi = e->sy_n_sets;
+    if (row_end - row_begin == 1) s_lo = e->h_sy_pod_set[static_cast<size_t>(row_begin)], s_hi = s_lo + 1;
+    SPX_HIP(e, hipMemsetAsync(e->d_sy_max.p, 0, static_cast<size_t>(e->sy_n_sets) * sizeof(int32_t), e->stream));
+    int chunks = 0;
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += sy_per_chunk, ++chunks) {
+      ya.set_begin = static_cast<int32_t>(s0);
+      ya.set_end = static_cast<int32_t>(std::min<int64_t>(s0 + sy_per_chunk, s_hi));
+      spx::launch_sysched_raw(ya, e->stream);
+      if (classes) spx::launch_sysched_norm(ya, e->stream);
+      else spx::launch_sysched_rows(ya, e->h_sy_first[static_cast<size_t>(ya.set_end)] - e->h_sy_first[static_cast<size_t>(ya.set_begin)], e->stream);
+    }
+    if (classes && e->sy_n_dups > 0)
+      spx::launch_rows_expand(static_cast<const int32_t*>(e->d_sy_dups.p), static_cast<const int32_t*>(e->d_sy_dups.p) + 2 * e->sy_n_dups, e->sy_n_tasks, ya.out_score, nullptr,
+                              e->row_stride, e->stream);
+    SPX_HIP(e, hipGetLastError());
+    e->sy_last_chunks = chunks;
+  }
   if (A && masked && !e->skip_alloc_masked && !alloc_by_net) {
     spx::ProfileArgs pa{};
     pa.n_nodes = e->n_nodes;
@@ -639,6 +694,7 @@ int spx_kernel_path(const spx_engine* e, int plugin) {
             (e->nrt_params.strategy != SPX_NRT_LEAST_NUMA_NODES || e->nrt_ln_ok)) ? 1 : 0;
   if (plugin == SPX_PLUGIN_NETOVERHEAD) return (e->net_nodes && e->net_class16 && e->net_n_classes > 0 && !forced_reference(e, SPX_PLUGIN_NETOVERHEAD)) ? 1 : 0;
   if (plugin == SPX_PLUGIN_LROC) return lroc_f32_ok(e) ? 1 : 0;
+  if (plugin == SPX_PLUGIN_SYSCHED) return e->sy_last_chunks;
   if (plugin == SPX_PLUGIN_TLP) return (e->tlp.target_utilization >= 1 && e->tlp.target_utilization <= 99 && !(launch_opts(e) & spx::kOptTrimaranExact)) ? 1 : 0;
   return 0;
 }
@@ -787,6 +843,22 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
     ka.row_end = pod_row + 1;
     ka.out_raw = static_cast<int64_t*>(e->d_raw_row.p);
     spx::launch_peaks(ka, e->stream);
+    SPX_HIP(e, hipGetLastError());
+    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
+    SPX_HIP(e, hipStreamSynchronize(e->stream));
+    return SPX_OK;
+  }
+  if (plugin == SPX_PLUGIN_SYSCHED) {  // SySched.Score before NormalizeScore; math.MaxInt64 for a pod with the empty set
+    if (!(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
+    if (e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
+    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
+    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
+    spx::SyschedArgs ya{};
+    fill_sysched(e, ya);
+    ya.set_begin = e->h_sy_pod_set[static_cast<size_t>(pod_row)];
+    ya.set_end = ya.set_begin + 1;
+    ya.out_raw64 = static_cast<int64_t*>(e->d_raw_row.p);
+    spx::launch_sysched_raw(ya, e->stream);
     SPX_HIP(e, hipGetLastError());
     SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
     SPX_HIP(e, hipStreamSynchronize(e->stream));
@@ -943,7 +1015,7 @@ int decide_masked(spx_engine* e, uint32_t eval_mask, uint32_t score_mask, int64_
   pa.row_ptr = e->row_indirect;
   pa.alloc_rel = static_cast<const uint32_t*>(e->d_alloc_rel.p);
   for (int k = 0; k < SPX_NUM_PLUGINS; ++k) {
-    const bool has_score = k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS;
+    const bool has_score = plugin_has_score(k);
     // the tables the sweep below will have written by the time the kernel runs (engine-owned or bound: same row stride)
     if ((score_mask & (1u << k)) && has_score && k != SPX_PLUGIN_ALLOCATABLE) pa.score[k] = reinterpret_cast<const uint8_t*>(uintptr_t{1});
     pa.weight[k] = e->plugin_weight[k];
@@ -999,7 +1071,7 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
     uint32_t want = plugin_mask & kFilterPlugins;
     if (p == SPX_PLUGIN_NETOVERHEAD) want &= ~(1u << SPX_PLUGIN_NETOVERHEAD), want |= i.filters & (1u << SPX_PLUGIN_NETOVERHEAD);  // its own Filter is implied
     if (ctx_matters && (i.filters != want || i.ext_gen != e->ext_gen))
-      return fail(e, SPX_ERR_STATE, "spx_eval_best: a normalising plugin (Allocatable / NetworkOverhead / Peaks) was evaluated under a different Filter set "
+      return fail(e, SPX_ERR_STATE, "spx_eval_best: a normalising plugin (Allocatable / NetworkOverhead / Peaks / SySched) was evaluated under a different Filter set "
                                     "or feasibility mask than this argmax uses; evaluate the whole profile in one spx_eval");
   }
   const size_t P = static_cast<size_t>(e->n_pods);
@@ -1015,7 +1087,7 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
   pa.status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
   pa.prefilter = (plugin_mask & (1u << SPX_PLUGIN_CAPACITY)) ? static_cast<const uint8_t*>(e->d_q_status.p) : nullptr;
   for (int k = 0; k < SPX_NUM_PLUGINS; ++k) {
-    const bool has_score = k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS;
+    const bool has_score = plugin_has_score(k);
     if ((plugin_mask & (1u << k)) && has_score) {
       if (e->score_stride[k] != e->row_stride) return fail(e, SPX_ERR_STATE, "score table stride differs from the engine row stride");
       pa.score[k] = static_cast<const uint8_t*>(e->score[k].p);

@@ -235,6 +235,39 @@ struct PeaksArgs {
 void launch_peaks(const PeaksArgs& a, hipStream_t s);
 int peaks_est_plan(uint32_t opts, int64_t row_stride, int64_t swept, size_t* seg_bytes, size_t* cnt_bytes);
 
+// ---------------------------------------------------------------- SySched (kernels_sysched.hip)
+// The raw table is scratch: a sweep builds it in chunks of distinct sets that fit this many bytes (and a launch's grid)
+constexpr size_t kSyschedRawBudget = size_t{256} << 20;
+constexpr int64_t kSyschedMaxChunkSets = 65535;
+struct SyschedArgs {
+  int64_t n_nodes;
+  int64_t row_stride;
+  int32_t n_words;
+  const uint64_t* host_bits;        // [n_words][N]
+  const uint8_t* present;           // [N]
+  const int32_t* n_resident;        // [N] k
+  const int32_t* resident_missing;  // [N] a
+  const int32_t* stale_ptr;         // [N+1]
+  const int32_t* stale_bit;
+  const int32_t* stale_count;
+  const uint64_t* set_bits;         // [n_sets][n_words]
+  const uint8_t* set_empty;         // [n_sets]
+  const int32_t* pod_set;           // [P]
+  const int32_t* order;             // [P] pod rows sorted by (set, row)
+  const int32_t* set_first;         // [n_sets+1] position in `order` of each set's first pod
+  int32_t set_begin, set_end;       // the chunk of sets this launch works on
+  int32_t* raw;                     // [set_end - set_begin][row_stride] scratch
+  int32_t* set_max;                 // [n_sets] maximum of each set's raw row over all nodes (zeroed before the sweep)
+  int64_t* out_raw64;               // when set: the int64 raw row of set_begin alone, no table writes
+  const uint8_t* other_status[3];   // Filter plugins' status tables [P][row_stride] (0 = passed), NULL = unused
+  int64_t row_begin, row_end;       // k_sysched_rows: the pod rows wanted
+  uint8_t* out_score;               // [P][row_stride]
+};
+void launch_sysched_raw(const SyschedArgs& a, hipStream_t s);
+void launch_sysched_norm(const SyschedArgs& a, hipStream_t s);
+// a workgroup per pod of the chunk's sets (n_listed of them, consecutive in `order`)
+void launch_sysched_rows(const SyschedArgs& a, int64_t n_listed, hipStream_t s);
+
 // ---------------------------------------------------------------- NodeResourceTopologyMatch
 struct NrtArgs {
   uint32_t opts;

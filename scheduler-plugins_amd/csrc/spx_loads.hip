@@ -57,6 +57,27 @@ int spx_load_trimaran_pods(spx_engine* e, const spx_pod_objects* pods) {
   return SPX_OK;
 }
 
+// SySched: both tables from the object image (interned names, distinct sets, residents)
+int spx_load_sysched(spx_engine* e, const spx_sysched_objects* o) {
+  if (!e || !o) return SPX_ERR_ARG;
+  int32_t W = 0;
+  int64_t n_stale = 0;
+  if (spx_flatten_sysched_nodes(o, 0, &W, &n_stale, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != SPX_OK)
+    return fail(e, SPX_ERR_ARG, "spx_flatten_sysched_nodes failed (more than SPX_SYSCHED_MAX_NAMES names, or an id out of range)");
+  const size_t N = static_cast<size_t>(o->n_nodes), P = static_cast<size_t>(o->n_pods), S = static_cast<size_t>(o->n_sets);
+  std::vector<uint64_t> host(N * static_cast<size_t>(W) + 1), sets(S * static_cast<size_t>(W) + 1);
+  std::vector<uint8_t> present(N + 1);
+  std::vector<int32_t> k(N + 1), a(N + 1), sptr(N + 1), sbit(static_cast<size_t>(n_stale) + 1), scnt(static_cast<size_t>(n_stale) + 1), pod_set(P + 1);
+  if (spx_flatten_sysched_nodes(o, n_stale, &W, &n_stale, host.data(), present.data(), k.data(), a.data(), sptr.data(), sbit.data(), scnt.data()) != SPX_OK)
+    return fail(e, SPX_ERR_ARG, "spx_flatten_sysched_nodes failed");
+  if (spx_flatten_sysched_pods(o, sets.data(), pod_set.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_sysched_pods failed");
+  const spx_sysched_nodes_soa ns{o->n_nodes, W, host.data(), present.data(), k.data(), a.data(), sptr.data(), sbit.data(), scnt.data()};
+  int rc_;
+  if ((rc_ = spx_upload_sysched_nodes(e, &ns))) return rc_;
+  const spx_sysched_pods_soa ps{o->n_pods, W, o->n_sets, sets.data(), pod_set.data()};
+  return spx_upload_sysched_pods(e, &ps);
+}
+
 }  // extern "C"
 
 namespace {

@@ -145,6 +145,76 @@ int ship_nrt_rows(spx_engine* e, const spx_nrt_nodes_soa* t, const std::vector<i
   return SPX_OK;
 }
 
+// Rows of a SySched node table to the device: row i of `t` describes node ix[i] (`whole`: every node, in order — a full upload).  The
+// word columns and the three per-node columns leave in one blob and are scattered (or, whole, copied) into place; the stale CSR is
+// rebuilt on the host from the engine's copy with the listed nodes' lists replaced, and uploaded whole (the lists are short and
+// rare).  Everything is validated before the first byte moves.  The caller waits for the stream.
+int ship_sysched_rows(spx_engine* e, const spx_sysched_nodes_soa* t, const std::vector<int32_t>& ix, bool whole) {
+  const int64_t n = t->n_nodes, N = e->n_nodes;
+  const int32_t W = t->n_words;
+  if (!t->host_bits || !t->present || !t->n_resident || !t->resident_missing || !t->stale_ptr) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  if (t->stale_ptr[0] < 0 || (t->stale_ptr[n] > t->stale_ptr[0] && (!t->stale_bit || !t->stale_count))) return fail(e, SPX_ERR_ARG, "SySched: bad stale list");
+  for (int64_t i = 0; i < n; ++i) {
+    if (t->stale_ptr[i + 1] < t->stale_ptr[i]) return fail(e, SPX_ERR_ARG, "SySched: stale_ptr is not monotone");
+    int64_t stale_sum = 0;
+    for (int32_t j = t->stale_ptr[i]; j < t->stale_ptr[i + 1]; ++j) {
+      if (t->stale_bit[j] < 0 || t->stale_bit[j] >= W * 64 || t->stale_count[j] < 0) return fail(e, SPX_ERR_ARG, "SySched: stale entry out of range");
+      stale_sum += t->stale_count[j];
+    }
+    // the largest score any pod can get on this node: every name outside H, k times — 100 x that is formed in 32 bits
+    const int64_t k = t->n_resident[i], a = t->resident_missing[i];
+    if (k < 0 || a < 0 || a + (k + 1) * static_cast<int64_t>(W) * 64 >= SPX_SYSCHED_MAX_SCORE || stale_sum > a + (k + 1) * static_cast<int64_t>(W) * 64)
+      return fail(e, SPX_ERR_ARG, "SySched: a node's largest possible score reaches SPX_SYSCHED_MAX_SCORE");
+  }
+  // the stale CSR with the listed nodes' lists replaced
+  std::vector<int32_t> sptr(static_cast<size_t>(N) + 1, 0), sbit, scnt;
+  if (whole) {
+    const int32_t base = t->stale_ptr[0];
+    for (int64_t i = 0; i <= N; ++i) sptr[static_cast<size_t>(i)] = t->stale_ptr[i] - base;
+    sbit.assign(t->stale_bit + base, t->stale_bit + t->stale_ptr[N]);
+    scnt.assign(t->stale_count + base, t->stale_count + t->stale_ptr[N]);
+  } else {
+    std::vector<int64_t> row_of(static_cast<size_t>(N), -1);
+    for (int64_t i = 0; i < n; ++i) row_of[static_cast<size_t>(ix[static_cast<size_t>(i)])] = i;
+    for (int64_t node = 0; node < N; ++node) {
+      const int64_t r = row_of[static_cast<size_t>(node)];
+      const int32_t* b = r >= 0 ? t->stale_bit : e->h_sy_sbit.data();
+      const int32_t* c = r >= 0 ? t->stale_count : e->h_sy_scnt.data();
+      const int32_t j0 = r >= 0 ? t->stale_ptr[r] : e->h_sy_sptr[static_cast<size_t>(node)], j1 = r >= 0 ? t->stale_ptr[r + 1] : e->h_sy_sptr[static_cast<size_t>(node) + 1];
+      for (int32_t j = j0; j < j1; ++j) sbit.push_back(b[j]), scnt.push_back(c[j]);
+      sptr[static_cast<size_t>(node) + 1] = static_cast<int32_t>(sbit.size());
+    }
+  }
+  int rc;
+  const size_t m = static_cast<size_t>(n);
+  DeltaBlob b{e};
+  const size_t o_idx = b.add(ix.data(), m * 4);
+  const size_t o_bits = b.add(t->host_bits, m * static_cast<size_t>(W) * 8), o_pres = b.add(t->present, m), o_k = b.add(t->n_resident, m * 4),
+               o_a = b.add(t->resident_missing, m * 4);
+  if ((rc = b.ship())) return rc;
+  const int32_t* d_idx = reinterpret_cast<const int32_t*>(b.dev(o_idx));
+  hipStream_t s = e->stream;
+  if (whole) {  // the staged columns are the device columns as they are
+    SPX_HIP(e, hipMemcpyAsync(e->d_sy_host.p, b.dev(o_bits), m * static_cast<size_t>(W) * 8, hipMemcpyDeviceToDevice, s));
+    SPX_HIP(e, hipMemcpyAsync(e->d_sy_present.p, b.dev(o_pres), m, hipMemcpyDeviceToDevice, s));
+    SPX_HIP(e, hipMemcpyAsync(e->d_sy_k.p, b.dev(o_k), m * 4, hipMemcpyDeviceToDevice, s));
+    SPX_HIP(e, hipMemcpyAsync(e->d_sy_a.p, b.dev(o_a), m * 4, hipMemcpyDeviceToDevice, s));
+  } else {
+    for (int32_t w = 0; w < W; ++w)  // word w of the rows [W][n] -> word column w of the table [W][N]
+      spx::launch_scatter_rows(static_cast<uint64_t*>(e->d_sy_host.p) + static_cast<size_t>(w) * N, N, 1, d_idx, b.dev(o_bits + static_cast<size_t>(w) * m * 8), n, 8, s);
+    spx::launch_scatter_rows(e->d_sy_present.p, N, 1, d_idx, b.dev(o_pres), n, 1, s);
+    spx::launch_scatter_rows(e->d_sy_k.p, N, 1, d_idx, b.dev(o_k), n, 4, s);
+    spx::launch_scatter_rows(e->d_sy_a.p, N, 1, d_idx, b.dev(o_a), n, 4, s);
+    SPX_HIP(e, hipGetLastError());
+  }
+  if ((rc = upload(e, e->d_sy_sptr, sptr.data(), sptr.size() * 4)) || (rc = upload(e, e->d_sy_sbit, sbit.data(), sbit.size() * 4)) ||
+      (rc = upload(e, e->d_sy_scnt, scnt.data(), scnt.size() * 4)))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // sptr / sbit / scnt are about to move
+  e->h_sy_sptr = std::move(sptr), e->h_sy_sbit = std::move(sbit), e->h_sy_scnt = std::move(scnt);
+  return SPX_OK;
+}
+
 // The float64 formulation's view of an NRT slot table: the cpu slot, whether the weights are in its range, and per slot subset the sum
 // of the weights with its biased reciprocal ([2^n_res][2]; zeros when they are not in range).
 struct NrtSlotWeights {
@@ -508,6 +578,93 @@ int spx_upload_peaks_pods(spx_engine* e, const spx_peaks_pods_soa* t) {
   }
   e->peaks_pods = true;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
+  return SPX_OK;
+}
+
+int spx_upload_sysched_nodes(spx_engine* e, const spx_sysched_nodes_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (t->n_words < 1 || t->n_words > SPX_SYSCHED_MAX_WORDS) return fail(e, SPX_ERR_ARG, "SySched: n_words must be in [1, SPX_SYSCHED_MAX_WORDS]");
+  int rc = set_nodes(e, t->n_nodes);
+  if (rc) return rc;
+  const size_t n = static_cast<size_t>(t->n_nodes);
+  e->sy_nodes = false;
+  if ((rc = ensure(e, e->d_sy_host, n * static_cast<size_t>(t->n_words) * 8)) || (rc = ensure(e, e->d_sy_present, n)) || (rc = ensure(e, e->d_sy_k, n * 4)) ||
+      (rc = ensure(e, e->d_sy_a, n * 4)))
+    return rc;
+  std::vector<int32_t> ix(n);
+  for (size_t i = 0; i < n; ++i) ix[i] = static_cast<int32_t>(i);
+  if ((rc = ship_sysched_rows(e, t, ix, true))) return rc;
+  e->sy_node_words = t->n_words;
+  e->sy_nodes = true;
+  e->evaluated &= ~(1u << SPX_PLUGIN_SYSCHED);
+  e->best_valid = false;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  return SPX_OK;
+}
+
+int spx_update_sysched_nodes(spx_engine* e, const int64_t* idx, const spx_sysched_nodes_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (!e->sy_nodes) return fail(e, SPX_ERR_STATE, "SySched node delta: upload the full table first");
+  if (t->n_words != e->sy_node_words) return fail(e, SPX_ERR_ARG, "SySched node delta: n_words differs from the table in place");
+  const int64_t n = t->n_nodes;
+  if (n == 0) return SPX_OK;
+  std::vector<int32_t> ix;
+  int rc = delta_indices(e, idx, n, ix);
+  if (rc) return rc;
+  if ((rc = ship_sysched_rows(e, t, ix, false))) return rc;
+  e->evaluated = 0;  // every table computed from the old rows is stale
+  e->best_valid = false;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // host columns are only borrowed for the call
+  return SPX_OK;
+}
+
+int spx_upload_sysched_pods(spx_engine* e, const spx_sysched_pods_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (t->n_words < 1 || t->n_words > SPX_SYSCHED_MAX_WORDS) return fail(e, SPX_ERR_ARG, "SySched: n_words must be in [1, SPX_SYSCHED_MAX_WORDS]");
+  if (t->n_sets < 1 || !t->set_bits || !t->pod_set) return fail(e, SPX_ERR_ARG, "SySched: the pod table needs at least one set");
+  int rc = set_pods(e, t->n_pods);
+  if (rc) return rc;
+  const size_t P = static_cast<size_t>(t->n_pods), S = static_cast<size_t>(t->n_sets), W = static_cast<size_t>(t->n_words);
+  // Pod classes are the sets: a pod enters Score through getSyscalls(pod) alone (sysched.go:244).  The pods in (set, row) order, each
+  // set's first position in that order, and the (row, representative) pairs of the pods that are not the first with their set.
+  std::vector<int32_t> first(S + 1, 0), order(P), dups;
+  for (size_t p = 0; p < P; ++p) {
+    if (t->pod_set[p] < 0 || static_cast<size_t>(t->pod_set[p]) >= S) return fail(e, SPX_ERR_ARG, "SySched: pod_set out of range");
+    ++first[static_cast<size_t>(t->pod_set[p]) + 1];
+  }
+  for (size_t s = 0; s < S; ++s) first[s + 1] += first[s];
+  {
+    std::vector<int32_t> at(first.begin(), first.end() - 1);
+    for (size_t p = 0; p < P; ++p) order[static_cast<size_t>(at[static_cast<size_t>(t->pod_set[p])]++)] = static_cast<int32_t>(p);
+  }
+  for (size_t p = 0; p < P; ++p) {
+    const int32_t rep = order[static_cast<size_t>(first[static_cast<size_t>(t->pod_set[p])])];
+    if (rep != static_cast<int32_t>(p)) dups.push_back(static_cast<int32_t>(p)), dups.push_back(rep);
+  }
+  std::vector<uint8_t> empty(S);
+  for (size_t s = 0; s < S; ++s) {
+    uint64_t any = 0;
+    for (size_t w = 0; w < W; ++w) any |= t->set_bits[s * W + w];
+    empty[s] = any == 0;
+  }
+  e->sy_pods = false;
+  e->sy_n_dups = static_cast<int64_t>(dups.size() / 2);
+  e->sy_n_tasks = expand_tasks(dups, t->n_pods);
+  if ((rc = upload(e, e->d_sy_sets, t->set_bits, S * W * 8)) || (rc = upload(e, e->d_sy_empty, empty.data(), S)) || (rc = upload(e, e->d_sy_pod_set, t->pod_set, P * 4)) ||
+      (rc = upload(e, e->d_sy_order, order.data(), P * 4)) || (rc = upload(e, e->d_sy_first, first.data(), (S + 1) * 4)) ||
+      (rc = upload(e, e->d_sy_dups, dups.data(), dups.size() * 4)))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->h_sy_pod_set.assign(t->pod_set, t->pod_set + P);
+  e->h_sy_first = std::move(first);
+  e->sy_pod_words = t->n_words;
+  e->sy_n_sets = t->n_sets;
+  e->sy_pods = true;
+  e->evaluated &= ~(1u << SPX_PLUGIN_SYSCHED);
+  e->best_valid = false;
   return SPX_OK;
 }
 

@@ -18,8 +18,8 @@ PLUGINS = {
     "CapacityScheduling": 5,
     "TopologicalSort": 6,
 }
-ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, TOPOSORT, LROC, PEAKS = range(9)
-NUM_PLUGINS = 9  # SPX_NUM_PLUGINS
+ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, TOPOSORT, LROC, PEAKS, SYSCHED = range(10)
+NUM_PLUGINS = 10  # SPX_NUM_PLUGINS
 
 
 def mask_of(*plugins: int) -> int:
@@ -151,6 +151,13 @@ class Engine:
         """(rows that are the first with their cpu request, rows that repeat one) of the uploaded Peaks pod batch (spx_peaks_pod_classes)"""
         u, d = C.c_int64(), C.c_int64()
         self._ck(self._lib.spx_peaks_pod_classes(self._h, C.byref(u), C.byref(d)))
+        return int(u.value), int(d.value)
+
+    def sysched_pod_classes(self):
+        """(pods that are the first of the batch with their syscall set, pods that repeat one) of the uploaded SySched pod batch
+        (spx_sysched_pod_classes)"""
+        u, d = C.c_int64(), C.c_int64()
+        self._ck(self._lib.spx_sysched_pod_classes(self._h, C.byref(u), C.byref(d)))
         return int(u.value), int(d.value)
 
     def force_reference_kernels(self, *plugins: int) -> None:
@@ -347,6 +354,60 @@ class Engine:
 
     def load_peaks_objects(self, nodes: Table, metrics: Table, power_models: Optional[Table], pods: Table) -> None:
         self.upload_peaks(self.flatten_peaks(nodes, metrics, power_models, pods))
+
+    # ------------------------------------------------------------------ SySched
+    def flatten_sysched(self, objects: Table) -> dict:
+        """spx_sysched_objects -> {"nodes": spx_sysched_nodes_soa columns, "pods": spx_sysched_pods_soa columns, "W", "N", "P", "S"}"""
+        o = objects.struct
+        n, p, s = o.n_nodes, o.n_pods, o.n_sets
+        w, n_stale = C.c_int32(), C.c_int64()
+        fn = self._lib.spx_flatten_sysched_nodes
+        self._ck_static(fn(objects.ref(), 0, C.byref(w), C.byref(n_stale), *([None] * 7)))
+        W, ns = int(w.value), int(n_stale.value)
+        nodes = {"host_bits": np.zeros((W, n), np.uint64), "present": np.zeros(n, np.uint8), "n_resident": np.zeros(n, np.int32),
+                 "resident_missing": np.zeros(n, np.int32), "stale_ptr": np.zeros(n + 1, np.int32), "stale_bit": np.zeros(max(ns, 1), np.int32),
+                 "stale_count": np.zeros(max(ns, 1), np.int32)}
+        self._ck_static(fn(objects.ref(), ns, C.byref(w), C.byref(n_stale), *[v.ctypes.data_as(t) for v, t in zip(nodes.values(), fn.argtypes[4:])]))
+        nodes["stale_bit"], nodes["stale_count"] = nodes["stale_bit"][:ns], nodes["stale_count"][:ns]
+        pods = {"set_bits": np.zeros((max(s, 1), W), np.uint64), "pod_set": np.zeros(max(p, 1), np.int32)}
+        fp = self._lib.spx_flatten_sysched_pods
+        self._ck_static(fp(objects.ref(), *[v.ctypes.data_as(t) for v, t in zip(pods.values(), fp.argtypes[1:])]))
+        pods["set_bits"], pods["pod_set"] = pods["set_bits"][:s], pods["pod_set"][:p]
+        return {"nodes": nodes, "pods": pods, "W": W, "N": n, "P": p, "S": s}
+
+    @staticmethod
+    def sysched_node_rows(nodes: Dict[str, np.ndarray], idx) -> Dict[str, np.ndarray]:
+        """the rows `idx` of flattened SySched node columns, in the layout spx_update_sysched_nodes takes"""
+        idx = np.asarray(idx, np.int64)
+        ptr = nodes["stale_ptr"]
+        lens = ptr[idx + 1] - ptr[idx]
+        take = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in idx]).astype(np.int64) if len(idx) else np.zeros(0, np.int64)
+        return {"host_bits": np.ascontiguousarray(nodes["host_bits"][:, idx]), "present": nodes["present"][idx], "n_resident": nodes["n_resident"][idx],
+                "resident_missing": nodes["resident_missing"][idx], "stale_ptr": np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
+                "stale_bit": nodes["stale_bit"][take], "stale_count": nodes["stale_count"][take]}
+
+    def upload_sysched_nodes(self, nodes: Dict[str, np.ndarray]) -> None:
+        W, n = nodes["host_bits"].shape
+        self._ck(self._lib.spx_upload_sysched_nodes(self._h, Table(self._hdr, "spx_sysched_nodes_soa", n_nodes=n, n_words=W, **nodes).ref()))
+        self.n_nodes = n
+
+    def update_sysched_nodes(self, idx, rows: Dict[str, np.ndarray]) -> None:
+        """rows: sysched_node_rows(...) of the changed nodes `idx` (spx_update_sysched_nodes)"""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        W = rows["host_bits"].shape[0]
+        t = Table(self._hdr, "spx_sysched_nodes_soa", n_nodes=len(idx), n_words=W, **rows)
+        self._ck(self._lib.spx_update_sysched_nodes(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), t.ref()))
+
+    def upload_sysched_pods(self, pods: Dict[str, np.ndarray]) -> None:
+        s, W = pods["set_bits"].shape
+        p = len(pods["pod_set"])
+        self._ck(self._lib.spx_upload_sysched_pods(self._h, Table(self._hdr, "spx_sysched_pods_soa", n_pods=p, n_words=W, n_sets=s, **pods).ref()))
+        self.n_pods = p
+
+    def load_sysched_objects(self, objects: Table) -> None:
+        """flatten + upload both SySched tables in one call (spx_load_sysched)"""
+        self._ck(self._lib.spx_load_sysched(self._h, objects.ref()))
+        self.n_nodes, self.n_pods = objects.struct.n_nodes, objects.struct.n_pods
 
     # ------------------------------------------------------------------ NodeResourceTopologyMatch
     def load_nrt_objects(self, nodes: Table, nrt: Table, rc: Optional[Table], pods: Table, params: Table) -> None:

@@ -504,3 +504,109 @@ def build_quota_objects(hdr: Header, res: Resources, namespaces: Sequence[Option
         nom_priority=np.array([n[1] for n in nominated], dtype=np.int32),
         nom_pending_index=np.array([n[2] for n in nominated], dtype=np.int64), nom_pods=nom_pods,
     )
+
+
+# ---------------------------------------------------------------------------------------------------------------- SySched
+# What the Go side does once per snapshot for pkg/sysched: resolve every pod's seccomp profiles to a syscall set (getSyscalls,
+# sysched.go:124-210), intern the names, and ship the distinct sets, the pods' set ids, the cached host sets and the resident lists.
+SPO_ANNOTATION = "seccomp.security.alpha.kubernetes.io"  # sysched.go:46
+SCMP_READ_ACTIONS = ("SCMP_ACT_ALLOW", "SCMP_ACT_LOG")  # the only categories readSPOProfileCR merges, sysched.go:112
+SYSCHED_MAX_NAMES = 1024  # SPX_SYSCHED_MAX_NAMES
+
+
+def parse_name_ns(profile_path: str):
+    """parseNameNS (sysched.go:67-83): (namespace, name) of `[localhost/]operator/<namespace>/<file>.json`; the name is the last
+    path element without its extension (Go's path.Ext: from the last dot of that element on)"""
+    if profile_path == "":
+        return "", ""
+    parts = profile_path.split("/")
+    if len(parts) < 2:
+        return "", ""
+    last = parts[-1]
+    dot = last.rfind(".")
+    return parts[-2], (last[:dot] if dot >= 0 else last)
+
+
+def seccomp_profile(name: str, namespace: str, syscalls: Sequence[dict]) -> dict:
+    """a SeccompProfile CR: syscalls = [{"action": "SCMP_ACT_ALLOW", "names": [...]}, ...]"""
+    return {"name": name, "namespace": namespace, "syscalls": list(syscalls)}
+
+
+def sysched_pod(security_context: Optional[str] = None, containers: Iterable[Optional[str]] = (), init_containers: Iterable[Optional[str]] = (),
+                annotations: Optional[Dict[str, str]] = None) -> dict:
+    """the parts of a v1.Pod getSyscalls reads: the Localhost seccomp profile path of the pod security context and of each container
+    (None = no Localhost profile), and the annotations"""
+    return {"security_context": security_context, "containers": list(containers), "init_containers": list(init_containers),
+            "annotations": dict(annotations or {})}
+
+
+class SeccompProfiles:
+    """the SeccompProfile CRs by (namespace, name) plus SySchedArgs' default profile"""
+
+    def __init__(self, profiles: Iterable[dict] = (), default_name: str = "", default_namespace: str = ""):
+        self.by_key = {(p["namespace"], p["name"]): p for p in profiles}
+        self.default_name, self.default_namespace = default_name, default_namespace
+
+    def read(self, name: str, namespace: str):
+        """readSPOProfileCR (sysched.go:86-118) -> (set, found): an empty name or namespace reads as an empty set without error, a
+        missing CR as an empty set with one; only SCMP_ACT_ALLOW and SCMP_ACT_LOG entries are merged"""
+        if name == "" or namespace == "":
+            return frozenset(), True
+        cr = self.by_key.get((namespace, name))
+        if cr is None:
+            return frozenset(), False
+        out = set()
+        for cat in cr["syscalls"]:
+            if cat["action"] in SCMP_READ_ACTIONS:
+                out.update(cat["names"])
+        return frozenset(out), True
+
+    def get_syscalls(self, pod: dict) -> frozenset:
+        """getSyscalls (sysched.go:124-210).  Init containers are not read.  The reference takes the first annotation whose key
+        contains SPO_ANNOTATION in Go map order, so a pod with several is UNPINNED there; here: the smallest such key (a missing CR
+        moves on to the next key, :183-186; anything else stops the loop, :192)."""
+        r = set()
+        for path in [pod.get("security_context")] + list(pod.get("containers", ())):
+            if path is None:
+                continue
+            ns, name = parse_name_ns(path)
+            if ns and name:
+                r |= self.read(name, ns)[0]
+        for k in sorted(pod.get("annotations", {})):
+            if SPO_ANNOTATION in k:
+                ns, name = parse_name_ns(pod["annotations"][k])
+                if ns and name:
+                    got, found = self.read(name, ns)
+                    if not found:
+                        continue
+                    r |= got
+                break
+        if not r:
+            r |= self.read(self.default_name, self.default_namespace)[0]
+        return frozenset(r)
+
+
+def build_sysched_objects(hdr: Header, pod_sets: Sequence[frozenset], host_sets: Sequence[Optional[frozenset]],
+                          resident_sets: Sequence[Sequence[frozenset]]) -> Table:
+    """spx_sysched_objects from the resolved sets: pod_sets[p] = getSyscalls(pending pod p); host_sets[n] = HostSyscalls[node n] (None =
+    no entry); resident_sets[n] = getSyscalls of each pod of HostToPods[node n].  Names are interned in sorted order, sets in
+    first-seen order.  More than SYSCHED_MAX_NAMES names is left to the flattener to refuse."""
+    names = set()
+    for s in pod_sets:
+        names |= s
+    for s in host_sets:
+        names |= s or frozenset()
+    for rs in resident_sets:
+        for s in rs:
+            names |= s
+    name_id = {nm: i for i, nm in enumerate(sorted(names))}
+    set_id: Dict[frozenset, int] = {}
+    for s in list(pod_sets) + [s for rs in resident_sets for s in rs]:
+        set_id.setdefault(s, len(set_id))
+    ordered = sorted(set_id, key=set_id.get)
+    return Table(hdr, "spx_sysched_objects", n_names=len(name_id), n_sets=len(ordered),
+                 set_ptr=_csr(ordered), set_name=np.array([name_id[x] for s in ordered for x in sorted(s)], np.int32),
+                 n_pods=len(pod_sets), pod_set=np.array([set_id[s] for s in pod_sets], np.int32),
+                 n_nodes=len(host_sets), host_present=np.array([s is not None for s in host_sets], np.uint8),
+                 host_ptr=_csr([s or () for s in host_sets]), host_name=np.array([name_id[x] for s in host_sets for x in sorted(s or ())], np.int32),
+                 res_ptr=_csr(resident_sets), res_set=np.array([set_id[s] for rs in resident_sets for s in rs], np.int32))

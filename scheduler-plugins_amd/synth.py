@@ -670,3 +670,81 @@ def full_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, pods
     snap["quota"] = synth_quota(hdr, snap["pods"], seed, n_namespaces=n_namespaces, device_res=RES_DEVICE,
                                 hugepage_res=RES_HUGEPAGES_2MI, sized_for_batch=quota_sized_for_batch)
     return snap
+
+
+def sysched_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, n_profiles: int = 32, stale_frac: float = 0.03,
+                     absent_frac: float = 0.03, empty_frac: float = 0.003, n_names: int = 400, core: int = 150, max_residents: int = 12,
+                     distinct_pods: bool = False, node_states: Optional[int] = None) -> dict:
+    """A SySched snapshot (pkg/sysched): syscall profiles drawn as subsets of an n_names universe around a common core of `core`
+    names; 0..max_residents resident pods per node, each with one of the profiles; absent_frac of the nodes without a HostSyscalls
+    entry, stale_frac with a resident whose set is no longer inside the cached host set (a SeccompProfile changed after addPod
+    cached it); empty_frac of the pods with the empty set (no profile and no default: Score answers math.MaxInt64).
+    distinct_pods: every pending pod has a set of its own.  node_states: that many distinct node states, each node taking one of
+    them (None: every node its own).
+
+    Returns {"objects": spx_sysched_objects Table, "names": [str], "sets": [frozenset of names] by set id, "pod_set": int32 [P],
+    "host": [frozenset or None] per node, "residents": [tuple of set ids] per node}; nodes of one state share their host object."""
+    rng = np.random.default_rng(seed)
+    names = [f"sys_{i:04d}" for i in range(n_names)]
+
+    def draw(k):
+        m = rng.random((k, n_names)) < 0.45
+        m[:, :min(core, n_names)] = True
+        return m
+
+    prof = draw(n_profiles)
+    empty_id = -1
+    if distinct_pods:
+        member = np.concatenate([prof, draw(n_pods)])
+        # (rows are random over >= n_names - core free bits; equal rows would merge two pods into one set: checked)
+        assert len(np.unique(np.packbits(member, axis=1), axis=0)) == len(member) or n_names - core < 40
+        pod_set = n_profiles + np.arange(n_pods, dtype=np.int32)
+    else:
+        member = prof
+        pod_set = rng.integers(0, n_profiles, n_pods).astype(np.int32)
+    if empty_frac > 0:
+        member = np.concatenate([member, np.zeros((1, n_names), bool)])
+        empty_id = len(member) - 1
+        is_empty = rng.random(n_pods) < empty_frac
+        if n_pods >= 8:
+            is_empty[rng.integers(0, n_pods)] = True
+        pod_set = np.where(is_empty, empty_id, pod_set).astype(np.int32)
+    n_sets = len(member)
+
+    S = n_nodes if node_states is None else node_states
+    k = rng.integers(0, max_residents + 1, S)
+    res_ptr_s = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+    res_set_s = rng.integers(0, n_profiles, int(res_ptr_s[-1])).astype(np.int32)
+    host_s = np.zeros((S, n_names), bool)
+    owner = np.repeat(np.arange(S), k)
+    np.logical_or.at(host_s, owner, prof[res_set_s])  # the union addPod accumulates (sysched.go:310-333)
+    present_s = rng.random(S) >= absent_frac
+    # a present node without residents keeps whatever removePod left; give half of them a leftover profile
+    leftover = (k == 0) & (rng.random(S) < 0.5)
+    host_s[leftover] = prof[rng.integers(0, n_profiles, int(leftover.sum()))]
+    stale = (k > 0) & (rng.random(S) < stale_frac)
+    for s in np.flatnonzero(stale):  # names some resident holds drop out of the cached set; a few names nobody holds join it
+        held = np.flatnonzero(host_s[s, core:]) + core
+        if len(held):
+            host_s[s, rng.choice(held, size=min(len(held), int(rng.integers(1, 6))), replace=False)] = False
+        host_s[s, rng.integers(core, n_names, 2)] = True
+    state = np.arange(n_nodes) if node_states is None else rng.integers(0, S, n_nodes)
+
+    def csr_of(mask):
+        ptr = np.concatenate([[0], np.cumsum(mask.sum(1))]).astype(np.int32)
+        return ptr, np.nonzero(mask)[1].astype(np.int32)
+
+    set_ptr, set_name = csr_of(member)
+    host_n = host_s[state] & present_s[state][:, None]
+    host_ptr, host_name = csr_of(host_n)
+    kn = k[state]
+    res_ptr = np.concatenate([[0], np.cumsum(kn)]).astype(np.int32)
+    take = np.concatenate([np.arange(res_ptr_s[s], res_ptr_s[s + 1]) for s in state]).astype(np.int64) if n_nodes else np.zeros(0, np.int64)
+    res_set = res_set_s[take]
+    objects = Table(hdr, "spx_sysched_objects", n_names=n_names, n_sets=n_sets, set_ptr=set_ptr, set_name=set_name, n_pods=n_pods, pod_set=pod_set,
+                    n_nodes=n_nodes, host_present=present_s[state].astype(np.uint8), host_ptr=host_ptr, host_name=host_name, res_ptr=res_ptr, res_set=res_set)
+    sets = [frozenset(names[j] for j in np.flatnonzero(member[i])) for i in range(n_sets)]
+    host_objs = [frozenset(names[j] for j in np.flatnonzero(host_s[s])) if present_s[s] else None for s in range(S)]
+    res_objs = [tuple(int(x) for x in res_set_s[res_ptr_s[s]:res_ptr_s[s + 1]]) for s in range(S)]
+    return {"objects": objects, "names": names, "sets": sets, "pod_set": pod_set, "host": [host_objs[s] for s in state],
+            "residents": [res_objs[s] for s in state], "n_stale_states": int(stale.sum()), "empty_set": empty_id}
