@@ -579,12 +579,27 @@ typedef struct spx_net_nodes_soa {
   const int32_t* zone;
 } spx_net_nodes_soa;
 
+/* region_cost [n_regions * n_regions], zone_cost [n_zones * n_zones], row = origin, -1 = no entry.  The 32-bit tables select the
+ * 32-bit sweep as long as (largest entry) x (most pairs of any workload key) stays below 2^31; beyond that the engine widens them
+ * and runs the 64-bit sweep (spx_kernel_path reports 2). */
 typedef struct spx_net_topo_soa {
   int32_t n_regions;
   int32_t n_zones;
   const int32_t* region_cost;
   const int32_t* zone_cost;
 } spx_net_topo_soa;
+
+/* The same columns with the CRD's own int64 entries (NetworkTopology costs and MaxNetworkCost are int64): entries of any size >= -1.
+ * An engine that holds these runs the 64-bit sweep: int64 accumulation and the reference's float64 NormalizeScore
+ * (networkoverhead.go:389-418, :576-638).  The engine holds one width at a time: an upload of either replaces the other.  A snapshot
+ * whose (largest entry) x (most pairs of any workload key) reaches 2^63 is refused by spx_eval with SPX_ERR_ARG: the reference's own
+ * sum could wrap there. */
+typedef struct spx_net_topo_wide {
+  int32_t n_regions;
+  int32_t n_zones;
+  const int64_t* region_cost;
+  const int64_t* zone_cost;
+} spx_net_topo_wide;
 
 typedef struct spx_net_pods_soa {
   int64_t n_pods;
@@ -752,6 +767,8 @@ int spx_upload_nrt_pods_wide(spx_engine* e, const spx_nrt_pods_wide* t);
 int spx_nrt_wide(const spx_engine* e);
 int spx_upload_net_nodes(spx_engine* e, const spx_net_nodes_soa* t);
 int spx_upload_net_topo(spx_engine* e, const spx_net_topo_soa* t);
+/* the int64 cost matrices (spx_flatten_net_topo_wide); replaces the 32-bit ones, as a later spx_upload_net_topo replaces these */
+int spx_upload_net_topo_wide(spx_engine* e, const spx_net_topo_wide* t);
 int spx_upload_net_pods(spx_engine* e, const spx_net_pods_soa* t);
 int spx_upload_quota(spx_engine* e, const spx_quota_soa* t);
 /* after spx_upload_net_pods; only spx_commit_sequential with NETOVERHEAD in its mask needs it */
@@ -964,7 +981,8 @@ int spx_sysched_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_c
  * engine's current plugin parameters and their result is uploaded.  For callers that hold object tables — marshalled by the shim or
  * decoded by spx_ingest_* — and would rather not size and own the intermediate arrays (the cgo shim: shim/go/pkg/spx/snapshot.go).
  * spx_load_trimaran serves Allocatable + TargetLoadPacking + LoadVariationRiskBalancing (rc / assigned may be NULL);
- * spx_load_network also uploads the commit effects spx_commit_sequential needs. */
+ * spx_load_network also uploads the commit effects spx_commit_sequential needs; it flattens the cost matrices in int64 and uploads the
+ * 32-bit tables when every entry fits them, the wide ones otherwise (spx_upload_net_topo_wide): the caller sees no difference. */
 int spx_load_trimaran(spx_engine* e, const spx_node_objects* nodes, const spx_resource_classes* rc, const spx_pod_objects* pods, const spx_metrics_objects* metrics, const spx_assigned_objects* assigned);
 /* a new pending batch only (node tables stay): the trimaran / Allocatable pod columns flattened straight into pinned staging, one pass */
 int spx_load_trimaran_pods(spx_engine* e, const spx_pod_objects* pods);
@@ -1015,6 +1033,9 @@ int spx_nrt_packed_score_slots(const spx_engine* e);
 /* which formulation of a plugin's sweep the uploaded tables select: 0 = generic (reference arithmetic, operation for
  * operation), 1 = fast formulation (same results; see DESIGN.md for each kernel's preconditions); <0 on error.
  * Tests use it to make sure both formulations are exercised.
+ * SPX_PLUGIN_NETOVERHEAD also reports 2 = the 64-bit sweep (kernels_network_wide.hip): the engine holds int64 cost matrices, or
+ * (largest cost entry) x (most pairs of any workload key) reaches 2^31.  SPX_OPT_REFERENCE_KERNELS selects the per-node form of the
+ * same 64-bit arithmetic there, and the value stays 2.
  * SPX_PLUGIN_SYSCHED has one formulation; for it the call reports how many chunks of distinct sets the last SySched sweep of
  * spx_eval built its raw table in (the table is scratch bounded at 256 MiB, kernels_sysched.hip), 0 before the first sweep. */
 int spx_kernel_path(const spx_engine* e, int plugin);
@@ -1128,6 +1149,9 @@ int spx_flatten_nrt_pods_wide(const spx_pod_objects* pods, const spx_resource_cl
  * spx_flatten_net_keys sizes: *n_keys_out and *n_pairs_out first (pass NULL arrays), then fill
  * pod_key[P], topo_order[P], key_score_equally[n_keys], pair_ptr[n_keys+1], pair_node/pair_max_cost[n_pairs]. */
 int spx_flatten_net_topo(const spx_nettopo_objects* nt, int32_t* region_cost, int32_t* zone_cost);
+/* the same with int64 outputs (spx_net_topo_wide): entries of any size, only negative ones are SPX_ERR_ARG; spx_flatten_net_topo
+ * refuses entries above INT32_MAX */
+int spx_flatten_net_topo_wide(const spx_nettopo_objects* nt, int64_t* region_cost, int64_t* zone_cost);
 int spx_flatten_net_keys(const spx_pod_objects* pods, const spx_appgroup_objects* ag, int32_t* n_keys_out, int64_t* n_pairs_out, int32_t* pod_key, int32_t* topo_order, uint8_t* key_score_equally, int32_t* pair_ptr, int32_t* pair_node, int64_t* pair_max_cost);
 /* TopologicalSort.Less (topologicalsort.go:102-132) for n pairs of pod indices, from the flattened keys */
 int spx_toposort_less(const spx_pod_objects* pods, const int32_t* topo_order, int64_t n_pairs, const int64_t* a, const int64_t* b, uint8_t* less_out);

@@ -59,6 +59,7 @@ int commit_coop(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t 
     if (!e->h_nrt_long_rows.empty()) return SPX_OK;  // pods with more than 8 containers: the per-pod loop runs kernels_nrt_long.hip
   }
   if (W) {
+    if (e->net_wide_dev) return SPX_OK;  // a wide snapshot: the kernel keeps int cost matrices in LDS and accumulates in int32
     if (e->net_n_classes <= 0 || e->net_n_classes > spx::kCoopMaxClasses || e->net_n_keys <= 0) return SPX_OK;
     for (size_t k = 0; k + 1 < dyn_ptr.size(); ++k)
       if (dyn_ptr[k + 1] - dyn_ptr[k] > spx::kCoopMaxPairs) return SPX_OK;
@@ -203,8 +204,9 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
     std::vector<int32_t> dyn_end(K);
     for (size_t k = 0; k < K; ++k) dyn_end[k] = dyn_ptr[k] + (e->h_pair_ptr[k + 1] - e->h_pair_ptr[k]);
     const size_t cap = static_cast<size_t>(dyn_ptr[K]);
-    if (static_cast<int64_t>(e->net_max_cost) * std::max<int64_t>(1, *std::max_element(extra.begin(), extra.end()) + e->net_max_pairs) >= (int64_t{1} << 31))
-      return fail(e, SPX_ERR_ARG, "NetworkOverhead: accumulated cost of a node may exceed 2^31 once the batch is bound; this build sweeps in int32");
+    // the bound with the batch's bindings counted in selects the sweep for the whole loop (a wide one widens the cost matrices here,
+    // before anything is captured)
+    if ((rc = net_prepare(e, K ? *std::max_element(extra.begin(), extra.end()) : 0, ", once the batch is bound"))) return rc;
     if ((rc = upload(e, e->d_net_dyn_ptr, dyn_ptr.data(), (K + 1) * 4))) return rc;
     if ((rc = upload(e, e->d_net_dyn_end, dyn_end.data(), K * 4))) return rc;
     if ((rc = ensure(e, e->d_net_dyn_node, cap * 4)) || (rc = ensure(e, e->d_net_dyn_max, cap * 8))) return rc;

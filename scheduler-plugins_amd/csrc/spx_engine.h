@@ -195,7 +195,9 @@ struct spx_engine {
   // NetworkOverhead / TopologicalSort
   bool net_nodes = false, net_topo = false, net_pods = false;
   int32_t net_n_regions = 0, net_n_zones = 0, net_n_classes = 0;
-  int64_t net_max_cost = SPX_NET_MAX_COST, net_max_pairs = 0;  // bound of a row's accumulated cost (the sweep adds in int32)
+  int64_t net_max_cost = SPX_NET_MAX_COST, net_max_pairs = 0;  // bound of a row's accumulated cost: their product (net_cost_bound) selects the 32- or the 64-bit sweep
+  bool net_wide_dev = false;                  // d_net_rcost / d_net_zcost hold int64 entries (a wide upload, or widened by net_prepare); never both widths
+  std::vector<int64_t> h_net_rcost, h_net_zcost;  // host copy of the cost matrices (net_prepare widens from it)
   DevBuf d_net_region, d_net_zone, d_net_class, d_net_class16, d_net_cls_size, d_net_cls_region, d_net_cls_zone, d_net_rcost, d_net_zcost;
   bool net_class16 = false;
   DevBuf d_net_pod_key, d_net_key_flag, d_net_pair_ptr, d_net_pair_node, d_net_pair_max;
@@ -786,8 +788,14 @@ void fill_net(const spx_engine* e, spx::NetArgs& g) {
   g.cls_size = static_cast<const int32_t*>(e->d_net_cls_size.p);
   g.cls_region = static_cast<const int32_t*>(e->d_net_cls_region.p);
   g.cls_zone = static_cast<const int32_t*>(e->d_net_cls_zone.p);
-  g.region_cost = static_cast<const int32_t*>(e->d_net_rcost.p);
-  g.zone_cost = static_cast<const int32_t*>(e->d_net_zcost.p);
+  if (e->net_wide_dev) {
+    g.cost_wide = 1;
+    g.region_cost64 = static_cast<const int64_t*>(e->d_net_rcost.p);
+    g.zone_cost64 = static_cast<const int64_t*>(e->d_net_zcost.p);
+  } else {
+    g.region_cost = static_cast<const int32_t*>(e->d_net_rcost.p);
+    g.zone_cost = static_cast<const int32_t*>(e->d_net_zcost.p);
+  }
   g.pod_key = static_cast<const int32_t*>(e->d_net_pod_key.p);
   g.key_flag = static_cast<const uint8_t*>(e->d_net_key_flag.p);
   g.pair_ptr = static_cast<const int32_t*>(e->d_net_pair_ptr.p);
@@ -799,6 +807,54 @@ void fill_net(const spx_engine* e, spx::NetArgs& g) {
     g.pair_node = static_cast<const int32_t*>(e->d_net_dyn_node.p);
     g.pair_max = static_cast<const int64_t*>(e->d_net_dyn_max.p);
   }
+}
+
+// NetworkOverhead: the bound of a node's accumulated cost, (largest cost entry) x (most pairs of any workload key, `extra_pairs`
+// more once a batch is bound), INT64_MAX when the product does not fit int64
+int64_t net_cost_bound(const spx_engine* e, int64_t extra_pairs) {
+  int64_t b;
+  return __builtin_mul_overflow(e->net_max_cost, std::max<int64_t>(e->net_max_pairs + extra_pairs, 1), &b) ? std::numeric_limits<int64_t>::max() : b;
+}
+
+// the 64-bit sweep (kernels_network_wide.hip) runs when the device holds int64 cost matrices or the bound reaches 2^31
+bool net_wide(const spx_engine* e, int64_t extra_pairs) { return e->net_wide_dev || net_cost_bound(e, extra_pairs) >= (int64_t{1} << 31); }
+
+// Before a NetworkOverhead launch: refuses a snapshot whose bound reaches 2^63, and widens narrow cost matrices on the device (once:
+// they stay int64 until the next topology upload) when the bound asks for the 64-bit sweep.  `when`: which bound, for the message.
+int net_prepare(spx_engine* e, int64_t extra_pairs, const char* when) {
+  if (net_cost_bound(e, extra_pairs) == std::numeric_limits<int64_t>::max())
+    return fail(e, SPX_ERR_ARG, std::string("NetworkOverhead: accumulated cost of a node may reach 2^63 (cost entries x dependency pairs") + when +
+                                    "); the reference's own int64 sum would wrap there");
+  if (e->net_wide_dev || !net_wide(e, extra_pairs)) return SPX_OK;
+  int rc;
+  if ((rc = upload(e, e->d_net_rcost, e->h_net_rcost.data(), e->h_net_rcost.size() * 8)) || (rc = upload(e, e->d_net_zcost, e->h_net_zcost.data(), e->h_net_zcost.size() * 8)))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->net_wide_dev = true;
+  return SPX_OK;
+}
+
+// the cost matrices of either width onto the device (one pair of buffers: an upload of one width replaces the other), their int64
+// host copy and the largest entry
+template <typename T>
+int upload_net_costs(spx_engine* e, int32_t n_regions, int32_t n_zones, const T* region_cost, const T* zone_cost) {
+  if (n_regions < 0 || n_zones < 0) return fail(e, SPX_ERR_ARG, "negative topology size");
+  const size_t rr = static_cast<size_t>(n_regions) * n_regions, zz = static_cast<size_t>(n_zones) * n_zones;
+  int rc;
+  if ((rc = upload(e, e->d_net_rcost, region_cost ? static_cast<const void*>(region_cost) : static_cast<const void*>(&rc), rr * sizeof(T)))) return rc;
+  if ((rc = upload(e, e->d_net_zcost, zone_cost ? static_cast<const void*>(zone_cost) : static_cast<const void*>(&rc), zz * sizeof(T)))) return rc;
+  e->net_n_regions = n_regions;
+  e->net_n_zones = n_zones;
+  e->net_wide_dev = sizeof(T) == 8;
+  e->h_net_rcost.assign(region_cost ? region_cost : nullptr, region_cost ? region_cost + rr : nullptr);
+  e->h_net_zcost.assign(zone_cost ? zone_cost : nullptr, zone_cost ? zone_cost + zz : nullptr);
+  e->h_net_rcost.resize(rr, -1), e->h_net_zcost.resize(zz, -1);  // (a NULL column: net_prepare widens to "no entry", full size)
+  e->net_max_cost = SPX_NET_MAX_COST;
+  for (const int64_t c : e->h_net_rcost) e->net_max_cost = std::max(e->net_max_cost, c);
+  for (const int64_t c : e->h_net_zcost) e->net_max_cost = std::max(e->net_max_cost, c);
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->net_topo = true;
+  return SPX_OK;
 }
 
 // host [N][inner] -> device [inner][N] so that lane = node reads coalesce

@@ -258,10 +258,10 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   if (A && (rc = prepare_alloc(e))) return rc;
   const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD);
   if (W && !(e->net_nodes && e->net_topo && e->net_pods)) return fail(e, SPX_ERR_STATE, "NetworkOverhead node/topology/pod tables not uploaded");
-  // the reference accumulates a node's cost in int64 (networkoverhead.go:605-633); the sweeps add in int32 and keep the Filter
-  // verdict in the sign bit, which is exact as long as (largest cost entry) x (most pairs of any workload) stays below 2^31
-  if (W && e->net_max_cost * std::max<int64_t>(e->net_max_pairs, 1) >= (int64_t{1} << 31))
-    return fail(e, SPX_ERR_ARG, "NetworkOverhead: accumulated cost of a node may exceed 2^31 (cost entries x dependency pairs); this build sweeps in int32");
+  // the reference accumulates a node's cost in int64 (networkoverhead.go:605-633); the narrow sweeps add in int32 and keep the Filter
+  // verdict in the sign bit, which is exact as long as (largest cost entry) x (most pairs of any workload) stays below 2^31; from
+  // there on the 64-bit sweep runs (kernels_network_wide.hip), up to the 2^63 at which the reference's own sum could wrap
+  if (W && (rc = net_prepare(e, 0, ""))) return rc;
   for (int p = 0; p < 5; ++p)
     if ((plugin_mask & (1u << p)) && (rc = ensure_score_table(e, p))) return rc;
   if (R && (rc = ensure_score_table(e, SPX_PLUGIN_LROC))) return rc;
@@ -692,7 +692,10 @@ int spx_kernel_path(const spx_engine* e, int plugin) {
   if (plugin == SPX_PLUGIN_NRT)
     return (e->nrt_fast_slots && e->nrt_fast_nodes && e->nrt_fast_pods && !forced_reference(e, SPX_PLUGIN_NRT) &&
             (e->nrt_params.strategy != SPX_NRT_LEAST_NUMA_NODES || e->nrt_ln_ok)) ? 1 : 0;
-  if (plugin == SPX_PLUGIN_NETOVERHEAD) return (e->net_nodes && e->net_class16 && e->net_n_classes > 0 && !forced_reference(e, SPX_PLUGIN_NETOVERHEAD)) ? 1 : 0;
+  if (plugin == SPX_PLUGIN_NETOVERHEAD) {
+    if (e->net_topo && net_wide(e, 0)) return 2;  // the 64-bit sweep, in either of its forms
+    return (e->net_nodes && e->net_class16 && e->net_n_classes > 0 && !forced_reference(e, SPX_PLUGIN_NETOVERHEAD)) ? 1 : 0;
+  }
   if (plugin == SPX_PLUGIN_LROC) return lroc_f32_ok(e) ? 1 : 0;
   if (plugin == SPX_PLUGIN_SYSCHED) return e->sy_last_chunks;
   if (plugin == SPX_PLUGIN_TLP) return (e->tlp.target_utilization >= 1 && e->tlp.target_utilization <= 99 && !(launch_opts(e) & spx::kOptTrimaranExact)) ? 1 : 0;
@@ -821,6 +824,7 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
     if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
     if (which < SPX_NET_RAW_COST || which > SPX_NET_RAW_VIOLATED) return fail(e, SPX_ERR_ARG, "which: 0 cost, 1 satisfied, 2 violated");
     if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
+    if ((rc = net_prepare(e, 0, ""))) return rc;
     spx::NetArgs g{};
     fill_net(e, g);
     g.row_begin = pod_row;

@@ -558,13 +558,20 @@ struct NetArgs {
   int32_t n_regions;
   int32_t n_zones;
   int32_t n_classes;            // 0 = no class table: every node takes the exact per-pair path
+  int32_t cost_wide;            // 1 = a wide snapshot: the cost matrices hold int64 entries (region_cost64 / zone_cost64)
   const int32_t* region;        // [N] interned topology.kubernetes.io/region label, -1 = unset
   const int32_t* zone;          // [N]
   const int32_t* node_class;    // [N] index into cls_*
   const int32_t* cls_region;    // [n_classes]
   const int32_t* cls_zone;      // [n_classes]
-  const int32_t* region_cost;   // [n_regions^2], -1 = no entry
-  const int32_t* zone_cost;     // [n_zones^2]
+  union {                       // [n_regions^2], -1 = no entry
+    const int32_t* region_cost;
+    const int64_t* region_cost64;
+  };
+  union {                       // [n_zones^2]
+    const int32_t* zone_cost;
+    const int64_t* zone_cost64;
+  };
   const uint16_t* node_class16; // [round_up(N, 4)] the same class ids, 16 bit (table sweep); NULL when they do not fit
   const int32_t* cls_size;      // [n_classes] nodes per class
   const int32_t* pod_key;       // [P]
@@ -586,6 +593,13 @@ struct NetArgs {
 // true = the launch also wrote NetArgs::out_alloc (k_net_cls ran)
 bool launch_net(const NetArgs& g, hipStream_t s);
 size_t net_lds_bytes(int n_classes, int64_t n_nodes);
+// the 64-bit formulation (NetArgs::cost_wide set; launch_net hands such launches over): int64 accumulation, NormalizeScore in
+// the reference's float64 sequence; never carries Allocatable's normalisation
+void launch_net_wide(const NetArgs& g, hipStream_t s);
+size_t net_wide_lds_bytes(int n_classes, int64_t n_nodes);
+constexpr int kNetRowThreads = 1024;  // threads a single-row launch (the sequential commit loop) puts on its row
+constexpr int kNetStagePairs = 512;   // pairs of a key staged in LDS by a single-row launch
+constexpr size_t kNetLdsBudget = 52 * 1024;  // class tables + bitmaps of a launch: 64 KB with a single-row launch's staged pairs
 
 // ---------------------------------------------------------------- TopologicalSort (kernels_sort.hip)
 struct SortArgs {

@@ -250,8 +250,14 @@ int spx_load_network(spx_engine* e, const spx_node_objects* nodes, const spx_pod
   if (!e || !nodes || !pods || !appgroups || !nettopo) return SPX_ERR_ARG;
   const size_t P = static_cast<size_t>(pods->n_pods);
   const size_t rg = static_cast<size_t>(nettopo->n_regions), zc = static_cast<size_t>(nettopo->n_zones);
-  std::vector<int32_t> rcost(rg * rg ? rg * rg : 1, -1), zcost(zc * zc ? zc * zc : 1, -1);
-  if (spx_flatten_net_topo(nettopo, rcost.data(), zcost.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_net_topo failed");
+  // the cost matrices are flattened in the CRD's own int64; a snapshot whose entries all fit int32 is narrowed and takes the 32-bit
+  // tables as before, any other one the wide tables (spx_upload_net_topo_wide)
+  std::vector<int64_t> rcost64(rg * rg ? rg * rg : 1, -1), zcost64(zc * zc ? zc * zc : 1, -1);
+  if (spx_flatten_net_topo_wide(nettopo, rcost64.data(), zcost64.data()) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_net_topo_wide failed");
+  const auto fits = [](const std::vector<int64_t>& v) { return std::all_of(v.begin(), v.end(), [](int64_t c) { return c <= INT32_MAX; }); };
+  const bool narrow = fits(rcost64) && fits(zcost64);
+  std::vector<int32_t> rcost, zcost;
+  if (narrow) rcost.assign(rcost64.begin(), rcost64.end()), zcost.assign(zcost64.begin(), zcost64.end());
   int32_t n_keys = 0;
   int64_t n_pairs = 0, n_eff = 0;
   if (spx_flatten_net_keys(pods, appgroups, &n_keys, &n_pairs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != SPX_OK)
@@ -268,8 +274,13 @@ int spx_load_network(spx_engine* e, const spx_node_objects* nodes, const spx_pod
   int rc_;
   const spx_net_nodes_soa nn{nodes->n_nodes, nodes->region, nodes->zone};
   if ((rc_ = spx_upload_net_nodes(e, &nn))) return rc_;
-  const spx_net_topo_soa nt{nettopo->n_regions, nettopo->n_zones, rcost.data(), zcost.data()};
-  if ((rc_ = spx_upload_net_topo(e, &nt))) return rc_;
+  if (narrow) {
+    const spx_net_topo_soa nt{nettopo->n_regions, nettopo->n_zones, rcost.data(), zcost.data()};
+    if ((rc_ = spx_upload_net_topo(e, &nt))) return rc_;
+  } else {
+    const spx_net_topo_wide nt{nettopo->n_regions, nettopo->n_zones, rcost64.data(), zcost64.data()};
+    if ((rc_ = spx_upload_net_topo_wide(e, &nt))) return rc_;
+  }
   const spx_net_pods_soa np{pods->n_pods, n_keys, pod_key.data(), eq.data(), pair_ptr.data(), pair_node.data(), pair_max.data(), topo.data()};
   if ((rc_ = spx_upload_net_pods(e, &np))) return rc_;
   const spx_net_commit_soa nc{pods->n_pods, eff_ptr.data(), eff_key.data(), eff_cost.data()};

@@ -1215,7 +1215,7 @@ int spx_upload_net_nodes(spx_engine* e, const spx_net_nodes_soa* t) {
     }
   }
   int32_t n_classes = static_cast<int32_t>(cr.size());
-  if (spx::net_lds_bytes(n_classes, n) > 52 * 1024) n_classes = 0;  // too many label pairs for LDS (64 KB with a single-row launch's staged pairs): exact path only
+  if (spx::net_lds_bytes(n_classes, n) > spx::kNetLdsBudget) n_classes = 0;  // too many label pairs for LDS (64 KB with a single-row launch's staged pairs): exact path only
   e->net_n_classes = n_classes;
   if ((rc = upload(e, e->d_net_region, t->region, static_cast<size_t>(n) * 4))) return rc;
   if ((rc = upload(e, e->d_net_zone, t->zone, static_cast<size_t>(n) * 4))) return rc;
@@ -1242,22 +1242,13 @@ int spx_upload_net_nodes(spx_engine* e, const spx_net_nodes_soa* t) {
 int spx_upload_net_topo(spx_engine* e, const spx_net_topo_soa* t) {
   if (!e || !t) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
-  if (t->n_regions < 0 || t->n_zones < 0) return fail(e, SPX_ERR_ARG, "negative topology size");
-  int rc;
-  if ((rc = upload(e, e->d_net_rcost, t->region_cost ? static_cast<const void*>(t->region_cost) : static_cast<const void*>(&rc),
-                   static_cast<size_t>(t->n_regions) * t->n_regions * 4)))
-    return rc;
-  if ((rc = upload(e, e->d_net_zcost, t->zone_cost ? static_cast<const void*>(t->zone_cost) : static_cast<const void*>(&rc),
-                   static_cast<size_t>(t->n_zones) * t->n_zones * 4)))
-    return rc;
-  e->net_n_regions = t->n_regions;
-  e->net_n_zones = t->n_zones;
-  e->net_max_cost = SPX_NET_MAX_COST;
-  for (int64_t i = 0; t->region_cost && i < static_cast<int64_t>(t->n_regions) * t->n_regions; ++i) e->net_max_cost = std::max<int64_t>(e->net_max_cost, t->region_cost[i]);
-  for (int64_t i = 0; t->zone_cost && i < static_cast<int64_t>(t->n_zones) * t->n_zones; ++i) e->net_max_cost = std::max<int64_t>(e->net_max_cost, t->zone_cost[i]);
-  SPX_HIP(e, hipStreamSynchronize(e->stream));
-  e->net_topo = true;
-  return SPX_OK;
+  return upload_net_costs<int32_t>(e, t->n_regions, t->n_zones, t->region_cost, t->zone_cost);
+}
+
+int spx_upload_net_topo_wide(spx_engine* e, const spx_net_topo_wide* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  return upload_net_costs<int64_t>(e, t->n_regions, t->n_zones, t->region_cost, t->zone_cost);
 }
 
 int spx_upload_net_pods(spx_engine* e, const spx_net_pods_soa* t) {

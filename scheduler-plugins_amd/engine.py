@@ -668,9 +668,12 @@ class Engine:
         i32p, i64p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
         N, P = nodes.struct.n_nodes, pods.struct.n_pods
         rg, zc = nettopo.struct.n_regions, nettopo.struct.n_zones
-        rcost = np.full(max(rg * rg, 1), -1, np.int32)
-        zcost = np.full(max(zc * zc, 1), -1, np.int32)
-        self._ck(L.spx_flatten_net_topo(nettopo.ref(), rcost.ctypes.data_as(i32p), zcost.ctypes.data_as(i32p)))
+        # the cost matrices in the CRD's own int64; a snapshot whose entries all fit int32 is narrowed and travels as before
+        rcost = np.full(max(rg * rg, 1), -1, np.int64)
+        zcost = np.full(max(zc * zc, 1), -1, np.int64)
+        self._ck(L.spx_flatten_net_topo_wide(nettopo.ref(), rcost.ctypes.data_as(i64p), zcost.ctypes.data_as(i64p)))
+        if max(rcost.max(), zcost.max()) <= np.iinfo(np.int32).max:
+            rcost, zcost = rcost.astype(np.int32), zcost.astype(np.int32)
         nk, npairs = C.c_int32(), C.c_int64()
         self._ck(L.spx_flatten_net_keys(pods.ref(), appgroups.ref(), C.byref(nk), C.byref(npairs), None, None, None, None, None, None))
         cols = dict(pod_key=np.zeros(P, np.int32), topo_order=np.zeros(P, np.int32), key_score_equally=np.zeros(nk.value, np.uint8),
@@ -692,8 +695,12 @@ class Engine:
     def upload_network(self, f: dict, rows=None) -> None:
         L, H = self._lib, self._hdr
         self._ck(L.spx_upload_net_nodes(self._h, Table(H, "spx_net_nodes_soa", n_nodes=f["N"], region=f["region"], zone=f["zone"]).ref()))
-        self._ck(L.spx_upload_net_topo(self._h, Table(H, "spx_net_topo_soa", n_regions=f["rg"], n_zones=f["zc"], region_cost=f["rcost"],
-                                                       zone_cost=f["zcost"]).ref()))
+        if f["rcost"].dtype == np.int64:  # int64 cost matrices: the wide tables (the engine then runs its 64-bit sweep)
+            self._ck(L.spx_upload_net_topo_wide(self._h, Table(H, "spx_net_topo_wide", n_regions=f["rg"], n_zones=f["zc"], region_cost=f["rcost"],
+                                                                zone_cost=f["zcost"]).ref()))
+        else:
+            self._ck(L.spx_upload_net_topo(self._h, Table(H, "spx_net_topo_soa", n_regions=f["rg"], n_zones=f["zc"], region_cost=f["rcost"],
+                                                           zone_cost=f["zcost"]).ref()))
         cols = dict(f["cols"])
         P = f["P"] if rows is None else rows[1] - rows[0]
         cols.update(_rows({k: cols[k] for k in ("pod_key", "topo_order")}, f["P"], rows))  # the key tables are per workload, not per pod
@@ -790,7 +797,7 @@ class Engine:
         self._ck(self._lib.spx_sync(self._h))
 
     def kernel_path(self, plugin: int) -> int:
-        """0 = generic sweep kernel, 1 = fast formulation (same results)."""
+        """0 = generic sweep kernel, 1 = fast formulation (same results); NETOVERHEAD: 2 = the 64-bit sweep (costs that need int64)."""
         return int(self._lib.spx_kernel_path(self._h, plugin))
 
     # ------------------------------------------------------------------ one-call loaders (spx_load_*: flatten + upload inside the library)

@@ -37,7 +37,11 @@ int32_t find_pod_order(const spx_appgroup_objects* ag, int32_t g, int32_t select
 
 }  // namespace
 
-extern "C" int spx_flatten_net_topo(const spx_nettopo_objects* nt, int32_t* region_cost, int32_t* zone_cost) {
+namespace {
+
+// populateCostMap (networkoverhead.go:448-497) into dense matrices of either width, -1 = no entry; `limit`: the largest entry T carries
+template <typename T>
+int flatten_net_topo(const spx_nettopo_objects* nt, T* region_cost, T* zone_cost, int64_t limit) {
   if (!nt || !region_cost || !zone_cost) return SPX_ERR_ARG;
   const int64_t rg = nt->n_regions, zc = nt->n_zones;
   for (int64_t i = 0; i < rg * rg; ++i) region_cost[i] = -1;
@@ -46,17 +50,29 @@ extern "C" int spx_flatten_net_topo(const spx_nettopo_objects* nt, int32_t* regi
     for (int32_t k = nt->rc_ptr[o]; k < nt->rc_ptr[o + 1]; ++k) {
       const int32_t d = nt->rc_dest[k];
       if (d < 0 || d >= nt->n_regions) continue;
-      if (nt->rc_cost[k] < 0 || nt->rc_cost[k] > INT32_MAX) return SPX_ERR_ARG;  // costs are small non-negative ints
-      region_cost[static_cast<int64_t>(o) * rg + d] = static_cast<int32_t>(nt->rc_cost[k]);
+      if (nt->rc_cost[k] < 0 || nt->rc_cost[k] > limit) return SPX_ERR_ARG;
+      region_cost[static_cast<int64_t>(o) * rg + d] = static_cast<T>(nt->rc_cost[k]);
     }
   for (int32_t o = 0; o < nt->n_zones; ++o)
     for (int32_t k = nt->zc_ptr[o]; k < nt->zc_ptr[o + 1]; ++k) {
       const int32_t d = nt->zc_dest[k];
       if (d < 0 || d >= nt->n_zones) continue;
-      if (nt->zc_cost[k] < 0 || nt->zc_cost[k] > INT32_MAX) return SPX_ERR_ARG;
-      zone_cost[static_cast<int64_t>(o) * zc + d] = static_cast<int32_t>(nt->zc_cost[k]);
+      if (nt->zc_cost[k] < 0 || nt->zc_cost[k] > limit) return SPX_ERR_ARG;
+      zone_cost[static_cast<int64_t>(o) * zc + d] = static_cast<T>(nt->zc_cost[k]);
     }
   return SPX_OK;
+}
+
+}  // namespace
+
+// entries above INT32_MAX are refused here: the 32-bit tables cannot carry them (spx_flatten_net_topo_wide does)
+extern "C" int spx_flatten_net_topo(const spx_nettopo_objects* nt, int32_t* region_cost, int32_t* zone_cost) {
+  return flatten_net_topo<int32_t>(nt, region_cost, zone_cost, INT32_MAX);
+}
+
+// the CRD's own int64 entries: only negative ones are refused
+extern "C" int spx_flatten_net_topo_wide(const spx_nettopo_objects* nt, int64_t* region_cost, int64_t* zone_cost) {
+  return flatten_net_topo<int64_t>(nt, region_cost, zone_cost, INT64_MAX);
 }
 
 
