@@ -21,6 +21,7 @@
 // compares both with the oracle's one-pod-at-a-time evaluation).
 #include <cstdlib>
 
+#include "net_norm.h"
 #include "nrt_fast_device.h"
 #include "spx_internal.h"
 #include "trimaran_math.h"
@@ -222,11 +223,7 @@ __device__ __forceinline__ void add_pair(Acc& a, int region, int zone, int hr, i
     }
   }
 }
-__device__ __forceinline__ int norm_cost(int cost, int mn, int mx) {  // networkoverhead.go:389-418 (as k_net_cls)
-  if (mn == 0 && mx == 0) return cost;
-  const int range = mx - mn;
-  return range != 0 ? 100 - (100 * (cost - mn)) / range : 100 - (cost - mn);
-}
+// NormalizeScore: norm_cost, net_norm.h (as k_net_cls)
 
 __device__ __forceinline__ int64_t wadd(int64_t a, int64_t b) { return static_cast<int64_t>(static_cast<uint64_t>(a) + static_cast<uint64_t>(b)); }
 

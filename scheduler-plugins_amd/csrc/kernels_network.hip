@@ -35,12 +35,7 @@ using Acc = AccT<int>;
 //   phase 3b lanes = classes: NormalizeScore per class -> (status << 8 | score) in LDS
 //   phase 4  lanes = 4 consecutive nodes: one 8-byte load of class ids, 4 LDS reads, host nodes (rare) patched
 //            exactly, one dword store per table.
-__device__ __forceinline__ int norm_cost(int cost, int mn, int mx) {
-  // networkoverhead.go:389-418; 100*d/r is never within 1e-6 of an integer from below, so int64(float) == integer division
-  if (mn == 0 && mx == 0) return cost;
-  const int range = mx - mn;
-  return range != 0 ? 100 - (100 * (cost - mn)) / range : 100 - (cost - mn);
-}
+// NormalizeScore per class (phase 3b) and per host node (phase 4): norm_cost, net_norm.h.
 
 // One wavefront per pod row in a batch launch; a single-row launch (the sequential commit loop) puts kRowThreads threads on
 // its row — every loop below strides by the block size, the one reduction combines the waves through LDS.

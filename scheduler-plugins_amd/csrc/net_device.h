@@ -4,14 +4,16 @@
 // engine checks (largest entry) x (most pairs of a workload key) < 2^31), kernels_network_wide.hip with T = int64_t (the reference's
 // own width, networkoverhead.go:576-638).  What differs between the two beyond the type:
 //   - the cost matrices are read as NetArgs::region_cost / zone_cost or as NetArgs::region_cost64 / zone_cost64;
-//   - NormalizeScore: the narrow form replaces int64(100.0*float64(d)/float64(r)) by integer division, which is proven for its
-//     range only; the wide form runs the reference's float64 sequence (norm_cost_f64).
+//   - NormalizeScore (net_norm.h): the narrow form replaces int64(100.0*float64(d)/float64(r)) by integer division while 100*d
+//     fits 32 bits (r < 2^31/100) and runs the reference's float64 sequence above that; the quotients are equal for every r < 2^31.
+//     The wide form always runs the float64 sequence (norm_cost_f64).
 //
 // Everything is in the anonymous namespace: each translation unit gets its own copy.
 #pragma once
 
 #include <limits>
 
+#include "net_norm.h"
 #include "spx_internal.h"
 
 namespace spx {
@@ -130,21 +132,7 @@ __device__ __forceinline__ T wave_max(T v) {
   return v;
 }
 
-// NormalizeScore of the wide form, networkoverhead.go:389-418 operation for operation: 100.0 * float64(s - min) / float64(max - min),
-// truncated; min == max: float64(s - min); min == max == 0: untouched.  Returned as the score byte.  A scored node has
-// min <= s <= max, so norm lies in [0, 100]; the differences wrap and norm is fenced for the cells outside that (nodes another
-// Filter plugin rejected, a row without a feasible node): their byte is never stored as a score.
-__device__ __forceinline__ int norm_cost_f64(int64_t cost, int64_t mn, int64_t mx) {
-  int64_t s = cost;
-  if (!(mn == 0 && mx == 0)) {
-    const int64_t d = static_cast<int64_t>(static_cast<uint64_t>(cost) - static_cast<uint64_t>(mn));
-    const int64_t r = static_cast<int64_t>(static_cast<uint64_t>(mx) - static_cast<uint64_t>(mn));
-    double norm = r != 0 ? 100.0 * static_cast<double>(d) / static_cast<double>(r) : static_cast<double>(d);
-    norm = norm < -1000.0 ? -1000.0 : (norm > 1000.0 ? 1000.0 : norm);
-    s = 100 - static_cast<int64_t>(norm);
-  }
-  return s < 0 ? 0 : (s > 255 ? 255 : static_cast<int>(s));
-}
+// NormalizeScore: norm_cost (T = int) and norm_cost_f64 (T = int64_t), net_norm.h
 
 // One wavefront per pod row, every node evaluated on its own:
 //   phase 1  lanes = topology classes: accumulate (satisfied, violated, cost) over the pod's pairs into LDS;
@@ -243,8 +231,6 @@ __global__ __launch_bounds__(64) void k_net(NetArgs g) {
   }
   mn = wave_min(mn);
   mx = wave_max(mx);
-  [[maybe_unused]] int range = 0;
-  if constexpr (!kWide) range = mx - mn;
 
   // ---- phase 4: NormalizeScore (networkoverhead.go:389-418) + stores
   for (int64_t t = 0; t < tiles; ++t) {
@@ -262,11 +248,7 @@ __global__ __launch_bounds__(64) void k_net(NetArgs g) {
       if constexpr (kWide) {
         if (feasible) score = norm_cost_f64(a.cost, mn, mx);
       } else {
-        if (feasible) {
-          if (mn == 0 && mx == 0) score = a.cost;                            // all minimum: untouched (== 0)
-          else if (range != 0) score = 100 - (100 * (a.cost - mn)) / range;  // == 100 - int64(100.0*d/r): 100*d/r is never within 1e-6 of an integer from below
-          else score = 100 - (a.cost - mn);                                  // max == min != 0
-        }
+        if (feasible) score = norm_cost(a.cost, mn, mx);
       }
       if (g.out_raw) {
         g.out_raw[n] = g.raw_which == SPX_NET_RAW_SATISFIED ? a.sat : (g.raw_which == SPX_NET_RAW_VIOLATED ? a.vio : a.cost);

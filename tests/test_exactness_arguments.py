@@ -763,3 +763,44 @@ def test_peaks_header_computes_what_the_replay_computes():
             assert same.all(), (regime, int((~same).sum()))
         cells += m * n
     assert cells > 2_000_000
+
+
+def test_network_normalize_integer_division_equals_float64_below_2_31():
+    """NetworkOverhead's NormalizeScore (networkoverhead.go:389-418) is int64(100.0 * float64(d) / float64(r)) with d = cost - min,
+    r = max - min.  The 32-bit sweeps (net_norm.h: norm_cost) compute (100 * d) / r in integers while the product fits 32 bits and
+    the float64 sequence above that; DESIGN section 3.5 says the two are the same number for every 0 <= d <= r < 2^31.  Reason:
+    100 * d < 2^38 is exact in float64, so the quotient carries one rounding, a relative 2^-53; a non-integer 100 * d / r lies at
+    least 1/r > 2^-31 from the next integer, an integer one is exact — truncation cannot land on the other side.  The claim is
+    about the quotient, not about a 32-bit product: the reference value here is int64 arithmetic, and 100 * d passes 2^31 for
+    every d >= 21 474 837.  Random pairs, the quotients on and next to an integer for many q (r = 100 q, and r odd), and the
+    ranges 1, 2, 99, 100, 101 and 2^31 - 1 with every kind of d."""
+    rng = np.random.default_rng(31)
+    top = (1 << 31) - 1
+    ds, rs = [], []
+
+    def add(d, r):
+        d, r = np.broadcast_arrays(np.asarray(d, np.int64), np.asarray(r, np.int64))
+        keep = (d >= 0) & (d <= r) & (r >= 1) & (r <= top)
+        ds.append(d[keep]), rs.append(r[keep])
+
+    n = 1_200_000
+    r = np.concatenate([rng.integers(1, top + 1, n // 2), (1 << rng.integers(1, 32, n // 4)) - rng.integers(0, 5, n // 4),
+                        rng.integers(top - 10_000, top + 1, n - 3 * (n // 4))]).clip(1, top)
+    add((rng.random(r.size) * (r + 1)).astype(np.int64), r)                      # random pairs
+    q = np.concatenate([rng.integers(1, top // 100 + 1, 4000), np.arange(top // 100 - 500, top // 100 + 1)])
+    j = np.arange(0, 101)
+    for rr in (100 * q, np.minimum(100 * q + 2 * rng.integers(0, 50, q.size) + 1, top)):   # r = 100 q: 100 d / r is the integer j at d = j q; r odd
+        base = (j[None, :] * rr[:, None]) // 100                                # floor(j r / 100): the d at which 100 d / r reaches or passes j
+        for off in (-1, 0, 1):
+            add(base + off, rr[:, None])
+    for rr in (1, 2, 99, 100, 101, top):
+        d = np.unique(np.concatenate([np.arange(0, min(rr, 2000) + 1), rr - np.arange(0, min(rr, 2000) + 1), rng.integers(0, rr + 1, 20_000),
+                                      (np.arange(0, 101) * rr) // 100, -(-np.arange(0, 101) * rr // 100)]))
+        add(d, rr)
+    d, r = np.concatenate(ds), np.concatenate(rs)
+    assert d.size >= 2_000_000 and int(r.max()) == top and int((100 * d).max()) >= 1 << 37
+    assert int((100 * d >= 1 << 31).sum()) > d.size // 2   # most pairs lie where a 32-bit product would have wrapped
+    exact = (100 * d) // r
+    f64 = np.trunc(100.0 * d.astype(np.float64) / r.astype(np.float64))
+    bad = np.flatnonzero(f64 != exact)
+    assert bad.size == 0, (bad.size, [(int(d[i]), int(r[i]), float(f64[i]), int(exact[i])) for i in bad[:5]])
