@@ -846,15 +846,31 @@ int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t r
  *   CAPACITY           Reserve: the namespace's Used grows by the pod's request, a nominated pod that gets bound stops counting as
  *                      nominated (capacity_scheduling.go:350-364, elasticquota.go:89-98) — needs spx_quota_soa.min;
  *   NETOVERHEAD        the pod joins its AppGroup's scheduled list (networkoverhead.go:205-224) — needs spx_upload_net_commit.
- * plugin_mask is a subset of {ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY}: LROC, PEAKS and SYSCHED are rejected (SySched's
- * bind-time bookkeeping — addPod's union into the host set, sysched.go:310-333 — is not carried by the loop).  Without a Filter plugin the whole chain runs in one
- * workgroup (about 3 us per pod); with one, every pod is one single-row spx_eval + spx_eval_best + a bookkeeping launch on the engine
- * stream (tens of us per pod), score / status tables end up holding each row as its pod saw it (except Allocatable's when Filter
+ *   LROC               the scheduler cache has assumed the bound pod, so it is in nodeInfo.GetPods() of the next cycle: its requests and
+ *                      its limits raised to the requests (the four numbers of spx_lroc_pods_soa) join the node's four sums of
+ *                      spx_lroc_nodes_soa (GetNodeRequestsAndLimits, resourcestats.go:163-225, read by computeRank,
+ *                      lowriskovercommitment.go:158-171).  Both risk terms of that node move: riskLimit through the sums, riskLoad
+ *                      through NodeRequestMinusPod (:210-246) — the node's Beta fit is redone on the device;
+ *   PEAKS              no commit state (load-watcher metric and node capacity only, peaks.go:103-144), but NormalizeScore is a
+ *                      min-max over the pod's feasible nodes (:150-166): with NRT or NETOVERHEAD in the mask each pod's row is
+ *                      normalised against that pod's own status rows; without one the rows are fixed and swept once up front.
+ * plugin_mask is a subset of {ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, LROC, PEAKS}; LROC and PEAKS need their node and
+ * pod tables uploaded.  SYSCHED is still rejected (SySched's bind-time bookkeeping — addPod's union into the host set,
+ * sysched.go:310-333 — is not carried by the loop).
+ * Route: a mask of ALLOCATABLE / TLP / LVRB alone runs the whole chain in one workgroup (about 3 us per pod).  Any other mask runs
+ * per pod: one single-row spx_eval + spx_eval_best + the bookkeeping launches on the engine stream (tens of us per pod), the first
+ * pod as plain launches, the rest replayed from one captured graph (a linear chain on the engine stream) whose kernels read the
+ * row from a device counter — or, for a mask with a Filter plugin and without LROC / PEAKS, as ONE cooperative persistent launch
+ * (SPX_OPT_COMMIT_COOP; it declines a mask with either scorer).  LowRiskOverCommitment's form (float32 / float64 / int64) is chosen
+ * once for the batch from bounds that hold after every possible commit — per column, (largest node sum) + (sum of the batch's pod
+ * column): below 2^47 with no limit below its request float32, below 2^52 float64, else int64; spx_kernel_path reports it.
+ * On the per-pod route the score / status tables end up holding each row as its pod saw it (except Allocatable's when Filter
  * plugins are in the mask: its feasibility-aware normalisation then happens inside the argmax kernel, as in spx_decide).  A pod that fails PreFilter or has no
  * feasible node gets node -1 and reserves nothing.  Per pod: the node with the highest
  * sum of plugin_weight x score (lowest index among ties; upstream's selectHost draws among them), that sum, and the size
  * of the tie set (NULL = not wanted).  tlp_missing_out (NULL = not wanted) receives the per-node missing utilisation after
- * the last commit.  The engine's uploaded tables are left untouched; with LVRB in the mask its score table is (re)evaluated
+ * the last commit.  The engine's uploaded tables are left untouched (every table the loop mutates — LROC's four node sums and its
+ * per-node table among them — is saved before and restored after); with LVRB in the mask its score table is (re)evaluated
  * for the row range first (LVRB carries no commit state, so the loop reads those rows).  Synchronous. */
 int spx_commit_sequential(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end, int32_t* node_idx, int64_t* weighted_score, int32_t* n_ties, int64_t* tlp_missing_out);
 
@@ -1013,8 +1029,8 @@ typedef struct spx_profile_objects {
 } spx_profile_objects;
 int spx_load_profile(spx_engine* e, const spx_profile_objects* o);
 
-/* Which form the last spx_commit_sequential ran: 1 = the one-workgroup chain of the Filter-less profile, 2 = per-pod single-row
- * launches (replayed from a graph), 3 = the cooperative persistent kernel; 0 = none yet */
+/* Which form the last spx_commit_sequential ran: 1 = the one-workgroup chain of a mask of ALLOCATABLE / TLP / LVRB, 2 = per-pod single-row
+ * launches (replayed from a graph; always with LROC or PEAKS in the mask), 3 = the cooperative persistent kernel; 0 = none yet */
 int spx_commit_path(const spx_engine* e);
 /* Which Filter launch the last NodeResourceTopologyMatch sweep ran: 1 = float64 compares (k_nrt_fast / the reference-arithmetic
  * kernel), 2 = rank space (SPX_OPT_NRT_RANK_FILTER: whole-batch sweeps), 3 = rank space inside the fused Filter + Score launch
@@ -1033,6 +1049,8 @@ int spx_nrt_packed_score_slots(const spx_engine* e);
 /* which formulation of a plugin's sweep the uploaded tables select: 0 = generic (reference arithmetic, operation for
  * operation), 1 = fast formulation (same results; see DESIGN.md for each kernel's preconditions); <0 on error.
  * Tests use it to make sure both formulations are exercised.
+ * SPX_PLUGIN_LROC: 1 = the float32 sweep; after a spx_commit_sequential with LROC in its mask, and until the next spx_eval of the
+ * plugin or upload of its tables, the form that loop chose for its batch (1 = float32, 0 = float64 or int64).
  * SPX_PLUGIN_NETOVERHEAD also reports 2 = the 64-bit sweep (kernels_network_wide.hip): the engine holds int64 cost matrices, or
  * (largest cost entry) x (most pairs of any workload key) reaches 2^31.  SPX_OPT_REFERENCE_KERNELS selects the per-node form of the
  * same 64-bit arithmetic there, and the value stays 2.

@@ -39,6 +39,7 @@
 
 #include <type_traits>
 
+#include "lroc_cell.h"
 #include "lroc_math.h"
 #include "spx_internal.h"
 
@@ -53,7 +54,6 @@ constexpr int kNplFast = 8;           // k_lroc_fast: two dwords per lane and ro
 constexpr int kTabCols = kLrocTabCols;
 constexpr double kNoOver = -1e30;     // "limit - capacity" of a node that must not contribute a riskLimit
 constexpr float kBand = 1.5e-4f;      // upper limit of the ambiguity band around k + 0.5 (float32 error of the score < 8.7e-5)
-typedef float F32x2 __attribute__((ext_vector_type(2)));
 
 template <typename T>
 __device__ __forceinline__ T uload(const T* p) {  // wave-uniform read of immutable input -> scalar load
@@ -119,29 +119,7 @@ struct NodeI {  // int64 form
   int64_t req_m, lim_m, cap_m;
 };
 
-// totalRisk of one resource (lowriskovercommitment.go:205-208, :250-253) given (1-w)*riskLoad
-__device__ __forceinline__ double total_risk(double w, double kl, double node_req, double node_lim, double cap, double pod_req, double pod_lim) {
-  const double limit = node_lim + pod_lim;                        // resourcestats.go:204-205
-  const double request = fmin(node_req + pod_req, cap);           // :202-203, :208-209
-  const double over = limit - cap;
-  const double risk_limit = over > 0.0 ? over / (limit - request) : 0.0;
-  const double total = w * risk_limit + kl;
-  return fmax(fmin(total, 1.0), 0.0);
-}
-__device__ __forceinline__ double total_risk(double w, double kl, int64_t node_req, int64_t node_lim, int64_t cap, int64_t pod_req, int64_t pod_lim) {
-  const int64_t limit = node_lim + pod_lim;
-  int64_t request = node_req + pod_req;
-  if (request > cap) request = cap;
-  const double risk_limit = limit > cap ? static_cast<double>(limit - cap) / static_cast<double>(limit - request) : 0.0;
-  const double total = w * risk_limit + kl;
-  return fmax(fmin(total, 1.0), 0.0);
-}
-
-__device__ __forceinline__ uint32_t score_byte(bool has, double risk_c, double risk_m) {
-  const double rank = 1 - fmax(risk_c, risk_m);                   // :165
-  const int v = static_cast<int>(round(rank * 100.0));            // :136-137
-  return has ? static_cast<uint32_t>(v < 0 ? 0 : (v > 100 ? 100 : v)) : 0u;
-}
+// (total_risk, score_byte and the float32 cell: lroc_cell.h, shared with the commit loop's single-row sweep)
 
 template <bool F64>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_lroc(LrocArgs a, int n_tiles) {
@@ -244,10 +222,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, 4) void k_lroc_fast(LrocArgs
   }
   const F32x2 w2{static_cast<float>(a.w_cpu), static_cast<float>(a.w_mem)};
   const int64_t np = a.n_pods_total;
-  constexpr float kMagic = 8388608.0f;   // 2^23: a sum in [2^23, 2^24) is a whole number, and the mantissa bits are that number - 2^23
-  constexpr float kScale = 6553600.0f;   // 100 * 2^16
-  constexpr float kBandUnits = 8.0f;     // the band around k + 1/2 in units of 2^-16: 1.22e-4 (float32 error of the score < 8.7e-5)
-  static_assert(kBandUnits * 0x1p-16f < kBand && kBandUnits == 8.0f, "the mask below clears log2(2 * kBandUnits) bits");
+  static_assert(kLrocBandUnits * 0x1p-16f < kBand && kLrocBandUnits == 8.0f, "lroc_cell_near clears log2(2 * kLrocBandUnits) bits");
 
   unsigned redone = 0;
   // per pod (host-prepared, one 32-byte scalar load): podLimit as two float32 and podLimit - podRequest for cpu, memory; the seventh
@@ -269,25 +244,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, 4) void k_lroc_fast(LrocArgs
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int i = j * 4 + q;
-          // riskLimit = over / max(D + d, over) for over > 0, else 0  ==  clamp(over / (D + d), 0, 1): over exact, then float32
-          // (high parts, low parts, then both: the high sum is exact whenever it cancels, the low sum always — within 3 ulp of A + limit)
-          const F32x2 ov = (Ah[i] + plh) + (Al[i] + pll);
-          const F32x2 dd = D[i] + df;
-          const float rr = __builtin_amdgcn_rcpf(dd.x * dd.y);  // one reciprocal for both quotients
-          const F32x2 x = ov * __builtin_shufflevector(dd, dd, 1, 0);
-          F32x2 qq, r2;
-          r2.x = rr;  // (.y is not read: op_sel_hi takes the low half for both products)
-          // (inline: the compiler has no packed clamp pattern; s_nop: the wait state a transcendental's consumer needs, which the
-          // hazard pass cannot add inside an asm statement)
-          asm("s_nop 0\n\tv_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0] clamp" : "=v"(qq) : "v"(x), "v"(r2));  // both quotients, clamped to [0, 1] (NaN cannot occur: rr and x are finite or x is an infinity)
-          const F32x2 t2 = __builtin_elementwise_fma(w2, qq, kl[i]);
-          const float t_c = t2.x, t_m = t2.y;
-          const float m = __builtin_amdgcn_fmed3f(__builtin_fmaxf(t_c, t_m), 0.0f, 1.0f);  // totalRisk's clamp (:252), after the max
-          // 100 * (1 - max risk) in units of 2^-16, + 1/2 + the band, rounded to a whole number by the sum with 2^23 (the fma rounds once):
-          // the mantissa then reads  score << 16 | fraction,  and a fraction below 2 * kBandUnits means "within the band of k + 1/2"
-          const float k = __builtin_fmaf(m, -kScale, kMagic + kScale + 32768.0f + kBandUnits);
-          kb[q] = __float_as_uint(k);
-          near[i] = __ballot((kb[q] & (0xffffu & ~(2u * static_cast<uint32_t>(kBandUnits) - 1u))) == 0u);  // (the comparison's lane mask: no vector work)
+          kb[q] = lroc_cell_f32(Ah[i], Al[i], D[i], kl[i], plh, pll, df, w2);
+          near[i] = __ballot(lroc_cell_near(kb[q]));  // (the comparison's lane mask: no vector work)
         }
         const uint32_t lo = __builtin_amdgcn_perm(kb[1], kb[0], 0x0c0c0602u), hi = __builtin_amdgcn_perm(kb[3], kb[2], 0x0c0c0602u);  // the scores: byte 2
         w[j] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);

@@ -37,6 +37,7 @@ int commit_coop(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t 
   const bool A = plugin_mask & (1u << SPX_PLUGIN_ALLOCATABLE), T = plugin_mask & (1u << SPX_PLUGIN_TLP), Lv = plugin_mask & (1u << SPX_PLUGIN_LVRB);
   const bool N = plugin_mask & (1u << SPX_PLUGIN_NRT), W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD), Q = plugin_mask & (1u << SPX_PLUGIN_CAPACITY);
   if (!e->option[SPX_OPT_COMMIT_COOP] || e->option[SPX_OPT_COMMIT_FROM_MEMORY]) return SPX_OK;
+  if (plugin_mask & ((1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS))) return SPX_OK;  // the kernel carries neither scorer: the per-pod loop runs
   for (int p : {SPX_PLUGIN_TLP, SPX_PLUGIN_LVRB, SPX_PLUGIN_NRT, SPX_PLUGIN_NETOVERHEAD})
     if (((plugin_mask >> p) & 1u) && forced_reference(e, p)) return SPX_OK;
   const int64_t n_wg = (e->n_nodes + spx::kCoopWindow - 1) / spx::kCoopWindow;
@@ -173,13 +174,14 @@ int commit_coop(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t 
   return SPX_OK;
 }
 
-// Sequential commit with Filter plugins in the profile: per pod one single-row evaluation of the whole plugin set on the
-// CURRENT device tables, the weighted argmax, and k_commit_apply.  Everything is enqueued on the engine stream without a host
-// sync; the tables the loop mutates are saved before and restored after.
+// Sequential commit with Filter plugins, LowRiskOverCommitment or Peaks in the profile: per pod one single-row evaluation of the
+// whole plugin set on the CURRENT device tables, the weighted argmax, k_commit_lroc_apply and k_commit_apply.  Everything is
+// enqueued on the engine stream without a host sync; the tables the loop mutates are saved before and restored after.
 int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end, int32_t* node_idx, int64_t* weighted_score,
                         int32_t* n_ties, int64_t* tlp_missing_out) {
   const bool T = plugin_mask & (1u << SPX_PLUGIN_TLP), N = plugin_mask & (1u << SPX_PLUGIN_NRT);
   const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD), Q = plugin_mask & (1u << SPX_PLUGIN_CAPACITY);
+  const bool Lr = plugin_mask & (1u << SPX_PLUGIN_LROC), Pk = plugin_mask & (1u << SPX_PLUGIN_PEAKS);
   if ((T || (plugin_mask & (1u << SPX_PLUGIN_LVRB))) && !(e->tri_nodes && e->tri_pods)) return fail(e, SPX_ERR_STATE, "trimaran node/pod tables not uploaded");
   if (N && e->nrt_wide)
     return fail(e, SPX_ERR_STATE, "NRT: spx_commit_sequential does not take a wide snapshot (more than 8 resource slots, or SPX_OPT_NRT_WIDE)");
@@ -228,7 +230,7 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
   struct LoopFlag {
     spx_engine* e;
     explicit LoopFlag(spx_engine* x) : e(x) { e->in_commit_loop = true, e->tlp_amb_built = false, e->nrt_pk_tab_built = e->nrt_wsort_built = false; }  // (k_commit_apply advances d_tlp_missing and the zone tables)
-    ~LoopFlag() { e->in_commit_loop = false, e->tlp_amb_built = false, e->nrt_pk_tab_built = e->nrt_wsort_built = false; }
+    ~LoopFlag() { e->in_commit_loop = false, e->tlp_amb_built = false, e->nrt_pk_tab_built = e->nrt_wsort_built = false, e->lroc_loop_form = -1, e->peaks_loop_row = false; }
   } loop_flag(e);
   // ---- save what the loop mutates
   struct Saved {
@@ -252,6 +254,34 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
         keep(e->d_q_nom_reqp, e->q_n_nominated), keep(e->d_q_other, NS * S * 8), keep(e->d_q_otherp, NS);
   }
   if (W) keep(e->d_net_key_flag, K);
+  spx::CommitLrocApplyArgs la{};
+  if (Lr) {
+    // the form for the whole batch, from bounds that hold after every possible commit (lroc_commit_form); chosen before anything is captured
+    int64_t pod_sum[4];
+    for (int c = 0; c < 4; ++c) {
+      int64_t sum = 0;
+      bool over = false;
+      for (int64_t i = row_begin; i < row_end; ++i) over = __builtin_add_overflow(sum, e->h_lroc_pod[c][static_cast<size_t>(i)], &sum) || over;
+      pod_sum[c] = over ? std::numeric_limits<int64_t>::max() : sum;
+    }
+    const int64_t alloc_max = e->lv_alloc_f32 ? 0 : (e->lv_alloc_exact ? (int64_t{1} << 47) : (int64_t{1} << 52));  // (what the upload recorded of the allocatable columns)
+    int form = spx_host::lroc_commit_form(e->lroc_node_max, pod_sum, alloc_max, e->lroc_nodes_cover && e->lroc_pods_cover);
+    if (forced_reference(e, SPX_PLUGIN_LROC)) form = spx::kLrocFormI64;
+    if (form == spx::kLrocFormF32 && (e->option[SPX_OPT_LROC_FLOAT64] || !e->lroc_pods_f32 || !e->d_lroc_podf.p)) form = spx::kLrocFormF64;  // (no float32 pod records)
+    if ((rc = ensure_score_table(e, SPX_PLUGIN_LROC))) return rc;
+    if ((rc = ensure(e, e->d_lroc_tab, static_cast<size_t>(e->row_stride) * spx::kLrocTabCols * sizeof(double)))) return rc;
+    fill_lroc(e, la.l);
+    if (!e->lroc_tab_ready) {  // per-node riskLoad of the snapshot: what the loop saves, re-prepares node by node, and restores
+      spx::launch_lroc_prepare(la.l, e->stream);
+      SPX_HIP(e, hipGetLastError());
+      e->lroc_tab_ready = true;
+    }
+    la.node_req_cpu = static_cast<int64_t*>(e->d_lroc_nreq_c.p), la.node_req_mem = static_cast<int64_t*>(e->d_lroc_nreq_m.p);
+    la.node_lim_cpu = static_cast<int64_t*>(e->d_lroc_nlim_c.p), la.node_lim_mem = static_cast<int64_t*>(e->d_lroc_nlim_m.p);
+    keep(e->d_lroc_nreq_c, Nn * 8), keep(e->d_lroc_nreq_m, Nn * 8), keep(e->d_lroc_nlim_c, Nn * 8), keep(e->d_lroc_nlim_m, Nn * 8);
+    keep(e->d_lroc_tab, static_cast<size_t>(e->row_stride) * spx::kLrocTabCols * sizeof(double));
+    e->lroc_loop_form = e->lroc_last_form = form;
+  }
   if ((rc = ensure(e, e->d_commit_save, total))) return rc;
   for (const Saved& sv : saved)
     SPX_HIP(e, hipMemcpyAsync(static_cast<char*>(e->d_commit_save.p) + sv.off, sv.buf->p, sv.bytes, hipMemcpyDeviceToDevice, e->stream));
@@ -261,6 +291,7 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
   ca.n_nodes = e->n_nodes;
   ca.n_pods = e->n_pods;
   ca.best_node = reinterpret_cast<const int32_t*>(static_cast<const int64_t*>(e->d_best.p) + P);
+  la.best_node = ca.best_node;
   if (T) {
     ca.tlp_missing = static_cast<int64_t*>(e->d_tlp_missing.p);
     ca.tlp_pod_milli = static_cast<const int64_t*>(e->d_tlp_pod.p);
@@ -309,9 +340,14 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
     e->net_dyn_active = true;
   }
   // LoadVariationRiskBalancing carries no commit state: its rows are swept once, the per-pod evaluation leaves it out
-  const uint32_t lvrb_bit = 1u << SPX_PLUGIN_LVRB;
-  const uint32_t step_mask = plugin_mask & ~lvrb_bit;
-  rc = (plugin_mask & lvrb_bit) ? spx_eval(e, lvrb_bit, row_begin, row_end) : SPX_OK;
+  // Peaks carries no commit state either, but its NormalizeScore runs over the pod's feasible nodes (peaks.go:150-166): with a Filter
+  // plugin in the mask that set depends on the commits before, and the row is normalised per pod against the pod's status rows;
+  // without one its rows are fixed and swept once, as LVRB's
+  const uint32_t lvrb_bit = 1u << SPX_PLUGIN_LVRB, peaks_bit = 1u << SPX_PLUGIN_PEAKS;
+  const uint32_t once_mask = plugin_mask & (lvrb_bit | ((N || W) ? 0u : peaks_bit));
+  const uint32_t step_mask = plugin_mask & ~once_mask;
+  rc = once_mask ? spx_eval(e, once_mask, row_begin, row_end) : SPX_OK;
+  e->peaks_loop_row = Pk && (N || W);
   auto step = [&](int64_t pod) -> int {  // one pod: sweep its row on the current tables, argmax, Reserve bookkeeping
     int r;
     bool decided = false;  // Allocatable's masked normalisation and the argmax in one kernel where that form applies
@@ -319,6 +355,11 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
     if (!decided) {
       if ((r = spx_eval(e, step_mask, pod, pod + 1))) return r;
       if ((r = spx_eval_best(e, plugin_mask, pod, pod + 1))) return r;
+    }
+    if (Lr) {  // before k_commit_apply: that one advances the row counter
+      la.pod = pod;
+      spx::launch_commit_lroc_apply(la, e->stream);
+      if (hipGetLastError() != hipSuccess) return fail(e, SPX_ERR_HIP, "k_commit_lroc_apply launch failed");
     }
     ca.pod = pod;
     spx::launch_commit_apply(ca, e->stream);
@@ -340,9 +381,11 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
           hipStreamBeginCapture(e->stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
         e->row_indirect = static_cast<const int64_t*>(e->d_row_counter.p);
         ca.row_counter = static_cast<int64_t*>(e->d_row_counter.p);
+        la.row_counter = ca.row_counter;
         const int crc = step(first);  // the row number only sizes the grids (one row); the kernels read the counter
         e->row_indirect = nullptr;
         ca.row_counter = nullptr;
+        la.row_counter = nullptr;
         const hipError_t end = hipStreamEndCapture(e->stream, &graph);
         if (crc == SPX_OK && end == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
           replayed = true;
@@ -394,9 +437,16 @@ int spx_commit_sequential(spx_engine* e, uint32_t plugin_mask, int64_t row_begin
   SPX_HIP(e, hipSetDevice(e->device));
   const uint32_t allowed = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_TLP) | (1u << SPX_PLUGIN_LVRB);
   const uint32_t with_filters = allowed | (1u << SPX_PLUGIN_NRT) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY);
-  if (plugin_mask == 0 || (plugin_mask & ~with_filters))
+  const uint32_t scorers = (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS);  // carried by the per-pod route only
+  if (plugin_mask == 0 || (plugin_mask & ~(with_filters | scorers)))
     return fail(e, SPX_ERR_ARG, "spx_commit_sequential supports Allocatable / TargetLoadPacking / LoadVariationRiskBalancing / NodeResourceTopologyMatch / "
                                 "NetworkOverhead / CapacityScheduling");
+  if ((plugin_mask & (1u << SPX_PLUGIN_LROC)) && !(e->tri_nodes && e->lroc_nodes && e->lroc_pods))
+    return fail(e, SPX_ERR_STATE, "spx_commit_sequential supports LowRiskOverCommitment only with its node and pod tables uploaded (spx_upload_lroc_nodes / "
+                                  "spx_upload_lroc_pods)");
+  if ((plugin_mask & (1u << SPX_PLUGIN_PEAKS)) && !(e->peaks_nodes && e->peaks_pods))
+    return fail(e, SPX_ERR_STATE, "spx_commit_sequential supports Peaks only with its node and pod tables uploaded (spx_upload_peaks_nodes / "
+                                  "spx_upload_peaks_pods)");
   if (plugin_mask & ~allowed) {
     if (e->n_pods <= 0 || e->n_nodes <= 0) return fail(e, SPX_ERR_STATE, "shape unknown");
     if (row_begin < 0 || row_end > e->n_pods || row_begin > row_end) return fail(e, SPX_ERR_ARG, "row range out of bounds");

@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "spx_internal.h"
+#include "../host/lroc_form.hpp"
 #include "../host/nrt_streams.hpp"
 #include "../host/parallel.hpp"
 
@@ -100,6 +101,14 @@ struct spx_engine {
   bool lroc_nodes_exact = false, lroc_pods_exact = false, lv_alloc_exact = false;  // all values in [0, 2^52)
   // the float32 sweep's preconditions (kernels_lroc.hip): all values in [0, 2^47), limits not below requests
   bool lroc_nodes_f32 = false, lroc_pods_f32 = false, lv_alloc_f32 = false;
+  // what selects the form a sequential commit of a batch runs (lroc_commit_form, host/lroc_form.hpp): per column {req cpu, req mem,
+  // lim cpu, lim mem} the largest node sum and the pods' values, and "no limit below its request" for the node sums / the pods
+  int64_t lroc_node_max[4] = {0, 0, 0, 0};
+  std::vector<int64_t> h_lroc_pod[4];
+  bool lroc_nodes_cover = false, lroc_pods_cover = false;
+  int lroc_loop_form = -1;  // spx::kLrocForm* while the sequential commit loop evaluates LowRiskOverCommitment, -1 otherwise (spx_eval)
+  bool peaks_loop_row = false;  // the sequential commit loop evaluates Peaks per pod, against the pod's current status rows (Filter plugins in the mask)
+  int lroc_last_form = -1;  // the form the last sequential commit ran, until the next spx_eval of the plugin or upload (spx_kernel_path)
 
   // Peaks
   DevBuf d_pk_cap, d_pk_util, d_pk_valid, d_pk_k1, d_pk_k2, d_pk_pod, d_pk_min, d_pk_max, d_pk_rowc, d_pk_tab, d_pk_seg, d_pk_segn;

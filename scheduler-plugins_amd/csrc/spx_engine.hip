@@ -554,7 +554,15 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       SPX_HIP(e, hipGetLastError());
       e->lroc_tab_ready = true;
     }
-    spx::launch_lroc(la, e->stream);
+    // inside the sequential commit loop: one row, a whole workgroup on it, in the form chosen for the batch (kernels_commit_scorers.hip)
+    if (e->lroc_loop_form >= 0) {
+      if (row_end - row_begin != 1) return fail(e, SPX_ERR_STATE, "internal: the commit loop evaluates LowRiskOverCommitment one row at a time");
+      if (e->lroc_loop_form != spx::kLrocFormF32) la.pod_f32 = nullptr;
+      spx::launch_commit_lroc_row(la, e->row_indirect, e->lroc_loop_form, e->stream);
+    } else {
+      e->lroc_last_form = -1;
+      spx::launch_lroc(la, e->stream);
+    }
     SPX_HIP(e, hipGetLastError());
   }
   if (K) {  // after the Filter plugins: NormalizeScore runs over each pod's feasible nodes
@@ -574,7 +582,7 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       ka.row_list = static_cast<const int32_t*>(e->d_pk_uniq.p);
       ka.n_list = e->pk_n_uniq;
     }
-    if (e->pk_negative) ka.opts &= ~spx::kOptPeaksEstimate;  // (the float64 passes take whatever the table holds)
+    if (e->pk_negative || e->peaks_loop_row) ka.opts &= ~spx::kOptPeaksEstimate;  // (the float64 passes take whatever the table holds; one row needs no lists)
     if (ka.opts & spx::kOptPeaksEstimate) {  // the undecided cells' list: sized by the rows this sweep walks
       size_t seg_bytes = 0, cnt_bytes = 0;
       ka.est_pods = spx::peaks_est_plan(ka.opts, e->row_stride, classes ? ka.n_list : row_end - row_begin, &seg_bytes, &cnt_bytes);
@@ -582,7 +590,12 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       ka.seg = e->d_pk_seg.p;
       ka.seg_n = static_cast<int32_t*>(e->d_pk_segn.p);
     }
-    spx::launch_peaks(ka, e->stream);
+    // inside the sequential commit loop with Filter plugins: the pod's row against its CURRENT status rows, one workgroup, no estimate scratch
+    if (e->peaks_loop_row) {
+      if (row_end - row_begin != 1) return fail(e, SPX_ERR_STATE, "internal: the commit loop evaluates Peaks one row at a time");
+      spx::launch_commit_peaks_row(ka, e->row_indirect, e->stream);
+    } else
+      spx::launch_peaks(ka, e->stream);
     if (classes)
       spx::launch_rows_expand(static_cast<const int32_t*>(e->d_pk_dups.p), static_cast<const int32_t*>(e->d_pk_dups.p) + 2 * e->pk_n_dups, e->pk_n_tasks, ka.out_score, nullptr,
                               e->row_stride, e->stream);
@@ -696,7 +709,10 @@ int spx_kernel_path(const spx_engine* e, int plugin) {
     if (e->net_topo && net_wide(e, 0)) return 2;  // the 64-bit sweep, in either of its forms
     return (e->net_nodes && e->net_class16 && e->net_n_classes > 0 && !forced_reference(e, SPX_PLUGIN_NETOVERHEAD)) ? 1 : 0;
   }
-  if (plugin == SPX_PLUGIN_LROC) return lroc_f32_ok(e) ? 1 : 0;
+  if (plugin == SPX_PLUGIN_LROC) {  // after a sequential commit: the form the loop chose for the batch
+    if (e->lroc_last_form >= 0) return e->lroc_last_form == spx::kLrocFormF32 ? 1 : 0;
+    return lroc_f32_ok(e) ? 1 : 0;
+  }
   if (plugin == SPX_PLUGIN_SYSCHED) return e->sy_last_chunks;
   if (plugin == SPX_PLUGIN_TLP) return (e->tlp.target_utilization >= 1 && e->tlp.target_utilization <= 99 && !(launch_opts(e) & spx::kOptTrimaranExact)) ? 1 : 0;
   return 0;

@@ -694,6 +694,31 @@ struct CommitApplyArgs {
 };
 void launch_commit_apply(const CommitApplyArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- sequential commit: LowRiskOverCommitment and Peaks per pod (kernels_commit_scorers.hip)
+// LowRiskOverCommitment's Reserve-time state: the bound pod is in nodeInfo.GetPods() of the next cycle, so its requests and its
+// limits (raised to the requests) join the node's four sums (GetNodeRequestsAndLimits, resourcestats.go:163-225), and the node's
+// columns of LrocArgs::node_tab are rewritten as launch_lroc_prepare would write them.  One workgroup; runs after the argmax of
+// the pod and BEFORE launch_commit_apply (which advances the row counter).
+struct CommitLrocApplyArgs {
+  int64_t pod;                 // row just decided
+  const int64_t* row_counter;  // when set: the row is *row_counter (graph replay); not advanced here
+  const int32_t* best_node;    // [P] (spx_eval_best layout)
+  int64_t* node_req_cpu;       // [N] the four sums of spx_lroc_nodes_soa, mutable
+  int64_t* node_req_mem;
+  int64_t* node_lim_cpu;
+  int64_t* node_lim_mem;
+  LrocArgs l;                  // node and pod columns, parameters, node_tab
+};
+void launch_commit_lroc_apply(const CommitLrocApplyArgs& a, hipStream_t s);
+// ONE row of LowRiskOverCommitment's table with a whole workgroup on it: row *row_ptr when set (SPX_RESOLVE_ROWS), else a.row_begin.
+// form: kLrocFormF32 (in-band cells recomputed in float64 in the same launch), kLrocFormF64, kLrocFormI64 — the same cell
+// arithmetic (lroc_cell.h) and the same bytes as launch_lroc's three kernels.
+constexpr int kLrocFormI64 = 0, kLrocFormF32 = 1, kLrocFormF64 = 2;
+void launch_commit_lroc_row(const LrocArgs& a, const int64_t* row_ptr, int form, hipStream_t s);
+// ONE row of Peaks' table, one workgroup: min / max of the raw scores (float64, peaks_cell.h) over the nodes every status table of
+// a.other_status passes for that row, then NormalizeScore's byte per feasible cell, 0 elsewhere.  Reads none of the estimate scratch.
+void launch_commit_peaks_row(const PeaksArgs& a, const int64_t* row_ptr, hipStream_t s);
+
 // ---------------------------------------------------------------- sequential commit, cooperative persistent kernel (kernels_commit_coop.hip)
 // One launch schedules a whole row range one pod at a time for profiles with Filter plugins.  A workgroup owns a window of 256 nodes
 // and keeps their state in registers; per pod the workgroups exchange two sets of self-tagged 8-byte granules (feasible-set

@@ -488,6 +488,10 @@ int spx_upload_lroc_nodes(spx_engine* e, const spx_lroc_nodes_soa* t) {
                         all_below_2p52(t->lim_mem, n);
   e->lroc_nodes_f32 = all_below_2p47(t->req_cpu_milli, n) && all_below_2p47(t->req_mem, n) && all_below_2p47(t->lim_cpu_milli, n) && all_below_2p47(t->lim_mem, n) &&
                       none_below(t->lim_cpu_milli, t->req_cpu_milli, n) && none_below(t->lim_mem, t->req_mem, n);
+  const int64_t* ncols[4] = {t->req_cpu_milli, t->req_mem, t->lim_cpu_milli, t->lim_mem};
+  for (int c = 0; c < 4; ++c) e->lroc_node_max[c] = n ? *std::max_element(ncols[c], ncols[c] + n) : 0;
+  e->lroc_nodes_cover = none_below(t->lim_cpu_milli, t->req_cpu_milli, n) && none_below(t->lim_mem, t->req_mem, n);
+  e->lroc_last_form = -1;
   e->lroc_nodes = true;
   e->lroc_tab_ready = false;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
@@ -525,6 +529,10 @@ int spx_upload_lroc_pods(spx_engine* e, const spx_lroc_pods_soa* t) {
     if ((rc = upload(e, e->d_lroc_podf, f.data(), f.size() * sizeof(float)))) return rc;
     SPX_HIP(e, hipStreamSynchronize(e->stream));  // f goes out of scope
   }
+  const int64_t* pcols[4] = {t->req_cpu_milli, t->req_mem, t->lim_cpu_milli, t->lim_mem};
+  for (int c = 0; c < 4; ++c) e->h_lroc_pod[c].assign(pcols[c], pcols[c] + p);
+  e->lroc_pods_cover = none_below(t->lim_cpu_milli, t->req_cpu_milli, p) && none_below(t->lim_mem, t->req_mem, p);
+  e->lroc_last_form = -1;
   e->lroc_pods = true;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   return SPX_OK;

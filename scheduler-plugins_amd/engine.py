@@ -917,7 +917,9 @@ class Engine:
 
     def commit_sequential(self, plugin_mask: int, row_begin: int = 0, row_end: Optional[int] = None, want_ties: bool = True):
         """pods in row order, each seeing the commits before it -> (node, weighted score, ties, missing); plugin_mask may hold
-        Allocatable / TLP / LVRB / NRT / NetworkOverhead / CapacityScheduling (spx_commit_sequential)"""
+        Allocatable / TLP / LVRB / NRT / NetworkOverhead / CapacityScheduling / LowRiskOverCommitment / Peaks (spx_commit_sequential;
+        the last two with their tables loaded: a bound pod joins its node's LROC sums, Peaks is normalised per pod over the pod's
+        feasible nodes); SySched is rejected"""
         row_end = self.n_pods if row_end is None else row_end
         n = row_end - row_begin
         node, score, ties = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32)
