@@ -63,11 +63,24 @@ extern "C" {
 #define SPX_PLUGIN_PEAKS 8 /* trimaran Peaks */
 #define SPX_PLUGIN_SYSCHED 9 /* SySched (pkg/sysched) */
 #define SPX_NUM_PLUGINS 10
+/* Coscheduling (pkg/coscheduling): a PreFilter gate per pending pod.  It owns no score table, no status table and no weight, so the
+ * id lies outside SPX_NUM_PLUGINS (which sizes those per-plugin arrays, on the host and in the argmax kernels); bit 10 of a plugin
+ * mask is accepted by spx_eval, spx_eval_best, spx_decide and spx_fetch_prefilter. */
+#define SPX_PLUGIN_COSCHED 10
+#define SPX_NUM_PLUGIN_IDS 11
 
 /* fwk.Status codes (k8s.io/kube-scheduler/framework) */
 #define SPX_STATUS_SUCCESS 0
 #define SPX_STATUS_ERROR 1
 #define SPX_STATUS_UNSCHEDULABLE 2
+
+/* Coscheduling PreFilter status per pending pod (0 = Success), in the order PodGroupManager.PreFilter returns them
+ * (pkg/coscheduling/core/core.go:243-305) */
+#define SPX_COSCHED_ST_BACKED_OFF 1   /* the group is in backedOffPG                              :251-253 */
+#define SPX_COSCHED_ST_FEW_SIBLINGS 2 /* MinMember - listed pods > 0                              :262-266 */
+#define SPX_COSCHED_ST_GATED 3        /* MinMember - listed + gated > 0                           :270-277 */
+#define SPX_COSCHED_ST_RESOURCE_GAP 4 /* CheckClusterResource failed on MinResources + pods       :295-302 */
+#define SPX_COSCHED_MAX_SLOTS 16
 
 /* canonical resource ids; quantities are int64 in canonical units:
  * cpu = millicores (Quantity.MilliValue()), everything else = Quantity.Value() */
@@ -209,6 +222,48 @@ typedef struct spx_sysched_objects {
   const int32_t* res_ptr;
   const int32_t* res_set;
 } spx_sysched_objects;
+
+/* Coscheduling (pkg/coscheduling/core/core.go): what PodGroupManager.PreFilter and Coscheduling.Less read.
+ * Groups: one entry per PodGroup full name ("namespace/label value") that a pod of the snapshot carries or a PodGroup object has.
+ * g_ns / g_name are the caller's interned ids of the two halves (kept for the caller; the flatteners identify a group by its
+ * index).  g_exists = the PodGroup object exists (GetPodGroup's pg != nil, :392-402); the columns after it up to g_permitted
+ * are read only for such a group.  MinResources is the CSR g_res_ptr / g_res_id / g_res_qty in canonical units (cpu in milli,
+ * rounded up: spx_ingest_quantity(text, 1, ..)); an entry for SPX_RES_PODS is ignored, PreFilter overwrites it with MinMember
+ * (:296-297).  g_backed_off / g_permitted: the group is in backedOffPG / permittedPG now (TTL caches the control plane owns; the
+ * engine does not age them).  g_created_ns = PodGroup.CreationTimestamp, g_has_last_failed / g_last_failed_ns =
+ * lastFailedSchedulePG (:368-384; it is looked up by full name, so it may be set for a group that does not exist).
+ * g_listed = pods of the namespace that carry the label, pending and assigned (podLister, :255-257); g_gated = those of them with
+ * SchedulingGates.  pod_group[p] = pending pod p's group or -1 (no label).
+ * Assigned pods: node n hosts the entries a_ptr[n] .. a_ptr[n+1]; a_group = the entry's group or -1; its effective request
+ * (what NodeInfo.AddPod charged: max(sum of containers, init containers) + overhead) is the CSR a_req_ptr / a_req_res / a_req_qty.
+ * Every pod on the node must be listed: the node's Requested and its pod count are their sums.  node_present = Node() != nil. */
+typedef struct spx_cosched_objects {
+  int32_t n_groups;
+  const int32_t* g_ns;
+  const int32_t* g_name;
+  const uint8_t* g_exists;
+  const int32_t* g_min_member;
+  const uint8_t* g_has_min_resources;
+  const int32_t* g_res_ptr;
+  const int32_t* g_res_id;
+  const int64_t* g_res_qty;
+  const uint8_t* g_backed_off;
+  const uint8_t* g_permitted;
+  const int64_t* g_created_ns;
+  const uint8_t* g_has_last_failed;
+  const int64_t* g_last_failed_ns;
+  const int32_t* g_listed;
+  const int32_t* g_gated;
+  int64_t n_pods;
+  const int32_t* pod_group;
+  int64_t n_nodes;
+  const uint8_t* node_present;
+  const int32_t* a_ptr;
+  const int32_t* a_group;
+  const int32_t* a_req_ptr;
+  const int32_t* a_req_res;
+  const int64_t* a_req_qty;
+} spx_cosched_objects;
 
 /* NodeResourceTopology CR image per node plus the NRT cache's verdict for it
  * (pkg/noderesourcetopology/cache: GetCachedNRTCopy -> (nrt, CachedNRTInfo{Fresh})).
@@ -447,6 +502,38 @@ typedef struct spx_sysched_pods_soa {
   const int32_t* pod_set;
 } spx_sysched_pods_soa;
 
+/* Coscheduling.  CheckClusterResource (core.go:406-426) subtracts, node by node in list order, what getNodeResource (:433-467)
+ * leaves on the node once the group's own pods are removed, and deletes a resource for good the first time it is <= 0.  So with
+ * left_g[i][r] = left_base[r][i] + (what g's pods on node i requested, +1 pod each) and S_g,r[i] its prefix sum over the present
+ * nodes up to i, the check succeeds iff every named resource has a present node i with S_g,r[i] >= req_r.
+ * Slots: the resources any group's MinResources names plus SPX_RES_PODS, ascending id, at most SPX_COSCHED_MAX_SLOTS.
+ * left_base is slot-major [n_slots][n_nodes], 0 on a node that is not present or does not list the resource.  req [n_groups]
+ * [n_slots] with req_mask (bit s = slot s named; 0 for a group without MinResources or without a PodGroup object).  The steps of
+ * group g are step_ptr[g] .. step_ptr[g+1]: step_node strictly ascending present nodes, step_add [n_steps][n_slots] >= 0.
+ * Limits: for every slot, sum_i |left_base| + sum over all steps of step_add < 2^62, and |req| < 2^62 (spx_cosched_check). */
+typedef struct spx_cosched_soa {
+  int64_t n_nodes;
+  int32_t n_slots;
+  const int32_t* slot_res;
+  const int64_t* left_base;
+  const uint8_t* node_present;
+  int32_t n_groups;
+  const uint8_t* g_exists;
+  const int32_t* min_member;
+  const uint8_t* has_min_resources;
+  const uint8_t* backed_off;
+  const uint8_t* permitted;
+  const int32_t* listed;
+  const int32_t* gated;
+  const int64_t* req;
+  const uint32_t* req_mask;
+  const int32_t* step_ptr;
+  const int32_t* step_node;
+  const int64_t* step_add;
+  int64_t n_pods;
+  const int32_t* pod_group;
+} spx_cosched_soa;
+
 /* NodeResourceTopologyMatch.  Resources are renumbered into dense "slots" 0..n_res-1 (the union of
  * what pods request and zones report; slot_res gives the canonical id).  Limits of this build:
  * NUMA zones per node <= 8 (flatten fails beyond them).  The dense tables below (spx_nrt_nodes_soa,
@@ -682,6 +769,9 @@ typedef struct spx_net_commit_soa {
  *   spx_fetch_raw(NETOVERHEAD, cost/sat/vio)   NetworkOverhead.Score, PreFilterState   networkoverhead.go:362-386, :85-115
  *   spx_eval + spx_fetch_scores(NETOVERHEAD)   NetworkOverhead.NormalizeScore          networkoverhead.go:389-418
  *   spx_eval + spx_fetch_prefilter(CAPACITY)   CapacityScheduling.PreFilter            pkg/capacityscheduling/capacity_scheduling.go:208-283
+ *   spx_eval + spx_fetch_prefilter(COSCHED)    PodGroupManager.PreFilter               pkg/coscheduling/core/core.go:243-305
+ *   spx_fetch_cosched_gap                      CheckClusterResource, getNodeResource   core.go:406-426, :433-467 (the "resource gap" of the error text)
+ *   spx_cosched_less                           Coscheduling.Less, GetCreationTimestamp pkg/coscheduling/coscheduling.go:133-145, core.go:368-384
  *   spx_flatten_net_keys + spx_toposort_less   TopologicalSort.Less, FindPodOrder      pkg/networkaware/topologicalsort/topologicalsort.go:102-132, util/util.go:138-153
  *   spx_upload_sort_keys + spx_sort_keys       the activeQ ordering TopologicalSort.Less induces, as one device sort
  *   spx_flatten_trimaran_*                     GetNodeMetrics / ScheduledPodsCache / PredictUtilisation / GetResourceRequested
@@ -730,6 +820,13 @@ int spx_upload_peaks_pods(spx_engine* e, const spx_peaks_pods_soa* t);
  * whose largest possible score reaches SPX_SYSCHED_MAX_SCORE, a stale bit outside the names */
 int spx_upload_sysched_nodes(spx_engine* e, const spx_sysched_nodes_soa* t);
 int spx_upload_sysched_pods(spx_engine* e, const spx_sysched_pods_soa* t);
+/* Coscheduling tables (spx_flatten_cosched_*).  SPX_ERR_ARG: more than SPX_COSCHED_MAX_SLOTS slots, a group / node index out of range,
+ * steps that are not strictly ascending present nodes, a negative add-back, or a table spx_cosched_check refuses (the text names the
+ * slot).  Every upload marks the gate stale: the next spx_eval with the COSCHED bit scans and gates again. */
+int spx_upload_cosched(spx_engine* e, const spx_cosched_soa* t);
+/* the limits of the device's int64 sums (the reference falls into inf.Dec there): SPX_ERR_ARG and *bad_slot = the first slot whose
+ * sum_i |left_base| + (all add-backs) reaches 2^62, or that holds a request with |req| >= 2^62; SPX_OK and -1 otherwise.  Host only. */
+int spx_cosched_check(const spx_cosched_soa* t, int32_t* bad_slot);
 /* Snapshot deltas (SURVEY 8d "upload deltas"): `t` holds t->n_nodes ROWS in the layout of the full upload; row i replaces node
  * idx[i] of the table already on the device (spx_upload_* must have run once: it fixes the shape).  The changed rows travel as one
  * staged blob and are scattered into the device columns; for NRT the float64 formulation's derived columns are recomputed on the
@@ -784,6 +881,13 @@ int spx_upload_sort_keys(spx_engine* e, const spx_sort_keys_soa* t);
 int spx_sort_keys(spx_engine* e, int32_t* perm_out);
 /* CapacityScheduling.PreFilter status per pod (n_pods bytes: 0 Success, SPX_QUOTA_ST_*); valid after spx_eval with the CAPACITY bit */
 int spx_fetch_prefilter(spx_engine* e, int plugin, int64_t row_begin, int64_t row_end, uint8_t* out);
+/* with plugin == SPX_PLUGIN_COSCHED the same call returns PodGroupManager.PreFilter's status per pod (0 Success, SPX_COSCHED_ST_*),
+ * valid after spx_eval with the COSCHED bit.  With that bit in the mask of spx_eval_best or spx_decide, a pod whose gate failed
+ * reads back through spx_fetch_best as node -1 / score 0 / 0 ties / 0 feasible, as a pod failing CapacityScheduling's does.
+ * spx_fetch_cosched_gap: CheckClusterResource per group [group_begin, group_end) of the last evaluation, whatever permittedPG says:
+ * pass_mask bit s = named slot s closed, open_mask bit s = named slot s still open after the last node, gap [groups][n_slots] =
+ * req - S_g[last present node] for an open slot (what the reference's "resource gap" lists), 0 otherwise. */
+int spx_fetch_cosched_gap(spx_engine* e, int32_t group_begin, int32_t group_end, uint32_t* pass_mask, uint32_t* open_mask, int64_t* gap);
 
 /* optional per-(pod,node) feasibility mask for normalizing score plugins: uint8 [n_pods][n_nodes],
  * non-zero = node passed Filter for that pod (upstream scores feasible nodes only).  NULL clears it. */
@@ -1056,6 +1160,8 @@ int spx_nrt_packed_score_slots(const spx_engine* e);
  * same 64-bit arithmetic there, and the value stays 2.
  * SPX_PLUGIN_SYSCHED has one formulation; for it the call reports how many chunks of distinct sets the last SySched sweep of
  * spx_eval built its raw table in (the table is scratch bounded at 256 MiB, kernels_sysched.hip), 0 before the first sweep. */
+/* SPX_PLUGIN_COSCHED: how many groups of the last evaluation of the gate took the walk (the groups with assigned pods: a workgroup
+ * each over the nodes, kernels_cosched.hip); the others read their slots' overall maxima. */
 int spx_kernel_path(const spx_engine* e, int plugin);
 
 /* make the engine write a Filter plugin's status table (NRT, NETOVERHEAD) into caller-owned device memory; row_stride must be
@@ -1172,6 +1278,19 @@ int spx_flatten_net_topo(const spx_nettopo_objects* nt, int32_t* region_cost, in
 int spx_flatten_net_topo_wide(const spx_nettopo_objects* nt, int64_t* region_cost, int64_t* zone_cost);
 int spx_flatten_net_keys(const spx_pod_objects* pods, const spx_appgroup_objects* ag, int32_t* n_keys_out, int64_t* n_pairs_out, int32_t* pod_key, int32_t* topo_order, uint8_t* key_score_equally, int32_t* pair_ptr, int32_t* pair_node, int64_t* pair_max_cost);
 /* TopologicalSort.Less (topologicalsort.go:102-132) for n pairs of pod indices, from the flattened keys */
+/* Coscheduling.Less over pairs (coscheduling.go:133-145): priority descending, then GetCreationTimestamp (the group's last failure
+ * time if recorded, else the PodGroup's creation time if the object exists, else the pod's initial-attempt timestamp; a pod without
+ * a label: that timestamp), then the pods' "namespace/name" as strings: key i is the bytes key_bytes[key_ptr[i] .. key_ptr[i+1]).
+ * pod_group comes from `o` (o->n_pods entries); a[i], b[i] index pods; less_out[i] = Less(a[i], b[i]).  Host only. */
+int spx_cosched_less(const spx_cosched_objects* o, const int32_t* priority, const int64_t* initial_attempt_ns, const int64_t* key_ptr, const uint8_t* key_bytes, int64_t n_pairs, const int64_t* a, const int64_t* b, uint8_t* less_out);
+/* Coscheduling flatteners.  _slots: slot_res [SPX_COSCHED_MAX_SLOTS], *n_slots_out is written even when it exceeds the cap (SPX_ERR_ARG).
+ * _nodes: left_base [n_slots][N], node_present [N] (nodes->n_nodes must equal o->n_nodes).  _groups: *n_steps_out is written first;
+ * with step_node and step_add NULL the call only counts; otherwise req [G][n_slots], req_mask [G], step_ptr [G+1], step_node
+ * [step_cap], step_add [step_cap][n_slots].  An add-back on a node that does not list the resource is 0, as getNodeResource's
+ * left-over is (:457-464); assigned pods on a node that is not present are skipped with the node (:408-410). */
+int spx_flatten_cosched_slots(const spx_cosched_objects* o, int32_t* n_slots_out, int32_t* slot_res);
+int spx_flatten_cosched_nodes(const spx_node_objects* nodes, const spx_cosched_objects* o, int32_t n_slots, const int32_t* slot_res, int64_t* left_base, uint8_t* node_present);
+int spx_flatten_cosched_groups(const spx_node_objects* nodes, const spx_cosched_objects* o, int32_t n_slots, const int32_t* slot_res, int64_t step_cap, int64_t* n_steps_out, int64_t* req, uint32_t* req_mask, int32_t* step_ptr, int32_t* step_node, int64_t* step_add);
 int spx_toposort_less(const spx_pod_objects* pods, const int32_t* topo_order, int64_t n_pairs, const int64_t* a, const int64_t* b, uint8_t* less_out);
 /* spx_net_commit_soa columns: *n_entries_out first (NULL arrays), then eff_ptr[P+1], eff_key / eff_max_cost[n_entries] */
 int spx_flatten_net_commit(const spx_pod_objects* pods, const spx_appgroup_objects* ag, int64_t* n_entries_out, int32_t* eff_ptr, int32_t* eff_key, int64_t* eff_max_cost);

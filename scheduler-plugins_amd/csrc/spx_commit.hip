@@ -438,6 +438,9 @@ int spx_commit_sequential(spx_engine* e, uint32_t plugin_mask, int64_t row_begin
   const uint32_t allowed = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_TLP) | (1u << SPX_PLUGIN_LVRB);
   const uint32_t with_filters = allowed | (1u << SPX_PLUGIN_NRT) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY);
   const uint32_t scorers = (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS);  // carried by the per-pod route only
+  if (plugin_mask & (1u << SPX_PLUGIN_COSCHED))
+    return fail(e, SPX_ERR_ARG, "spx_commit_sequential does not carry Coscheduling: Permit and the waiting-pod set are control-plane state, and a gang's "
+                                "roll-back is not part of the loop");
   if (plugin_mask == 0 || (plugin_mask & ~(with_filters | scorers)))
     return fail(e, SPX_ERR_ARG, "spx_commit_sequential supports Allocatable / TargetLoadPacking / LoadVariationRiskBalancing / NodeResourceTopologyMatch / "
                                 "NetworkOverhead / CapacityScheduling");

@@ -124,6 +124,15 @@ struct spx_engine {
   int64_t sy_n_dups = 0, sy_n_tasks = 0;
   int sy_last_chunks = 0;  // spx_kernel_path(SYSCHED)
 
+  // Coscheduling: the snapshot's left-overs and their scan, the groups' requests / steps / flags, the verdicts and the pods' status.
+  // cs_gate_valid: scan and gate hold for the tables in place (any upload clears it); cs_rows: the pod rows whose status is current
+  DevBuf d_cs_left, d_cs_present, d_cs_prefix, d_cs_smax, d_cs_stotal, d_cs_any, d_cs_req, d_cs_mask, d_cs_sptr, d_cs_snode, d_cs_scum, d_cs_walk;
+  DevBuf d_cs_pass, d_cs_open, d_cs_gap, d_cs_exists, d_cs_minm, d_cs_hasres, d_cs_backoff, d_cs_permit, d_cs_listed, d_cs_gated, d_cs_pod_group, d_cs_status;
+  bool cosched = false, cs_gate_valid = false;
+  int32_t cs_n_slots = 0, cs_n_groups = 0, cs_n_walk = 0;
+  int cs_last_walk = 0;  // spx_kernel_path(COSCHED)
+  int64_t cs_row_begin = 0, cs_row_end = 0;
+
   // NodeResourceTopologyMatch
   spx_nrt_params nrt_params{SPX_NRT_LEAST_ALLOCATED, 0, nullptr, nullptr};  // defaults.go:87-90
   int32_t nrt_n_res = 0;
@@ -549,6 +558,37 @@ void fill_sysched(const spx_engine* e, spx::SyschedArgs& a) {
   a.set_first = static_cast<const int32_t*>(e->d_sy_first.p);
   a.raw = static_cast<int32_t*>(e->d_sy_raw.p);
   a.set_max = static_cast<int32_t*>(e->d_sy_max.p);
+}
+
+void fill_cosched(const spx_engine* e, spx::CoschedArgs& a) {
+  a.n_nodes = e->n_nodes;
+  a.n_slots = e->cs_n_slots;
+  a.n_groups = e->cs_n_groups;
+  a.n_walk = e->cs_n_walk;
+  a.left_base = static_cast<const int64_t*>(e->d_cs_left.p);
+  a.node_present = static_cast<const uint8_t*>(e->d_cs_present.p);
+  a.prefix = static_cast<int64_t*>(e->d_cs_prefix.p);
+  a.slot_max = static_cast<int64_t*>(e->d_cs_smax.p);
+  a.slot_total = static_cast<int64_t*>(e->d_cs_stotal.p);
+  a.any_present = static_cast<int32_t*>(e->d_cs_any.p);
+  a.req = static_cast<const int64_t*>(e->d_cs_req.p);
+  a.req_mask = static_cast<const uint32_t*>(e->d_cs_mask.p);
+  a.step_ptr = static_cast<const int32_t*>(e->d_cs_sptr.p);
+  a.step_node = static_cast<const int32_t*>(e->d_cs_snode.p);
+  a.step_cum = static_cast<const int64_t*>(e->d_cs_scum.p);
+  a.walk_group = static_cast<const int32_t*>(e->d_cs_walk.p);
+  a.pass_mask = static_cast<uint32_t*>(e->d_cs_pass.p);
+  a.open_mask = static_cast<uint32_t*>(e->d_cs_open.p);
+  a.gap = static_cast<int64_t*>(e->d_cs_gap.p);
+  a.g_exists = static_cast<const uint8_t*>(e->d_cs_exists.p);
+  a.min_member = static_cast<const int32_t*>(e->d_cs_minm.p);
+  a.has_min_resources = static_cast<const uint8_t*>(e->d_cs_hasres.p);
+  a.backed_off = static_cast<const uint8_t*>(e->d_cs_backoff.p);
+  a.permitted = static_cast<const uint8_t*>(e->d_cs_permit.p);
+  a.listed = static_cast<const int32_t*>(e->d_cs_listed.p);
+  a.gated = static_cast<const int32_t*>(e->d_cs_gated.p);
+  a.pod_group = static_cast<const int32_t*>(e->d_cs_pod_group.p);
+  a.out_status = static_cast<uint8_t*>(e->d_cs_status.p);
 }
 
 void fill_trimaran(const spx_engine* e, spx::TrimaranArgs& a) {

@@ -80,7 +80,10 @@ int spx_destroy(spx_engine* e) {
                     &e->d_nrtw_avail, &e->d_nrtw_cost, &e->d_nrtw_minavg, &e->d_nrtw_np, &e->d_nrtw_qos, &e->d_nrtw_nn, &e->d_nrtw_rptr,
                     &e->d_nrtw_rslot, &e->d_nrtw_rqty, &e->d_nrtw_cptr, &e->d_nrtw_ckind, &e->d_nrtw_eptr, &e->d_nrtw_eslot, &e->d_nrtw_eqty,
                     &e->d_sy_host, &e->d_sy_present, &e->d_sy_k, &e->d_sy_a, &e->d_sy_sptr, &e->d_sy_sbit, &e->d_sy_scnt, &e->d_sy_sets, &e->d_sy_empty,
-                    &e->d_sy_pod_set, &e->d_sy_order, &e->d_sy_first, &e->d_sy_dups, &e->d_sy_raw, &e->d_sy_max};
+                    &e->d_sy_pod_set, &e->d_sy_order, &e->d_sy_first, &e->d_sy_dups, &e->d_sy_raw, &e->d_sy_max,
+                    &e->d_cs_left, &e->d_cs_present, &e->d_cs_prefix, &e->d_cs_smax, &e->d_cs_stotal, &e->d_cs_any, &e->d_cs_req, &e->d_cs_mask, &e->d_cs_sptr,
+                    &e->d_cs_snode, &e->d_cs_scum, &e->d_cs_walk, &e->d_cs_pass, &e->d_cs_open, &e->d_cs_gap, &e->d_cs_exists, &e->d_cs_minm, &e->d_cs_hasres,
+                    &e->d_cs_backoff, &e->d_cs_permit, &e->d_cs_listed, &e->d_cs_gated, &e->d_cs_pod_group, &e->d_cs_status};
   for (DevBuf* b : bufs)
     if (b->p && !b->external) (void)hipFree(b->p);
   for (int i = 0; i < SPX_NUM_PLUGINS; ++i) {
@@ -227,7 +230,7 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   SPX_HIP(e, hipSetDevice(e->device));
   const uint32_t known = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_TLP) | (1u << SPX_PLUGIN_LVRB) | (1u << SPX_PLUGIN_NRT) |
                          (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY) | (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS) |
-                         (1u << SPX_PLUGIN_SYSCHED);
+                         (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_COSCHED);
   if (plugin_mask == 0 || (plugin_mask & ~known)) return fail(e, SPX_ERR_ARG, "plugin mask has unsupported bits");
   const bool R = plugin_mask & (1u << SPX_PLUGIN_LROC);
   if (R && !(e->tri_nodes && e->lroc_nodes && e->lroc_pods)) return fail(e, SPX_ERR_STATE, "LowRiskOverCommitment node/pod tables not uploaded");
@@ -237,6 +240,9 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   if (Y && !(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
   if (Y && e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
   if (Y && e->row_indirect) return fail(e, SPX_ERR_STATE, "SySched is not part of the sequential commit loop");
+  const bool G = plugin_mask & (1u << SPX_PLUGIN_COSCHED);
+  if (G && !e->cosched) return fail(e, SPX_ERR_STATE, "Coscheduling tables not uploaded");
+  if (G && e->row_indirect) return fail(e, SPX_ERR_STATE, "Coscheduling is not part of the sequential commit loop");
   const bool Q = plugin_mask & (1u << SPX_PLUGIN_CAPACITY);
   if (Q && !e->quota) return fail(e, SPX_ERR_STATE, "CapacityScheduling quota tables not uploaded");
   if (e->n_nodes <= 0 && plugin_mask != (1u << SPX_PLUGIN_CAPACITY)) return fail(e, SPX_ERR_STATE, "no node table uploaded");
@@ -368,6 +374,26 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     qa.out_status = static_cast<uint8_t*>(e->d_q_status.p);
     spx::launch_quota(qa, e->stream);
     SPX_HIP(e, hipGetLastError());
+  }
+  if (G) {  // the PodGroup gate: per snapshot the scan and the groups' verdicts (until the next upload), per call the rows' status bytes
+    spx::CoschedArgs ga{};
+    fill_cosched(e, ga);
+    ga.row_begin = row_begin;
+    ga.row_end = row_end;
+    if (!e->cs_gate_valid) {
+      spx::launch_cosched_gate(ga, e->stream);
+      e->cs_gate_valid = true;
+      e->cs_last_walk = e->cs_n_walk;
+      e->cs_row_begin = e->cs_row_end = 0;
+    }
+    spx::launch_cosched_status(ga, e->stream);
+    SPX_HIP(e, hipGetLastError());
+    if (row_end > row_begin) {
+      if (e->cs_row_end > e->cs_row_begin && row_begin <= e->cs_row_end && row_end >= e->cs_row_begin)
+        e->cs_row_begin = std::min(e->cs_row_begin, row_begin), e->cs_row_end = std::max(e->cs_row_end, row_end);
+      else
+        e->cs_row_begin = row_begin, e->cs_row_end = row_end;
+    }
   }
   if (N && e->nrt_wide) {  // the wide tables: one sparse launch over the row range (kernels_nrt_wide.hip)
     if (e->score_stride[SPX_PLUGIN_NRT] != e->row_stride)
@@ -714,6 +740,7 @@ int spx_kernel_path(const spx_engine* e, int plugin) {
     return lroc_f32_ok(e) ? 1 : 0;
   }
   if (plugin == SPX_PLUGIN_SYSCHED) return e->sy_last_chunks;
+  if (plugin == SPX_PLUGIN_COSCHED) return e->cs_last_walk;
   if (plugin == SPX_PLUGIN_TLP) return (e->tlp.target_utilization >= 1 && e->tlp.target_utilization <= 99 && !(launch_opts(e) & spx::kOptTrimaranExact)) ? 1 : 0;
   return 0;
 }
@@ -1094,6 +1121,10 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
       return fail(e, SPX_ERR_STATE, "spx_eval_best: a normalising plugin (Allocatable / NetworkOverhead / Peaks / SySched) was evaluated under a different Filter set "
                                     "or feasibility mask than this argmax uses; evaluate the whole profile in one spx_eval");
   }
+  const bool gate = plugin_mask & (1u << SPX_PLUGIN_COSCHED);
+  if (gate && row_end > row_begin && (!e->cs_gate_valid || row_begin < e->cs_row_begin || row_end > e->cs_row_end))
+    return fail(e, SPX_ERR_STATE, "spx_eval_best: Coscheduling's gate has not been evaluated for these rows since its last upload");
+  if (gate && e->row_indirect) return fail(e, SPX_ERR_STATE, "Coscheduling is not part of the sequential commit loop");
   const size_t P = static_cast<size_t>(e->n_pods);
   if ((rc = ensure(e, e->d_best, P * 20))) return rc;
   spx::ProfileArgs pa{};
@@ -1119,14 +1150,39 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
   pa.best_ties = pa.best_node + P;
   pa.best_feasible = pa.best_ties + P;
   spx::launch_best(pa, e->stream);
+  if (gate) spx::launch_cosched_unschedulable(static_cast<const uint8_t*>(e->d_cs_status.p), row_begin, row_end, pa.best_score, pa.best_node, pa.best_ties, pa.best_feasible, e->stream);
   SPX_HIP(e, hipGetLastError());
   e->best_valid = true;
   return SPX_OK;
 }
 
-int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end) {
+}  // extern "C"
+
+namespace {
+int decide_profile(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end);
+}
+
+extern "C" int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end) {
   if (!e) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
+  const uint32_t C = 1u << SPX_PLUGIN_COSCHED;
+  if (!(plugin_mask & C)) return decide_profile(e, plugin_mask, row_begin, row_end);
+  // Coscheduling's gate is a PreFilter: it is evaluated on its own, the rest of the profile decides as it would without it, and the
+  // rows of the pods it turned away are overwritten (the argmax kernels are the ones of a profile without the bit)
+  if ((plugin_mask & ~C) == 0) return fail(e, SPX_ERR_ARG, "spx_decide: Coscheduling alone scores nothing");
+  int rc;
+  if ((rc = spx_eval(e, C, row_begin, row_end))) return rc;
+  if ((rc = decide_profile(e, plugin_mask & ~C, row_begin, row_end))) return rc;
+  const size_t P = static_cast<size_t>(e->n_pods);
+  int64_t* bs = static_cast<int64_t*>(e->d_best.p);
+  int32_t* bn = reinterpret_cast<int32_t*>(bs + P);
+  spx::launch_cosched_unschedulable(static_cast<const uint8_t*>(e->d_cs_status.p), row_begin, row_end, bs, bn, bn + P, bn + 2 * P, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+namespace {
+int decide_profile(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end) {
   const uint32_t A = 1u << SPX_PLUGIN_ALLOCATABLE, T = 1u << SPX_PLUGIN_TLP;
   // Score-only plugins whose tables the fused sweep can fold in: no Filter, and their bytes are final once evaluated
   // (Peaks normalises inside its own sweep)
@@ -1196,6 +1252,9 @@ int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t r
   e->best_valid = true;
   return SPX_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int spx_fetch_best(spx_engine* e, int64_t row_begin, int64_t row_end, int32_t* node_idx, int64_t* weighted_score, int32_t* n_ties,
                    int32_t* n_feasible) {

@@ -268,6 +268,45 @@ void launch_sysched_norm(const SyschedArgs& a, hipStream_t s);
 // a workgroup per pod of the chunk's sets (n_listed of them, consecutive in `order`)
 void launch_sysched_rows(const SyschedArgs& a, int64_t n_listed, hipStream_t s);
 
+// ---------------------------------------------------------------- Coscheduling (kernels_cosched.hip)
+struct CoschedArgs {
+  int64_t n_nodes;
+  int32_t n_slots;
+  int32_t n_groups;
+  int32_t n_walk;                    // groups with assigned pods
+  const int64_t* left_base;          // [n_slots][N]
+  const uint8_t* node_present;       // [N]
+  int64_t* prefix;                   // [n_slots][N] S_base: inclusive prefix sums over the present nodes
+  int64_t* slot_max;                 // [n_slots] max of S_base over the present nodes
+  int64_t* slot_total;               // [n_slots] S_base at the last node
+  int32_t* any_present;              // [1]
+  const int64_t* req;                // [G][n_slots]
+  const uint32_t* req_mask;          // [G]
+  const int32_t* step_ptr;           // [G+1]
+  const int32_t* step_node;          // strictly ascending present nodes per group
+  const int64_t* step_cum;           // [n_steps][n_slots] add-backs summed over the group's steps up to this one
+  const int32_t* walk_group;         // [n_walk]
+  uint32_t* pass_mask;               // [G]
+  uint32_t* open_mask;               // [G]
+  int64_t* gap;                      // [G][n_slots]
+  const uint8_t* g_exists;           // [G] ...
+  const int32_t* min_member;
+  const uint8_t* has_min_resources;
+  const uint8_t* backed_off;
+  const uint8_t* permitted;
+  const int32_t* listed;
+  const int32_t* gated;
+  const int32_t* pod_group;          // [P]
+  int64_t row_begin, row_end;
+  uint8_t* out_status;               // [P]
+};
+// scan + both gate kernels (the whole snapshot), then the pods' status bytes of a row range
+void launch_cosched_gate(const CoschedArgs& a, hipStream_t s);
+void launch_cosched_status(const CoschedArgs& a, hipStream_t s);
+// decision rows (spx_fetch_best's block) of the pods whose status is not 0: node -1, score / ties / feasible 0
+void launch_cosched_unschedulable(const uint8_t* status, int64_t row_begin, int64_t row_end, int64_t* best_score, int32_t* best_node, int32_t* best_ties,
+                                  int32_t* best_feasible, hipStream_t s);
+
 // ---------------------------------------------------------------- NodeResourceTopologyMatch
 struct NrtArgs {
   uint32_t opts;

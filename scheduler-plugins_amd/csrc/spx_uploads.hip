@@ -676,6 +676,83 @@ int spx_upload_sysched_pods(spx_engine* e, const spx_sysched_pods_soa* t) {
   return SPX_OK;
 }
 
+int spx_upload_cosched(spx_engine* e, const spx_cosched_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (t->n_slots < 1 || t->n_slots > SPX_COSCHED_MAX_SLOTS || !t->slot_res) return fail(e, SPX_ERR_ARG, "Coscheduling: n_slots must be in [1, SPX_COSCHED_MAX_SLOTS]");
+  if (t->n_groups < 0 || t->n_nodes <= 0 || t->n_pods <= 0 || !t->left_base || !t->node_present || !t->pod_group) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  const size_t N = static_cast<size_t>(t->n_nodes), G = static_cast<size_t>(t->n_groups), P = static_cast<size_t>(t->n_pods), S = static_cast<size_t>(t->n_slots);
+  if (G && (!t->g_exists || !t->min_member || !t->has_min_resources || !t->backed_off || !t->permitted || !t->listed || !t->gated || !t->req || !t->req_mask || !t->step_ptr))
+    return fail(e, SPX_ERR_ARG, "NULL column in table");
+  for (size_t p = 0; p < P; ++p)
+    if (t->pod_group[p] < -1 || t->pod_group[p] >= t->n_groups) return fail(e, SPX_ERR_ARG, "Coscheduling: pod_group out of range");
+  // the steps: strictly ascending present nodes per group, non-negative add-backs; summed per group on the way (the walk reads the
+  // add-backs of every step up to a node as one number)
+  const int32_t zero_ptr[1] = {0};
+  const int32_t* sptr = G ? t->step_ptr : zero_ptr;
+  if (sptr[0] != 0) return fail(e, SPX_ERR_ARG, "Coscheduling: step_ptr must start at 0");
+  const size_t n_steps = static_cast<size_t>(sptr[G]);
+  if (n_steps && (!t->step_node || !t->step_add)) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  std::vector<int32_t> walk;
+  for (size_t g = 0; g < G; ++g) {
+    if (sptr[g + 1] < sptr[g]) return fail(e, SPX_ERR_ARG, "Coscheduling: step_ptr is not monotone");
+    if (t->req_mask[g] >> S) return fail(e, SPX_ERR_ARG, "Coscheduling: req_mask names a slot beyond n_slots");
+    if (sptr[g + 1] > sptr[g]) walk.push_back(static_cast<int32_t>(g));
+    for (int32_t k = sptr[g]; k < sptr[g + 1]; ++k) {
+      const int32_t node = t->step_node[k];
+      if (node < 0 || static_cast<size_t>(node) >= N || !t->node_present[node] || (k > sptr[g] && node <= t->step_node[k - 1]))
+        return fail(e, SPX_ERR_ARG, "Coscheduling: a group's steps must be strictly ascending present nodes");
+      for (size_t r = 0; r < S; ++r)
+        if (t->step_add[static_cast<size_t>(k) * S + r] < 0) return fail(e, SPX_ERR_ARG, "Coscheduling: negative add-back");
+    }
+  }
+  int32_t bad_slot = -1;
+  if (spx_cosched_check(t, &bad_slot) != SPX_OK)
+    return fail(e, SPX_ERR_ARG, "Coscheduling: slot " + std::to_string(bad_slot) + " (resource id " + std::to_string(bad_slot >= 0 ? t->slot_res[bad_slot] : -1) +
+                                    "): the left-overs and add-backs sum to 2^62 or more, or a request does; the device sums are int64");
+  std::vector<int64_t> cum(n_steps * S + 1, 0);
+  for (size_t g = 0; g < G; ++g)
+    for (int32_t k = sptr[g]; k < sptr[g + 1]; ++k)
+      for (size_t r = 0; r < S; ++r)
+        cum[static_cast<size_t>(k) * S + r] = t->step_add[static_cast<size_t>(k) * S + r] + (k > sptr[g] ? cum[static_cast<size_t>(k - 1) * S + r] : 0);
+  int rc = set_nodes(e, t->n_nodes);
+  if (rc) return rc;
+  if ((rc = set_pods(e, t->n_pods))) return rc;
+  e->cosched = e->cs_gate_valid = false;
+  e->evaluated &= ~(1u << SPX_PLUGIN_COSCHED);
+  e->best_valid = false;
+  e->cs_row_begin = e->cs_row_end = 0;
+  if ((rc = upload(e, e->d_cs_left, t->left_base, S * N * 8)) || (rc = upload(e, e->d_cs_present, t->node_present, N)) || (rc = ensure(e, e->d_cs_prefix, S * N * 8)) ||
+      (rc = ensure(e, e->d_cs_smax, S * 8)) || (rc = ensure(e, e->d_cs_stotal, S * 8)) || (rc = ensure(e, e->d_cs_any, 4)) || (rc = upload(e, e->d_cs_req, t->req, G * S * 8)) ||
+      (rc = upload(e, e->d_cs_mask, t->req_mask, G * 4)) || (rc = upload(e, e->d_cs_sptr, sptr, (G + 1) * 4)) || (rc = upload(e, e->d_cs_snode, t->step_node, n_steps * 4)) ||
+      (rc = upload(e, e->d_cs_scum, cum.data(), n_steps * S * 8)) || (rc = upload(e, e->d_cs_walk, walk.data(), walk.size() * 4)) || (rc = ensure(e, e->d_cs_pass, G * 4)) ||
+      (rc = ensure(e, e->d_cs_open, G * 4)) || (rc = ensure(e, e->d_cs_gap, G * S * 8)) || (rc = upload(e, e->d_cs_exists, t->g_exists, G)) ||
+      (rc = upload(e, e->d_cs_minm, t->min_member, G * 4)) || (rc = upload(e, e->d_cs_hasres, t->has_min_resources, G)) || (rc = upload(e, e->d_cs_backoff, t->backed_off, G)) ||
+      (rc = upload(e, e->d_cs_permit, t->permitted, G)) || (rc = upload(e, e->d_cs_listed, t->listed, G * 4)) || (rc = upload(e, e->d_cs_gated, t->gated, G * 4)) ||
+      (rc = upload(e, e->d_cs_pod_group, t->pod_group, P * 4)) || (rc = ensure(e, e->d_cs_status, P)))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // the host columns are only borrowed for the call
+  e->cs_n_slots = t->n_slots;
+  e->cs_n_groups = t->n_groups;
+  e->cs_n_walk = static_cast<int32_t>(walk.size());
+  e->cosched = true;
+  return SPX_OK;
+}
+
+int spx_fetch_cosched_gap(spx_engine* e, int32_t group_begin, int32_t group_end, uint32_t* pass_mask, uint32_t* open_mask, int64_t* gap) {
+  if (!e) return SPX_ERR_ARG;
+  if (!e->cosched || !e->cs_gate_valid) return fail(e, SPX_ERR_STATE, "Coscheduling's gate has not been evaluated since its last upload");
+  if (group_begin < 0 || group_end > e->cs_n_groups || group_begin > group_end) return fail(e, SPX_ERR_ARG, "group range out of bounds");
+  SPX_HIP(e, hipSetDevice(e->device));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  const size_t n = static_cast<size_t>(group_end - group_begin), S = static_cast<size_t>(e->cs_n_slots);
+  if (n == 0) return SPX_OK;
+  if (pass_mask) SPX_HIP(e, hipMemcpy(pass_mask, static_cast<const uint32_t*>(e->d_cs_pass.p) + group_begin, n * 4, hipMemcpyDeviceToHost));
+  if (open_mask) SPX_HIP(e, hipMemcpy(open_mask, static_cast<const uint32_t*>(e->d_cs_open.p) + group_begin, n * 4, hipMemcpyDeviceToHost));
+  if (gap) SPX_HIP(e, hipMemcpy(gap, static_cast<const int64_t*>(e->d_cs_gap.p) + static_cast<size_t>(group_begin) * S, n * S * 8, hipMemcpyDeviceToHost));
+  return SPX_OK;
+}
+
 int spx_upload_trimaran_pods(spx_engine* e, const spx_trimaran_pods_soa* t) {
   if (!e || !t) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
@@ -1383,6 +1460,18 @@ int spx_upload_quota(spx_engine* e, const spx_quota_soa* t) {
 
 int spx_fetch_prefilter(spx_engine* e, int plugin, int64_t row_begin, int64_t row_end, uint8_t* out) {
   if (!e || !out) return SPX_ERR_ARG;
+  if (plugin == SPX_PLUGIN_COSCHED) {
+    if (!e->cosched || !e->cs_gate_valid || !(e->evaluated & (1u << SPX_PLUGIN_COSCHED)))
+      return fail(e, SPX_ERR_STATE, "Coscheduling's PreFilter has not been evaluated since its last upload");
+    if (row_begin < 0 || row_end > e->n_pods || row_begin > row_end) return fail(e, SPX_ERR_ARG, "row range out of bounds");
+    if (row_end > row_begin && (row_begin < e->cs_row_begin || row_end > e->cs_row_end))
+      return fail(e, SPX_ERR_STATE, "rows requested have not been evaluated for this plugin (spx_eval covers [" + std::to_string(e->cs_row_begin) + ", " +
+                                        std::to_string(e->cs_row_end) + "))");
+    SPX_HIP(e, hipSetDevice(e->device));
+    SPX_HIP(e, hipStreamSynchronize(e->stream));
+    SPX_HIP(e, hipMemcpy(out, static_cast<const uint8_t*>(e->d_cs_status.p) + row_begin, static_cast<size_t>(row_end - row_begin), hipMemcpyDeviceToHost));
+    return SPX_OK;
+  }
   if (plugin != SPX_PLUGIN_CAPACITY || !(e->evaluated & (1u << SPX_PLUGIN_CAPACITY)))
     return fail(e, SPX_ERR_STATE, "CapacityScheduling.PreFilter has not been evaluated");
   if (row_begin < 0 || row_end > e->n_pods || row_begin > row_end) return fail(e, SPX_ERR_ARG, "row range out of bounds");

@@ -20,6 +20,8 @@ PLUGINS = {
 }
 ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, TOPOSORT, LROC, PEAKS, SYSCHED = range(10)
 NUM_PLUGINS = 10  # SPX_NUM_PLUGINS
+COSCHED = 10  # SPX_PLUGIN_COSCHED: a PreFilter gate without tables or a weight, outside NUM_PLUGINS
+COSCHED_ST = {"BACKED_OFF": 1, "FEW_SIBLINGS": 2, "GATED": 3, "RESOURCE_GAP": 4}  # SPX_COSCHED_ST_*
 
 
 def mask_of(*plugins: int) -> int:
@@ -408,6 +410,79 @@ class Engine:
         """flatten + upload both SySched tables in one call (spx_load_sysched)"""
         self._ck(self._lib.spx_load_sysched(self._h, objects.ref()))
         self.n_nodes, self.n_pods = objects.struct.n_nodes, objects.struct.n_pods
+
+    # ------------------------------------------------------------------ Coscheduling
+    def flatten_cosched(self, nodes: Table, objects: Table) -> dict:
+        """spx_node_objects + spx_cosched_objects -> the columns of spx_cosched_soa (spx_flatten_cosched_slots / _nodes / _groups)"""
+        L, o = self._lib, objects.struct
+        N, G, P = int(o.n_nodes), int(o.n_groups), int(o.n_pods)
+        n_slots, slot_res = C.c_int32(), np.zeros(self._hdr.consts["SPX_COSCHED_MAX_SLOTS"], np.int32)
+        i32, i64, u8, u32 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+        self._ck_static(L.spx_flatten_cosched_slots(objects.ref(), C.byref(n_slots), slot_res.ctypes.data_as(i32)))
+        S = int(n_slots.value)
+        left, present = np.zeros((S, max(N, 1)), np.int64), np.zeros(max(N, 1), np.uint8)
+        self._ck_static(L.spx_flatten_cosched_nodes(nodes.ref(), objects.ref(), S, slot_res.ctypes.data_as(i32), left.ctypes.data_as(i64), present.ctypes.data_as(u8)))
+        n_steps = C.c_int64()
+        self._ck_static(L.spx_flatten_cosched_groups(nodes.ref(), objects.ref(), S, slot_res.ctypes.data_as(i32), 0, C.byref(n_steps), None, None, None, None, None))
+        K = int(n_steps.value)
+        req, mask, sptr = np.zeros((max(G, 1), S), np.int64), np.zeros(max(G, 1), np.uint32), np.zeros(G + 1, np.int32)
+        snode, sadd = np.zeros(max(K, 1), np.int32), np.zeros((max(K, 1), S), np.int64)
+        self._ck_static(L.spx_flatten_cosched_groups(nodes.ref(), objects.ref(), S, slot_res.ctypes.data_as(i32), K, C.byref(n_steps), req.ctypes.data_as(i64),
+                                                     mask.ctypes.data_as(u32), sptr.ctypes.data_as(i32), snode.ctypes.data_as(i32), sadd.ctypes.data_as(i64)))
+        g = lambda k: objects.array(k)[:G] if G else np.zeros(0, objects.array(k).dtype)
+        return {"N": N, "G": G, "P": P, "S": S, "slot_res": slot_res[:S].copy(), "left_base": left[:, :N], "node_present": present[:N],
+                "g_exists": g("g_exists"), "min_member": g("g_min_member"), "has_min_resources": g("g_has_min_resources"), "backed_off": g("g_backed_off"),
+                "permitted": g("g_permitted"), "listed": g("g_listed"), "gated": g("g_gated"), "req": req[:G], "req_mask": mask[:G], "step_ptr": sptr,
+                "step_node": snode[:K], "step_add": sadd[:K], "pod_group": objects.array("pod_group")[:P]}
+
+    def cosched_table(self, f: dict) -> Table:
+        cols = {k: np.ascontiguousarray(f[k]) for k in ("slot_res", "left_base", "node_present", "g_exists", "min_member", "has_min_resources", "backed_off", "permitted",
+                                                         "listed", "gated", "req", "req_mask", "step_ptr", "step_node", "step_add", "pod_group")}
+        return Table(self._hdr, "spx_cosched_soa", n_nodes=f["N"], n_slots=f["S"], n_groups=f["G"], n_pods=f["P"], **cols)
+
+    def cosched_check(self, f: dict) -> int:
+        """the slot whose sums reach 2^62 (spx_cosched_check), -1 when the table is within the device's int64 range"""
+        bad = C.c_int32(-1)
+        rc = self._lib.spx_cosched_check(self.cosched_table(f).ref(), C.byref(bad))
+        if rc != 0 and bad.value < 0:
+            self._ck_static(rc)
+        return int(bad.value)
+
+    def upload_cosched(self, f: dict) -> None:
+        """flatten_cosched's columns to the device; every upload makes the gate stale (spx_upload_cosched)"""
+        self._ck(self._lib.spx_upload_cosched(self._h, self.cosched_table(f).ref()))
+        self.n_nodes, self.n_pods = f["N"], f["P"]
+        self._cosched_shape = (f["G"], f["S"])
+
+    def load_cosched_objects(self, nodes: Table, objects: Table) -> None:
+        self.upload_cosched(self.flatten_cosched(nodes, objects))
+
+    def cosched_gap(self, group_begin: int = 0, group_end: Optional[int] = None):
+        """(pass_mask [G], open_mask [G], gap [G][n_slots]) of CheckClusterResource per group (spx_fetch_cosched_gap)"""
+        G, S = getattr(self, "_cosched_shape", (0, 1))
+        group_end = G if group_end is None else group_end
+        n = group_end - group_begin
+        pm, om, gap = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, S), np.int64)
+        u32 = C.POINTER(C.c_uint32)
+        self._ck(self._lib.spx_fetch_cosched_gap(self._h, group_begin, group_end, pm.ctypes.data_as(u32), om.ctypes.data_as(u32), gap.ctypes.data_as(C.POINTER(C.c_int64))))
+        return pm, om, gap
+
+    def cosched_less(self, objects: Table, priority, initial_attempt_ns, keys: Sequence[str], a: Sequence[int], b: Sequence[int]) -> np.ndarray:
+        """Coscheduling.Less for the pairs (a[i], b[i]) of pending pods; keys[p] = pod p's "namespace/name" (spx_cosched_less)"""
+        enc = [k.encode() for k in keys]
+        ptr = np.zeros(len(enc) + 1, np.int64)
+        ptr[1:] = np.cumsum([len(k) for k in enc])
+        blob = np.frombuffer(b"".join(enc) + b"\0", np.uint8).copy()
+        pr = np.ascontiguousarray(priority, dtype=np.int32)
+        ts = np.ascontiguousarray(initial_attempt_ns, dtype=np.int64)
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        b = np.ascontiguousarray(b, dtype=np.int64)
+        out = np.zeros(len(a), np.uint8)
+        i64 = C.POINTER(C.c_int64)
+        self._ck_static(self._lib.spx_cosched_less(objects.ref(), pr.ctypes.data_as(C.POINTER(C.c_int32)), ts.ctypes.data_as(i64), ptr.ctypes.data_as(i64),
+                                                   blob.ctypes.data_as(C.POINTER(C.c_uint8)), len(a), a.ctypes.data_as(i64), b.ctypes.data_as(i64),
+                                                   out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out.astype(bool)
 
     # ------------------------------------------------------------------ NodeResourceTopologyMatch
     def load_nrt_objects(self, nodes: Table, nrt: Table, rc: Optional[Table], pods: Table, params: Table) -> None:

@@ -610,3 +610,86 @@ def build_sysched_objects(hdr: Header, pod_sets: Sequence[frozenset], host_sets:
                  n_nodes=len(host_sets), host_present=np.array([s is not None for s in host_sets], np.uint8),
                  host_ptr=_csr([s or () for s in host_sets]), host_name=np.array([name_id[x] for s in host_sets for x in sorted(s or ())], np.int32),
                  res_ptr=_csr(resident_sets), res_set=np.array([set_id[s] for rs in resident_sets for s in rs], np.int32))
+
+
+# ---------------------------------------------------------------------- Coscheduling (pkg/coscheduling)
+POD_GROUP_LABEL = "scheduling.x-k8s.io/pod-group"  # v1alpha1.PodGroupLabel (apis/scheduling/v1alpha1/types.go)
+
+
+def pod_group_full_name(namespace: str, label: str) -> str:
+    """util.GetPodGroupFullName / GetPodGroup's key: "<namespace>/<label value>"; "" for a pod without the label"""
+    return f"{namespace}/{label}" if label else ""
+
+
+def pod_key(namespace: str, name: str) -> str:
+    """core.GetNamespacedName: the last key Coscheduling.Less compares"""
+    return f"{namespace}/{name}"
+
+
+def pod_group(namespace: str, name: str, min_member: int = 0, min_resources: Optional[dict] = None, created_ns: int = 0, backed_off: bool = False,
+              permitted: bool = False, last_failed_ns: Optional[int] = None, exists: bool = True) -> dict:
+    """a PodGroup object (exists=False: only the label is known, e.g. through lastFailedSchedulePG or a pod that names it)"""
+    return {"namespace": namespace, "name": name, "min_member": min_member, "min_resources": min_resources, "created_ns": created_ns,
+            "backed_off": backed_off, "permitted": permitted, "last_failed_ns": last_failed_ns, "exists": exists}
+
+
+def cosched_pod(namespace: str = "default", name: str = "", labels: Optional[dict] = None, gated: bool = False, node: Optional[int] = None,
+                requests: Optional[dict] = None) -> dict:
+    """a pod as Coscheduling sees it: its labels, whether it has SchedulingGates, the node it is assigned to (None: pending) and its
+    effective request (a v1.ResourceList-like dict)"""
+    return {"namespace": namespace, "name": name, "labels": labels or {}, "gated": gated, "node": node, "requests": requests or {}}
+
+
+def build_cosched_objects(hdr: Header, res: Resources, groups: Sequence[dict], pending: Sequence[dict], assigned: Sequence[dict],
+                          node_present: Sequence[bool], other_listed: Sequence[dict] = ()) -> Table:
+    """spx_cosched_objects.  `pending` are the batch's pods (row order), `assigned` the pods on nodes (each with "node"),
+    `other_listed` further pods the pod lister returns that are neither (pending pods outside the batch, e.g. gated ones).  Labels that
+    name a group without a PodGroup object get an entry with exists = 0."""
+    groups = [dict(g) for g in groups]
+    index = {pod_group_full_name(g["namespace"], g["name"]): i for i, g in enumerate(groups)}
+    namespaces, names = Interner(), Interner()
+
+    def group_of(p):
+        full = pod_group_full_name(p["namespace"], p["labels"].get(POD_GROUP_LABEL, ""))
+        if not full:
+            return -1
+        if full not in index:
+            index[full] = len(groups)
+            groups.append(pod_group(p["namespace"], p["labels"][POD_GROUP_LABEL], exists=False))
+        return index[full]
+
+    pod_group_col = [group_of(p) for p in pending]
+    a_group = [group_of(p) for p in assigned]
+    other_group = [group_of(p) for p in other_listed]
+    G = len(groups)
+    listed, gated = [0] * G, [0] * G
+    for p, g in list(zip(pending, pod_group_col)) + list(zip(assigned, a_group)) + list(zip(other_listed, other_group)):
+        if g >= 0:
+            listed[g] += 1
+            gated[g] += 1 if p.get("gated") else 0
+    n_nodes = len(node_present)
+    order = sorted(range(len(assigned)), key=lambda i: assigned[i]["node"])  # stable: the node's own order is kept
+    a_ptr = np.zeros(n_nodes + 1, np.int32)
+    for i in order:
+        a_ptr[assigned[i]["node"] + 1] += 1
+    a_ptr = np.cumsum(a_ptr).astype(np.int32)
+    a_req = [_rl(res, assigned[i]["requests"]) for i in order]
+    g_res = [[x for x in _rl(res, g["min_resources"])] if g["min_resources"] is not None else [] for g in groups]
+    return Table(
+        hdr, "spx_cosched_objects",
+        n_groups=G,
+        g_ns=[namespaces.id(g["namespace"]) for g in groups], g_name=[names.id(g["name"]) for g in groups],
+        g_exists=[1 if g.get("exists", True) else 0 for g in groups],
+        g_min_member=[g["min_member"] for g in groups],
+        g_has_min_resources=[1 if g["min_resources"] is not None else 0 for g in groups],
+        g_res_ptr=_csr(g_res), g_res_id=[x[0] for l in g_res for x in l], g_res_qty=[x[1] for l in g_res for x in l],
+        g_backed_off=[1 if g["backed_off"] else 0 for g in groups], g_permitted=[1 if g["permitted"] else 0 for g in groups],
+        g_created_ns=[g["created_ns"] for g in groups],
+        g_has_last_failed=[0 if g["last_failed_ns"] is None else 1 for g in groups],
+        g_last_failed_ns=[g["last_failed_ns"] or 0 for g in groups],
+        g_listed=listed, g_gated=gated,
+        n_pods=len(pending), pod_group=pod_group_col,
+        n_nodes=n_nodes, node_present=[1 if x else 0 for x in node_present],
+        a_ptr=a_ptr, a_group=[a_group[i] for i in order],
+        a_req_ptr=_csr(a_req), a_req_res=[x[0] for l in a_req for x in l], a_req_qty=[x[1] for l in a_req for x in l],
+    )
