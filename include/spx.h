@@ -908,8 +908,9 @@ int spx_fetch_score_rows(spx_engine* e, int plugin, int64_t row_begin, int64_t r
 int spx_fetch_status_rows(spx_engine* e, int plugin, int64_t row_begin, int64_t row_end, uint8_t* out, int64_t out_stride);
 /* exactness bookkeeping of the fast formulations: how many cells the float32 sweeps of TLP, LVRB and
  * LowRiskOverCommitment could not prove to round like the reference and re-evaluated with the reference's float64 sequence,
- * accumulated per plugin id since the last reset (SPX_NUM_PLUGINS entries; plugins without a fallback report 0).  Synchronises
- * the engine stream. */
+ * accumulated per plugin id since the last reset (SPX_NUM_PLUGINS entries; plugins without a fallback report 0).  The count is of
+ * EVALUATIONS: a TargetLoadPacking sweep in the class form (SPX_OPT_TLP_POD_CLASSES) evaluates a run of rows with equal pod values
+ * once and counts its re-evaluated cells once, not once per row of the table that holds them.  Synchronises the engine stream. */
 int spx_fetch_stats(spx_engine* e, int64_t* reevaluated_cells, int reset);
 /* raw int64 Score() row (before NormalizeScore) recomputed for one pod — the parity harness
  * and direct-call tests observe raw values (e.g. networkoverhead_test.go:803) */
@@ -1057,6 +1058,16 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
  *                              assumes that issued launches execute: a caller that captures spx_eval into a graph of its own and does not
  *                              replay it sets the option to 0 as well.  0 = every spx_eval writes the rows.  Same tables either
  *                              way; spx_alloc_table_path reports what the last spx_eval did
+ *   SPX_OPT_TLP_POD_CLASSES    1 (default) = a whole-batch spx_eval of TargetLoadPacking (rows [0, n_pods), at least 256 of them, under the
+ *                              conditions of SPX_OPT_TLP_AMB_TABLE, which must be on) sweeps the rows in the order of their pod value —
+ *                              the pod enters a TargetLoadPacking row through the one number spx_flatten_trimaran_pods computes for it
+ *                              (targetloadpacking.go:137-160), so rows with equal values are equal byte for byte — and evaluates a run of
+ *                              equal values once per 64 positions of that order, storing the result to every row of the run.  The order
+ *                              is built on the device whenever the pod column is uploaded (spx_upload_trimaran_pods, spx_load_trimaran,
+ *                              spx_load_trimaran_pods); a batch takes this form only when enough of its rows are such copies
+ *                              (spx_tlp_pod_classes reports the count).  2 = whenever at least one row is a copy (measurements);
+ *                              0 = every row is evaluated, in row order.  Same tables either way; spx_tlp_form reports what ran.
+ *                              spx_decide's sweep and partial row ranges always evaluate every row
  */
 #define SPX_OPT_ROW_ALIGN 0
 #define SPX_OPT_REFERENCE_KERNELS 1
@@ -1079,7 +1090,8 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
 #define SPX_OPT_NRT_FUSED 18
 #define SPX_OPT_NRT_WIDE 19
 #define SPX_OPT_ALLOC_TABLE_KEEP 20
-#define SPX_NUM_OPTIONS 21
+#define SPX_OPT_TLP_POD_CLASSES 21
+#define SPX_NUM_OPTIONS 22
 int spx_set_option(spx_engine* e, int option, int64_t value);
 int spx_get_option(const spx_engine* e, int option, int64_t* value);
 
@@ -1092,6 +1104,14 @@ int spx_nrt_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_copie
  * peaks.go:134 (GetResourceRequestQuantity) — so pods that request the same amount get the same raw row, and, when no Filter plugin
  * or feasibility mask narrows a pod's node list, the same NormalizeScore (peaks.go:150-166). */
 int spx_peaks_pod_classes(const spx_engine* e, int64_t* n_unique, int64_t* n_copies);
+
+/* The same for TargetLoadPacking and the uploaded trimaran pod batch, in the terms of the class form's sweep (SPX_OPT_TLP_POD_CLASSES):
+ * rows_evaluated = positions of the value-sorted row order that start a chunk of 64 or hold another value than the position before,
+ * rows_copied = n_pods - rows_evaluated, the rows that are stores of a result the wave already holds.  SPX_ERR_STATE without a batch. */
+int spx_tlp_pod_classes(const spx_engine* e, int64_t* rows_evaluated, int64_t* rows_copied);
+/* Which form the last spx_eval with TargetLoadPacking in the mask launched for it: 1 = every row evaluated in row order, 2 = the class
+ * form; 0 = none yet, or the reference-arithmetic kernel ran (SPX_OPT_REFERENCE_KERNELS, a target outside [1, 99]) */
+int spx_tlp_form(const spx_engine* e);
 
 /* The same for the uploaded SySched pod batch (spx_upload_sysched_pods): a pod enters SySched.Score through its syscall set alone, so
  * n_unique = pods that are the first of the batch with their set, n_copies = the rest. */

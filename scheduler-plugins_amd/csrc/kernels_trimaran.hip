@@ -440,6 +440,13 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
   return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
+// lane l gets lane l - 1's value (lane 0 its own); every lane must be live
+__device__ __forceinline__ uint64_t shfl_up1_u64(uint64_t v) {
+  const uint32_t lo = static_cast<uint32_t>(__shfl_up(static_cast<int>(static_cast<uint32_t>(v)), 1));
+  const uint32_t hi = static_cast<uint32_t>(__shfl_up(static_cast<int>(static_cast<uint32_t>(v >> 32)), 1));
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
 // one cell through the reference's float64 sequence, from the original node columns (the fast sweep's rare path)
 __device__ __forceinline__ uint32_t tlp_cell_exact(const TrimaranArgs& a, int64_t n, double pod_milli) {
   TlpNode tn;
@@ -460,10 +467,17 @@ __device__ __forceinline__ uint32_t tlp_cell_exact(const TrimaranArgs& a, int64_
 // pairs of cells (round 8, see the row loop); the other rows (~8 % of the (row, tile) pairs on continuous inputs), rows of pods
 // outside the table and waves holding an always-exact node take the checked cell exactly as before.  Which rows those are is one
 // 64-bit mask per chunk, tested with scalar instructions.
-template <int NPL, bool A, bool D = false, bool AMB = false>
+//   CLS (round 10, whole-batch table launches with the ambiguity table only): the pod enters a row through the one integer
+// tlp_pod_milli[row] — the streamlined cell, the checked cell, tlp_cell_exact and the rows outside the table all read nothing else of
+// the pod — so two rows with the same value hold the same bytes in every tile.  A wave's 64 rows are then 64 consecutive POSITIONS of
+// a.tlp_order (the rows sorted by value, launch_tlp_order) instead of 64 consecutive rows: one ballot marks the positions whose value
+// equals the previous position's of the same chunk (position 0 of a chunk never: the wave holds no registers of the chunk before),
+// the row loop tests that bit on the scalar unit and, when it is set, stores the w[] it already holds to this position's row.
+template <int NPL, bool A, bool D = false, bool AMB = false, bool CLS = false>
 __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(TrimaranArgs a, int n_tiles, double c1, double c2, DecideArgs dec) {
   SPX_RESOLVE_ROWS(a);
   static_assert(kPodsPerChunk == kWave, "one pod record per lane");
+  static_assert(!CLS || (!D && AMB), "the class form exists for the table-writing launch with the ambiguity table");
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t unit = static_cast<int64_t>(blockIdx.x) * static_cast<int>(blockDim.x >> 6) + wave;
@@ -477,7 +491,11 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
 
   // one pod record per lane: predicted millicores as float32 (exact below 2^23; larger or negative values send
   // the whole row to the exact path)
-  const int64_t my_pod_i = (lane < n_rows) ? a.tlp_pod_milli[pod0 + lane] : 0;
+  // (CLS: pod0 is a position of the order; both loads are selects, so that every lane writes my_row / my_pod_i — the sources of the
+  // v_readlane broadcasts and of the ballots below — under a full exec mask)
+  // (the row index is clamped to the batch: whatever the order held, no store leaves the table)
+  const int32_t my_row = CLS ? static_cast<int32_t>(min(static_cast<uint32_t>((lane < n_rows) ? a.tlp_order[pod0 + lane] : 0), static_cast<uint32_t>(a.row_end - 1))) : 0;
+  const int64_t my_pod_i = (lane < n_rows) ? a.tlp_pod_milli[CLS ? static_cast<int64_t>(my_row) : pod0 + lane] : 0;
   const int pod_bits = __float_as_int(static_cast<float>(my_pod_i));
   const int pod_bad = (my_pod_i < 0 || my_pod_i >= (1 << 23)) ? 1 : 0;
   int pod_slow = 1;  // this row takes the checked cell in this tile
@@ -541,15 +559,23 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
   // sources are written by every lane (no early exit above), so the rule for v_readlane holds for it as well.
   const uint64_t bad_rows = __ballot(pod_bad != 0);
   const uint64_t slow_rows = (!AMB || wave_nan) ? ~0ull : __ballot((pod_slow | pod_bad) != 0);
+  // CLS: bit r set = position r holds the value of position r - 1 of this chunk (never bit 0; lanes past the batch never)
+  uint64_t same_rows = 0;
+  if constexpr (CLS) {
+    const uint64_t prev = shfl_up1_u64(static_cast<uint64_t>(my_pod_i));
+    same_rows = __ballot(lane > 0 && lane < n_rows && static_cast<uint64_t>(my_pod_i) == prev);
+  }
 
+  uint32_t w[NPL / 4] = {};  // (CLS: carried from the row that was evaluated to its copies)
   for (int r = 0; r < n_rows; ++r) {
-    const int64_t row = (pod0 + r) * a.row_stride + node0;
+    const int64_t row_id = CLS ? static_cast<int64_t>(__builtin_amdgcn_readlane(my_row, r)) : pod0 + r;
+    const int64_t row = row_id * a.row_stride + node0;
     if constexpr (A && !D) {
       if (active) store_bytes<NPL>(a.out_alloc + row, alloc_w);
     }
-    const float pod_f = __int_as_float(__builtin_amdgcn_readlane(pod_bits, r));
-    uint32_t w[NPL / 4];
     uint32_t tb[D ? NPL : 1];  // decisions-only mode: the byte of each cell on its own (the table mode packs four per dword)
+    if (!CLS || ((same_rows >> r) & 1ull) == 0) {  // (CLS: a copy keeps w)
+    const float pod_f = __int_as_float(__builtin_amdgcn_readlane(pod_bits, r));
     const F32x2 pod2{pod_f, pod_f};
     const F32x2 off2{tf, 100.0f};
     const bool row_slow = ((slow_rows >> r) & 1ull) != 0;
@@ -648,7 +674,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
     if (__builtin_expect(any, 0)) {
       // rare (~8e-5 of cells on continuous inputs): find the ambiguous cells again and re-evaluate them exactly from
       // the original node columns.  Recomputing the flags here is cheaper than carrying 16 of them across the branch.
-      const double pod_milli = static_cast<double>(a.tlp_pod_milli[pod0 + r]);
+      const double pod_milli = static_cast<double>(a.tlp_pod_milli[row_id]);
       float pf = pod_f;
       asm volatile("" : "+v"(pf));  // opaque copy: keeps the compiler from carrying the 16 flags across the branch instead
       const F32x2 pod2s{pf, pf};
@@ -672,6 +698,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, D ? 3 : 1) void k_tlp_fast2(
       }
     }
     }  // checked row
+    }  // evaluated row
     if constexpr (!D) {
       if (active) store_bytes<NPL>(a.out_tlp + row, w);
     } else {
@@ -1093,8 +1120,17 @@ void launch_tlp_fast(const TrimaranArgs& a, hipStream_t s) {
   const double t = a.tlp_target;
   const double c1 = t / (100.0 - t), c2 = (100.0 - t) / t;
   const int64_t n_slots = static_cast<int64_t>(n_tiles) * tile_nodes;
+  if (a.tlp_form) *a.tlp_form = 1;
   if (tlp_prepare(a, rows, n_slots, c1, c2, tile_nodes, s)) {
-    if (a.out_alloc)
+    // the class form: the owner passes the order of a whole batch only (row_begin == 0, row_end == the order's length), and it rides
+    // on the ambiguity table's launch conditions (no row_ptr, >= 256 rows, SPX_OPT_TLP_AMB_TABLE)
+    const bool cls = a.tlp_order && a.row_begin == 0;
+    if (cls && a.tlp_form) *a.tlp_form = 2;
+    if (cls && a.out_alloc)
+      hipLaunchKernelGGL((k_tlp_fast2<NPL, true, false, true, true>), dim3(blocks), dim3(kWave * kWavesPerBlock), 0, s, a, n_tiles, c1, c2, DecideArgs{});
+    else if (cls)
+      hipLaunchKernelGGL((k_tlp_fast2<NPL, false, false, true, true>), dim3(blocks), dim3(kWave * kWavesPerBlock), 0, s, a, n_tiles, c1, c2, DecideArgs{});
+    else if (a.out_alloc)
       hipLaunchKernelGGL((k_tlp_fast2<NPL, true, false, true>), dim3(blocks), dim3(kWave * kWavesPerBlock), 0, s, a, n_tiles, c1, c2, DecideArgs{});
     else
       hipLaunchKernelGGL((k_tlp_fast2<NPL, false, false, true>), dim3(blocks), dim3(kWave * kWavesPerBlock), 0, s, a, n_tiles, c1, c2, DecideArgs{});

@@ -61,7 +61,7 @@ struct spx_engine {
   int64_t row_stride = 0;
 
   // spx_set_option state (per engine; nothing is read from the environment)
-  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0, 1};
+  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0, 1, 1};
 
   // params
   int32_t alloc_mode = SPX_MODE_LEAST;
@@ -90,6 +90,12 @@ struct spx_engine {
   bool lv_amb_built = false;     // ... and whether d_lv_exact / d_lv_fast / d_lv_amb still describe the LVRB node columns and parameters
   int64_t tlp_amb_geom[3] = {0, 0, 0}, lv_amb_geom[3] = {0, 0, 0};  // the tiling / stride / target the tables were built for (tlp_prepare compares)
   bool tlp_amb_built = false;    // ... and whether it still describes d_cap_cpu / d_tlp_util / d_tlp_missing / d_tlp_valid and the target (cleared by every writer of those)
+  // TargetLoadPacking's pod classes (SPX_OPT_TLP_POD_CLASSES): the rows of d_tlp_pod sorted by value, built by every writer of that
+  // column (tlp_build_order) and invalidated by it first, so that no sweep can meet an order of another batch
+  DevBuf d_tlp_order, d_tlp_order_scratch;
+  bool tlp_order_valid = false;
+  int64_t tlp_rows_evaluated = 0;  // of the batch in the class form: chunk starts of the order + changes of value
+  int tlp_last_form = 0;           // spx_tlp_form: what the last spx_eval of TargetLoadPacking launched (0 none, 1 plain, 2 classes)
   DevBuf d_commit;               // scratch of spx_commit_sequential
   DevBuf d_decide;               // per-tile partial decisions of spx_decide
   DevBuf d_stats;                // uint64 [SPX_NUM_PLUGINS]: cells re-evaluated by the fast sweeps' exact fallback
@@ -374,6 +380,27 @@ int set_pods(spx_engine* e, int64_t p) {
   if (e->n_pods != -1 && e->n_pods != p)
     return fail(e, SPX_ERR_STATE, "n_pods differs from tables already uploaded");
   e->n_pods = p;
+  return SPX_OK;
+}
+
+// The order of TargetLoadPacking's class form for the pod column in place (n_pods rows of d_tlp_pod, queued on the stream before
+// this call): built on the stream, the count of evaluated rows read back.  The caller has cleared tlp_order_valid before it wrote the
+// column and synchronises the stream afterwards anyway; this synchronises for the one number.
+int tlp_build_order(spx_engine* e) {
+  e->tlp_order_valid = false;
+  if (e->n_pods <= 0 || e->n_pods > std::numeric_limits<int32_t>::max()) return SPX_OK;  // (rows are int32 in the order: such a batch sweeps plain)
+  int rc;
+  const size_t words = spx::tlp_order_scratch_words(spx::kTlpAmbSize);
+  if ((rc = ensure(e, e->d_tlp_order, static_cast<size_t>(e->n_pods) * sizeof(int32_t))) || (rc = ensure(e, e->d_tlp_order_scratch, words * sizeof(uint32_t))))
+    return rc;
+  uint32_t* scratch = static_cast<uint32_t*>(e->d_tlp_order_scratch.p);
+  spx::launch_tlp_order(static_cast<const int64_t*>(e->d_tlp_pod.p), e->n_pods, spx::kTlpAmbSize, static_cast<int32_t*>(e->d_tlp_order.p), scratch, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  uint32_t evaluated = 0;
+  SPX_HIP(e, hipMemcpyAsync(&evaluated, scratch + (words - 1), sizeof evaluated, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->tlp_rows_evaluated = evaluated;
+  e->tlp_order_valid = true;
   return SPX_OK;
 }
 

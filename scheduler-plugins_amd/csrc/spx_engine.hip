@@ -59,7 +59,7 @@ int spx_destroy(spx_engine* e) {
   DevBuf* bufs[] = {&e->d_alloc,   &e->d_alloc_w,  &e->d_alloc_raw, &e->d_alloc_norm, &e->d_alloc_rel, &e->d_alloc_prev, &e->d_cap_cpu, &e->d_tlp_util,
                     &e->d_tlp_missing, &e->d_tlp_valid, &e->d_lv_acpu, &e->d_lv_amem, &e->d_lv_cavg, &e->d_lv_cstd,
                     &e->d_lv_mavg, &e->d_lv_mstd,  &e->d_lv_flags,  &e->d_tlp_pod,    &e->d_lv_rcpu, &e->d_lv_rmem,
-                    &e->d_raw_row,   &e->d_lv_exact, &e->d_lv_fast, &e->d_tlp_fast, &e->d_tlp_amb, &e->d_lv_amb, &e->d_nrt_pk_tab, &e->d_commit, &e->d_nrt_flags, &e->d_nrt_max_numa, &e->d_nrt_nz, &e->d_nrt_zid, &e->d_nrt_zp,
+                    &e->d_raw_row,   &e->d_lv_exact, &e->d_lv_fast, &e->d_tlp_fast, &e->d_tlp_amb, &e->d_tlp_order, &e->d_tlp_order_scratch, &e->d_lv_amb, &e->d_nrt_pk_tab, &e->d_commit, &e->d_nrt_flags, &e->d_nrt_max_numa, &e->d_nrt_nz, &e->d_nrt_zid, &e->d_nrt_zp,
                     &e->d_nrt_avail, &e->d_nrt_cost,  &e->d_nrt_minavg, &e->d_nrt_np,    &e->d_nrt_qos, &e->d_nrt_nn,
                     &e->d_nrt_nctr,  &e->d_nrt_ckind, &e->d_nrt_cpres,  &e->d_nrt_creq,  &e->d_nrt_ppres, &e->d_nrt_preq,
                     &e->d_nrt_frcv, &e->d_nrt_fav,   &e->d_nrt_frc,   &e->d_nrt_fcpu,   &e->d_nrt_frep,  &e->d_nrt_items, &e->d_nrt_perm, &e->d_nrt_ln, &e->d_nrt_fbraw, &e->d_nrt_redo,
@@ -142,6 +142,9 @@ int spx_set_option(spx_engine* e, int option, int64_t value) {
     case SPX_OPT_NRT_WIDE:
     case SPX_OPT_ALLOC_TABLE_KEEP:
       if (value != 0 && value != 1) return fail(e, SPX_ERR_ARG, "option takes 0 or 1");
+      break;
+    case SPX_OPT_TLP_POD_CLASSES:
+      if (value < 0 || value > 2) return fail(e, SPX_ERR_ARG, "SPX_OPT_TLP_POD_CLASSES: 0, 1 or 2");
       break;
     case SPX_OPT_NRT_LN_LIST_PERMILLE:
       if (value < 1 || value > 1000) return fail(e, SPX_ERR_ARG, "SPX_OPT_NRT_LN_LIST_PERMILLE: 1..1000");
@@ -342,6 +345,15 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     a.tlp_amb_size = spx::kTlpAmbSize;
     a.tlp_amb_built = &e->tlp_amb_built;
     a.tlp_amb_geom = e->tlp_amb_geom;
+    // pod classes: a whole-batch evaluation whose order describes the column in place (every writer of d_tlp_pod clears the flag
+    // before it writes and rebuilds the order after), when enough of its rows are copies to pay for the scattered row order
+    e->tlp_last_form = 0;
+    a.tlp_form = &e->tlp_last_form;
+    const int64_t cls_opt = e->option[SPX_OPT_TLP_POD_CLASSES];
+    if (cls_opt && e->tlp_order_valid && row_begin == 0 && row_end == e->n_pods && !e->row_indirect && row_end >= 256) {
+      const int64_t copied = e->n_pods - e->tlp_rows_evaluated;
+      if (cls_opt == 2 ? copied > 0 : copied * 100 >= spx::kTlpClassMinCopyPct * e->n_pods) a.tlp_order = static_cast<const int32_t*>(e->d_tlp_order.p);
+    }
   }
   if (!e->hold_ev0) SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
   if (Q) {
@@ -708,6 +720,16 @@ int spx_sync(spx_engine* e) {
 int spx_nrt_filter_path(const spx_engine* e) { return e ? e->last_nrt_filter : 0; }
 
 int spx_alloc_table_path(const spx_engine* e) { return e ? e->last_alloc_table : 0; }
+
+int spx_tlp_pod_classes(const spx_engine* e, int64_t* rows_evaluated, int64_t* rows_copied) {
+  if (!e) return SPX_ERR_ARG;
+  if (!e->tri_pods || !e->tlp_order_valid) return fail(e, SPX_ERR_STATE, "TargetLoadPacking: no row order (no pod batch uploaded, or more than 2^31 - 1 rows)");
+  if (rows_evaluated) *rows_evaluated = e->tlp_rows_evaluated;
+  if (rows_copied) *rows_copied = e->n_pods - e->tlp_rows_evaluated;
+  return SPX_OK;
+}
+
+int spx_tlp_form(const spx_engine* e) { return e ? e->tlp_last_form : 0; }
 
 int spx_nrt_wide(const spx_engine* e) { return e && e->nrt_wide ? 1 : 0; }
 

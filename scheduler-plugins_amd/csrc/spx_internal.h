@@ -74,6 +74,12 @@ struct AllocPrepArgs {
 };
 void launch_alloc_prepare(const AllocPrepArgs& a, hipStream_t s);
 
+// SPX_OPT_TLP_POD_CLASSES 1: a whole batch takes the class form when at least this share (percent) of its rows are copies.  Measured
+// with tools/tlp_classes_ab.py on config #2's values with a fraction replaced by unique ones (10 000 x 50 000, both forms alternating,
+// profiles/r10/tlp_classes_ab.md): at 47.6 % copies the class form's median step is 13 % below the plain form's, more than either
+// form's min-to-max spread in that run; at 30.9 % it is 12 % below but inside the plain form's spread, at 15.7 % 4 % below and inside
+// both, from 9 % down the two are equal.  The smallest measured share that clears both spreads is the threshold.
+constexpr int64_t kTlpClassMinCopyPct = 47;
 constexpr int32_t kTlpAmbSize = 1 << 16;  // pod values (millicores) k_tlp_amb_build's table covers; larger pods take the checked cell
 
 // ---------------------------------------------------------------- fused Allocatable + TLP + LVRB sweep
@@ -119,6 +125,10 @@ struct TrimaranArgs {
   bool* lv_amb_built;    // as tlp_amb_built, for lv_exact / lv_fast / lv_amb: cleared by every writer of the LVRB node columns, margin or sensitivity
   bool* tlp_amb_built;   // host flag (may be NULL = always rebuild): true while tlp_amb describes the node columns / target in place; the launcher builds
                          // the table when it is false and sets it; the owner clears it whenever a column k_tlp_amb_build reads, or the target, changes
+  // TargetLoadPacking's class form (k_tlp_fast2<..., CLS>): int32 [row_end] permutation of the rows, equal pod values adjacent
+  // (launch_tlp_order).  Set by the owner for a whole-batch launch only (row_begin == 0, row_end == rows ordered); NULL = the plain form
+  const int32_t* tlp_order;
+  int* tlp_form;  // host, may be NULL: launch_tlp_fast leaves 1 (plain) or 2 (classes) there
   unsigned long long* stats;  // [SPX_NUM_PLUGINS][kStatSlots][kStatStride] cells the fast sweeps re-evaluated with the reference sequence (spx_fetch_stats); may be NULL
   // outputs: uint8 [n_pods][row_stride] each (NULL = plugin not evaluated)
   uint8_t* out_alloc;
@@ -127,6 +137,12 @@ struct TrimaranArgs {
 };
 // evaluates the plugins whose out_* pointer is non-NULL
 void launch_trimaran(const TrimaranArgs& a, hipStream_t s);
+// The row order of TargetLoadPacking's class form (kernels_tlp_order.hip): order[] = a permutation of [0, n_rows) with the rows whose
+// pod value lies in [0, amb_size) sorted by value and all others behind them; scratch: uint32 [tlp_order_scratch_words(amb_size)],
+// whose LAST word is left holding the number of positions p with p % 64 == 0 or pod[order[p]] != pod[order[p - 1]] — the rows the
+// class form evaluates.  Histogram, scan, scatter and that count for the rows outside the table, on the stream.
+size_t tlp_order_scratch_words(int32_t amb_size);
+void launch_tlp_order(const int64_t* pod_milli, int64_t n_rows, int32_t amb_size, int32_t* order, uint32_t* scratch, hipStream_t s);
 size_t lvrb_amb_bytes();
 // sequential commit loop over pod rows [t.row_begin, t.row_end) for Allocatable (bit 0) / TLP (bit 1) / LVRB (bit 2)
 struct CommitArgs {

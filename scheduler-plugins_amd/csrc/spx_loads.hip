@@ -49,10 +49,12 @@ int spx_load_trimaran_pods(spx_engine* e, const spx_pod_objects* pods) {
   int64_t* rcpu = reinterpret_cast<int64_t*>(h + col);
   int64_t* rmem = reinterpret_cast<int64_t*>(h + 2 * col);
   if (spx_flatten_trimaran_pods(pods, &e->tlp, tpod, rcpu, rmem) != SPX_OK) return fail(e, SPX_ERR_ARG, "spx_flatten_trimaran_pods failed");
+  e->tlp_order_valid = false;  // (as spx_upload_trimaran_pods)
   if ((rc = upload(e, e->d_tlp_pod, tpod, p * 8))) return rc;
   if ((rc = upload(e, e->d_lv_rcpu, rcpu, p * 8))) return rc;
   if ((rc = upload(e, e->d_lv_rmem, rmem, p * 8))) return rc;
   e->tri_pods = true;
+  if ((rc = tlp_build_order(e))) return rc;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   return SPX_OK;
 }

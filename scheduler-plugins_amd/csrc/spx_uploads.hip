@@ -759,10 +759,12 @@ int spx_upload_trimaran_pods(spx_engine* e, const spx_trimaran_pods_soa* t) {
   int rc = set_pods(e, t->n_pods);
   if (rc) return rc;
   const size_t p = static_cast<size_t>(t->n_pods);
+  e->tlp_order_valid = false;  // (before the column changes: a failed upload must not leave an order that describes the old one)
   if ((rc = upload(e, e->d_tlp_pod, t->tlp_pod_milli, p * 8))) return rc;
   if ((rc = upload(e, e->d_lv_rcpu, t->lv_req_cpu_milli, p * 8))) return rc;
   if ((rc = upload(e, e->d_lv_rmem, t->lv_req_mem, p * 8))) return rc;
   e->tri_pods = true;
+  if ((rc = tlp_build_order(e))) return rc;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   return SPX_OK;
 }

@@ -155,6 +155,16 @@ class Engine:
         self._ck(self._lib.spx_peaks_pod_classes(self._h, C.byref(u), C.byref(d)))
         return int(u.value), int(d.value)
 
+    def tlp_pod_classes(self):
+        """(rows evaluated, rows copied) of the uploaded trimaran pod batch in TargetLoadPacking's class form (spx_tlp_pod_classes)"""
+        u, d = C.c_int64(), C.c_int64()
+        self._ck(self._lib.spx_tlp_pod_classes(self._h, C.byref(u), C.byref(d)))
+        return int(u.value), int(d.value)
+
+    def tlp_form(self) -> int:
+        """what the last eval launched for TargetLoadPacking: 1 = every row in row order, 2 = the class form, 0 = neither (spx_tlp_form)"""
+        return int(self._lib.spx_tlp_form(self._h))
+
     def sysched_pod_classes(self):
         """(pods that are the first of the batch with their syscall set, pods that repeat one) of the uploaded SySched pod batch
         (spx_sysched_pod_classes)"""

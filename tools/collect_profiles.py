@@ -5,12 +5,15 @@ kernel stats CSV, a PMC summary per kernel, the bench line printed under rocprof
 import collections
 import csv
 import json
+import re
 import shutil
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
+if not re.fullmatch(r"r\d\d", rnd):  # (profiles/--help once came of `collect_profiles.py --help`)
+    sys.exit(f"usage: collect_profiles.py rNN [workload ...]   (round name {rnd!r} is not rNN)\n" + __doc__)
 only = set(sys.argv[2:])  # optional: the workloads to collect (default: every gpurun_out/prof_* directory)
 out = ROOT / "profiles" / rnd
 out.mkdir(parents=True, exist_ok=True)
