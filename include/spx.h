@@ -739,6 +739,85 @@ typedef struct spx_quota_soa {
   const uint8_t* min_present;  /* sequential commit loop reads them (a bound pod can push its quota over min, elasticquota.go:166-191) */
 } spx_quota_soa;
 
+/* CapacityScheduling.PostFilter's preemption dry run (capacity_scheduling.go:331-348 -> preemption.Evaluator.DryRunPreemption ->
+ * SelectVictimsOnNode :486-677), for many preemptors x all nodes in one launch (kernels_preempt.hip).
+ * Vectors have SPX_QUOTA_SLOTS int64 slots in spx_quota_objects' layout.  The node's assigned pods are a CSR IN WALK ORDER (least
+ * important first, :537-539: MoreImportantPod = priority higher, else start time earlier); pod_hi_order lists, per node, the positions
+ * of that list most important first.  The reference's sort.Slice is unstable: ties in (priority, start time) are broken here by the
+ * order of the table in both directions, by the flattener and by the test oracle alike.
+ *   allocatable / requested [N][8]: NodeInfo.Allocatable / Requested; slot 3 = AllowedPodNumber / len(Pods).  A scalar the node does
+ *     not list is 0 on both sides, which is all NodeResourcesFit reads, so the tables carry no presence mask for them.
+ *   pod_fit_req [..][8]: what NodeInfo.AddPod / RemovePod charges (slot 3 = 1); pod_quota_req + pod_quota_req_present:
+ *     computePodResourceRequest (:865-882), what the quota's Used moves by.
+ *   pod_flags: SPX_PREEMPT_POD_IN_QUOTA_SET = the pod is in its ElasticQuotaInfo's `pods` set (deletePodIfPresent only then shrinks
+ *     Used, elasticquota.go:172-187), SPX_PREEMPT_POD_TERMINATING = DeletionTimestamp set (spx_preempt_eligible reads it).
+ *   pod_pdb_mask: bit k = node-local PDB k matches the pod (label selector, namespace, not in DisruptedPods: host work, :899-917);
+ *     node-local PDBs keep the order of the PDB list; pdb_allowed [pdb_ptr[n] .. pdb_ptr[n+1]) their Status.DisruptionsAllowed.
+ *   nom_*: pods nominated to the node (PodNominator): priority, what NodeInfo.AddPod charges, the pending row or -1.
+ * NodeResourcesFit (default args), the rule that a node without victims is no candidate and pickOneNodeForPreemption restate upstream
+ * kube-scheduler code that is not part of the reference tree. */
+#define SPX_PREEMPT_MAX_NODE_PODS 256
+#define SPX_PREEMPT_MAX_NODE_PDBS 32
+#define SPX_PREEMPT_POD_IN_QUOTA_SET 1
+#define SPX_PREEMPT_POD_TERMINATING 2
+#define SPX_PREEMPT_ST_CANDIDATE 0     /* victims found: the cell takes part in the pick */
+#define SPX_PREEMPT_ST_NO_VICTIMS 1    /* "No victims found on node ..." (UnschedulableAndUnresolvable)         :596-599 */
+#define SPX_PREEMPT_ST_NOT_FIT 2       /* the Filter fails with every potential victim removed                  :607-609 */
+#define SPX_PREEMPT_ST_QUOTA 3         /* "global quota max exceeded"                                           :614-619 */
+#define SPX_PREEMPT_ST_ALL_REPRIEVED 4 /* success without a victim: upstream drops the node                              */
+#define SPX_PREEMPT_ST_REMOVE_TWICE 5  /* nodeInfo.RemovePod of a pod already removed: the node returns an error :639, :647 */
+#define SPX_PREEMPT_ST_SKIPPED 6       /* excluded by node_mask, or the node is absent                                   */
+typedef struct spx_preempt_nodes_soa {
+  int64_t n_nodes;
+  const uint8_t* present;
+  const int64_t* allocatable;
+  const int64_t* requested;
+  const int32_t* pod_ptr;
+  const int32_t* pod_priority;
+  const int64_t* pod_start;
+  const int32_t* pod_ns;
+  const int64_t* pod_fit_req;
+  const int64_t* pod_quota_req;
+  const uint8_t* pod_quota_req_present;
+  const uint8_t* pod_flags;
+  const uint32_t* pod_pdb_mask;
+  const int32_t* pod_hi_order;
+  const int32_t* nom_ptr;
+  const int32_t* nom_priority;
+  const int64_t* nom_fit_req;
+  const int64_t* nom_pending_row;
+  const int32_t* pdb_ptr;
+  const int32_t* pdb_allowed;
+} spx_preempt_nodes_soa;
+
+/* per pending pod row: what NodeResourcesFit reads of the preemptor (computePodResourceRequest-style vector, slot 3 unused: a pod
+ * counts once).  A scalar request of 0 and an absent one behave alike in fitsRequest, so there is no presence mask. */
+typedef struct spx_preempt_pods_soa {
+  int64_t n_pods;
+  const int64_t* fit_req;
+} spx_preempt_pods_soa;
+
+/* what spx_flatten_preempt_nodes reads besides the node objects: the assigned pods (any order; `assigned` supplies namespace, priority
+ * and containers), where and since when they run, set membership, PDB matches as indices into pdb_allowed (ascending per pod), and the
+ * nominated pods.  start_ns: Status.StartTime, or the caller's "now" where it is nil (GetPodStartTime).  node_present NULL = all. */
+typedef struct spx_preempt_objects {
+  int64_t n_assigned;
+  const spx_pod_objects* assigned;
+  const int64_t* assigned_node;
+  const int64_t* assigned_start_ns;
+  const uint8_t* assigned_in_quota_set;
+  const uint8_t* assigned_terminating;
+  const int32_t* assigned_pdb_ptr;
+  const int32_t* assigned_pdb;
+  int32_t n_pdbs;
+  const int32_t* pdb_allowed;
+  int64_t n_nominated;
+  const spx_pod_objects* nominated;
+  const int64_t* nominated_node;
+  const int64_t* nominated_pending_row;
+  const uint8_t* node_present;
+} spx_preempt_objects;
+
 /* NetworkOverhead bookkeeping of the sequential commit loop: what binding pending pod p adds to the AppGroup scheduled lists the
  * later pods see.  Entries of pod p: eff_key / eff_max_cost [eff_ptr[p], eff_ptr[p+1]); eff_max_cost >= 0: workload key eff_key gains
  * the pair (p's node, that MaxNetworkCost); -1: the key merely stops scoring equally.  Built by spx_flatten_net_commit. */
@@ -780,6 +859,9 @@ typedef struct spx_net_commit_soa {
  *                                              pkg/noderesourcetopology/pluginhelpers.go:105-173, nodeconfig/topologymanager.go:78-162, pkg/util/resource.go:51-85, cache/store.go:315-356
  *   spx_flatten_net_topo                       populateCostMap                         networkoverhead.go:448-497
  *   spx_flatten_quota                          ElasticQuotaInfos (used / min / max, nominated pods)   pkg/capacityscheduling/elasticquota.go:48-123
+ *   spx_preempt_dry_run + spx_fetch_preempt_*  CapacityScheduling.PostFilter: SelectVictimsOnNode per (pod, node), pickOneNodeForPreemption
+ *                                              capacity_scheduling.go:331-348, :486-677, :889-934
+ *   spx_preempt_eligible                       preemptor.PodEligibleToPreemptOthers    capacity_scheduling.go:409-484
  *   spx_eval_best + spx_fetch_best             upstream prioritizeNodes + selectHost input (sum of weight x score over feasible nodes)
  *   spx_decide + spx_fetch_best                the same decision input without materialising the per-plugin tables
  *   spx_commit_sequential                      upstream scheduleOne repeated over the queue, with trimaran's bind-time bookkeeping
@@ -888,6 +970,36 @@ int spx_fetch_prefilter(spx_engine* e, int plugin, int64_t row_begin, int64_t ro
  * pass_mask bit s = named slot s closed, open_mask bit s = named slot s still open after the last node, gap [groups][n_slots] =
  * req - S_g[last present node] for an open slot (what the reference's "resource gap" lists), 0 otherwise. */
 int spx_fetch_cosched_gap(spx_engine* e, int32_t group_begin, int32_t group_end, uint32_t* pass_mask, uint32_t* open_mask, int64_t* gap);
+
+/* The preemption dry run.  Tables: spx_upload_quota WITH min (namespace, priority, quota request and the nominated sums of a
+ * preemptor are formed exactly as CapacityScheduling.PreFilter's: a snapshot without quotas is a table whose has_quota is all 0),
+ * spx_upload_preempt_nodes, spx_upload_preempt_pods.  Every one of these uploads (and spx_update_quota_used) marks earlier results stale.
+ * SPX_ERR_ARG, the text naming the node: more than SPX_PREEMPT_MAX_NODE_PODS pods or SPX_PREEMPT_MAX_NODE_PDBS PDBs on a node, a
+ * negative request or allocatable, a slot whose absolute values sum to 2^62 or more (device sums are int64), a list that is not in walk
+ * order, a pod_hi_order that is no permutation, a PDB bit outside the node's PDBs.
+ * spx_preempt_dry_run: rows[n_rows] are pod rows of the uploaded batch (any order, gaps allowed, no duplicates needed); node_mask
+ * [n_rows][n_nodes], NULL = all, 0 = the Filter status of that node was UnschedulableAndUnresolvable (upstream's
+ * nodesWherePreemptionMightHelp).  All preemptors see the same frozen snapshot and every (preemptor, node) cell starts from a fresh copy
+ * of the node and of the ElasticQuotaInfos, as the reference's per-node clone does.  Asynchronous on the engine stream;
+ * spx_last_eval_ms reports its device time.  The call holds 32 bytes per cell (n_rows rounded up to 64, times n_nodes) plus 320 bytes
+ * per row; a row list whose records do not fit the device's free memory is refused with SPX_ERR_ARG before anything is allocated.
+ * SPX_ERR_STATE without the quota tables (with min) or the preempt tables.
+ * spx_fetch_preempt_cells / _pick address the rows by their index i in the row list of the last dry run: status u8, n_victims and
+ * n_violations int32 [i_end - i_begin][n_nodes] (each may be NULL); pick: node (-1 = no candidate), the picked cell's n_victims and
+ * n_violations, the number of CANDIDATE cells, and the size of the final tie set (upstream takes "the first" of an unordered map; the
+ * lowest node index of the set is returned).  Order of pickOneNodeForPreemption: fewest violations, lowest highest-victim priority,
+ * smallest sum of (priority + 2^31), fewest victims, latest earliest-start-time among the highest-priority victims.
+ * spx_fetch_preempt_victims recomputes one cell and returns the victims as positions in the node's list, most important first
+ * (:672-675); *n_out is written even when it exceeds cap (SPX_ERR_ARG then).  *status_out (may be NULL) = the cell's status. */
+int spx_upload_preempt_nodes(spx_engine* e, const spx_preempt_nodes_soa* t);
+int spx_upload_preempt_pods(spx_engine* e, const spx_preempt_pods_soa* t);
+int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* node_mask);
+int spx_fetch_preempt_cells(spx_engine* e, int64_t i_begin, int64_t i_end, uint8_t* status, int32_t* n_victims, int32_t* n_violations);
+/* the keys pickOneNodeForPreemption compares, per cell [i_end - i_begin][n_nodes] (each may be NULL; 0 where the cell is no CANDIDATE): the
+ * highest victim priority, the sum of (priority + 2^31) over the victims, the earliest start time among the victims of that priority */
+int spx_fetch_preempt_keys(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* hi_priority, int64_t* priority_sum, int64_t* start);
+int spx_fetch_preempt_pick(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* node, int32_t* n_victims, int32_t* n_violations, int32_t* n_candidates, int32_t* n_ties);
+int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* pod_pos_out, int32_t cap, int32_t* n_out, int32_t* status_out);
 
 /* optional per-(pod,node) feasibility mask for normalizing score plugins: uint8 [n_pods][n_nodes],
  * non-zero = node passed Filter for that pod (upstream scores feasible nodes only).  NULL clears it. */
@@ -1340,6 +1452,23 @@ int spx_nrt_post_eviction(const spx_nrt_objects* nrt, const spx_resource_classes
  * (capacity_scheduling.go:248-250), i.e. total minus the namespace's own share; nom_* are the nominated pods
  * grouped by namespace (nom_ptr[NS+1]); n_nominated entries. */
 int spx_flatten_quota(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_quota_objects* q, int32_t* pod_ns, int32_t* pod_priority, int64_t* pod_req, uint8_t* pod_req_present, int64_t* agg_used, uint8_t* agg_used_present, int64_t* agg_min, uint8_t* agg_min_present, int64_t* other_nominated, uint8_t* other_nominated_present, int32_t* nom_ptr, int32_t* nom_priority, int64_t* nom_pending_index, int64_t* nom_req, uint8_t* nom_req_present);
+
+/* Preemption dry run, host side.  spx_flatten_preempt_nodes: node objects + spx_preempt_objects -> the columns of
+ * spx_preempt_nodes_soa.  Requests are formed as spx_flatten_quota forms them (q supplies the scalar slots); pod_fit_req is the same
+ * vector with slot 3 = 1.  *n_pods_out / *n_nom_out / *n_pdb_out are written first; called with every output column NULL the call
+ * only counts (and still checks).  Columns: present [N], allocatable / requested [N][8], pod_ptr / nom_ptr / pdb_ptr [N+1], the pod
+ * columns [*n_pods_out] (pod_src: index of the table's pod in `o->assigned`), the nominated columns [*n_nom_out], pdb_allowed
+ * [*n_pdb_out].  Pods on an absent node, or with node -1, are left out.  SPX_ERR_ARG with *bad_out = the node (or -1 - the assigned
+ * pod's index for a request it cannot hold): more than SPX_PREEMPT_MAX_NODE_PODS pods or SPX_PREEMPT_MAX_NODE_PDBS distinct PDBs on
+ * a node, a request in a scalar outside the quota's slots, a negative request, a slot whose absolute values sum to 2^62 or more. */
+int spx_flatten_preempt_nodes(const spx_node_objects* nodes, const spx_resource_classes* rc, const spx_quota_objects* q, const spx_preempt_objects* o, int64_t* n_pods_out, int64_t* n_nom_out, int64_t* n_pdb_out, int64_t* bad_out, uint8_t* present, int64_t* allocatable, int64_t* requested, int32_t* pod_ptr, int32_t* pod_src, int32_t* pod_priority, int64_t* pod_start, int32_t* pod_ns, int64_t* pod_fit_req, int64_t* pod_quota_req, uint8_t* pod_quota_req_present, uint8_t* pod_flags, uint32_t* pod_pdb_mask, int32_t* pod_hi_order, int32_t* nom_ptr, int32_t* nom_priority, int64_t* nom_fit_req, int64_t* nom_pending_row, int32_t* pdb_ptr, int32_t* pdb_allowed);
+/* the checks spx_upload_preempt_nodes applies, host only: SPX_OK, or SPX_ERR_ARG with *bad_node_out = the first offending node */
+int spx_preempt_check(const spx_preempt_nodes_soa* t, int64_t* bad_node_out);
+/* preemptor.PodEligibleToPreemptOthers (:409-484) for n pods: ns / priority / preempt_never of the pod, nominated_node (-1 = none, an
+ * absent node answers eligible as a nil NodeInfo does), nominated_unresolvable = the nominated node's Filter status code was
+ * UnschedulableAndUnresolvable, more_than_min = usedOverMinWith(nominatedPodsReqInEQWithPodReq) of the pod (read only when its
+ * namespace has a quota), over_min [n_namespaces] = usedOverMin() of each quota.  Host only. */
+int spx_preempt_eligible(const spx_preempt_nodes_soa* t, const spx_quota_objects* q, const uint8_t* over_min, int64_t n, const int32_t* ns, const int32_t* priority, const uint8_t* preempt_never, const int64_t* nominated_node, const uint8_t* nominated_unresolvable, const uint8_t* more_than_min, uint8_t* eligible_out);
 
 /* ------------------------------------------------------------------ wire format -> object tables (first slice)
  *

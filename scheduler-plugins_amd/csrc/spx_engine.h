@@ -249,6 +249,14 @@ struct spx_engine {
   bool q_has_min = false;
   size_t q_n_nominated = 0;
   const int64_t* q_agg_dyn = nullptr;  // set while the sequential commit loop runs: k_quota reads the aggregate from the device
+  // CapacityScheduling.PostFilter, the preemption dry run (spx_preempt.hip): the uploaded tables (k_preempt_marks completes the pods' marks), and the
+  // last dry run's row list, node mask, row records, cells and picks.  pre_marks_valid: the marks describe the quota and node tables
+  // in place; pre_valid: so do the results (every upload of either clears both)
+  DevBuf d_pre_nodes, d_pre_podrec, d_pre_noms, d_pre_pdb_allowed;  // spx::PreemptNode / PreemptPod / PreemptNom records, packed by the upload
+  DevBuf d_pre_pod_fit, d_pre_rows, d_pre_mask, d_pre_rec, d_pre_cells, d_pre_pick, d_pre_one;
+  bool pre_nodes = false, pre_pods = false, pre_marks_valid = false, pre_valid = false, pre_has_mask = false;
+  int64_t pre_n_rows = 0, pre_row_stride = 0;
+  std::vector<int32_t> h_pre_pod_ptr, h_pre_hi;  // host copies: spx_fetch_preempt_victims orders a cell's victim set by them
   // NetworkOverhead in the commit loop: per-pod effects + the workload pair lists rebuilt with room to grow
   std::vector<int32_t> h_pair_ptr, h_eff_ptr, h_eff_key;
   std::vector<uint8_t> h_key_flag;            // host copy of key_score_equally (spx_update_net_placed edits it)

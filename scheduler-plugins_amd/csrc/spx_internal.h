@@ -698,6 +698,93 @@ struct QuotaArgs {
 };
 void launch_quota(const QuotaArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- CapacityScheduling.PostFilter: the preemption dry run (kernels_preempt.hip)
+struct PreemptCell {  // one (preemptor, node) cell: the status and the keys pickOneNodeForPreemption reads
+  int64_t prio_sum;   // sum over the victims of priority + 2^31
+  int64_t start;      // earliest start time among the victims of the highest priority
+  int32_t hi_prio;
+  int32_t n_victims;
+  int32_t n_violations;
+  int32_t status;     // SPX_PREEMPT_ST_*
+};
+static_assert(sizeof(PreemptCell) == 32, "the memory a dry run takes is stated as 32 bytes per cell");
+// the uploaded tables as records, so that a wave reads a node and its pods through one base pointer each (wave-uniform loads)
+struct PreemptPod {
+  int64_t fit[SPX_QUOTA_SLOTS];   // pod_fit_req
+  int64_t qreq[SPX_QUOTA_SLOTS];  // pod_quota_req
+  int64_t start;
+  int32_t prio;
+  int32_t ns;
+  uint32_t pdb_mask;
+  int32_t hi_order;   // position k of the node's most-important-first order -> position in the list
+  uint8_t qreq_present;
+  uint8_t marks;      // upload: bit 0 = in the quota's set; k_preempt_marks adds bit 1: the namespace has a quota, bit 2: removed when a
+                      // preemptor of another namespace borrows back (step b's third case)
+  uint8_t pad[6];
+};
+struct PreemptNode {
+  int64_t alloc[SPX_QUOTA_SLOTS];
+  int64_t requested[SPX_QUOTA_SLOTS];
+  int32_t pod_begin, pod_end, nom_begin, nom_end, pdb_begin, pdb_end;
+  int32_t present;
+  int32_t pad;
+};
+struct PreemptNom {
+  int64_t fit[SPX_QUOTA_SLOTS];
+  int64_t row;  // pending row, -1 = not in the batch
+  int32_t prio;
+  int32_t pad;
+};
+static_assert(sizeof(PreemptPod) == 160 && sizeof(PreemptNode) == 160 && sizeof(PreemptNom) == 80, "record layouts");
+constexpr int kPreemptRowFields = 36;  // int64 columns of the per-preemptor record, [field][row_stride]: see k_preempt_rows
+struct PreemptArgs {
+  int64_t n_nodes;
+  int64_t n_rows;
+  int64_t row_stride;        // n_rows rounded up to 64: cells are [node][row_stride], row records [field][row_stride]
+  int64_t node_begin;        // the launch covers nodes [node_begin, node_begin + grid.x)
+  const int64_t* rows;       // [n_rows] pod rows of the batch
+  const uint8_t* node_mask;  // [n_rows][n_nodes] or NULL
+  // the quota tables (QuotaArgs' columns, plus Used presence and Min)
+  int32_t n_namespaces;
+  const int32_t* pod_ns;
+  const int32_t* pod_priority;
+  const int64_t* pod_req;
+  const uint8_t* pod_req_present;
+  const uint8_t* has_quota;
+  const int64_t* used;
+  const uint8_t* used_present;
+  const int64_t* min;
+  const uint8_t* min_present;
+  const int64_t* max;
+  const uint8_t* max_present;
+  int64_t agg_used[SPX_QUOTA_SLOTS];
+  uint32_t agg_used_present;
+  int64_t agg_min[SPX_QUOTA_SLOTS];
+  uint32_t agg_min_present;
+  const int64_t* other_nominated;
+  const uint8_t* other_nominated_present;
+  const int32_t* q_nom_ptr;
+  const int32_t* q_nom_priority;
+  const int64_t* q_nom_pending_index;
+  const int64_t* q_nom_req;
+  const uint8_t* q_nom_req_present;
+  // spx_preempt_pods_soa / spx_preempt_nodes_soa
+  const int64_t* pre_fit;    // [P][8]
+  const PreemptNode* nodes;
+  PreemptPod* pods;          // (k_preempt_marks completes `marks`)
+  const PreemptNom* noms;
+  const int32_t* pdb_allowed;
+  // results
+  int64_t* row_rec;          // [kPreemptRowFields][row_stride]
+  PreemptCell* cells;        // [grid.x][row_stride]
+  uint32_t* victims_out;     // when set: n_rows == 1 and the lane writes the cell's 256-bit victim mask (bit = position in the node's list)
+  int32_t* pick;             // [5][row_stride]: node, n_victims, n_violations, n_candidates, n_ties
+};
+void launch_preempt_marks(const PreemptArgs& a, hipStream_t s);
+void launch_preempt_rows(const PreemptArgs& a, hipStream_t s);
+void launch_preempt_cells(const PreemptArgs& a, unsigned n_nodes_launch, hipStream_t s);
+void launch_preempt_pick(const PreemptArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- sequential commit with Filter plugins (kernels_commit.hip)
 // Bookkeeping of ONE bound pod (row `pod`, node = best_node[pod]) on the engine's device tables: what the reference's Reserve /
 // assume-time hooks do between two scheduling cycles.  NULL table groups are skipped.

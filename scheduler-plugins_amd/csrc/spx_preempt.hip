@@ -1,0 +1,349 @@
+// spx_preempt.hip — the preemption dry run's entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
+// spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip, and the fetches.  State: spx_engine.h.
+#include "spx_engine.h"
+
+namespace {
+
+constexpr int S = SPX_QUOTA_SLOTS;
+constexpr int64_t kSumLimit = int64_t{1} << 62;
+
+// The first node the device cannot take, or -1: the limits of include/spx.h, and everything the kernels index with.
+int64_t preempt_bad_node(const spx_preempt_nodes_soa* t, std::string* why) {
+  auto bad = [&](int64_t n, const char* text) {
+    if (why) *why = text;
+    return n;
+  };
+  const int64_t N = t->n_nodes;
+  if (t->pod_ptr[0] != 0 || t->nom_ptr[0] != 0 || t->pdb_ptr[0] != 0) return bad(0, "a CSR does not start at 0");
+  // per slot: sum of |values| over everything a cell can add up (one node's side at a time is what a lane sums, but the bound is
+  // kept global: it is the one spx_cosched_check states)
+  uint64_t total[S] = {0};
+  auto account = [&](const int64_t* v) {
+    for (int s = 0; s < S; ++s) {
+      if (v[s] < 0) return false;
+      total[s] += static_cast<uint64_t>(v[s]);
+      if (total[s] >= static_cast<uint64_t>(kSumLimit)) return false;
+    }
+    return true;
+  };
+  std::vector<uint8_t> seen(SPX_PREEMPT_MAX_NODE_PODS);
+  for (int64_t n = 0; n < N; ++n) {
+    const int64_t p0 = t->pod_ptr[n], p1 = t->pod_ptr[n + 1], L = p1 - p0;
+    if (L < 0 || t->nom_ptr[n + 1] < t->nom_ptr[n] || t->pdb_ptr[n + 1] < t->pdb_ptr[n]) return bad(n, "a CSR pointer decreases");
+    if (L > SPX_PREEMPT_MAX_NODE_PODS) return bad(n, "more than SPX_PREEMPT_MAX_NODE_PODS pods on the node");
+    const int n_pdb = t->pdb_ptr[n + 1] - t->pdb_ptr[n];
+    if (n_pdb > SPX_PREEMPT_MAX_NODE_PDBS) return bad(n, "more than SPX_PREEMPT_MAX_NODE_PDBS PDBs among the node's pods");
+    if (!account(t->allocatable + n * S) || !account(t->requested + n * S)) return bad(n, "a negative quantity, or a slot whose values sum to 2^62 or more");
+    std::fill(seen.begin(), seen.begin() + L, 0);
+    for (int64_t j = p0; j < p1; ++j) {
+      if (!account(t->pod_fit_req + j * S) || !account(t->pod_quota_req + j * S)) return bad(n, "a negative request, or a slot whose values sum to 2^62 or more");
+      if (n_pdb < 32 && (t->pod_pdb_mask[j] >> n_pdb)) return bad(n, "a PDB bit outside the node's PDBs");
+      if (j > p0 && (t->pod_priority[j] < t->pod_priority[j - 1] || (t->pod_priority[j] == t->pod_priority[j - 1] && t->pod_start[j] > t->pod_start[j - 1])))
+        return bad(n, "the node's pods are not in walk order (least important first)");
+      const int32_t h = t->pod_hi_order[j];
+      if (h < 0 || h >= L || seen[h]) return bad(n, "pod_hi_order is no permutation of the node's positions");
+      seen[h] = 1;
+    }
+    for (int64_t k = 1; k < L; ++k) {  // most important first, ties by position
+      const int64_t x = p0 + t->pod_hi_order[p0 + k - 1], y = p0 + t->pod_hi_order[p0 + k];
+      const bool ordered = t->pod_priority[x] > t->pod_priority[y] ||
+                           (t->pod_priority[x] == t->pod_priority[y] && (t->pod_start[x] < t->pod_start[y] || (t->pod_start[x] == t->pod_start[y] && x < y)));
+      if (!ordered) return bad(n, "pod_hi_order is not most important first with ties by position");
+    }
+    for (int64_t j = t->nom_ptr[n]; j < t->nom_ptr[n + 1]; ++j)
+      if (!account(t->nom_fit_req + j * S)) return bad(n, "a negative request, or a slot whose values sum to 2^62 or more");
+  }
+  return -1;
+}
+
+bool preempt_columns_present(const spx_preempt_nodes_soa* t) {
+  if (!t || t->n_nodes <= 0 || !t->present || !t->allocatable || !t->requested || !t->pod_ptr || !t->nom_ptr || !t->pdb_ptr) return false;
+  const int64_t A = t->pod_ptr[t->n_nodes], M = t->nom_ptr[t->n_nodes], B = t->pdb_ptr[t->n_nodes];
+  if (A < 0 || M < 0 || B < 0) return false;
+  if (A > 0 && (!t->pod_priority || !t->pod_start || !t->pod_ns || !t->pod_fit_req || !t->pod_quota_req || !t->pod_quota_req_present || !t->pod_flags ||
+                !t->pod_pdb_mask || !t->pod_hi_order))
+    return false;
+  if (M > 0 && (!t->nom_priority || !t->nom_fit_req || !t->nom_pending_row)) return false;
+  return B == 0 || t->pdb_allowed;
+}
+
+spx::PreemptArgs preempt_args(spx_engine* e) {
+  spx::PreemptArgs a{};
+  a.n_nodes = e->n_nodes;
+  a.n_rows = e->pre_n_rows;
+  a.row_stride = e->pre_row_stride;
+  a.rows = static_cast<const int64_t*>(e->d_pre_rows.p);
+  a.node_mask = e->pre_has_mask ? static_cast<const uint8_t*>(e->d_pre_mask.p) : nullptr;
+  a.n_namespaces = e->q_n_namespaces;
+  a.pod_ns = static_cast<const int32_t*>(e->d_q_pod_ns.p);
+  a.pod_priority = static_cast<const int32_t*>(e->d_q_pod_prio.p);
+  a.pod_req = static_cast<const int64_t*>(e->d_q_pod_req.p);
+  a.pod_req_present = static_cast<const uint8_t*>(e->d_q_pod_reqp.p);
+  a.has_quota = static_cast<const uint8_t*>(e->d_q_has.p);
+  a.used = static_cast<const int64_t*>(e->d_q_used.p);
+  a.used_present = static_cast<const uint8_t*>(e->d_q_usedp.p);
+  a.min = static_cast<const int64_t*>(e->d_q_min.p);
+  a.min_present = static_cast<const uint8_t*>(e->d_q_minp.p);
+  a.max = static_cast<const int64_t*>(e->d_q_max.p);
+  a.max_present = static_cast<const uint8_t*>(e->d_q_maxp.p);
+  std::memcpy(a.agg_used, e->q_agg_used, sizeof a.agg_used);
+  std::memcpy(a.agg_min, e->q_agg_min, sizeof a.agg_min);
+  a.agg_used_present = e->q_agg_used_present;
+  a.agg_min_present = e->q_agg_min_present;
+  a.other_nominated = static_cast<const int64_t*>(e->d_q_other.p);
+  a.other_nominated_present = static_cast<const uint8_t*>(e->d_q_otherp.p);
+  a.q_nom_ptr = static_cast<const int32_t*>(e->d_q_nom_ptr.p);
+  a.q_nom_priority = static_cast<const int32_t*>(e->d_q_nom_prio.p);
+  a.q_nom_pending_index = static_cast<const int64_t*>(e->d_q_nom_idx.p);
+  a.q_nom_req = static_cast<const int64_t*>(e->d_q_nom_req.p);
+  a.q_nom_req_present = static_cast<const uint8_t*>(e->d_q_nom_reqp.p);
+  a.pre_fit = static_cast<const int64_t*>(e->d_pre_pod_fit.p);
+  a.nodes = static_cast<const spx::PreemptNode*>(e->d_pre_nodes.p);
+  a.pods = static_cast<spx::PreemptPod*>(e->d_pre_podrec.p);
+  a.noms = static_cast<const spx::PreemptNom*>(e->d_pre_noms.p);
+  a.pdb_allowed = static_cast<const int32_t*>(e->d_pre_pdb_allowed.p);
+  a.row_rec = static_cast<int64_t*>(e->d_pre_rec.p);
+  a.cells = static_cast<spx::PreemptCell*>(e->d_pre_cells.p);
+  a.pick = static_cast<int32_t*>(e->d_pre_pick.p);
+  return a;
+}
+
+int preempt_results(spx_engine* e, int64_t i_begin, int64_t i_end) {
+  if (!e->pre_valid) return fail(e, SPX_ERR_STATE, "no preemption dry run since the last upload of its tables");
+  if (i_begin < 0 || i_end > e->pre_n_rows || i_begin > i_end) return fail(e, SPX_ERR_ARG, "preemption rows: index range outside the row list of the dry run");
+  return SPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spx_preempt_check(const spx_preempt_nodes_soa* t, int64_t* bad_node_out) {
+  if (!preempt_columns_present(t) || !bad_node_out) return SPX_ERR_ARG;
+  *bad_node_out = preempt_bad_node(t, nullptr);
+  return *bad_node_out < 0 ? SPX_OK : SPX_ERR_ARG;
+}
+
+int spx_upload_preempt_nodes(spx_engine* e, const spx_preempt_nodes_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  if (!preempt_columns_present(t)) return fail(e, SPX_ERR_ARG, "preempt nodes: NULL column in a non-empty table");
+  std::string why;
+  const int64_t badn = preempt_bad_node(t, &why);
+  if (badn >= 0) return fail(e, SPX_ERR_ARG, "preempt nodes: node " + std::to_string(badn) + ": " + why);
+  SPX_HIP(e, hipSetDevice(e->device));
+  int rc = set_nodes(e, t->n_nodes);
+  if (rc) return rc;
+  e->pre_nodes = e->pre_marks_valid = e->pre_valid = false;
+  const size_t N = static_cast<size_t>(t->n_nodes), A = static_cast<size_t>(t->pod_ptr[N]), M = static_cast<size_t>(t->nom_ptr[N]), B = static_cast<size_t>(t->pdb_ptr[N]);
+  // the columns as records: a wave reads a node and each of its pods through one base pointer
+  std::vector<spx::PreemptNode> nodes(N);
+  std::vector<spx::PreemptPod> pods(A);
+  std::vector<spx::PreemptNom> noms(M);
+  for (size_t n = 0; n < N; ++n) {
+    spx::PreemptNode& r = nodes[n];
+    std::memcpy(r.alloc, t->allocatable + n * S, sizeof r.alloc);
+    std::memcpy(r.requested, t->requested + n * S, sizeof r.requested);
+    r.pod_begin = t->pod_ptr[n], r.pod_end = t->pod_ptr[n + 1], r.nom_begin = t->nom_ptr[n], r.nom_end = t->nom_ptr[n + 1];
+    r.pdb_begin = t->pdb_ptr[n], r.pdb_end = t->pdb_ptr[n + 1], r.present = t->present[n] != 0, r.pad = 0;
+  }
+  for (size_t j = 0; j < A; ++j) {
+    spx::PreemptPod& r = pods[j];
+    std::memcpy(r.fit, t->pod_fit_req + j * S, sizeof r.fit);
+    std::memcpy(r.qreq, t->pod_quota_req + j * S, sizeof r.qreq);
+    r.start = t->pod_start[j], r.prio = t->pod_priority[j], r.ns = t->pod_ns[j], r.pdb_mask = t->pod_pdb_mask[j], r.hi_order = t->pod_hi_order[j];
+    r.qreq_present = t->pod_quota_req_present[j], r.marks = (t->pod_flags[j] & SPX_PREEMPT_POD_IN_QUOTA_SET) ? 1 : 0;
+    std::memset(r.pad, 0, sizeof r.pad);
+  }
+  for (size_t j = 0; j < M; ++j) {
+    spx::PreemptNom& r = noms[j];
+    std::memcpy(r.fit, t->nom_fit_req + j * S, sizeof r.fit);
+    r.row = t->nom_pending_row[j], r.prio = t->nom_priority[j], r.pad = 0;
+  }
+  struct Drain {  // the staged records live until the copies have landed
+    spx_engine* e;
+    ~Drain() { (void)hipStreamSynchronize(e->stream); }
+  } drain{e};
+  if ((rc = upload(e, e->d_pre_nodes, nodes.data(), N * sizeof(spx::PreemptNode))) || (rc = upload(e, e->d_pre_podrec, pods.data(), A * sizeof(spx::PreemptPod))) ||
+      (rc = upload(e, e->d_pre_noms, noms.data(), M * sizeof(spx::PreemptNom))) || (rc = upload(e, e->d_pre_pdb_allowed, t->pdb_allowed, B * 4)))
+    return rc;
+  e->h_pre_pod_ptr.assign(t->pod_ptr, t->pod_ptr + N + 1);
+  e->h_pre_hi.assign(t->pod_hi_order, t->pod_hi_order + A);  // (an empty column may be NULL: A == 0 then)
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->pre_nodes = true;
+  return SPX_OK;
+}
+
+int spx_upload_preempt_pods(spx_engine* e, const spx_preempt_pods_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  if (t->n_pods <= 0 || !t->fit_req) return fail(e, SPX_ERR_ARG, "preempt pods: empty table");
+  uint64_t total[S] = {0};
+  for (int64_t p = 0; p < t->n_pods; ++p)
+    for (int s = 0; s < S; ++s) {
+      const int64_t v = t->fit_req[p * S + s];
+      if (v < 0) return fail(e, SPX_ERR_ARG, "preempt pods: row " + std::to_string(p) + ": a negative request");
+      if ((total[s] += static_cast<uint64_t>(v)) >= static_cast<uint64_t>(kSumLimit))
+        return fail(e, SPX_ERR_ARG, "preempt pods: row " + std::to_string(p) + ": slot " + std::to_string(s) + " sums to 2^62 or more");
+    }
+  SPX_HIP(e, hipSetDevice(e->device));
+  int rc = set_pods(e, t->n_pods);
+  if (rc) return rc;
+  e->pre_pods = e->pre_valid = false;
+  if ((rc = upload(e, e->d_pre_pod_fit, t->fit_req, static_cast<size_t>(t->n_pods) * S * 8))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->pre_pods = true;
+  return SPX_OK;
+}
+
+int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* node_mask) {
+  if (!e) return SPX_ERR_ARG;
+  if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, "preemption dry run: the quota tables (spx_upload_quota with min) are not uploaded");
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, "preemption dry run: spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, "preemption dry run: empty row list");
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, "preemption dry run: rows[" + std::to_string(i) + "] is no row of the batch");
+  SPX_HIP(e, hipSetDevice(e->device));
+  const size_t N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(spx::round_up(n_rows, 64));
+  if (R > (size_t{1} << 24) || N > (size_t{1} << 31)) return fail(e, SPX_ERR_ARG, "preemption dry run: more than 2^24 rows");
+  const size_t cell_bytes = N * R * sizeof(spx::PreemptCell), rec_bytes = R * spx::kPreemptRowFields * 8, pick_bytes = R * 5 * 4,
+               mask_bytes = node_mask ? static_cast<size_t>(n_rows) * N : 0;
+  {  // refuse what cannot fit instead of failing in hipMalloc: what has to grow against what is free
+    size_t free_b = 0, total_b = 0, grow = 0;
+    SPX_HIP(e, hipMemGetInfo(&free_b, &total_b));
+    const std::pair<const DevBuf*, size_t> want[] = {{&e->d_pre_cells, cell_bytes}, {&e->d_pre_rec, rec_bytes}, {&e->d_pre_pick, pick_bytes},
+                                                      {&e->d_pre_mask, mask_bytes}, {&e->d_pre_rows, static_cast<size_t>(n_rows) * 8}};
+    for (const auto& w : want)
+      if (w.second > w.first->bytes) grow += w.second, free_b += w.first->bytes;  // ensure() frees the old allocation first
+    if (grow > free_b)
+      return fail(e, SPX_ERR_ARG, "preemption dry run: " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
+                                      " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
+  }
+  e->pre_valid = false;
+  int rc;
+  if ((rc = upload(e, e->d_pre_rows, rows, static_cast<size_t>(n_rows) * 8)) || (rc = ensure(e, e->d_pre_rec, rec_bytes)) || (rc = ensure(e, e->d_pre_cells, cell_bytes)) ||
+      (rc = ensure(e, e->d_pre_pick, pick_bytes)))
+    return rc;
+  if (node_mask && (rc = upload(e, e->d_pre_mask, node_mask, mask_bytes))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // rows and node_mask are only borrowed for the call
+  e->pre_has_mask = node_mask != nullptr;
+  e->pre_n_rows = n_rows;
+  e->pre_row_stride = static_cast<int64_t>(R);
+  spx::PreemptArgs a = preempt_args(e);
+  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  if (!e->pre_marks_valid) {
+    spx::launch_preempt_marks(a, e->stream);
+    e->pre_marks_valid = true;
+  }
+  spx::launch_preempt_rows(a, e->stream);
+  spx::launch_preempt_cells(a, static_cast<unsigned>(N), e->stream);
+  spx::launch_preempt_pick(a, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  e->timed = true;
+  e->pre_valid = true;
+  return SPX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// rows [i_begin, i_end) of the cell records, [node][i] on the host
+int fetch_cells(spx_engine* e, int64_t i_begin, int64_t i_end, std::vector<spx::PreemptCell>& h) {
+  if (int rc = preempt_results(e, i_begin, i_end)) return rc;
+  const size_t n = static_cast<size_t>(i_end - i_begin), N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(e->pre_row_stride);
+  h.resize(n * N);
+  if (n == 0) return SPX_OK;
+  SPX_HIP(e, hipSetDevice(e->device));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  SPX_HIP(e, hipMemcpy2D(h.data(), n * sizeof(spx::PreemptCell), static_cast<const spx::PreemptCell*>(e->d_pre_cells.p) + i_begin, R * sizeof(spx::PreemptCell),
+                         n * sizeof(spx::PreemptCell), N, hipMemcpyDeviceToHost));
+  return SPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spx_fetch_preempt_cells(spx_engine* e, int64_t i_begin, int64_t i_end, uint8_t* status, int32_t* n_victims, int32_t* n_violations) {
+  if (!e) return SPX_ERR_ARG;
+  std::vector<spx::PreemptCell> h;
+  if (int rc = fetch_cells(e, i_begin, i_end, h)) return rc;
+  const size_t n = static_cast<size_t>(i_end - i_begin), N = static_cast<size_t>(e->n_nodes);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t node = 0; node < N; ++node) {
+      const spx::PreemptCell& c = h[node * n + i];
+      if (status) status[i * N + node] = static_cast<uint8_t>(c.status);
+      if (n_victims) n_victims[i * N + node] = c.n_victims;
+      if (n_violations) n_violations[i * N + node] = c.n_violations;
+    }
+  return SPX_OK;
+}
+
+int spx_fetch_preempt_keys(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* hi_priority, int64_t* priority_sum, int64_t* start) {
+  if (!e) return SPX_ERR_ARG;
+  std::vector<spx::PreemptCell> h;
+  if (int rc = fetch_cells(e, i_begin, i_end, h)) return rc;
+  const size_t n = static_cast<size_t>(i_end - i_begin), N = static_cast<size_t>(e->n_nodes);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t node = 0; node < N; ++node) {
+      const spx::PreemptCell& c = h[node * n + i];
+      if (hi_priority) hi_priority[i * N + node] = c.hi_prio;
+      if (priority_sum) priority_sum[i * N + node] = c.prio_sum;
+      if (start) start[i * N + node] = c.start;
+    }
+  return SPX_OK;
+}
+
+int spx_fetch_preempt_pick(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* node, int32_t* n_victims, int32_t* n_violations, int32_t* n_candidates,
+                           int32_t* n_ties) {
+  if (!e) return SPX_ERR_ARG;
+  if (int rc = preempt_results(e, i_begin, i_end)) return rc;
+  const size_t n = static_cast<size_t>(i_end - i_begin), R = static_cast<size_t>(e->pre_row_stride);
+  SPX_HIP(e, hipSetDevice(e->device));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  int32_t* const out[5] = {node, n_victims, n_violations, n_candidates, n_ties};
+  for (int k = 0; k < 5; ++k)
+    if (out[k] && n) SPX_HIP(e, hipMemcpy(out[k], static_cast<const int32_t*>(e->d_pre_pick.p) + k * R + i_begin, n * 4, hipMemcpyDeviceToHost));
+  return SPX_OK;
+}
+
+int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* pod_pos_out, int32_t cap, int32_t* n_out, int32_t* status_out) {
+  if (!e || !n_out || cap < 0 || (cap > 0 && !pod_pos_out)) return SPX_ERR_ARG;
+  if (int rc = preempt_results(e, i, i + 1)) return rc;
+  if (node < 0 || node >= e->n_nodes) return fail(e, SPX_ERR_ARG, "preemption victims: node out of range");
+  SPX_HIP(e, hipSetDevice(e->device));
+  constexpr size_t kMaskBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
+  std::lock_guard<std::mutex> g(e->raw_mu);  // one scratch cell: concurrent callers take turns, as in spx_fetch_raw
+  if (int rc = ensure(e, e->d_pre_one, sizeof(spx::PreemptCell) + kMaskBytes)) return rc;
+  // the one cell again, as row 0 of a list of one: the row's record and mask row are addressed through offset pointers
+  spx::PreemptArgs a = preempt_args(e);
+  a.n_rows = 1;
+  a.row_rec += i;
+  if (a.node_mask) a.node_mask += i * e->n_nodes;
+  a.node_begin = node;
+  a.cells = static_cast<spx::PreemptCell*>(e->d_pre_one.p);
+  a.victims_out = reinterpret_cast<uint32_t*>(static_cast<char*>(e->d_pre_one.p) + sizeof(spx::PreemptCell));
+  spx::launch_preempt_cells(a, 1, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  struct {
+    spx::PreemptCell cell;
+    uint32_t mask[kMaskBytes / 4];
+  } h;
+  SPX_HIP(e, hipMemcpyAsync(&h.cell, a.cells, sizeof h.cell, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(h.mask, a.victims_out, kMaskBytes, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  if (status_out) *status_out = h.cell.status;
+  const int32_t p0 = e->h_pre_pod_ptr[node], L = e->h_pre_pod_ptr[node + 1] - p0;
+  int32_t n = 0;
+  for (int32_t k = 0; k < L; ++k) {
+    const int32_t pos = e->h_pre_hi[p0 + k];
+    if (!((h.mask[pos >> 5] >> (pos & 31)) & 1u)) continue;
+    if (n < cap) pod_pos_out[n] = pos;
+    ++n;
+  }
+  *n_out = n;
+  if (n > cap) return fail(e, SPX_ERR_ARG, "preemption victims: " + std::to_string(n) + " victims do not fit cap");
+  return SPX_OK;
+}
+
+}  // extern "C"

@@ -392,6 +392,7 @@ int spx_update_quota_used(spx_engine* e, int64_t n_rows, const int32_t* ns, cons
   if (!e || n_rows < 0 || !agg_used || !agg_used_present || (n_rows && (!ns || !used || !used_present))) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));
   if (!e->quota) return fail(e, SPX_ERR_STATE, "quota delta: upload the quota table first");
+  e->pre_marks_valid = e->pre_valid = false;  // the preemption dry run read the old Used
   constexpr size_t S = SPX_QUOTA_SLOTS;
   for (int64_t i = 0; i < n_rows; ++i)
     if (ns[i] < 0 || ns[i] >= e->q_n_namespaces) return fail(e, SPX_ERR_ARG, "quota delta: namespace index out of range");
@@ -1427,6 +1428,7 @@ int spx_upload_quota(spx_engine* e, const spx_quota_soa* t) {
   if ((rc = upload(e, e->d_q_used, col(t->used), NS * S * 8))) return rc;
   if (NS > 0 && !t->used_present) return fail(e, SPX_ERR_ARG, "quota: NULL column in a non-empty table");
   if ((rc = upload(e, e->d_q_usedp, col(t->used_present), NS))) return rc;
+  e->pre_marks_valid = e->pre_valid = false;  // the preemption dry run read the old tables
   e->q_has_min = t->min && t->min_present;
   if (e->q_has_min) {
     if ((rc = upload(e, e->d_q_min, t->min, NS * S * 8))) return rc;

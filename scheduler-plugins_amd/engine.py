@@ -22,6 +22,7 @@ ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, TOPOSORT, LROC, PEAKS, SYSCH
 NUM_PLUGINS = 10  # SPX_NUM_PLUGINS
 COSCHED = 10  # SPX_PLUGIN_COSCHED: a PreFilter gate without tables or a weight, outside NUM_PLUGINS
 COSCHED_ST = {"BACKED_OFF": 1, "FEW_SIBLINGS": 2, "GATED": 3, "RESOURCE_GAP": 4}  # SPX_COSCHED_ST_*
+PREEMPT_ST = {"CANDIDATE": 0, "NO_VICTIMS": 1, "NOT_FIT": 2, "QUOTA": 3, "ALL_REPRIEVED": 4, "REMOVE_TWICE": 5, "SKIPPED": 6}  # SPX_PREEMPT_ST_*
 
 
 def mask_of(*plugins: int) -> int:
@@ -861,6 +862,126 @@ class Engine:
         out = np.zeros(row_end - row_begin, np.uint8)
         self._ck(self._lib.spx_fetch_prefilter(self._h, plugin, row_begin, row_end, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ------------------------------------------------------------------ CapacityScheduling.PostFilter: the preemption dry run
+    _PREEMPT_NODE_COLS = ("present", "allocatable", "requested", "pod_ptr", "pod_priority", "pod_start", "pod_ns", "pod_fit_req", "pod_quota_req",
+                          "pod_quota_req_present", "pod_flags", "pod_pdb_mask", "pod_hi_order", "nom_ptr", "nom_priority", "nom_fit_req", "nom_pending_row",
+                          "pdb_ptr", "pdb_allowed")
+
+    def flatten_preempt_nodes(self, nodes: Table, rc: Optional[Table], quota: Table, objects: Table) -> dict:
+        """spx_node_objects + spx_preempt_objects -> the columns of spx_preempt_nodes_soa, plus "pod_src" (the table's pods as indices into
+        the assigned-pod objects) and "N" (spx_flatten_preempt_nodes, called once to count and once to fill).  SpxError(SPX_ERR_ARG)
+        names the node, or the assigned pod, the flattener refuses."""
+        fn, N = self._lib.spx_flatten_preempt_nodes, int(nodes.struct.n_nodes)
+        counts = [C.c_int64() for _ in range(4)]  # pods, nominated, PDB budgets, the refused node / pod
+        head = [nodes.ref(), rc.ref() if rc else None, quota.ref(), objects.ref(), *map(C.byref, counts)]
+
+        def call(arrays):
+            rc_ = fn(*head, *arrays)
+            if rc_ != 0:
+                bad = int(counts[3].value)
+                raise self._err(rc_, f"preempt flatten: refused at node {bad}" if bad >= 0 else f"preempt flatten: refused at assigned pod {-1 - bad}")
+
+        call([None] * (len(fn.argtypes) - len(head)))
+        A, M, B = (int(c.value) for c in counts[:3])
+        i32, i64, u8, u32 = np.int32, np.int64, np.uint8, np.uint32
+        cols = dict(present=np.zeros(N, u8), allocatable=np.zeros((N, 8), i64), requested=np.zeros((N, 8), i64), pod_ptr=np.zeros(N + 1, i32),
+                    pod_src=np.zeros(A, i32), pod_priority=np.zeros(A, i32), pod_start=np.zeros(A, i64), pod_ns=np.zeros(A, i32),
+                    pod_fit_req=np.zeros((A, 8), i64), pod_quota_req=np.zeros((A, 8), i64), pod_quota_req_present=np.zeros(A, u8), pod_flags=np.zeros(A, u8),
+                    pod_pdb_mask=np.zeros(A, u32), pod_hi_order=np.zeros(A, i32), nom_ptr=np.zeros(N + 1, i32), nom_priority=np.zeros(M, i32),
+                    nom_fit_req=np.zeros((M, 8), i64), nom_pending_row=np.zeros(M, i64), pdb_ptr=np.zeros(N + 1, i32), pdb_allowed=np.zeros(B, i32))
+        keep = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in cols.items()}  # never hand C a NULL for an empty column
+        call([keep[k].ctypes.data_as(t) for k, t in zip(cols, fn.argtypes[len(head):])])
+        return {"N": N, **cols}
+
+    def load_preempt_objects(self, t: dict) -> dict:
+        """objects.build_preempt_tables' tables through the flatteners to the device: the quota tables, the node side and the pending pods'
+        fit vectors (what computePodResourceRequest gives, as the NodeInfo charges it).  Returns flatten_preempt_nodes' columns."""
+        fq = self.flatten_quota(t["pods"], t["rc"], t["quota"])
+        self.upload_quota(fq)
+        f = self.flatten_preempt_nodes(t["nodes"], t["rc"], t["quota"], t["preempt"])
+        self.upload_preempt_nodes(f)
+        self.upload_preempt_pods(fq["cols"]["pod_req"].reshape(-1, 8))
+        return f
+
+    def preempt_nodes_table(self, f: dict) -> Table:
+        return Table(self._hdr, "spx_preempt_nodes_soa", n_nodes=f["N"], **{k: np.ascontiguousarray(f[k]) for k in self._PREEMPT_NODE_COLS})
+
+    def preempt_check(self, f: dict) -> int:
+        """the first node spx_upload_preempt_nodes would refuse (spx_preempt_check), -1 when the table is within the device's limits"""
+        bad = C.c_int64(-1)
+        rc = self._lib.spx_preempt_check(self.preempt_nodes_table(f).ref(), C.byref(bad))
+        if rc != 0 and bad.value < 0:
+            self._ck_static(rc)
+        return int(bad.value)
+
+    def upload_preempt_nodes(self, f: dict) -> None:
+        """the node side of the dry run: flatten_preempt_nodes' columns (spx_upload_preempt_nodes); earlier results become stale"""
+        self._ck(self._lib.spx_upload_preempt_nodes(self._h, self.preempt_nodes_table(f).ref()))
+        self.n_nodes = f["N"]
+
+    def upload_preempt_pods(self, fit_req) -> None:
+        """fit_req [P][8]: what NodeResourcesFit reads of each pending pod (spx_upload_preempt_pods); earlier results become stale"""
+        fit = np.ascontiguousarray(fit_req, dtype=np.int64).reshape(-1, 8)
+        self._ck(self._lib.spx_upload_preempt_pods(self._h, Table(self._hdr, "spx_preempt_pods_soa", n_pods=len(fit), fit_req=fit).ref()))
+        self.n_pods = len(fit)
+
+    def preempt_dry_run(self, rows, node_mask=None) -> None:
+        """SelectVictimsOnNode for the pod rows `rows` x all nodes and the pick per row (spx_preempt_dry_run); node_mask [len(rows)][n_nodes],
+        0 = excluded.  Asynchronous; the fetches below address a row by its index in `rows`."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        mask = None
+        if node_mask is not None:
+            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
+            if mask.shape != (len(rows), self.n_nodes):
+                raise ValueError("node_mask must be [len(rows)][n_nodes]")
+        self._ck(self._lib.spx_preempt_dry_run(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows),
+                                               mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None))
+        self._preempt_rows = len(rows)
+
+    def preempt_cells(self, i_begin: int = 0, i_end: Optional[int] = None):
+        """(status uint8, n_victims, n_violations), each [i_end - i_begin][n_nodes] (spx_fetch_preempt_cells)"""
+        i_end = getattr(self, "_preempt_rows", 0) if i_end is None else i_end
+        n = max(i_end - i_begin, 0)
+        st, nv, nx = np.zeros((n, self.n_nodes), np.uint8), np.zeros((n, self.n_nodes), np.int32), np.zeros((n, self.n_nodes), np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._ck(self._lib.spx_fetch_preempt_cells(self._h, i_begin, i_end, st.ctypes.data_as(C.POINTER(C.c_uint8)), nv.ctypes.data_as(i32), nx.ctypes.data_as(i32)))
+        return st, nv, nx
+
+    def preempt_keys(self, i_begin: int = 0, i_end: Optional[int] = None):
+        """(highest victim priority int32, sum of priority + 2^31 int64, earliest start among the highest int64), each [rows][n_nodes]"""
+        i_end = getattr(self, "_preempt_rows", 0) if i_end is None else i_end
+        n = max(i_end - i_begin, 0)
+        hi, sm, st = np.zeros((n, self.n_nodes), np.int32), np.zeros((n, self.n_nodes), np.int64), np.zeros((n, self.n_nodes), np.int64)
+        i64 = C.POINTER(C.c_int64)
+        self._ck(self._lib.spx_fetch_preempt_keys(self._h, i_begin, i_end, hi.ctypes.data_as(C.POINTER(C.c_int32)), sm.ctypes.data_as(i64), st.ctypes.data_as(i64)))
+        return hi, sm, st
+
+    def preempt_pick(self, i_begin: int = 0, i_end: Optional[int] = None) -> dict:
+        """pickOneNodeForPreemption per row: node (-1 = none), n_victims, n_violations, n_candidates, n_ties (spx_fetch_preempt_pick)"""
+        i_end = getattr(self, "_preempt_rows", 0) if i_end is None else i_end
+        out = {k: np.zeros(max(i_end - i_begin, 0), np.int32) for k in ("node", "n_victims", "n_violations", "n_candidates", "n_ties")}
+        self._ck(self._lib.spx_fetch_preempt_pick(self._h, i_begin, i_end, *[v.ctypes.data_as(C.POINTER(C.c_int32)) for v in out.values()]))
+        return out
+
+    def preempt_victims(self, i: int, node: int):
+        """(status, victims as positions in the node's list, most important first) of one cell, recomputed (spx_fetch_preempt_victims)"""
+        cap = self._hdr.consts["SPX_PREEMPT_MAX_NODE_PODS"]
+        pos, n, st = np.zeros(cap, np.int32), C.c_int32(), C.c_int32()
+        self._ck(self._lib.spx_fetch_preempt_victims(self._h, i, node, pos.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(n), C.byref(st)))
+        return int(st.value), pos[:n.value].copy()
+
+    def preempt_eligible(self, f: dict, quota: Table, over_min, ns, priority, preempt_never, nominated_node, nominated_unresolvable, more_than_min) -> np.ndarray:
+        """PodEligibleToPreemptOthers per pod from the node table's terminating bits (spx_preempt_eligible, host only)"""
+        u8, i32, i64 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        arr = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
+        om, ns, pr, never = arr(over_min, np.uint8), arr(ns, np.int32), arr(priority, np.int32), arr(preempt_never, np.uint8)
+        nn, un, mm = arr(nominated_node, np.int64), arr(nominated_unresolvable, np.uint8), arr(more_than_min, np.uint8)
+        out = np.zeros(len(ns), np.uint8)
+        self._ck_static(self._lib.spx_preempt_eligible(self.preempt_nodes_table(f).ref(), quota.ref(), om.ctypes.data_as(u8), len(ns), ns.ctypes.data_as(i32),
+                                                       pr.ctypes.data_as(i32), never.ctypes.data_as(u8), nn.ctypes.data_as(i64), un.ctypes.data_as(u8),
+                                                       mm.ctypes.data_as(u8), out.ctypes.data_as(u8)))
+        return out.astype(bool)
 
     def status(self, plugin: int, pod_row: int) -> np.ndarray:
         out = np.empty(self.n_nodes, dtype=np.uint8)

@@ -506,6 +506,78 @@ def build_quota_objects(hdr: Header, res: Resources, namespaces: Sequence[Option
     )
 
 
+# ---------------------------------------------------------------------------------------------------------------- preemption dry run
+# A snapshot for CapacityScheduling.PostFilter as plain dicts (synth.preempt_model builds one; tests/preempt_oracle.py walks it):
+#   {"n_namespaces", "quotas": {ns: {"min", "max", "used": Resource, "pods": set of pod keys}}, "pdbs": [DisruptionsAllowed],
+#    "nodes": [{"present", "alloc": [8], "pods": [pod], "nominated": [pod]}], "pending": [pod]}
+# Resource = {"v": [8 ints], "p": scalar-key mask}; pod = {"key", "ns", "prio", "start", "fit", "req": Resource, "pdbs", "terminating", "row"}.
+PREEMPT_SCALARS = tuple(f"example.com/slot{i}" for i in range(4))  # the names the vector's scalar slots 4..7 travel under
+
+
+def _preempt_fields(r: dict) -> dict:
+    """Resource -> the framework.Resource field names _resource_vec reads"""
+    if any(r["v"][s] and not (r["p"] >> s) & 1 for s in range(4, QUOTA_SLOTS)):
+        raise ValueError("a scalar slot holds a value without its key: an absent key reads 0")
+    return {"MilliCPU": r["v"][0], "Memory": r["v"][1], "EphemeralStorage": r["v"][2], "AllowedPodNumber": r["v"][3],
+            "ScalarResources": {PREEMPT_SCALARS[s - 4]: r["v"][s] for s in range(4, QUOTA_SLOTS) if (r["p"] >> s) & 1}}
+
+
+def _preempt_pod(p: dict) -> dict:
+    """a pod of the model as a one-container v1.Pod whose computePodResourceRequest is p["req"]"""
+    r = p["req"]
+    _preempt_fields(r)
+    req = {"cpu": f"{r['v'][0]}m", "memory": r["v"][1], "ephemeral-storage": r["v"][2]}
+    req.update({PREEMPT_SCALARS[s - 4]: r["v"][s] for s in range(4, QUOTA_SLOTS) if (r["p"] >> s) & 1})
+    return pod([container(req)], priority=p["prio"], ns=p["ns"])
+
+
+def build_preempt_tables(hdr: Header, model: dict) -> dict:
+    """the model as object tables: "nodes", "rc", "pods" (the pending batch), "quota", "preempt" (spx_preempt_objects), and "assigned_at":
+    (node, position in the node's list) of every assigned-pod object, which spx_flatten_preempt_nodes' pod_src refers to.  The node charges
+    of the model's pods must equal their quota requests (fit == req outside slot 3): that is what the flattener forms."""
+    res = Resources()
+    for name in PREEMPT_SCALARS:
+        res.id(name)
+    node_objs = []
+    for n in model["nodes"]:
+        a = n["alloc"]
+        al = {"cpu": f"{a[0]}m", "memory": a[1], "ephemeral-storage": a[2], "pods": a[3]}
+        al.update({PREEMPT_SCALARS[s - 4]: a[s] for s in range(4, QUOTA_SLOTS) if a[s]})
+        node_objs.append(node(al))
+    assigned, assigned_at, nominated, nominated_node = [], [], [], []
+    for i, n in enumerate(model["nodes"]):
+        for k, p in enumerate(n["pods"]):
+            if any(p["fit"][s] != p["req"]["v"][s] for s in range(QUOTA_SLOTS) if s != 3):
+                raise ValueError("build_preempt_tables: a pod's node charge differs from its quota request")
+            assigned.append(p), assigned_at.append((i, k))
+        for p in n["nominated"]:
+            nominated.append(p), nominated_node.append(i)
+    quotas = model["quotas"]
+    namespaces = [None] * model["n_namespaces"]
+    for ns, eq in quotas.items():
+        namespaces[ns] = {"min": _preempt_fields(eq["min"]), "max": _preempt_fields(eq["max"]), "used": _preempt_fields(eq["used"])}
+    quota = build_quota_objects(hdr, res, namespaces, [(p["ns"], p["prio"], p["row"], _preempt_pod(p)) for p in nominated])
+    slots = list(quota.array("scalar_res")[:quota.struct.n_scalar_slots])
+    for name in PREEMPT_SCALARS:  # every scalar of the model gets a slot, whether a quota names it or not
+        if res.id(name) not in slots:
+            slots.append(res.id(name))
+    quota.array("scalar_res")[:len(slots)] = slots
+    quota.struct.n_scalar_slots = len(slots)
+    pdb_lists = [sorted(p["pdbs"]) for p in assigned]
+    u8 = lambda xs: np.array(list(xs), dtype=np.uint8)
+    pre = Table(
+        hdr, "spx_preempt_objects", n_assigned=len(assigned), assigned=build_pod_objects(hdr, res, [_preempt_pod(p) for p in assigned] or [pod()]),
+        assigned_node=np.array([a[0] for a in assigned_at], dtype=np.int64), assigned_start_ns=np.array([p["start"] for p in assigned], dtype=np.int64),
+        assigned_in_quota_set=u8(p["ns"] in quotas and p["key"] in quotas[p["ns"]]["pods"] for p in assigned),
+        assigned_terminating=u8(p["terminating"] for p in assigned), assigned_pdb_ptr=_csr(pdb_lists),
+        assigned_pdb=np.array([x for l in pdb_lists for x in l], dtype=np.int32), n_pdbs=len(model["pdbs"]), pdb_allowed=np.array(model["pdbs"], dtype=np.int32),
+        n_nominated=len(nominated), nominated=build_pod_objects(hdr, res, [_preempt_pod(p) for p in nominated] or [pod()]),
+        nominated_node=np.array(nominated_node, dtype=np.int64), nominated_pending_row=np.array([p["row"] for p in nominated], dtype=np.int64),
+        node_present=u8(n["present"] for n in model["nodes"]))
+    return {"nodes": build_node_objects(hdr, res, node_objs), "rc": res.table(hdr), "pods": build_pod_objects(hdr, res, [_preempt_pod(p) for p in model["pending"]]),
+            "quota": quota, "preempt": pre, "assigned_at": assigned_at}
+
+
 # ---------------------------------------------------------------------------------------------------------------- SySched
 # What the Go side does once per snapshot for pkg/sysched: resolve every pod's seccomp profiles to a syscall set (getSyscalls,
 # sysched.go:124-210), intern the names, and ship the distinct sets, the pods' set ids, the cached host sets and the resident lists.

@@ -748,3 +748,117 @@ def sysched_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, n
     res_objs = [tuple(int(x) for x in res_set_s[res_ptr_s[s]:res_ptr_s[s + 1]]) for s in range(S)]
     return {"objects": objects, "names": names, "sets": sets, "pod_set": pod_set, "host": [host_objs[s] for s in state],
             "residents": [res_objs[s] for s in state], "n_stale_states": int(stale.sum()), "empty_set": empty_id}
+
+
+def preempt_model(n_nodes: int, n_pending: int, seed: int = SEED, pods_per_node: float = 3.0, node_pods=None, n_pdbs: int = 12, quotas: bool = True, scenarios: bool = True) -> dict:
+    """A snapshot for the preemption dry run as plain dicts (objects.build_preempt_tables describes the form).  Few distinct priorities,
+    start times and sizes, so that cells tie at every level of pickOneNodeForPreemption; node sizes from tiny to large and requests from
+    nothing to a whole node, so that a preemptor has anything from one candidate to hundreds; tight and loose quotas, pods outside their
+    quota's set, nominated pods (some of them rows of the batch), PDBs with budgets from -1 to 2, absent nodes.  node_pods: the number
+    of pods per node (cycled) instead of a draw around pods_per_node.  quotas=False: no namespace has an ElasticQuota.  scenarios: from 64 nodes x 64 pods on, _preempt_scenarios' scenes replace the last nodes and rows."""
+    rng = np.random.default_rng(seed)
+    n_ns, n_quota = 8, 5 if quotas else 0
+    pick = lambda xs, p=None: xs[int(rng.choice(len(xs), p=p))]
+    unit = GiB
+
+    def request(big: bool = False):
+        v = [0] * 8
+        v[0] = pick([0, 500, 1000, 2000, 4000, 16000] if big else [0, 500, 1000, 2000])
+        v[1] = pick([0, 1, 2, 4, 8, 32] if big else [0, 1, 2, 4]) * unit
+        v[2] = pick([0, 0, 0, 10]) * unit
+        p = 0
+        g = pick([None, None, 0, 1, 2])
+        if g is not None:
+            v[4], p = g, p | 1 << 4
+        if rng.random() < 0.05:
+            v[5], p = 1, p | 1 << 5
+        return {"v": v, "p": p}
+
+    def pod(key, ns, prio, start, req, row=-1, terminating=False, pdbs=()):
+        fit = list(req["v"])
+        fit[3] = 1
+        return {"key": key, "ns": ns, "prio": prio, "start": start, "fit": fit, "req": req, "pdbs": sorted(pdbs), "terminating": terminating, "row": row}
+
+    pending = [pod(f"pending-{i}", int(rng.integers(n_ns)), pick([5, 50, 500, 5000]), 0, request(big=True), row=i) for i in range(n_pending)]
+    nodes = []
+    for n in range(n_nodes):
+        alloc = [pick([2000, 4000, 8000, 16000, 64000]), pick([4, 8, 16, 32, 128]) * unit, pick([0, 20, 100]) * unit, pick([2, 4, 8, 110, 300]), pick([0, 2, 4, 8]), pick([0, 0, 1]), 0, 0]
+        count = int(node_pods[n % len(node_pods)]) if node_pods is not None else min(int(rng.poisson(pods_per_node)), 256)
+        pods = []
+        for k in range(count):
+            matches = [int(b) for b in rng.choice(n_pdbs, size=min(3, n_pdbs), replace=False) if rng.random() < 0.25] if n_pdbs else []
+            pods.append(pod(f"n{n}-p{k}", int(rng.integers(n_ns)), pick([-(1 << 31), 0, 10, 100, 1000], [0.15, 0.25, 0.25, 0.2, 0.15]), pick([1000, 2000, 3000]),
+                            request(), terminating=bool(rng.random() < 0.05), pdbs=matches))
+        nominated = []
+        if rng.random() < 0.1:
+            for k in range(int(rng.integers(1, 3))):
+                if n_pending and rng.random() < 0.5:
+                    src = pending[int(rng.integers(n_pending))]
+                    nominated.append(dict(src, key=src["key"]))
+                else:
+                    nominated.append(pod(f"n{n}-nom{k}", int(rng.integers(n_ns)), pick([5, 50, 500, 5000]), 0, request()))
+        nodes.append({"present": bool(rng.random() >= 0.02), "alloc": alloc, "pods": pods, "nominated": nominated})
+    eqs = {}
+    for ns in range(n_quota):
+        used, members = {"v": [0] * 8, "p": 0}, set()
+        for node in nodes:
+            for p in node["pods"]:
+                if p["ns"] == ns and rng.random() < 0.85:
+                    members.add(p["key"])
+                    used["v"] = [a + b for a, b in zip(used["v"], p["req"]["v"])]
+                    used["p"] |= p["req"]["p"]
+        if ns == 4:  # a quota without min: newElasticQuotaInfo's zeros, every use is over it
+            mn = {"v": [0] * 8, "p": 0}
+        else:  # around the use: some quotas lend, some borrow
+            f = pick([0.5, 0.9, 1.0, 1.5, 4.0])
+            mp = used["p"] if rng.random() < 0.7 else 0
+            mn = {"v": [int(u * f) if s < 4 or (mp >> s) & 1 else 0 for s, u in enumerate(used["v"])], "p": mp}  # an absent key holds nothing
+        if ns % 2:  # a tight max, scalar keys included
+            mx = {"v": [u + pick([0, 1000, 4000]) * (1 if s == 0 else unit if s < 3 else 1) for s, u in enumerate(used["v"])], "p": used["p"]}
+            mx["v"] = [0 if s == 3 or (s > 3 and not (mx["p"] >> s) & 1) else v for s, v in enumerate(mx["v"])]
+        else:
+            mx = {"v": [(1 << 63) - 1] * 3 + [0] * 5, "p": 0}
+        eqs[ns] = {"min": mn, "max": mx, "used": used, "pods": members}
+    model = {"n_namespaces": n_ns, "quotas": eqs, "pdbs": [pick([-1, 0, 1, 2]) for _ in range(n_pdbs)], "nodes": nodes, "pending": pending}
+    if scenarios and n_nodes >= 64 and n_pending >= 64:
+        _preempt_scenarios(model, pod, quotas)
+    return model
+
+
+def _preempt_scenarios(model: dict, pod, quotas: bool) -> None:
+    """The last 14 nodes and 7 pending rows become seven two-node scenes, one per level of pickOneNodeForPreemption and one for the
+    double removal (capacity_scheduling.go:639, :647).  Scene j is closed to everyone else by two scalar slots nothing else uses: its
+    preemptor asks for 2^j of slot 6 and 2^(6-j) of slot 7, which only its own nodes offer both of.  Victims are pods of namespace 7
+    (no quota), the preemptors have priority 50."""
+    lo, scenes = -(1 << 31), []
+    victim = lambda name, prio, cpu, start=1000, pdbs=(): pod(name, 7, prio, start, {"v": [cpu, 0, 0, 0, 0, 0, 0, 0], "p": 0}, pdbs=pdbs)
+    model["pdbs"].append(0)  # a budget of its own for the first scene: its one match violates it
+    scenes.append(([victim("s0-a", 10, 1000, pdbs=[len(model["pdbs"]) - 1])], [victim("s0-b", 10, 1000)]))  # fewest violations
+    scenes.append(([victim("s1-a", 10, 1000)], [victim("s1-b", 0, 1000)]))                                   # lowest highest priority
+    scenes.append(([victim("s2-a0", 10, 500), victim("s2-a1", 0, 500)], [victim("s2-b", 10, 1000)]))         # smallest sum
+    scenes.append(([victim("s3-a0", 10, 500), victim("s3-a1", lo, 500)], [victim("s3-b", 10, 1000)]))        # equal sums, fewest victims
+    scenes.append(([victim("s4-a", 10, 1000, start=1000)], [victim("s4-b", 10, 1000, start=2000)]))          # latest start
+    scenes.append(([victim("s5-a", 10, 1000)], [victim("s5-b", 10, 1000)]))                                  # the first of a tie of two
+    scenes.append(([], []))
+    n_nodes, n_pending = len(model["nodes"]), len(model["pending"])
+    for j, (a, b) in enumerate(scenes):
+        iso = [1 << j, 1 << (6 - j)]
+        req = {"v": [1000, 0, 0, 0, 0, 0] + iso, "p": 3 << 6}
+        row = n_pending - 7 + j
+        model["pending"][row] = pod(f"pending-{row}", 7, 50, 0, req, row=row)
+        for k, pods in enumerate((a, b)):
+            model["nodes"][n_nodes - 14 + 2 * j + k] = {"present": True, "alloc": [1000, 0, 0, 110, 0, 0] + iso, "pods": pods, "nominated": []}
+    if not quotas:
+        return
+    # the double removal: the preemptor's quota (namespace 5) is over its max with the nominated pod counted, and the node cannot take
+    # the victim back.  Min is set so that the aggregate check passes exactly once the victim is gone; cpu puts the quota over its min.
+    eqs, row, x, y = model["quotas"], n_pending - 1, model["nodes"][n_nodes - 2], model["nodes"][n_nodes - 1]
+    req = dict(model["pending"][row]["req"], v=[1000, 50, 0, 0, 0, 0, 64, 1])
+    gap = [sum(q["used"]["v"][s] for q in eqs.values()) - sum(q["min"]["v"][s] for q in eqs.values()) for s in range(8)]
+    mn = [max(0, gap[s] + req["v"][s]) for s in range(8)]
+    big = max(0, gap[0]) + 1
+    v = pod("s6-v", 5, 0, 1000, {"v": [big, 50, 0, 0, 0, 0, 0, 0], "p": 0})
+    eqs[5] = {"min": {"v": mn, "p": 0xF0}, "max": {"v": [(1 << 63) - 1, 99, (1 << 63) - 1, 0, 0, 0, 0, 0], "p": 0}, "used": {"v": list(v["req"]["v"]), "p": 0}, "pods": {"s6-v"}}
+    model["pending"][row] = pod(f"pending-{row}", 5, 50, 0, req, row=row)
+    x["alloc"], x["pods"] = [big + 999, 100, 0, 110, 0, 0, 64, 1], [v]
+    y["nominated"] = [pod("s6-nom", 5, 500, 0, {"v": [0, 50, 0, 0, 0, 0, 0, 0], "p": 0})]
