@@ -1001,6 +1001,41 @@ int spx_fetch_preempt_keys(spx_engine* e, int64_t i_begin, int64_t i_end, int32_
 int spx_fetch_preempt_pick(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* node, int32_t* n_victims, int32_t* n_violations, int32_t* n_candidates, int32_t* n_ties);
 int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* pod_pos_out, int32_t cap, int32_t* n_out, int32_t* status_out);
 
+/* PreemptionToleration.PostFilter's dry run (pkg/preemptiontoleration/preemption_toleration.go:188-299; kernels_ptol.hip, DESIGN.md
+ * 3.9d): DefaultPreemption's SelectVictimsOnNode with one more predicate per (preemptor, lower-priority pod) pair,
+ * ExemptedFromPreemption (:129-181), decided by the annotations of the pod's PriorityClass (preemption_toleration_policy.go).  There
+ * are no quotas: the call needs the node and pod tables of spx_upload_preempt_nodes / _pods and the side table below, nothing else.
+ * spx_preempt_toleration_soa: one entry per assigned pod in the order of spx_preempt_nodes_soa's pod CSR (n_pods == pod_ptr[N]):
+ *   flags            SPX_PTOL_POD_HAS_CLASS = PriorityClassName is set and the class exists; SPX_PTOL_POD_CLASS_MISSING = it is set and
+ *                    the lister does not have it (:139-142, an error: the node ends with it); neither = the name is empty (:136)
+ *   min_preemptable  Policy.MinimumPreemptablePriority; INT32_MIN for a policy that does not parse (:153-162: no toleration at all,
+ *                    but a PreemptNever preemptor was answered before the parse, :148-150, which HAS_CLASS still carries)
+ *   exempt_until_ns  the pod is exempted from a preemptor of priority < min_preemptable while exempt_until_ns > now (strict, :180):
+ *                    INT64_MAX for TolerationSeconds < 0 (:168) or a pod without a PodScheduled=True condition (:173-176), else
+ *                    scheduledAt + time.Duration(TolerationSeconds) * time.Second with the product wrapped to int64 as Go wraps it
+ *                    and the sum clamped to int64 (Time.Add does not wrap).  spx_flatten_preempt_toleration forms all three.
+ * A pod of priority < the preemptor's is a potential victim unless it is exempted; if any such pod's class is missing the cell's status
+ * is SPX_PREEMPT_ST_CLASS_ERROR, whatever else holds.  NO_VICTIMS, NOT_FIT, ALL_REPRIEVED, CANDIDATE, SKIPPED, the five keys and the
+ * pick are spx_preempt_dry_run's; QUOTA and REMOVE_TWICE cannot occur.
+ * spx_upload_preempt_toleration: SPX_ERR_STATE before spx_upload_preempt_nodes; SPX_ERR_ARG when n_pods differs from the node table's
+ * pod count or an entry has both flags.  It marks earlier results stale; a later spx_upload_preempt_nodes drops the table.
+ * spx_preempt_toleration_dry_run: rows / node_mask as in spx_preempt_dry_run; priority / preempt_never [n_rows] are the preemptors'
+ * PodPriority and PreemptionPolicy == Never, per entry of rows; now_ns = the plugin's curTime, INT64_MAX is refused (SPX_ERR_ARG: an
+ * exempt_until_ns of INT64_MAX means "for ever").  No quota upload is needed.  Memory: 32 bytes per cell plus 80 bytes per row, checked
+ * against the device's free memory first; at most 2^24 rows; spx_last_eval_ms reports its device time.
+ * spx_fetch_preempt_cells / _keys / _pick / _victims answer for whichever of the two dry runs ran last. */
+#define SPX_PREEMPT_ST_CLASS_ERROR 7   /* a lower-priority pod names a PriorityClass that does not exist           ptol :139-142, :225-228 */
+#define SPX_PTOL_POD_HAS_CLASS 1
+#define SPX_PTOL_POD_CLASS_MISSING 2
+typedef struct spx_preempt_toleration_soa {
+  int64_t n_pods;
+  const int32_t* min_preemptable;
+  const int64_t* exempt_until_ns;
+  const uint8_t* flags;
+} spx_preempt_toleration_soa;
+int spx_upload_preempt_toleration(spx_engine* e, const spx_preempt_toleration_soa* t);
+int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns, const uint8_t* node_mask);
+
 /* optional per-(pod,node) feasibility mask for normalizing score plugins: uint8 [n_pods][n_nodes],
  * non-zero = node passed Filter for that pod (upstream scores feasible nodes only).  NULL clears it. */
 int spx_upload_feasible_mask(spx_engine* e, const uint8_t* mask, int64_t n_pods, int64_t n_nodes);
@@ -1469,6 +1504,29 @@ int spx_preempt_check(const spx_preempt_nodes_soa* t, int64_t* bad_node_out);
  * UnschedulableAndUnresolvable, more_than_min = usedOverMinWith(nominatedPodsReqInEQWithPodReq) of the pod (read only when its
  * namespace has a quota), over_min [n_namespaces] = usedOverMin() of each quota.  Host only. */
 int spx_preempt_eligible(const spx_preempt_nodes_soa* t, const spx_quota_objects* q, const uint8_t* over_min, int64_t n, const int32_t* ns, const int32_t* priority, const uint8_t* preempt_never, const int64_t* nominated_node, const uint8_t* nominated_unresolvable, const uint8_t* more_than_min, uint8_t* eligible_out);
+
+/* PreemptionToleration, host side.  The PriorityClasses the assigned pods name: present = the lister has the class, value = its
+ * Value, and the texts of the annotations preemption-toleration.scheduling.x-k8s.io/minimum-preemptable-priority and
+ * .../toleration-seconds (NULL = the annotation is absent; NULL columns = no class has it). */
+typedef struct spx_priority_classes {
+  int32_t n_classes;
+  const uint8_t* present;
+  const int32_t* value;
+  const char* const* minimum_preemptable_priority;
+  const char* const* toleration_seconds;
+} spx_priority_classes;
+/* parsePreemptionTolerationPolicy (preemption_toleration_policy.go:55-83) and the part of ExemptedFromPreemption that does not depend
+ * on the preemptor, per assigned pod IN OBJECT ORDER (the `assigned` pods of spx_preempt_objects): pod_class = index into the class
+ * table, -1 = empty PriorityClassName; pod_scheduled = a PodScheduled condition with status True exists, pod_scheduled_at_ns its
+ * LastTransitionTime.  pod_src [n_pods] = spx_flatten_preempt_nodes' column: the outputs (the columns of spx_preempt_toleration_soa,
+ * [n_pods] each) are in the node table's CSR order.  strconv.ParseInt(s, 10, bits) is restated here: one optional sign, then digits only,
+ * within the range of the bit size.  An absent minimum-preemptable-priority is Value + 1 in int32 arithmetic (2^31-1 gives -2^31).
+ * SPX_ERR_ARG: a class index outside [-1, n_classes), a pod_src outside [0, n_assigned). */
+int spx_flatten_preempt_toleration(const spx_priority_classes* classes, int64_t n_assigned, const int32_t* pod_class, const uint8_t* pod_scheduled, const int64_t* pod_scheduled_at_ns, int64_t n_pods, const int32_t* pod_src, int32_t* min_preemptable, int64_t* exempt_until_ns, uint8_t* flags);
+/* PreemptionToleration.PodEligibleToPreemptOthers (preemption_toleration.go:339-364) for n pods: false for PreemptNever; true when the
+ * nominated node (-1 = none) was UnschedulableAndUnresolvable or is absent; false when a terminating pod of lower priority sits on it;
+ * else true.  Reads pod_ptr, pod_priority, pod_flags & SPX_PREEMPT_POD_TERMINATING and present.  Host only. */
+int spx_preempt_toleration_eligible(const spx_preempt_nodes_soa* t, int64_t n, const int32_t* priority, const uint8_t* preempt_never, const int64_t* nominated_node, const uint8_t* nominated_unresolvable, uint8_t* eligible_out);
 
 /* ------------------------------------------------------------------ wire format -> object tables (first slice)
  *

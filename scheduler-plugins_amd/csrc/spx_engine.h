@@ -257,6 +257,12 @@ struct spx_engine {
   bool pre_nodes = false, pre_pods = false, pre_marks_valid = false, pre_valid = false, pre_has_mask = false;
   int64_t pre_n_rows = 0, pre_row_stride = 0;
   std::vector<int32_t> h_pre_pod_ptr, h_pre_hi;  // host copies: spx_fetch_preempt_victims orders a cell's victim set by them
+  // PreemptionToleration's dry run shares the tables, the cells and the picks above.  ptol_table: spx_upload_preempt_toleration's records
+  // describe the node table in place (spx_upload_preempt_nodes clears it); pre_toleration: the last dry run was the toleration one, so
+  // the fetches read ptol's row records and spx_fetch_preempt_victims recomputes with k_ptol_cells at ptol_now
+  DevBuf d_ptol_pods, d_ptol_meta, d_ptol_rec;
+  bool ptol_table = false, pre_toleration = false;
+  int64_t ptol_now = 0;
   // NetworkOverhead in the commit loop: per-pod effects + the workload pair lists rebuilt with room to grow
   std::vector<int32_t> h_pair_ptr, h_eff_ptr, h_eff_key;
   std::vector<uint8_t> h_key_flag;            // host copy of key_score_equally (spx_update_net_placed edits it)

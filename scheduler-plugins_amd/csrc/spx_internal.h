@@ -785,6 +785,37 @@ void launch_preempt_rows(const PreemptArgs& a, hipStream_t s);
 void launch_preempt_cells(const PreemptArgs& a, unsigned n_nodes_launch, hipStream_t s);
 void launch_preempt_pick(const PreemptArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- PreemptionToleration.PostFilter: its dry run (kernels_ptol.hip)
+// spx_preempt_toleration_soa as records parallel to PreemptPod: the pod at position k of a node's list is pods[k] and tol[k]
+struct PtolPod {
+  int64_t until;     // exempt_until_ns
+  int32_t min_prio;  // min_preemptable
+  uint32_t flags;    // SPX_PTOL_POD_*
+};
+static_assert(sizeof(PtolPod) == 16, "record layout");
+constexpr int kPtolRowFields = 10;  // int64 columns of the per-preemptor record, [field][row_stride]: see k_ptol_rows
+struct PtolArgs {
+  int64_t n_nodes;
+  int64_t n_rows;
+  int64_t row_stride;        // as PreemptArgs'
+  int64_t node_begin;
+  int64_t now;               // the plugin's curTime, ns
+  const int64_t* rows;       // [n_rows] pod rows of the batch
+  const int64_t* row_meta;   // [n_rows] the preemptor's priority (low 32 bits) and PreemptNever (bit 32), per entry of rows
+  const uint8_t* node_mask;  // [n_rows][n_nodes] or NULL
+  const int64_t* pre_fit;    // [P][8]
+  const PreemptNode* nodes;
+  const PreemptPod* pods;
+  const PtolPod* tol;
+  const PreemptNom* noms;
+  const int32_t* pdb_allowed;
+  int64_t* row_rec;          // [kPtolRowFields][row_stride]
+  PreemptCell* cells;        // [grid.x][row_stride]
+  uint32_t* victims_out;     // as PreemptArgs'
+};
+void launch_ptol_rows(const PtolArgs& a, hipStream_t s);
+void launch_ptol_cells(const PtolArgs& a, unsigned n_nodes_launch, hipStream_t s);
+
 // ---------------------------------------------------------------- sequential commit with Filter plugins (kernels_commit.hip)
 // Bookkeeping of ONE bound pod (row `pod`, node = best_node[pod]) on the engine's device tables: what the reference's Reserve /
 // assume-time hooks do between two scheduling cycles.  NULL table groups are skipped.

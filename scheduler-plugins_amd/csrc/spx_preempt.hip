@@ -1,5 +1,6 @@
-// spx_preempt.hip — the preemption dry run's entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
-// spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip, and the fetches.  State: spx_engine.h.
+// spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
+// spx_preempt_toleration_dry_run, spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip and
+// kernels_ptol.hip, and the fetches, which serve whichever dry run ran last.  State: spx_engine.h.
 #include "spx_engine.h"
 
 namespace {
@@ -108,6 +109,26 @@ spx::PreemptArgs preempt_args(spx_engine* e) {
   return a;
 }
 
+spx::PtolArgs ptol_args(spx_engine* e) {
+  spx::PtolArgs a{};
+  a.n_nodes = e->n_nodes;
+  a.n_rows = e->pre_n_rows;
+  a.row_stride = e->pre_row_stride;
+  a.now = e->ptol_now;
+  a.rows = static_cast<const int64_t*>(e->d_pre_rows.p);
+  a.row_meta = static_cast<const int64_t*>(e->d_ptol_meta.p);
+  a.node_mask = e->pre_has_mask ? static_cast<const uint8_t*>(e->d_pre_mask.p) : nullptr;
+  a.pre_fit = static_cast<const int64_t*>(e->d_pre_pod_fit.p);
+  a.nodes = static_cast<const spx::PreemptNode*>(e->d_pre_nodes.p);
+  a.pods = static_cast<const spx::PreemptPod*>(e->d_pre_podrec.p);
+  a.tol = static_cast<const spx::PtolPod*>(e->d_ptol_pods.p);
+  a.noms = static_cast<const spx::PreemptNom*>(e->d_pre_noms.p);
+  a.pdb_allowed = static_cast<const int32_t*>(e->d_pre_pdb_allowed.p);
+  a.row_rec = static_cast<int64_t*>(e->d_ptol_rec.p);
+  a.cells = static_cast<spx::PreemptCell*>(e->d_pre_cells.p);
+  return a;
+}
+
 int preempt_results(spx_engine* e, int64_t i_begin, int64_t i_end) {
   if (!e->pre_valid) return fail(e, SPX_ERR_STATE, "no preemption dry run since the last upload of its tables");
   if (i_begin < 0 || i_end > e->pre_n_rows || i_begin > i_end) return fail(e, SPX_ERR_ARG, "preemption rows: index range outside the row list of the dry run");
@@ -133,7 +154,7 @@ int spx_upload_preempt_nodes(spx_engine* e, const spx_preempt_nodes_soa* t) {
   SPX_HIP(e, hipSetDevice(e->device));
   int rc = set_nodes(e, t->n_nodes);
   if (rc) return rc;
-  e->pre_nodes = e->pre_marks_valid = e->pre_valid = false;
+  e->pre_nodes = e->pre_marks_valid = e->pre_valid = e->ptol_table = false;
   const size_t N = static_cast<size_t>(t->n_nodes), A = static_cast<size_t>(t->pod_ptr[N]), M = static_cast<size_t>(t->nom_ptr[N]), B = static_cast<size_t>(t->pdb_ptr[N]);
   // the columns as records: a wave reads a node and each of its pods through one base pointer
   std::vector<spx::PreemptNode> nodes(N);
@@ -227,6 +248,7 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
   e->pre_has_mask = node_mask != nullptr;
   e->pre_n_rows = n_rows;
   e->pre_row_stride = static_cast<int64_t>(R);
+  e->pre_toleration = false;
   spx::PreemptArgs a = preempt_args(e);
   SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
   if (!e->pre_marks_valid) {
@@ -236,6 +258,79 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
   spx::launch_preempt_rows(a, e->stream);
   spx::launch_preempt_cells(a, static_cast<unsigned>(N), e->stream);
   spx::launch_preempt_pick(a, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  e->timed = true;
+  e->pre_valid = true;
+  return SPX_OK;
+}
+
+int spx_upload_preempt_toleration(spx_engine* e, const spx_preempt_toleration_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  if (!e->pre_nodes) return fail(e, SPX_ERR_STATE, "preempt toleration: spx_upload_preempt_nodes not called");
+  const int64_t A = e->h_pre_pod_ptr.back();
+  if (t->n_pods != A) return fail(e, SPX_ERR_ARG, "preempt toleration: " + std::to_string(t->n_pods) + " entries for the node table's " + std::to_string(A) + " pods");
+  if (A > 0 && (!t->min_preemptable || !t->exempt_until_ns || !t->flags)) return fail(e, SPX_ERR_ARG, "preempt toleration: NULL column in a non-empty table");
+  std::vector<spx::PtolPod> rec(static_cast<size_t>(A));
+  for (int64_t j = 0; j < A; ++j) {
+    const uint8_t f = t->flags[j];
+    if ((f & SPX_PTOL_POD_HAS_CLASS) && (f & SPX_PTOL_POD_CLASS_MISSING))
+      return fail(e, SPX_ERR_ARG, "preempt toleration: pod " + std::to_string(j) + " has its class and misses it");
+    rec[j] = spx::PtolPod{t->exempt_until_ns[j], t->min_preemptable[j], static_cast<uint32_t>(f & (SPX_PTOL_POD_HAS_CLASS | SPX_PTOL_POD_CLASS_MISSING))};
+  }
+  SPX_HIP(e, hipSetDevice(e->device));
+  e->ptol_table = e->pre_valid = false;
+  if (int rc = upload(e, e->d_ptol_pods, rec.data(), rec.size() * sizeof(spx::PtolPod))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // the staged records live until the copy has landed
+  e->ptol_table = true;
+  return SPX_OK;
+}
+
+int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns,
+                                   const uint8_t* node_mask) {
+  if (!e) return SPX_ERR_ARG;
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, "preemption toleration dry run: spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  if (!e->ptol_table) return fail(e, SPX_ERR_STATE, "preemption toleration dry run: no spx_upload_preempt_toleration since the last spx_upload_preempt_nodes");
+  if (!rows || n_rows <= 0 || !priority || !preempt_never) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: empty row list");
+  if (now_ns == INT64_MAX) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: now_ns == INT64_MAX (an exempt_until_ns of INT64_MAX means for ever)");
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: rows[" + std::to_string(i) + "] is no row of the batch");
+  SPX_HIP(e, hipSetDevice(e->device));
+  const size_t N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(spx::round_up(n_rows, 64));
+  if (R > (size_t{1} << 24) || N > (size_t{1} << 31)) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: more than 2^24 rows");
+  const size_t cell_bytes = N * R * sizeof(spx::PreemptCell), rec_bytes = R * spx::kPtolRowFields * 8, pick_bytes = R * 5 * 4,
+               mask_bytes = node_mask ? static_cast<size_t>(n_rows) * N : 0, list_bytes = static_cast<size_t>(n_rows) * 8;
+  {  // refuse what cannot fit instead of failing in hipMalloc: what has to grow against what is free
+    size_t free_b = 0, total_b = 0, grow = 0;
+    SPX_HIP(e, hipMemGetInfo(&free_b, &total_b));
+    const std::pair<const DevBuf*, size_t> want[] = {{&e->d_pre_cells, cell_bytes}, {&e->d_ptol_rec, rec_bytes},  {&e->d_pre_pick, pick_bytes},
+                                                      {&e->d_pre_mask, mask_bytes},  {&e->d_pre_rows, list_bytes}, {&e->d_ptol_meta, list_bytes}};
+    for (const auto& w : want)
+      if (w.second > w.first->bytes) grow += w.second, free_b += w.first->bytes;  // ensure() frees the old allocation first
+    if (grow > free_b)
+      return fail(e, SPX_ERR_ARG, "preemption toleration dry run: " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
+                                      " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
+  }
+  std::vector<int64_t> meta(static_cast<size_t>(n_rows));
+  for (int64_t i = 0; i < n_rows; ++i) meta[i] = static_cast<int64_t>(static_cast<uint32_t>(priority[i])) | (preempt_never[i] ? int64_t{1} << 32 : 0);
+  e->pre_valid = false;
+  int rc;
+  if ((rc = upload(e, e->d_pre_rows, rows, list_bytes)) || (rc = upload(e, e->d_ptol_meta, meta.data(), list_bytes)) || (rc = ensure(e, e->d_ptol_rec, rec_bytes)) ||
+      (rc = ensure(e, e->d_pre_cells, cell_bytes)) || (rc = ensure(e, e->d_pre_pick, pick_bytes)))
+    return rc;
+  if (node_mask && (rc = upload(e, e->d_pre_mask, node_mask, mask_bytes))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // rows, meta and node_mask are only borrowed for the call
+  e->pre_has_mask = node_mask != nullptr;
+  e->pre_n_rows = n_rows;
+  e->pre_row_stride = static_cast<int64_t>(R);
+  e->pre_toleration = true;
+  e->ptol_now = now_ns;
+  const spx::PtolArgs a = ptol_args(e);
+  spx::PreemptArgs pick = preempt_args(e);  // k_preempt_pick reads the sizes, the cells and the pick columns alone
+  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  spx::launch_ptol_rows(a, e->stream);
+  spx::launch_ptol_cells(a, static_cast<unsigned>(N), e->stream);
+  spx::launch_preempt_pick(pick, e->stream);
   SPX_HIP(e, hipGetLastError());
   SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
   e->timed = true;
@@ -315,22 +410,28 @@ int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* p
   constexpr size_t kMaskBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
   std::lock_guard<std::mutex> g(e->raw_mu);  // one scratch cell: concurrent callers take turns, as in spx_fetch_raw
   if (int rc = ensure(e, e->d_pre_one, sizeof(spx::PreemptCell) + kMaskBytes)) return rc;
-  // the one cell again, as row 0 of a list of one: the row's record and mask row are addressed through offset pointers
-  spx::PreemptArgs a = preempt_args(e);
-  a.n_rows = 1;
-  a.row_rec += i;
-  if (a.node_mask) a.node_mask += i * e->n_nodes;
-  a.node_begin = node;
-  a.cells = static_cast<spx::PreemptCell*>(e->d_pre_one.p);
-  a.victims_out = reinterpret_cast<uint32_t*>(static_cast<char*>(e->d_pre_one.p) + sizeof(spx::PreemptCell));
-  spx::launch_preempt_cells(a, 1, e->stream);
+  // the one cell again, as row 0 of a list of one, by the kernel of the dry run that ran last: the row's record and mask row are
+  // addressed through offset pointers
+  spx::PreemptCell* const d_cell = static_cast<spx::PreemptCell*>(e->d_pre_one.p);
+  uint32_t* const d_mask = reinterpret_cast<uint32_t*>(static_cast<char*>(e->d_pre_one.p) + sizeof(spx::PreemptCell));
+  auto one_cell = [&](auto a) {
+    a.n_rows = 1;
+    a.row_rec += i;
+    if (a.node_mask) a.node_mask += i * e->n_nodes;
+    a.node_begin = node;
+    a.cells = d_cell;
+    a.victims_out = d_mask;
+    return a;
+  };
+  if (e->pre_toleration) spx::launch_ptol_cells(one_cell(ptol_args(e)), 1, e->stream);
+  else spx::launch_preempt_cells(one_cell(preempt_args(e)), 1, e->stream);
   SPX_HIP(e, hipGetLastError());
   struct {
     spx::PreemptCell cell;
     uint32_t mask[kMaskBytes / 4];
   } h;
-  SPX_HIP(e, hipMemcpyAsync(&h.cell, a.cells, sizeof h.cell, hipMemcpyDeviceToHost, e->stream));
-  SPX_HIP(e, hipMemcpyAsync(h.mask, a.victims_out, kMaskBytes, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(&h.cell, d_cell, sizeof h.cell, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(h.mask, d_mask, kMaskBytes, hipMemcpyDeviceToHost, e->stream));
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   if (status_out) *status_out = h.cell.status;
   const int32_t p0 = e->h_pre_pod_ptr[node], L = e->h_pre_pod_ptr[node + 1] - p0;

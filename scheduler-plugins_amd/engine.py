@@ -983,6 +983,70 @@ class Engine:
                                                        mm.ctypes.data_as(u8), out.ctypes.data_as(u8)))
         return out.astype(bool)
 
+    # ------------------------------------------------------------------ PreemptionToleration.PostFilter: its dry run on the same tables
+    _PTOL_COLS = ("min_preemptable", "exempt_until_ns", "flags")
+
+    def flatten_preempt_toleration(self, classes: Table, pod_class, pod_scheduled, pod_scheduled_at_ns, pod_src) -> dict:
+        """the PriorityClass table (objects.build_priority_classes) and, per assigned pod in object order, its class index (-1 = no name),
+        whether it has a PodScheduled=True condition and since when -> the columns of spx_preempt_toleration_soa in the order of
+        flatten_preempt_nodes' table, whose "pod_src" permutes them (spx_flatten_preempt_toleration, host only)"""
+        arr = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
+        pc, sc, at, src = arr(pod_class, np.int32), arr(pod_scheduled, np.uint8), arr(pod_scheduled_at_ns, np.int64), arr(pod_src, np.int32)
+        if not len(pc) == len(sc) == len(at):
+            raise ValueError("the per-pod columns differ in length")
+        A = len(src)
+        out = {"min_preemptable": np.zeros(A, np.int32), "exempt_until_ns": np.zeros(A, np.int64), "flags": np.zeros(A, np.uint8)}
+        ptr = lambda v, t: (v if v.size else np.zeros(1, v.dtype)).ctypes.data_as(C.POINTER(t))  # never hand C a NULL for an empty column
+        self._ck_static(self._lib.spx_flatten_preempt_toleration(classes.ref(), len(pc), ptr(pc, C.c_int32), ptr(sc, C.c_uint8), ptr(at, C.c_int64), A, ptr(src, C.c_int32),
+                                                                 out["min_preemptable"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                 out["exempt_until_ns"].ctypes.data_as(C.POINTER(C.c_int64)), out["flags"].ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def upload_preempt_toleration(self, cols: dict) -> None:
+        """flatten_preempt_toleration's columns, one entry per pod of the uploaded node table (spx_upload_preempt_toleration); earlier
+        results become stale, and a later upload_preempt_nodes drops the table"""
+        n = len(cols["flags"])
+        self._ck(self._lib.spx_upload_preempt_toleration(self._h, Table(self._hdr, "spx_preempt_toleration_soa", n_pods=n, **{k: cols[k] for k in self._PTOL_COLS}).ref()))
+
+    def load_preempt_toleration_objects(self, t: dict) -> dict:
+        """objects.build_preempt_toleration_tables' tables through the flatteners to the device: the node side, the pending pods' fit vectors
+        and the toleration table.  No quota table is uploaded.  Returns flatten_preempt_nodes' columns plus "toleration"."""
+        fq = self.flatten_quota(t["pods"], t["rc"], t["quota"])  # host only: computePodResourceRequest of the pending pods
+        f = self.flatten_preempt_nodes(t["nodes"], t["rc"], t["quota"], t["preempt"])
+        self.upload_preempt_nodes(f)
+        self.upload_preempt_pods(fq["cols"]["pod_req"].reshape(-1, 8))
+        f["toleration"] = self.flatten_preempt_toleration(t["classes"], t["pod_class"], t["pod_scheduled"], t["pod_scheduled_at_ns"], f["pod_src"])
+        self.upload_preempt_toleration(f["toleration"])
+        return f
+
+    def preempt_toleration_dry_run(self, rows, priority, preempt_never, now_ns: int, node_mask=None) -> None:
+        """PreemptionToleration's SelectVictimsOnNode for the pod rows `rows` x all nodes and the pick per row
+        (spx_preempt_toleration_dry_run); priority / preempt_never per entry of rows, now_ns the plugin's clock.  The preempt_* fetches
+        answer for this run until the next dry run of either kind."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        prio, never = np.ascontiguousarray(priority, dtype=np.int32), np.ascontiguousarray(preempt_never, dtype=np.uint8)
+        if not len(rows) == len(prio) == len(never):
+            raise ValueError("priority and preempt_never must have one entry per row")
+        mask = None
+        if node_mask is not None:
+            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
+            if mask.shape != (len(rows), self.n_nodes):
+                raise ValueError("node_mask must be [len(rows)][n_nodes]")
+        self._ck(self._lib.spx_preempt_toleration_dry_run(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows), prio.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          never.ctypes.data_as(C.POINTER(C.c_uint8)), int(now_ns),
+                                                          mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None))
+        self._preempt_rows = len(rows)
+
+    def preempt_toleration_eligible(self, f: dict, priority, preempt_never, nominated_node, nominated_unresolvable) -> np.ndarray:
+        """PreemptionToleration's PodEligibleToPreemptOthers per pod (spx_preempt_toleration_eligible, host only)"""
+        u8, i32, i64 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        arr = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
+        pr, never, nn, un = arr(priority, np.int32), arr(preempt_never, np.uint8), arr(nominated_node, np.int64), arr(nominated_unresolvable, np.uint8)
+        out = np.zeros(len(pr), np.uint8)
+        self._ck_static(self._lib.spx_preempt_toleration_eligible(self.preempt_nodes_table(f).ref(), len(pr), pr.ctypes.data_as(i32), never.ctypes.data_as(u8),
+                                                                  nn.ctypes.data_as(i64), un.ctypes.data_as(u8), out.ctypes.data_as(u8)))
+        return out.astype(bool)
+
     def status(self, plugin: int, pod_row: int) -> np.ndarray:
         out = np.empty(self.n_nodes, dtype=np.uint8)
         self._ck(self._lib.spx_fetch_status(self._h, plugin, pod_row, out.ctypes.data_as(C.POINTER(C.c_uint8))))

@@ -578,6 +578,49 @@ def build_preempt_tables(hdr: Header, model: dict) -> dict:
             "quota": quota, "preempt": pre, "assigned_at": assigned_at}
 
 
+# ---------------------------------------------------------------------------------------------------------------- PreemptionToleration
+# The preemption model above without quotas, decorated (synth.ptol_model builds one; tests/ptol_oracle.py walks it):
+#   "classes": {name: {"value": int32, "annotations": {key: text}}}   the PriorityClasses the lister has
+#   "now": the plugin's clock, ns;  every assigned pod: "pc" (PriorityClassName, "" = none; a name outside "classes" = not found) and
+#   "scheduled_at" (LastTransitionTime of its PodScheduled=True condition in ns, None = no such condition);  every pending pod: "never".
+PTOL_ANNOTATION_PREFIX = "preemption-toleration.scheduling.x-k8s.io/"  # preemption_toleration_policy.go:25-29
+PTOL_ANNOTATION_MIN = PTOL_ANNOTATION_PREFIX + "minimum-preemptable-priority"
+PTOL_ANNOTATION_TOLERATION = PTOL_ANNOTATION_PREFIX + "toleration-seconds"
+
+
+def build_priority_classes(hdr: Header, names: Sequence[str], classes: dict) -> Table:
+    """spx_priority_classes for the class names `names` (index = position): present = the name is in `classes`; the two annotations as
+    C strings, NULL where a class does not carry them"""
+    import ctypes as C
+    known = [classes.get(n) for n in names]
+    t = Table(hdr, "spx_priority_classes", n_classes=len(names), present=np.array([c is not None for c in known], dtype=np.uint8),
+              value=np.array([c["value"] if c else 0 for c in known], dtype=np.int32))
+    for field, key in (("minimum_preemptable_priority", PTOL_ANNOTATION_MIN), ("toleration_seconds", PTOL_ANNOTATION_TOLERATION)):
+        texts = [c["annotations"][key].encode() if c and key in c["annotations"] else None for c in known]
+        arr = (C.c_char_p * max(len(texts), 1))(*texts)
+        t._keep[field] = arr
+        setattr(t.struct, field, C.cast(arr, dict(t.struct._fields_)[field]))
+    return t
+
+
+def build_preempt_toleration_tables(hdr: Header, model: dict) -> dict:
+    """build_preempt_tables' tables plus what spx_flatten_preempt_toleration and the dry run read: "classes" (spx_priority_classes over
+    "class_names", every name a pod carries, found or not), per assigned pod in object order "pod_class" / "pod_scheduled" /
+    "pod_scheduled_at_ns", per pending row "priority" / "never", and "now".  Quotas of the model, if any, stay in the tables for the
+    other dry run; this plugin does not read them."""
+    t = build_preempt_tables(hdr, model)
+    assigned = [p for n in model["nodes"] for p in n["pods"]]  # build_preempt_tables' object order
+    names = sorted({p["pc"] for p in assigned if p["pc"]})
+    index = {n: i for i, n in enumerate(names)}
+    t.update(class_names=names, classes=build_priority_classes(hdr, names, model["classes"]),
+             pod_class=np.array([index[p["pc"]] if p["pc"] else -1 for p in assigned], dtype=np.int32),
+             pod_scheduled=np.array([p["scheduled_at"] is not None for p in assigned], dtype=np.uint8),
+             pod_scheduled_at_ns=np.array([p["scheduled_at"] or 0 for p in assigned], dtype=np.int64),
+             priority=np.array([p["prio"] for p in model["pending"]], dtype=np.int32), never=np.array([p["never"] for p in model["pending"]], dtype=np.uint8),
+             now=model["now"])
+    return t
+
+
 # ---------------------------------------------------------------------------------------------------------------- SySched
 # What the Go side does once per snapshot for pkg/sysched: resolve every pod's seccomp profiles to a syscall set (getSyscalls,
 # sysched.go:124-210), intern the names, and ship the distinct sets, the pods' set ids, the cached host sets and the resident lists.

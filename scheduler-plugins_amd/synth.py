@@ -862,3 +862,55 @@ def _preempt_scenarios(model: dict, pod, quotas: bool) -> None:
     model["pending"][row] = pod(f"pending-{row}", 5, 50, 0, req, row=row)
     x["alloc"], x["pods"] = [big + 999, 100, 0, 110, 0, 0, 64, 1], [v]
     y["nominated"] = [pod("s6-nom", 5, 500, 0, {"v": [0, 50, 0, 0, 0, 0, 0, 0], "p": 0})]
+
+
+PTOL_NOW = 1_700_000_000 * 10**9
+
+
+def ptol_model(n_nodes: int, n_pending: int, seed: int = SEED, now: int = PTOL_NOW, **kw) -> dict:
+    """preempt_model(quotas=False, ...) decorated for PreemptionToleration (objects.build_preempt_toleration_tables describes the form):
+    "classes", a "pc" / "scheduled_at" per assigned pod, a "never" per pending pod and "now".  The decoration is drawn from a stream of
+    its own, so the undecorated model is preempt_model's to the bit.  Values sit on the edges of ExemptedFromPreemption: minimum
+    preemptable priorities around the pending priorities {5, 50, 500, 5000} and one that does not parse, a class of value 2^31-1
+    without the annotation (Value + 1 wraps), toleration seconds absent / 0 / -1 / 30 / 9 223 372 037 (whose Duration wraps), and
+    scheduled times that put now before, on and after the end of a 30 s toleration.  About 3 % of the pods name a class that does not
+    exist, gathered on one node in twenty.  _preempt_scenarios' scenes stay as they are: their pods name no class."""
+    from .objects import PTOL_ANNOTATION_MIN, PTOL_ANNOTATION_TOLERATION
+    model = preempt_model(n_nodes, n_pending, seed=seed, quotas=False, **kw)
+    rng = np.random.default_rng([seed, 0x70746F6C])
+    pick = lambda xs, p=None: xs[int(rng.choice(len(xs), p=p))]
+    sec = 10**9
+    scenes = kw.get("scenarios", True) and n_nodes >= 64 and n_pending >= 64
+    classes = {}
+
+    def class_of(value, mn, tol):
+        name = f"pc{value}-min-{'none' if mn is None else mn}-tol-{'none' if tol is None else tol}"
+        ann = {}
+        if mn is not None:
+            ann[PTOL_ANNOTATION_MIN] = mn
+        if tol is not None:
+            ann[PTOL_ANNOTATION_TOLERATION] = tol
+        classes.setdefault(name, {"value": value, "annotations": ann})
+        return name
+
+    for n, node in enumerate(model["nodes"]):
+        scene = scenes and n >= n_nodes - 14
+        broken = (not scene) and rng.random() < 0.05
+        for p in node["pods"]:
+            p["pc"], p["scheduled_at"] = "", None
+            if scene:
+                continue
+            p["scheduled_at"] = pick([None, now - 30 * sec, now - 29 * sec, now - 31 * sec, now + sec])
+            u = rng.random()
+            if broken and u < 0.6:
+                p["pc"] = "no-such-class"
+            elif u < 0.3:
+                pass  # an empty PriorityClassName
+            elif u < 0.35:
+                p["pc"] = class_of((1 << 31) - 1, None, pick([None, "-1", "30"]))
+            else:
+                p["pc"] = class_of(p["prio"], pick([None, "50", "51", "500", "5001", "a"]), pick([None, "0", "-1", "30", "9223372037"]))
+    for i, p in enumerate(model["pending"]):
+        p["never"] = bool(rng.random() < 0.1) and not (scenes and i >= n_pending - 7)
+    model["classes"], model["now"] = classes, now
+    return model
