@@ -1036,6 +1036,35 @@ typedef struct spx_preempt_toleration_soa {
 int spx_upload_preempt_toleration(spx_engine* e, const spx_preempt_toleration_soa* t);
 int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns, const uint8_t* node_mask);
 
+/* PreemptionToleration's sequential preemption loop (kernels_ptol_seq.hip).  Tables, argument checks, limits, the memory
+ * pre-check and staleness are spx_preempt_toleration_dry_run's; in addition a pod row listed twice is SPX_ERR_ARG.  With an all-zero
+ * flags column in spx_preempt_toleration_soa this is upstream's DefaultPreemption.
+ * The rows are attempted once each, in list order.  Step i evaluates rows[i] on every unmasked node (the dry run's SelectVictimsOnNode
+ * and pick) against the state that steps 0..i-1 left, then moves the state to the scheduler's cache as it is once the events of the
+ * step have been observed (restated from upstream kube-scheduler, unpinned by a reference test):
+ *   T1  the victims of the picked cell leave the picked node n: Requested and the pod count shrink, nobody walks them again (NodeInfo.RemovePod)
+ *   T2  rows[i] becomes a pod nominated to n, with its priority and its fit_req; later preemptors charge it by the existing rule
+ *       (nominated priority >= the preemptor's)
+ *   T3  nominated pods of n with a priority BELOW rows[i]'s lose their nomination, uploaded ones and rows nominated earlier in the loop
+ *       alike (prepareCandidate / getLowerPriorityNominatedPods)
+ *   T4  every uploaded nomination of rows[i] itself (nom_pending_row == rows[i], on any node) is dropped: the nominator moves it when a
+ *       node was picked; without a candidate upstream returns an empty nominated node, which clears it
+ * Two kinds of row change nothing.  preempt_never[i]: upstream never lets such a pod into PostFilter's preemption; its cells, pick and
+ * victims are what spx_preempt_toleration_dry_run gives for it, on the uploaded state, whatever the rows before it did.  eligible[i] == 0
+ * (NULL = all eligible): the row is evaluated at its own step like any other, its pick is reported and not applied.
+ * PDB DisruptionsAllowed stays as uploaded at every step: it is the disruption controller's status, not the scheduler's.  A row whose
+ * nomination T3 cleared is not attempted again.  The uploaded tables are left unchanged: a spx_preempt_toleration_dry_run or
+ * spx_preempt_dry_run after the loop gives what it gave before it.
+ * Asynchronous on the engine stream and without a host round trip between steps; spx_last_eval_ms reports the device time of the whole
+ * loop.  Memory beyond the dry run's: 100 bytes per node, 37 bytes per row, one byte per nominated record and 4 bytes per row and
+ * dirty slot (1 + the most uploaded nominations any one listed row has).
+ * The fetches answer for the loop until the next dry run of either kind: spx_fetch_preempt_pick gives row i's pick at its own step;
+ * spx_fetch_preempt_cells / _keys give row i's cells as it saw them at its own step (a step re-evaluates only the rows after it, so
+ * row i's cells are never rewritten after step i); spx_fetch_preempt_victims(i, node) answers for node == row i's picked node from the
+ * victim set stored at the step, as positions in the UPLOADED list of the node, most important first, and is SPX_ERR_ARG for any other
+ * node (the state that cell saw is gone). */
+int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible, int64_t now_ns, const uint8_t* node_mask);
+
 /* optional per-(pod,node) feasibility mask for normalizing score plugins: uint8 [n_pods][n_nodes],
  * non-zero = node passed Filter for that pod (upstream scores feasible nodes only).  NULL clears it. */
 int spx_upload_feasible_mask(spx_engine* e, const uint8_t* mask, int64_t n_pods, int64_t n_nodes);

@@ -263,6 +263,15 @@ struct spx_engine {
   DevBuf d_ptol_pods, d_ptol_meta, d_ptol_rec;
   bool ptol_table = false, pre_toleration = false;
   int64_t ptol_now = 0;
+  // The sequential loop (spx_preempt_toleration_sequential) is the third mode: pre_sequential implies pre_toleration.  d_pseq: the
+  // overlay, the stored victim sets and the dirty lists, carved from one allocation; d_pseq_nom: the host-built CSR of each row's own
+  // uploaded nominations.  pseq_victims: where the victim sets start.  h_pre_nom_*: host copies of the nominated records' node CSR and
+  // pending rows, from which that CSR is built.
+  DevBuf d_pseq, d_pseq_nom;
+  bool pre_sequential = false;
+  const uint32_t* pseq_victims = nullptr;
+  std::vector<int32_t> h_pre_nom_ptr;
+  std::vector<int64_t> h_pre_nom_row;
   // NetworkOverhead in the commit loop: per-pod effects + the workload pair lists rebuilt with room to grow
   std::vector<int32_t> h_pair_ptr, h_eff_ptr, h_eff_key;
   std::vector<uint8_t> h_key_flag;            // host copy of key_score_equally (spx_update_net_placed edits it)

@@ -816,6 +816,30 @@ struct PtolArgs {
 void launch_ptol_rows(const PtolArgs& a, hipStream_t s);
 void launch_ptol_cells(const PtolArgs& a, unsigned n_nodes_launch, hipStream_t s);
 
+// ---------------------------------------------------------------- PreemptionToleration: the sequential preemption loop (kernels_ptol_seq.hip)
+// The tables and results of the dry run, plus the overlay the loop keeps next to the uploaded records.  row_nom*: per
+// entry of the row list, the uploaded nominated records whose pending row it is (T4), as a CSR built by the host.
+struct PtolSeqArgs {
+  PtolArgs t;
+  int64_t step;                 // the row of the list this launch is about
+  int32_t n_dirty;              // dirty slots per step: 1 + the most nominated records any one row of the list has
+  int32_t pad;
+  int32_t* pick;                // [5][row_stride], as PreemptArgs'
+  uint32_t* gone;               // [n_nodes][SPX_PREEMPT_MAX_NODE_PODS / 32]
+  int64_t* requested;           // [n_nodes][8]
+  uint8_t* nom_cleared;         // [nominated records]
+  uint8_t* row_cleared;         // [row_stride]
+  int32_t* row_next;            // [row_stride]
+  int32_t* head;                // [n_nodes], -1 = no row nominated to the node
+  const int32_t* row_nom_ptr;   // [n_rows + 1]
+  const int32_t* row_nom;       // index into noms
+  const int32_t* row_nom_node;  // the node that record belongs to
+  uint32_t* victims;            // [row_stride][SPX_PREEMPT_MAX_NODE_PODS / 32]: the victim set of each row's picked cell
+  int32_t* dirty;               // [n_rows][n_dirty]: the nodes step i changed, -1 = unused slot
+};
+void launch_ptol_seq_init(const PtolSeqArgs& q, hipStream_t s);
+void launch_ptol_seq_step(const PtolSeqArgs& q, hipStream_t s);
+
 // ---------------------------------------------------------------- sequential commit with Filter plugins (kernels_commit.hip)
 // Bookkeeping of ONE bound pod (row `pod`, node = best_node[pod]) on the engine's device tables: what the reference's Reserve /
 // assume-time hooks do between two scheduling cycles.  NULL table groups are skipped.

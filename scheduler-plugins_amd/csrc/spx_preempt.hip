@@ -1,6 +1,7 @@
 // spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
-// spx_preempt_toleration_dry_run, spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip and
-// kernels_ptol.hip, and the fetches, which serve whichever dry run ran last.  State: spx_engine.h.
+// spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_fetch_preempt_*): table checks and uploads, the launches of
+// kernels_preempt.hip, kernels_ptol.hip and kernels_ptol_seq.hip, and the fetches, which serve whichever of the three ran last.
+// State: spx_engine.h.
 #include "spx_engine.h"
 
 namespace {
@@ -135,6 +136,58 @@ int preempt_results(spx_engine* e, int64_t i_begin, int64_t i_end) {
   return SPX_OK;
 }
 
+// What the two toleration entry points check before anything moves: state first, then the arguments.
+int ptol_check(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns) {
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  if (!e->ptol_table) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_toleration since the last spx_upload_preempt_nodes");
+  if (!rows || n_rows <= 0 || !priority || !preempt_never) return fail(e, SPX_ERR_ARG, who + ": empty row list");
+  if (now_ns == INT64_MAX) return fail(e, SPX_ERR_ARG, who + ": now_ns == INT64_MAX (an exempt_until_ns of INT64_MAX means for ever)");
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is no row of the batch");
+  return SPX_OK;
+}
+
+// The row list, its meta column (priority, PreemptNever, and "not eligible" where `eligible` is given and 0) and the node mask on the
+// device, the result buffers and `more` sized, after the memory pre-check; then the engine's view of the run.
+int ptol_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
+               int64_t now_ns, const uint8_t* node_mask, std::vector<std::pair<DevBuf*, size_t>> more) {
+  SPX_HIP(e, hipSetDevice(e->device));
+  const size_t N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(spx::round_up(n_rows, 64));
+  if (R > (size_t{1} << 24) || N > (size_t{1} << 31)) return fail(e, SPX_ERR_ARG, who + ": more than 2^24 rows");
+  const size_t cell_bytes = N * R * sizeof(spx::PreemptCell), rec_bytes = R * spx::kPtolRowFields * 8, pick_bytes = R * 5 * 4,
+               mask_bytes = node_mask ? static_cast<size_t>(n_rows) * N : 0, list_bytes = static_cast<size_t>(n_rows) * 8;
+  {  // refuse what cannot fit instead of failing in hipMalloc: what has to grow against what is free
+    size_t free_b = 0, total_b = 0, grow = 0;
+    SPX_HIP(e, hipMemGetInfo(&free_b, &total_b));
+    std::vector<std::pair<DevBuf*, size_t>> want = {{&e->d_pre_cells, cell_bytes}, {&e->d_ptol_rec, rec_bytes},  {&e->d_pre_pick, pick_bytes},
+                                                    {&e->d_pre_mask, mask_bytes},  {&e->d_pre_rows, list_bytes}, {&e->d_ptol_meta, list_bytes}};
+    want.insert(want.end(), more.begin(), more.end());
+    for (const auto& w : want)
+      if (w.second > w.first->bytes) grow += w.second, free_b += w.first->bytes;  // ensure() frees the old allocation first
+    if (grow > free_b)
+      return fail(e, SPX_ERR_ARG, who + ": " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
+                                      " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
+  }
+  std::vector<int64_t> meta(static_cast<size_t>(n_rows));
+  for (int64_t i = 0; i < n_rows; ++i)
+    meta[i] = static_cast<int64_t>(static_cast<uint32_t>(priority[i])) | (preempt_never[i] ? int64_t{1} << 32 : 0) | (eligible && !eligible[i] ? int64_t{1} << 33 : 0);
+  e->pre_valid = false;
+  int rc;
+  if ((rc = upload(e, e->d_pre_rows, rows, list_bytes)) || (rc = upload(e, e->d_ptol_meta, meta.data(), list_bytes)) || (rc = ensure(e, e->d_ptol_rec, rec_bytes)) ||
+      (rc = ensure(e, e->d_pre_cells, cell_bytes)) || (rc = ensure(e, e->d_pre_pick, pick_bytes)))
+    return rc;
+  for (const auto& w : more)
+    if ((rc = ensure(e, *w.first, w.second))) return rc;
+  if (node_mask && (rc = upload(e, e->d_pre_mask, node_mask, mask_bytes))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // rows, meta and node_mask are only borrowed for the call
+  e->pre_has_mask = node_mask != nullptr;
+  e->pre_n_rows = n_rows;
+  e->pre_row_stride = static_cast<int64_t>(R);
+  e->pre_toleration = true;
+  e->ptol_now = now_ns;
+  return SPX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -189,6 +242,8 @@ int spx_upload_preempt_nodes(spx_engine* e, const spx_preempt_nodes_soa* t) {
     return rc;
   e->h_pre_pod_ptr.assign(t->pod_ptr, t->pod_ptr + N + 1);
   e->h_pre_hi.assign(t->pod_hi_order, t->pod_hi_order + A);  // (an empty column may be NULL: A == 0 then)
+  e->h_pre_nom_ptr.assign(t->nom_ptr, t->nom_ptr + N + 1);
+  e->h_pre_nom_row.assign(t->nom_pending_row, t->nom_pending_row + M);
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   e->pre_nodes = true;
   return SPX_OK;
@@ -248,7 +303,7 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
   e->pre_has_mask = node_mask != nullptr;
   e->pre_n_rows = n_rows;
   e->pre_row_stride = static_cast<int64_t>(R);
-  e->pre_toleration = false;
+  e->pre_toleration = e->pre_sequential = false;
   spx::PreemptArgs a = preempt_args(e);
   SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
   if (!e->pre_marks_valid) {
@@ -289,48 +344,93 @@ int spx_upload_preempt_toleration(spx_engine* e, const spx_preempt_toleration_so
 int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns,
                                    const uint8_t* node_mask) {
   if (!e) return SPX_ERR_ARG;
-  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, "preemption toleration dry run: spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
-  if (!e->ptol_table) return fail(e, SPX_ERR_STATE, "preemption toleration dry run: no spx_upload_preempt_toleration since the last spx_upload_preempt_nodes");
-  if (!rows || n_rows <= 0 || !priority || !preempt_never) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: empty row list");
-  if (now_ns == INT64_MAX) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: now_ns == INT64_MAX (an exempt_until_ns of INT64_MAX means for ever)");
-  for (int64_t i = 0; i < n_rows; ++i)
-    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: rows[" + std::to_string(i) + "] is no row of the batch");
-  SPX_HIP(e, hipSetDevice(e->device));
-  const size_t N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(spx::round_up(n_rows, 64));
-  if (R > (size_t{1} << 24) || N > (size_t{1} << 31)) return fail(e, SPX_ERR_ARG, "preemption toleration dry run: more than 2^24 rows");
-  const size_t cell_bytes = N * R * sizeof(spx::PreemptCell), rec_bytes = R * spx::kPtolRowFields * 8, pick_bytes = R * 5 * 4,
-               mask_bytes = node_mask ? static_cast<size_t>(n_rows) * N : 0, list_bytes = static_cast<size_t>(n_rows) * 8;
-  {  // refuse what cannot fit instead of failing in hipMalloc: what has to grow against what is free
-    size_t free_b = 0, total_b = 0, grow = 0;
-    SPX_HIP(e, hipMemGetInfo(&free_b, &total_b));
-    const std::pair<const DevBuf*, size_t> want[] = {{&e->d_pre_cells, cell_bytes}, {&e->d_ptol_rec, rec_bytes},  {&e->d_pre_pick, pick_bytes},
-                                                      {&e->d_pre_mask, mask_bytes},  {&e->d_pre_rows, list_bytes}, {&e->d_ptol_meta, list_bytes}};
-    for (const auto& w : want)
-      if (w.second > w.first->bytes) grow += w.second, free_b += w.first->bytes;  // ensure() frees the old allocation first
-    if (grow > free_b)
-      return fail(e, SPX_ERR_ARG, "preemption toleration dry run: " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
-                                      " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
-  }
-  std::vector<int64_t> meta(static_cast<size_t>(n_rows));
-  for (int64_t i = 0; i < n_rows; ++i) meta[i] = static_cast<int64_t>(static_cast<uint32_t>(priority[i])) | (preempt_never[i] ? int64_t{1} << 32 : 0);
-  e->pre_valid = false;
+  const std::string who = "preemption toleration dry run";
   int rc;
-  if ((rc = upload(e, e->d_pre_rows, rows, list_bytes)) || (rc = upload(e, e->d_ptol_meta, meta.data(), list_bytes)) || (rc = ensure(e, e->d_ptol_rec, rec_bytes)) ||
-      (rc = ensure(e, e->d_pre_cells, cell_bytes)) || (rc = ensure(e, e->d_pre_pick, pick_bytes)))
+  if ((rc = ptol_check(e, who, rows, n_rows, priority, preempt_never, now_ns)) || (rc = ptol_stage(e, who, rows, n_rows, priority, preempt_never, nullptr, now_ns, node_mask, {})))
     return rc;
-  if (node_mask && (rc = upload(e, e->d_pre_mask, node_mask, mask_bytes))) return rc;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));  // rows, meta and node_mask are only borrowed for the call
-  e->pre_has_mask = node_mask != nullptr;
-  e->pre_n_rows = n_rows;
-  e->pre_row_stride = static_cast<int64_t>(R);
-  e->pre_toleration = true;
-  e->ptol_now = now_ns;
+  e->pre_sequential = false;
   const spx::PtolArgs a = ptol_args(e);
   spx::PreemptArgs pick = preempt_args(e);  // k_preempt_pick reads the sizes, the cells and the pick columns alone
   SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
   spx::launch_ptol_rows(a, e->stream);
-  spx::launch_ptol_cells(a, static_cast<unsigned>(N), e->stream);
+  spx::launch_ptol_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
   spx::launch_preempt_pick(pick, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  e->timed = true;
+  e->pre_valid = true;
+  return SPX_OK;
+}
+
+int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
+                                      int64_t now_ns, const uint8_t* node_mask) {
+  if (!e) return SPX_ERR_ARG;
+  const std::string who = "sequential preemption";
+  if (int rc = ptol_check(e, who, rows, n_rows, priority, preempt_never, now_ns)) return rc;
+  // a row is attempted once; and the uploaded nominations each row came with (T4), as a CSR over the row list
+  std::unordered_map<int64_t, int64_t> at;  // pod row -> its index in the list
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (!at.emplace(rows[i], i).second) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is listed twice");
+  const int64_t N = e->n_nodes, M = e->h_pre_nom_ptr.back();
+  std::vector<int32_t> csr(static_cast<size_t>(n_rows) + 1, 0);
+  for (int64_t j = 0; j < M; ++j) {
+    const auto it = at.find(e->h_pre_nom_row[j]);
+    if (it != at.end()) ++csr[it->second + 1];
+  }
+  int32_t n_dirty = 1;
+  for (int64_t i = 0; i < n_rows; ++i) n_dirty = std::max(n_dirty, 1 + csr[i + 1]), csr[i + 1] += csr[i];
+  const size_t own = static_cast<size_t>(csr[n_rows]);
+  std::vector<int32_t> fill(csr.begin(), csr.end() - 1);
+  csr.resize(static_cast<size_t>(n_rows) + 1 + 2 * own);  // [ptr | record | node of the record]
+  for (int64_t n = 0; n < N; ++n)
+    for (int32_t j = e->h_pre_nom_ptr[n]; j < e->h_pre_nom_ptr[n + 1]; ++j) {
+      const auto it = at.find(e->h_pre_nom_row[j]);
+      if (it == at.end()) continue;
+      const size_t k = static_cast<size_t>(fill[it->second]++);
+      csr[n_rows + 1 + k] = j, csr[n_rows + 1 + own + k] = static_cast<int32_t>(n);
+    }
+  // the overlay, the stored victim sets and the dirty lists: one allocation, carved
+  const size_t R = static_cast<size_t>(spx::round_up(n_rows, 64));
+  constexpr size_t kSetBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
+  size_t total = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = total;
+    total += static_cast<size_t>(spx::round_up(static_cast<int64_t>(bytes), 256));
+    return o;
+  };
+  const size_t o_gone = carve(static_cast<size_t>(N) * kSetBytes), o_clear = carve(static_cast<size_t>(M)), o_rowclear = carve(R), zeroed = total;
+  const size_t o_head = carve(static_cast<size_t>(N) * 4), minus_one = total - o_head;
+  const size_t o_req = carve(static_cast<size_t>(N) * S * 8), o_next = carve(R * 4), o_vict = carve(R * kSetBytes),
+               o_dirty = carve(static_cast<size_t>(n_rows) * static_cast<size_t>(n_dirty) * 4);
+  if (int rc = ptol_stage(e, who, rows, n_rows, priority, preempt_never, eligible, now_ns, node_mask, {{&e->d_pseq, total}, {&e->d_pseq_nom, csr.size() * 4}})) return rc;
+  if (int rc = upload(e, e->d_pseq_nom, csr.data(), csr.size() * 4)) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // the staged CSR lives until the copy has landed
+  char* const base = static_cast<char*>(e->d_pseq.p);
+  spx::PtolSeqArgs q{};
+  q.t = ptol_args(e);
+  q.n_dirty = n_dirty;
+  q.pick = static_cast<int32_t*>(e->d_pre_pick.p);
+  q.gone = reinterpret_cast<uint32_t*>(base + o_gone);
+  q.nom_cleared = reinterpret_cast<uint8_t*>(base + o_clear);
+  q.row_cleared = reinterpret_cast<uint8_t*>(base + o_rowclear);
+  q.head = reinterpret_cast<int32_t*>(base + o_head);
+  q.requested = reinterpret_cast<int64_t*>(base + o_req);
+  q.row_next = reinterpret_cast<int32_t*>(base + o_next);
+  q.victims = reinterpret_cast<uint32_t*>(base + o_vict);
+  q.dirty = reinterpret_cast<int32_t*>(base + o_dirty);
+  q.row_nom_ptr = static_cast<const int32_t*>(e->d_pseq_nom.p);
+  q.row_nom = q.row_nom_ptr + n_rows + 1;
+  q.row_nom_node = q.row_nom + own;
+  e->pre_sequential = true;
+  e->pseq_victims = q.victims;
+  // everything is enqueued here; each step reads what the one before it left on the device, and nothing is read back in between
+  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  SPX_HIP(e, hipMemsetAsync(base, 0, zeroed, e->stream));
+  SPX_HIP(e, hipMemsetAsync(base + o_head, 0xFF, minus_one, e->stream));
+  spx::launch_ptol_seq_init(q, e->stream);
+  spx::launch_ptol_rows(q.t, e->stream);
+  spx::launch_ptol_cells(q.t, static_cast<unsigned>(N), e->stream);  // the untouched state: no row of the list has moved anything yet
+  for (q.step = 0; q.step < n_rows; ++q.step) spx::launch_ptol_seq_step(q, e->stream);
   SPX_HIP(e, hipGetLastError());
   SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
   e->timed = true;
@@ -352,6 +452,21 @@ int fetch_cells(spx_engine* e, int64_t i_begin, int64_t i_end, std::vector<spx::
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   SPX_HIP(e, hipMemcpy2D(h.data(), n * sizeof(spx::PreemptCell), static_cast<const spx::PreemptCell*>(e->d_pre_cells.p) + i_begin, R * sizeof(spx::PreemptCell),
                          n * sizeof(spx::PreemptCell), N, hipMemcpyDeviceToHost));
+  return SPX_OK;
+}
+
+// a victim set of `node` (bit = position in its uploaded list) as positions, most important first
+int victims_in_order(spx_engine* e, int64_t node, const uint32_t* mask, int32_t* pod_pos_out, int32_t cap, int32_t* n_out) {
+  const int32_t p0 = e->h_pre_pod_ptr[node], L = e->h_pre_pod_ptr[node + 1] - p0;
+  int32_t n = 0;
+  for (int32_t k = 0; k < L; ++k) {
+    const int32_t pos = e->h_pre_hi[p0 + k];
+    if (!((mask[pos >> 5] >> (pos & 31)) & 1u)) continue;
+    if (n < cap) pod_pos_out[n] = pos;
+    ++n;
+  }
+  *n_out = n;
+  if (n > cap) return fail(e, SPX_ERR_ARG, "preemption victims: " + std::to_string(n) + " victims do not fit cap");
   return SPX_OK;
 }
 
@@ -408,6 +523,17 @@ int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* p
   if (node < 0 || node >= e->n_nodes) return fail(e, SPX_ERR_ARG, "preemption victims: node out of range");
   SPX_HIP(e, hipSetDevice(e->device));
   constexpr size_t kMaskBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
+  if (e->pre_sequential) {
+    // the loop stored the victim set of the row's picked cell at its step; the state any other cell of the row saw is gone
+    int32_t picked = -1;
+    uint32_t mask[kMaskBytes / 4];
+    SPX_HIP(e, hipStreamSynchronize(e->stream));
+    SPX_HIP(e, hipMemcpy(&picked, static_cast<const int32_t*>(e->d_pre_pick.p) + i, 4, hipMemcpyDeviceToHost));
+    if (picked != node) return fail(e, SPX_ERR_ARG, "preemption victims: after the sequential loop only the row's picked node is answered for");
+    SPX_HIP(e, hipMemcpy(mask, e->pseq_victims + i * (kMaskBytes / 4), kMaskBytes, hipMemcpyDeviceToHost));
+    if (status_out) *status_out = SPX_PREEMPT_ST_CANDIDATE;
+    return victims_in_order(e, node, mask, pod_pos_out, cap, n_out);
+  }
   std::lock_guard<std::mutex> g(e->raw_mu);  // one scratch cell: concurrent callers take turns, as in spx_fetch_raw
   if (int rc = ensure(e, e->d_pre_one, sizeof(spx::PreemptCell) + kMaskBytes)) return rc;
   // the one cell again, as row 0 of a list of one, by the kernel of the dry run that ran last: the row's record and mask row are
@@ -434,17 +560,7 @@ int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* p
   SPX_HIP(e, hipMemcpyAsync(h.mask, d_mask, kMaskBytes, hipMemcpyDeviceToHost, e->stream));
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   if (status_out) *status_out = h.cell.status;
-  const int32_t p0 = e->h_pre_pod_ptr[node], L = e->h_pre_pod_ptr[node + 1] - p0;
-  int32_t n = 0;
-  for (int32_t k = 0; k < L; ++k) {
-    const int32_t pos = e->h_pre_hi[p0 + k];
-    if (!((h.mask[pos >> 5] >> (pos & 31)) & 1u)) continue;
-    if (n < cap) pod_pos_out[n] = pos;
-    ++n;
-  }
-  *n_out = n;
-  if (n > cap) return fail(e, SPX_ERR_ARG, "preemption victims: " + std::to_string(n) + " victims do not fit cap");
-  return SPX_OK;
+  return victims_in_order(e, node, h.mask, pod_pos_out, cap, n_out);
 }
 
 }  // extern "C"

@@ -1037,6 +1037,27 @@ class Engine:
                                                           mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None))
         self._preempt_rows = len(rows)
 
+    def preempt_toleration_sequential(self, rows, priority, preempt_never, now_ns: int, eligible=None, node_mask=None) -> None:
+        """The sequential preemption loop (spx_preempt_toleration_sequential): the rows are attempted once each in list order, each against
+        the state the rows before it left (victims gone, the preemptor nominated, lower nominations cleared, its own old nomination
+        dropped).  eligible: per entry of rows, 0 = evaluated at its step but nothing applied (None = all).  The preempt_* fetches
+        answer per row as it saw the state at its own step; preempt_victims answers for the row's picked node alone."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        prio, never = np.ascontiguousarray(priority, dtype=np.int32), np.ascontiguousarray(preempt_never, dtype=np.uint8)
+        elig = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+        if not len(rows) == len(prio) == len(never) or (elig is not None and len(elig) != len(rows)):
+            raise ValueError("priority, preempt_never and eligible must have one entry per row")
+        mask = None
+        if node_mask is not None:
+            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
+            if mask.shape != (len(rows), self.n_nodes):
+                raise ValueError("node_mask must be [len(rows)][n_nodes]")
+        u8 = C.POINTER(C.c_uint8)
+        self._ck(self._lib.spx_preempt_toleration_sequential(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows), prio.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                             never.ctypes.data_as(u8), elig.ctypes.data_as(u8) if elig is not None else None, int(now_ns),
+                                                             mask.ctypes.data_as(u8) if mask is not None else None))
+        self._preempt_rows = len(rows)
+
     def preempt_toleration_eligible(self, f: dict, priority, preempt_never, nominated_node, nominated_unresolvable) -> np.ndarray:
         """PreemptionToleration's PodEligibleToPreemptOthers per pod (spx_preempt_toleration_eligible, host only)"""
         u8, i32, i64 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
