@@ -18,19 +18,15 @@
 // removal always shrinks Used.  Key presence of a scalar in Used only grows (SetScalar).
 //
 // NodeResourcesFit (default args), "no victims left: no candidate" and pickOneNodeForPreemption restate upstream kube-scheduler code
-// that is not in the reference tree.  cmp2 and the nominated sums are restated from kernels_capacity.hip, whose machine code stays
-// as it is.  Integer vector code only; every sum is bounded by the upload's 2^62 check.
-#include "spx_internal.h"
+// that is not in the reference tree.  The launch constants, in_vgpr, the bit-set select chains, fits and the pick's key are
+// preempt_device.h's, shared with kernels_ptol.hip and kernels_ptol_seq.hip.  cmp2 and the nominated sums are restated from
+// kernels_capacity.hip, whose machine code stays as it is.  Integer vector code only; every sum is bounded by the upload's 2^62 check.
+#include "preempt_device.h"
 
 namespace spx {
 
 namespace {
 
-constexpr int S = SPX_QUOTA_SLOTS;
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kWords = SPX_PREEMPT_MAX_NODE_PODS / 32;
-constexpr int kPdbs = SPX_PREEMPT_MAX_NODE_PDBS;
 // fields of the row record
 constexpr int kReq = 0, kInEq = 8, kTotal = 16, kFit = 24, kPrio = 32, kNs = 33, kFlags = 34, kRow = 35;
 static_assert(kRow + 1 == kPreemptRowFields, "row record layout");
@@ -52,26 +48,6 @@ __device__ __forceinline__ bool cmp2(const int64_t* x1, uint32_t x1p, const int6
     over |= ((x1p >> s) & 1u) && wadd(x1[s], x2 ? x2[s] : 0) > yq;
   }
   return over;
-}
-
-// A wave-uniform value the whole cell keeps reading (the node's Allocatable, the aggregate Min) would sit in scalar registers for the
-// length of the kernel, next to the pod records the walk streams through them, and the allocator runs out of those first; a vector
-// register per lane is what this kernel has to spare.
-__device__ __forceinline__ int64_t in_vgpr(int64_t x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-// bit k of a 256-bit set kept as eight registers; k is wave-uniform, so every index below is a compile-time one
-__device__ __forceinline__ bool get_bit(const uint32_t* m, int k) {
-  uint32_t w = 0;
-#pragma unroll
-  for (int i = 0; i < kWords; ++i) w = (k >> 5) == i ? m[i] : w;
-  return (w >> (k & 31)) & 1u;
-}
-__device__ __forceinline__ void set_bit(uint32_t* m, int k, bool pred) {
-#pragma unroll
-  for (int i = 0; i < kWords; ++i) m[i] |= (pred && (k >> 5) == i) ? (1u << (k & 31)) : 0u;
 }
 
 __global__ __launch_bounds__(kBlock) void k_preempt_marks(PreemptArgs a) {
@@ -135,16 +111,6 @@ __global__ __launch_bounds__(kBlock) void k_preempt_rows(PreemptArgs a) {
   a.row_rec[kNs * R + r] = ns;
   a.row_rec[kFlags * R + r] = flags;
   a.row_rec[kRow * R + r] = pod;
-}
-
-// NodeResourcesFit.fitsRequest with default args on the lane's copy of the node (nominated pods already charged): the pod count, then per
-// resource "insufficient iff req > 0 && req > allocatable - requested".  A pod whose requests are all zero fails none of those.
-__device__ __forceinline__ bool fits(const int64_t* fit, const int64_t* alloc, const int64_t* requested) {
-  bool ok = requested[3] + 1 <= alloc[3];
-#pragma unroll
-  for (int s = 0; s < S; ++s)
-    if (s != 3) ok &= !(fit[s] > 0 && fit[s] > alloc[s] - requested[s]);
-  return ok;
 }
 
 __global__ __launch_bounds__(kBlock) void k_preempt_cells(PreemptArgs a) {
@@ -315,20 +281,6 @@ __global__ __launch_bounds__(kBlock) void k_preempt_cells(PreemptArgs a) {
   }
 }
 
-// a candidate's keys in the order pickOneNodeForPreemption compares them; smaller is better
-struct PickKey {
-  int32_t viol, hi, n_vict;
-  int64_t sum, neg_start;
-};
-__device__ __forceinline__ int cmp_key(const PickKey& x, const PickKey& y) {
-  if (x.viol != y.viol) return x.viol < y.viol ? -1 : 1;
-  if (x.hi != y.hi) return x.hi < y.hi ? -1 : 1;
-  if (x.sum != y.sum) return x.sum < y.sum ? -1 : 1;
-  if (x.n_vict != y.n_vict) return x.n_vict < y.n_vict ? -1 : 1;
-  if (x.neg_start != y.neg_start) return x.neg_start < y.neg_start ? -1 : 1;
-  return 0;
-}
-
 __global__ __launch_bounds__(kBlock) void k_preempt_pick(PreemptArgs a) {
   __shared__ PickKey s_key[kWaves][64];
   __shared__ int32_t s_node[kWaves][64], s_cand[kWaves][64], s_ties[kWaves][64];
@@ -363,8 +315,6 @@ __global__ __launch_bounds__(kBlock) void k_preempt_pick(PreemptArgs a) {
   a.pick[3 * R + r] = cand;
   a.pick[4 * R + r] = ties;
 }
-
-inline unsigned blocks_for(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
 
 }  // namespace
 

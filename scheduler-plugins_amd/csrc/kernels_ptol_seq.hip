@@ -15,213 +15,26 @@
 //                      the candidate and tie counts of k_preempt_pick; the step waits for it, so it is as wide as a workgroup gets
 //   k_ptol_seq_apply   one wave: cell (i, picked node) again for its victim set, which is stored (32 B per row); then T1-T4 and the
 //                      ids of the nodes whose state moved (the picked node and the nodes a dropped nomination sat on; -1 = unused slot)
-//   k_ptol_seq_cells   dirty slots x ceil(rows / 256): the column of each dirty node for the rows after i, k_ptol_cells' walk with
-//                      the overlay applied.  Rows <= i store nothing, so the cells of row i stay what row i saw at its own step.
+//   k_ptol_seq_cells   dirty slots x ceil(rows / 256): the column of each dirty node for the rows after i, ptol_cell.h's walk with
+//                      the overlay on.  Rows <= i store nothing, so the cells of row i stay what row i saw at its own step.
 //
 // A PreemptNever row keeps the cells of the untouched state (the full sweep of k_ptol_cells before step 0): no step stores to them, and
 // its victim set is computed with the overlay switched off.
 //
-// The walk, NodeResourcesFit with default args and the bit-set helpers are restated from kernels_ptol.hip, whose machine code stays as it
-// is.  Integer vector code only; every sum is bounded by the upload's 2^62 check (the loop only ever moves requests between sums).
-#include "spx_internal.h"
+// The walk and the row record are ptol_cell.h's, shared with kernels_ptol.hip; NodeResourcesFit with default args, the bit-set helpers
+// and the pick's key are preempt_device.h's, shared with kernels_preempt.hip as well.  Integer vector code only; every sum is bounded by
+// the upload's 2^62 check (the loop only ever moves requests between sums).
+#include "ptol_cell.h"
 
 namespace spx {
 
 namespace {
-
-constexpr int S = SPX_QUOTA_SLOTS;
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kWords = SPX_PREEMPT_MAX_NODE_PODS / 32;
-constexpr int kPdbs = SPX_PREEMPT_MAX_NODE_PDBS;
-// fields of the row record (k_ptol_rows writes it)
-constexpr int kFit = 0, kMeta = 8, kRow = 9;
-static_assert(kRow + 1 == kPtolRowFields, "row record layout");
-constexpr int64_t kNever = int64_t{1} << 32;  // kMeta: the priority in the low 32 bits, PreemptNever above them,
-constexpr int64_t kHold = int64_t{1} << 33;   // and "not eligible": evaluated at its step, nothing applied
-
-__device__ __forceinline__ int64_t in_vgpr(int64_t x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-// bit k of a 256-bit set kept as eight registers; k is wave-uniform, so every index below is a compile-time one
-__device__ __forceinline__ bool get_bit(const uint32_t* m, int k) {
-  uint32_t w = 0;
-#pragma unroll
-  for (int i = 0; i < kWords; ++i) w = (k >> 5) == i ? m[i] : w;
-  return (w >> (k & 31)) & 1u;
-}
-__device__ __forceinline__ void set_bit(uint32_t* m, int k, bool pred) {
-#pragma unroll
-  for (int i = 0; i < kWords; ++i) m[i] |= (pred && (k >> 5) == i) ? (1u << (k & 31)) : 0u;
-}
-
-__device__ __forceinline__ bool fits(const int64_t* fit, const int64_t* alloc, const int64_t* requested) {
-  bool ok = requested[3] + 1 <= alloc[3];
-#pragma unroll
-  for (int s = 0; s < S; ++s)
-    if (s != 3) ok &= !(fit[s] > 0 && fit[s] > alloc[s] - requested[s]);
-  return ok;
-}
-
-__device__ __forceinline__ int prio_of(int64_t meta) { return static_cast<int>(static_cast<uint32_t>(meta)); }
-
-// One cell per lane: row rr of the list on `node`, for the lanes with want set.  frozen (wave-uniform): the untouched state, as
-// k_ptol_cells sees it.  budget: the wave's [kPdbs][64] int16 in LDS.  vict is all zero unless the cell is a CANDIDATE.
-__device__ __forceinline__ PreemptCell seq_cell(const PtolSeqArgs& q, int64_t node, int64_t rr, bool want, bool frozen, int16_t (*budget)[64], int lane, uint32_t* vict) {
-  const PtolArgs& a = q.t;
-  const int64_t R = a.row_stride;
-  int64_t fit[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) fit[s] = a.row_rec[(kFit + s) * R + rr];
-  const int64_t meta = a.row_rec[kMeta * R + rr];
-  const int prio = prio_of(meta);
-  const bool never = meta & kNever;
-  const int64_t pod_row = a.row_rec[kRow * R + rr];
-  const int64_t now = a.now;
-
-  PreemptCell out{0, 0, 0, 0, 0, SPX_PREEMPT_ST_SKIPPED};
-#pragma unroll
-  for (int i = 0; i < kWords; ++i) vict[i] = 0;
-  const PreemptNode& nd = a.nodes[node];
-  const PreemptPod* pods = a.pods + nd.pod_begin;  // position in the node's list -> record
-  const PtolPod* tol = a.tol + nd.pod_begin;
-  const uint32_t* gone = q.gone + node * kWords;
-  auto left = [&](int k) { return !frozen && ((gone[k >> 5] >> (k & 31)) & 1u); };  // wave-uniform: the skips below are branches of the wave
-  bool live = want && nd.present && (!a.node_mask || a.node_mask[rr * a.n_nodes + node]);
-
-  if (__any(live)) {
-    const int L = nd.pod_end - nd.pod_begin;
-    // the lane's copy of the node, the nominated pods that outrank the preemptor charged once
-    int64_t alloc[S], requested[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) alloc[s] = in_vgpr(nd.alloc[s]), requested[s] = frozen ? nd.requested[s] : q.requested[node * S + s];
-    for (int j = nd.nom_begin; j < nd.nom_end; ++j) {
-      if (!frozen && q.nom_cleared[j]) continue;
-      const bool add = a.noms[j].prio >= prio && a.noms[j].row != pod_row;
-#pragma unroll
-      for (int s = 0; s < S; ++s) requested[s] += add ? a.noms[j].fit[s] : 0;
-    }
-    if (!frozen) {
-      for (int k = q.head[node]; k >= 0; k = q.row_next[k]) {  // the loop's own nominations: earlier rows, so never the lane's own
-        if (q.row_cleared[k]) continue;
-        const bool add = prio_of(a.row_rec[kMeta * R + k]) >= prio;
-#pragma unroll
-        for (int s = 0; s < S; ++s) requested[s] += add ? (s == 3 ? 1 : a.row_rec[(kFit + s) * R + k]) : 0;  // a pod counts once
-      }
-    }
-    auto move_pod = [&](int k, bool pred, bool add) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const int64_t f = pods[k].fit[s];
-        requested[s] += pred ? (add ? f : -f) : 0;
-      }
-    };
-
-    // step 1: every lower-priority pod still on the node that is not exempted is a potential victim and is removed
-    uint32_t pot[kWords], viol[kWords];
-#pragma unroll
-    for (int i = 0; i < kWords; ++i) pot[i] = viol[i] = 0;
-    int n_pot = 0;
-    bool class_error = false;
-    for (int k = 0; k < L; ++k) {
-      if (left(k)) continue;
-      const int jprio = pods[k].prio;
-      const PtolPod t = tol[k];
-      const bool lower = live && jprio < prio;
-      const bool exempted = (t.flags & SPX_PTOL_POD_HAS_CLASS) && (never || (prio < t.min_prio && t.until > now));
-      class_error |= lower && (t.flags & SPX_PTOL_POD_CLASS_MISSING);
-      const bool pv = lower && !exempted;
-      if (!__any(pv)) continue;
-      set_bit(pot, k, pv);
-      n_pot += pv;
-      move_pod(k, pv, false);
-    }
-    if (live) {
-      if (class_error) out.status = SPX_PREEMPT_ST_CLASS_ERROR, live = false;
-      else if (n_pot == 0) out.status = SPX_PREEMPT_ST_NO_VICTIMS, live = false;
-      else if (!fits(fit, alloc, requested)) out.status = SPX_PREEMPT_ST_NOT_FIT, live = false;
-    }
-    if (__any(live)) {
-      // filterPodsWithPDBViolation over the potential victims, most important first; the budgets are the uploaded ones at every step
-      const int b0 = nd.pdb_begin, n_pdb = nd.pdb_end - b0;
-      if (n_pdb > 0) {
-        for (int i = 0; i < n_pdb; ++i) budget[i][lane] = static_cast<int16_t>(max(-1, min(32767, a.pdb_allowed[b0 + i])));
-        for (int k = 0; k < L; ++k) {
-          const int pos = pods[k].hi_order;
-          uint32_t bits = pods[pos].pdb_mask;
-          if (!bits || left(pos)) continue;
-          const bool pv = live && get_bit(pot, pos);
-          bool hit = false;
-          while (bits) {
-            const int i = __builtin_ctz(bits);
-            bits &= bits - 1;
-            if (pv) {
-              const int16_t rest = budget[i][lane] - 1;
-              budget[i][lane] = rest;
-              hit |= rest < 0;
-            }
-          }
-          set_bit(viol, pos, hit);
-        }
-      }
-      // reprieve, the violating pods first, each list most important first
-      int n_vict = 0, n_viol = 0, hi = INT32_MIN;
-      int64_t sum = 0, start = INT64_MAX;
-      for (int pass = n_pdb > 0 ? 0 : 1; pass < 2; ++pass) {
-        for (int k = 0; k < L; ++k) {
-          const int pos = pods[k].hi_order;
-          if (left(pos)) continue;
-          const bool pv = live && get_bit(pot, pos) && (get_bit(viol, pos) == (pass == 0));
-          if (!__any(pv)) continue;
-          move_pod(pos, pv, true);
-          const bool victim = pv && !fits(fit, alloc, requested);
-          move_pod(pos, victim, false);
-          set_bit(vict, pos, victim);
-          if (victim) {
-            const int jprio = pods[pos].prio;
-            const int64_t jstart = pods[pos].start;
-            ++n_vict;
-            n_viol += pass == 0;
-            sum += static_cast<int64_t>(jprio) + (int64_t{1} << 31);
-            start = jprio > hi ? jstart : (jprio == hi && jstart < start) ? jstart : start;
-            hi = jprio > hi ? jprio : hi;
-          }
-        }
-      }
-      if (live) {
-        if (n_vict == 0) out.status = SPX_PREEMPT_ST_ALL_REPRIEVED;
-        else out = PreemptCell{sum, start, hi, n_vict, n_viol, SPX_PREEMPT_ST_CANDIDATE};
-      }
-    }
-  }
-  if (out.status != SPX_PREEMPT_ST_CANDIDATE) {
-#pragma unroll
-    for (int i = 0; i < kWords; ++i) vict[i] = 0;
-  }
-  return out;
-}
 
 // the working copy of Requested; the other parts of the overlay start as all zero / all -1 bytes (launch_ptol_seq_init)
 __global__ __launch_bounds__(kBlock) void k_ptol_seq_init(PtolSeqArgs q) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (t >= q.t.n_nodes * S) return;
   q.requested[t] = q.t.nodes[t / S].requested[t % S];
-}
-
-// a candidate's keys in the order pickOneNodeForPreemption compares them; smaller is better
-struct PickKey {
-  int32_t viol, hi, n_vict;
-  int64_t sum, neg_start;
-};
-__device__ __forceinline__ int cmp_key(const PickKey& x, const PickKey& y) {
-  if (x.viol != y.viol) return x.viol < y.viol ? -1 : 1;
-  if (x.hi != y.hi) return x.hi < y.hi ? -1 : 1;
-  if (x.sum != y.sum) return x.sum < y.sum ? -1 : 1;
-  if (x.n_vict != y.n_vict) return x.n_vict < y.n_vict ? -1 : 1;
-  if (x.neg_start != y.neg_start) return x.neg_start < y.neg_start ? -1 : 1;
-  return 0;
 }
 
 constexpr int kPickBlock = 1024;
@@ -276,7 +89,7 @@ __global__ __launch_bounds__(64) void k_ptol_seq_apply(PtolSeqArgs q) {
   uint32_t vict[kWords];
 #pragma unroll
   for (int w = 0; w < kWords; ++w) vict[w] = 0;
-  if (n >= 0) (void)seq_cell(q, n, i, true, never, s_budget, lane, vict);
+  if (n >= 0) (void)ptol_cell<true>(a, &q, n, i, true, never, s_budget, lane, vict);
   if (lane == 0) {
 #pragma unroll
     for (int w = 0; w < kWords; ++w) q.victims[i * kWords + w] = vict[w];
@@ -338,11 +151,9 @@ __global__ __launch_bounds__(kBlock) void k_ptol_seq_cells(PtolSeqArgs q) {
   const int64_t rr = active ? r : a.n_rows - 1;  // an idle lane shadows the last row and stores nothing
   const bool want = active && !(a.row_rec[kMeta * R + rr] & kNever);  // a PreemptNever row keeps the cells of the untouched state
   uint32_t vict[kWords];
-  const PreemptCell out = seq_cell(q, node, rr, want, false, s_budget[wave], lane, vict);
+  const PreemptCell out = ptol_cell<true>(a, &q, node, rr, want, false, s_budget[wave], lane, vict);
   if (want) a.cells[node * R + r] = out;
 }
-
-inline unsigned blocks_for(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
 
 }  // namespace
 

@@ -136,53 +136,68 @@ int preempt_results(spx_engine* e, int64_t i_begin, int64_t i_end) {
   return SPX_OK;
 }
 
+// Every entry of a dry run's row list is a row of the batch.
+int rows_in_batch(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows) {
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is no row of the batch");
+  return SPX_OK;
+}
+
 // What the two toleration entry points check before anything moves: state first, then the arguments.
 int ptol_check(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns) {
   if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
   if (!e->ptol_table) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_toleration since the last spx_upload_preempt_nodes");
   if (!rows || n_rows <= 0 || !priority || !preempt_never) return fail(e, SPX_ERR_ARG, who + ": empty row list");
   if (now_ns == INT64_MAX) return fail(e, SPX_ERR_ARG, who + ": now_ns == INT64_MAX (an exempt_until_ns of INT64_MAX means for ever)");
-  for (int64_t i = 0; i < n_rows; ++i)
-    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is no row of the batch");
-  return SPX_OK;
+  return rows_in_batch(e, who, rows, n_rows);
 }
 
-// The row list, its meta column (priority, PreemptNever, and "not eligible" where `eligible` is given and 0) and the node mask on the
-// device, the result buffers and `more` sized, after the memory pre-check; then the engine's view of the run.
-int ptol_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
-               int64_t now_ns, const uint8_t* node_mask, std::vector<std::pair<DevBuf*, size_t>> more) {
+struct Staged {  // a device buffer a run needs at `bytes`; filled from src when that is set
+  DevBuf* buf;
+  size_t bytes;
+  const void* src;
+};
+
+// What every dry run stages once its arguments are checked: the limits, the memory pre-check, then the row list and the node mask on the
+// device, the row record (`fields` int64 columns), the cells, the pick and `more` sized or uploaded; then the engine's view of the run.
+int preempt_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const uint8_t* node_mask, DevBuf& rec, int fields, const std::vector<Staged>& more) {
   SPX_HIP(e, hipSetDevice(e->device));
   const size_t N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(spx::round_up(n_rows, 64));
   if (R > (size_t{1} << 24) || N > (size_t{1} << 31)) return fail(e, SPX_ERR_ARG, who + ": more than 2^24 rows");
-  const size_t cell_bytes = N * R * sizeof(spx::PreemptCell), rec_bytes = R * spx::kPtolRowFields * 8, pick_bytes = R * 5 * 4,
-               mask_bytes = node_mask ? static_cast<size_t>(n_rows) * N : 0, list_bytes = static_cast<size_t>(n_rows) * 8;
+  std::vector<Staged> want = {{&e->d_pre_rows, static_cast<size_t>(n_rows) * 8, rows},
+                              {&rec, R * static_cast<size_t>(fields) * 8, nullptr},
+                              {&e->d_pre_cells, N * R * sizeof(spx::PreemptCell), nullptr},
+                              {&e->d_pre_pick, R * 5 * 4, nullptr}};
+  want.insert(want.end(), more.begin(), more.end());
+  if (node_mask) want.push_back({&e->d_pre_mask, static_cast<size_t>(n_rows) * N, node_mask});
   {  // refuse what cannot fit instead of failing in hipMalloc: what has to grow against what is free
     size_t free_b = 0, total_b = 0, grow = 0;
     SPX_HIP(e, hipMemGetInfo(&free_b, &total_b));
-    std::vector<std::pair<DevBuf*, size_t>> want = {{&e->d_pre_cells, cell_bytes}, {&e->d_ptol_rec, rec_bytes},  {&e->d_pre_pick, pick_bytes},
-                                                    {&e->d_pre_mask, mask_bytes},  {&e->d_pre_rows, list_bytes}, {&e->d_ptol_meta, list_bytes}};
-    want.insert(want.end(), more.begin(), more.end());
-    for (const auto& w : want)
-      if (w.second > w.first->bytes) grow += w.second, free_b += w.first->bytes;  // ensure() frees the old allocation first
+    for (const Staged& w : want)
+      if (w.bytes > w.buf->bytes) grow += w.bytes, free_b += w.buf->bytes;  // ensure() frees the old allocation first
     if (grow > free_b)
       return fail(e, SPX_ERR_ARG, who + ": " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
                                       " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
   }
-  std::vector<int64_t> meta(static_cast<size_t>(n_rows));
-  for (int64_t i = 0; i < n_rows; ++i)
-    meta[i] = static_cast<int64_t>(static_cast<uint32_t>(priority[i])) | (preempt_never[i] ? int64_t{1} << 32 : 0) | (eligible && !eligible[i] ? int64_t{1} << 33 : 0);
   e->pre_valid = false;
-  int rc;
-  if ((rc = upload(e, e->d_pre_rows, rows, list_bytes)) || (rc = upload(e, e->d_ptol_meta, meta.data(), list_bytes)) || (rc = ensure(e, e->d_ptol_rec, rec_bytes)) ||
-      (rc = ensure(e, e->d_pre_cells, cell_bytes)) || (rc = ensure(e, e->d_pre_pick, pick_bytes)))
-    return rc;
-  for (const auto& w : more)
-    if ((rc = ensure(e, *w.first, w.second))) return rc;
-  if (node_mask && (rc = upload(e, e->d_pre_mask, node_mask, mask_bytes))) return rc;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));  // rows, meta and node_mask are only borrowed for the call
+  for (const Staged& w : want)
+    if (int rc = w.src ? upload(e, *w.buf, w.src, w.bytes) : ensure(e, *w.buf, w.bytes)) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // what was uploaded is only borrowed for the call
   e->pre_has_mask = node_mask != nullptr;
   e->pre_n_rows = n_rows;
   e->pre_row_stride = static_cast<int64_t>(R);
+  return SPX_OK;
+}
+
+// The toleration runs' staging: preempt_stage with the meta column of the row list (priority, PreemptNever, and "not eligible" where
+// `eligible` is given and 0) among the uploads.
+int ptol_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
+               int64_t now_ns, const uint8_t* node_mask, std::vector<Staged> more) {
+  std::vector<int64_t> meta(static_cast<size_t>(n_rows));
+  for (int64_t i = 0; i < n_rows; ++i)
+    meta[i] = static_cast<int64_t>(static_cast<uint32_t>(priority[i])) | (preempt_never[i] ? int64_t{1} << 32 : 0) | (eligible && !eligible[i] ? int64_t{1} << 33 : 0);
+  more.push_back({&e->d_ptol_meta, meta.size() * 8, meta.data()});
+  if (int rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_ptol_rec, spx::kPtolRowFields, more)) return rc;
   e->pre_toleration = true;
   e->ptol_now = now_ns;
   return SPX_OK;
@@ -274,35 +289,10 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
   if (!e) return SPX_ERR_ARG;
   if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, "preemption dry run: the quota tables (spx_upload_quota with min) are not uploaded");
   if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, "preemption dry run: spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
-  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, "preemption dry run: empty row list");
-  for (int64_t i = 0; i < n_rows; ++i)
-    if (rows[i] < 0 || rows[i] >= e->n_pods) return fail(e, SPX_ERR_ARG, "preemption dry run: rows[" + std::to_string(i) + "] is no row of the batch");
-  SPX_HIP(e, hipSetDevice(e->device));
-  const size_t N = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(spx::round_up(n_rows, 64));
-  if (R > (size_t{1} << 24) || N > (size_t{1} << 31)) return fail(e, SPX_ERR_ARG, "preemption dry run: more than 2^24 rows");
-  const size_t cell_bytes = N * R * sizeof(spx::PreemptCell), rec_bytes = R * spx::kPreemptRowFields * 8, pick_bytes = R * 5 * 4,
-               mask_bytes = node_mask ? static_cast<size_t>(n_rows) * N : 0;
-  {  // refuse what cannot fit instead of failing in hipMalloc: what has to grow against what is free
-    size_t free_b = 0, total_b = 0, grow = 0;
-    SPX_HIP(e, hipMemGetInfo(&free_b, &total_b));
-    const std::pair<const DevBuf*, size_t> want[] = {{&e->d_pre_cells, cell_bytes}, {&e->d_pre_rec, rec_bytes}, {&e->d_pre_pick, pick_bytes},
-                                                      {&e->d_pre_mask, mask_bytes}, {&e->d_pre_rows, static_cast<size_t>(n_rows) * 8}};
-    for (const auto& w : want)
-      if (w.second > w.first->bytes) grow += w.second, free_b += w.first->bytes;  // ensure() frees the old allocation first
-    if (grow > free_b)
-      return fail(e, SPX_ERR_ARG, "preemption dry run: " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
-                                      " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
-  }
-  e->pre_valid = false;
+  const std::string who = "preemption dry run";
+  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, who + ": empty row list");
   int rc;
-  if ((rc = upload(e, e->d_pre_rows, rows, static_cast<size_t>(n_rows) * 8)) || (rc = ensure(e, e->d_pre_rec, rec_bytes)) || (rc = ensure(e, e->d_pre_cells, cell_bytes)) ||
-      (rc = ensure(e, e->d_pre_pick, pick_bytes)))
-    return rc;
-  if (node_mask && (rc = upload(e, e->d_pre_mask, node_mask, mask_bytes))) return rc;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));  // rows and node_mask are only borrowed for the call
-  e->pre_has_mask = node_mask != nullptr;
-  e->pre_n_rows = n_rows;
-  e->pre_row_stride = static_cast<int64_t>(R);
+  if ((rc = rows_in_batch(e, who, rows, n_rows)) || (rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, {}))) return rc;
   e->pre_toleration = e->pre_sequential = false;
   spx::PreemptArgs a = preempt_args(e);
   SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
@@ -311,7 +301,7 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
     e->pre_marks_valid = true;
   }
   spx::launch_preempt_rows(a, e->stream);
-  spx::launch_preempt_cells(a, static_cast<unsigned>(N), e->stream);
+  spx::launch_preempt_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
   spx::launch_preempt_pick(a, e->stream);
   SPX_HIP(e, hipGetLastError());
   SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
@@ -402,9 +392,8 @@ int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_
   const size_t o_head = carve(static_cast<size_t>(N) * 4), minus_one = total - o_head;
   const size_t o_req = carve(static_cast<size_t>(N) * S * 8), o_next = carve(R * 4), o_vict = carve(R * kSetBytes),
                o_dirty = carve(static_cast<size_t>(n_rows) * static_cast<size_t>(n_dirty) * 4);
-  if (int rc = ptol_stage(e, who, rows, n_rows, priority, preempt_never, eligible, now_ns, node_mask, {{&e->d_pseq, total}, {&e->d_pseq_nom, csr.size() * 4}})) return rc;
-  if (int rc = upload(e, e->d_pseq_nom, csr.data(), csr.size() * 4)) return rc;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));  // the staged CSR lives until the copy has landed
+  if (int rc = ptol_stage(e, who, rows, n_rows, priority, preempt_never, eligible, now_ns, node_mask, {{&e->d_pseq, total, nullptr}, {&e->d_pseq_nom, csr.size() * 4, csr.data()}}))
+    return rc;
   char* const base = static_cast<char*>(e->d_pseq.p);
   spx::PtolSeqArgs q{};
   q.t = ptol_args(e);
