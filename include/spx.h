@@ -1244,6 +1244,11 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
  *                              (spx_tlp_pod_classes reports the count).  2 = whenever at least one row is a copy (measurements);
  *                              0 = every row is evaluated, in row order.  Same tables either way; spx_tlp_form reports what ran.
  *                              spx_decide's sweep and partial row ranges always evaluate every row
+ *   SPX_OPT_TLP_CHUNK_SCHED    1 (default) = the order of SPX_OPT_TLP_POD_CLASSES is launched heaviest chunk first: its chunks of 64 positions
+ *                              are sorted (stable) by descending number of positions the sweep evaluates in them, so that the launch ends
+ *                              in waves that only store instead of in the waves that compute most; the last, partial chunk stays last.
+ *                              0 = the chunks in value order.  Read when the order is built, i.e. it takes effect at the next upload of
+ *                              the pod column.  Same tables and the same spx_tlp_pod_classes either way
  */
 #define SPX_OPT_ROW_ALIGN 0
 #define SPX_OPT_REFERENCE_KERNELS 1
@@ -1267,7 +1272,8 @@ int spx_last_eval_ms(spx_engine* e, float* ms);
 #define SPX_OPT_NRT_WIDE 19
 #define SPX_OPT_ALLOC_TABLE_KEEP 20
 #define SPX_OPT_TLP_POD_CLASSES 21
-#define SPX_NUM_OPTIONS 22
+#define SPX_OPT_TLP_CHUNK_SCHED 22
+#define SPX_NUM_OPTIONS 23
 int spx_set_option(spx_engine* e, int option, int64_t value);
 int spx_get_option(const spx_engine* e, int option, int64_t* value);
 
@@ -1288,6 +1294,10 @@ int spx_tlp_pod_classes(const spx_engine* e, int64_t* rows_evaluated, int64_t* r
 /* Which form the last spx_eval with TargetLoadPacking in the mask launched for it: 1 = every row evaluated in row order, 2 = the class
  * form; 0 = none yet, or the reference-arithmetic kernel ran (SPX_OPT_REFERENCE_KERNELS, a target outside [1, 99]) */
 int spx_tlp_form(const spx_engine* e);
+/* The order the class form sweeps the uploaded batch in, copied to the host (tests, measurements): rows[pos] = the pod row at position
+ * pos, n_pods entries.  Positions [64 c, 64 c + 64) are one wave's chunk; SPX_OPT_TLP_CHUNK_SCHED decides the order of the chunks.
+ * SPX_ERR_STATE without an order. */
+int spx_tlp_fetch_order(spx_engine* e, int32_t* rows);
 
 /* The same for the uploaded SySched pod batch (spx_upload_sysched_pods): a pod enters SySched.Score through its syscall set alone, so
  * n_unique = pods that are the first of the batch with their set, n_copies = the rest. */

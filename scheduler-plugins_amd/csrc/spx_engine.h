@@ -61,7 +61,7 @@ struct spx_engine {
   int64_t row_stride = 0;
 
   // spx_set_option state (per engine; nothing is read from the environment)
-  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0, 1, 1};
+  int64_t option[SPX_NUM_OPTIONS] = {spx::kRowPad, 0, 0, 0, 0, 0, 44, 1, 1, 375, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1};
 
   // params
   int32_t alloc_mode = SPX_MODE_LEAST;
@@ -413,14 +413,16 @@ int tlp_build_order(spx_engine* e) {
   e->tlp_order_valid = false;
   if (e->n_pods <= 0 || e->n_pods > std::numeric_limits<int32_t>::max()) return SPX_OK;  // (rows are int32 in the order: such a batch sweeps plain)
   int rc;
-  const size_t words = spx::tlp_order_scratch_words(spx::kTlpAmbSize);
+  const size_t words = spx::tlp_order_scratch_words(spx::kTlpAmbSize, e->n_pods);
   if ((rc = ensure(e, e->d_tlp_order, static_cast<size_t>(e->n_pods) * sizeof(int32_t))) || (rc = ensure(e, e->d_tlp_order_scratch, words * sizeof(uint32_t))))
     return rc;
   uint32_t* scratch = static_cast<uint32_t*>(e->d_tlp_order_scratch.p);
-  spx::launch_tlp_order(static_cast<const int64_t*>(e->d_tlp_pod.p), e->n_pods, spx::kTlpAmbSize, static_cast<int32_t*>(e->d_tlp_order.p), scratch, e->stream);
+  // (SPX_OPT_TLP_CHUNK_SCHED is read here: the order in place keeps the schedule it was built with)
+  spx::launch_tlp_order(static_cast<const int64_t*>(e->d_tlp_pod.p), e->n_pods, spx::kTlpAmbSize, e->option[SPX_OPT_TLP_CHUNK_SCHED] != 0,
+                        static_cast<int32_t*>(e->d_tlp_order.p), scratch, e->stream);
   SPX_HIP(e, hipGetLastError());
   uint32_t evaluated = 0;
-  SPX_HIP(e, hipMemcpyAsync(&evaluated, scratch + (words - 1), sizeof evaluated, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(&evaluated, scratch + spx::tlp_order_evaluated_word(spx::kTlpAmbSize), sizeof evaluated, hipMemcpyDeviceToHost, e->stream));
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   e->tlp_rows_evaluated = evaluated;
   e->tlp_order_valid = true;

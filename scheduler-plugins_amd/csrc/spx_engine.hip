@@ -143,6 +143,7 @@ int spx_set_option(spx_engine* e, int option, int64_t value) {
     case SPX_OPT_NRT_FUSED:
     case SPX_OPT_NRT_WIDE:
     case SPX_OPT_ALLOC_TABLE_KEEP:
+    case SPX_OPT_TLP_CHUNK_SCHED:
       if (value != 0 && value != 1) return fail(e, SPX_ERR_ARG, "option takes 0 or 1");
       break;
     case SPX_OPT_TLP_POD_CLASSES:
@@ -732,6 +733,15 @@ int spx_tlp_pod_classes(const spx_engine* e, int64_t* rows_evaluated, int64_t* r
 }
 
 int spx_tlp_form(const spx_engine* e) { return e ? e->tlp_last_form : 0; }
+
+int spx_tlp_fetch_order(spx_engine* e, int32_t* rows) {
+  if (!e || !rows) return SPX_ERR_ARG;
+  if (!e->tri_pods || !e->tlp_order_valid) return fail(e, SPX_ERR_STATE, "TargetLoadPacking: no row order (no pod batch uploaded, or more than 2^31 - 1 rows)");
+  const size_t n = static_cast<size_t>(e->n_pods);
+  SPX_HIP(e, hipMemcpyAsync(rows, e->d_tlp_order.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  return SPX_OK;
+}
 
 int spx_nrt_wide(const spx_engine* e) { return e && e->nrt_wide ? 1 : 0; }
 

@@ -138,11 +138,15 @@ struct TrimaranArgs {
 // evaluates the plugins whose out_* pointer is non-NULL
 void launch_trimaran(const TrimaranArgs& a, hipStream_t s);
 // The row order of TargetLoadPacking's class form (kernels_tlp_order.hip): order[] = a permutation of [0, n_rows) with the rows whose
-// pod value lies in [0, amb_size) sorted by value and all others behind them; scratch: uint32 [tlp_order_scratch_words(amb_size)],
-// whose LAST word is left holding the number of positions p with p % 64 == 0 or pod[order[p]] != pod[order[p - 1]] — the rows the
-// class form evaluates.  Histogram, scan, scatter and that count for the rows outside the table, on the stream.
-size_t tlp_order_scratch_words(int32_t amb_size);
-void launch_tlp_order(const int64_t* pod_milli, int64_t n_rows, int32_t amb_size, int32_t* order, uint32_t* scratch, hipStream_t s);
+// pod value lies in [0, amb_size) sorted by value and all others behind them, in chunks of 64 positions; chunk_sched: the whole chunks
+// then stand in descending order of the positions the class form evaluates in them (stable; the last, partial chunk stays last), so
+// that the sweep launches its heaviest waves first — otherwise in value order.  scratch:
+// uint32 [tlp_order_scratch_words(amb_size, n_rows)], whose word tlp_order_evaluated_word(amb_size) is left holding the number of
+// positions p with p % 64 == 0 or pod[order[p]] != pod[order[p - 1]] — the rows the class form evaluates, whatever the schedule.
+// Histogram, scan, scatter, the chunks' keys (and that count for the rows outside the table), schedule and move, on the stream.
+size_t tlp_order_scratch_words(int32_t amb_size, int64_t n_rows);
+size_t tlp_order_evaluated_word(int32_t amb_size);
+void launch_tlp_order(const int64_t* pod_milli, int64_t n_rows, int32_t amb_size, bool chunk_sched, int32_t* order, uint32_t* scratch, hipStream_t s);
 size_t lvrb_amb_bytes();
 // sequential commit loop over pod rows [t.row_begin, t.row_end) for Allocatable (bit 0) / TLP (bit 1) / LVRB (bit 2)
 struct CommitArgs {

@@ -162,6 +162,12 @@ class Engine:
         self._ck(self._lib.spx_tlp_pod_classes(self._h, C.byref(u), C.byref(d)))
         return int(u.value), int(d.value)
 
+    def tlp_order(self):
+        """the pod row at every position of the class form's order (spx_tlp_fetch_order)"""
+        rows = np.zeros(self.n_pods, np.int32)
+        self._ck(self._lib.spx_tlp_fetch_order(self._h, rows.ctypes.data_as(C.POINTER(C.c_int32))))
+        return rows
+
     def tlp_form(self) -> int:
         """what the last eval launched for TargetLoadPacking: 1 = every row in row order, 2 = the class form, 0 = neither (spx_tlp_form)"""
         return int(self._lib.spx_tlp_form(self._h))
