@@ -1100,7 +1100,10 @@ int spx_bind_score_table(spx_engine* e, int plugin, void* dptr, int64_t row_stri
 
 /* per-pod weighted argmax over the evaluated plugins: best[k] node indices and their
  * sum_i weight[i]*score_i (upstream selectHost input); infeasible nodes are skipped.
- * `weights` holds SPX_NUM_PLUGINS entries indexed by plugin id */
+ * `weights` holds SPX_NUM_PLUGINS entries indexed by plugin id.  Any int64 is a weight, negative ones included (the general
+ * int64 argmax serves what the 32-bit one does not: a negative weight, a weight >= 2^23, sum of weight * 255 >= 2^31), as long
+ * as no total can leave int64: with sum of |weight| * 255 over the plugins that own a score table above INT64_MAX the call
+ * is refused with SPX_ERR_ARG and the weights in place stay (the largest single weight is 36170086419038336) */
 int spx_set_plugin_weights(spx_engine* e, const int64_t* weights);
 int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end);
 /* per pod in [row_begin,row_end): best node (lowest index among ties, -1 when no node is feasible or the pod

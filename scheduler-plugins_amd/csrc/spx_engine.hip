@@ -227,6 +227,12 @@ int spx_set_lvrb_params(spx_engine* e, const spx_lvrb_params* p) {
 
 int spx_set_plugin_weights(spx_engine* e, const int64_t* weights) {
   if (!e || !weights) return SPX_ERR_ARG;
+  // the argmax sums weight x byte (<= 255) over the score tables in int64 (k_best): weights whose totals could leave it are refused
+  unsigned __int128 bound = 0;
+  for (int k = 0; k < SPX_NUM_PLUGINS; ++k)
+    if (plugin_has_score(k)) bound += static_cast<unsigned __int128>(weights[k] < 0 ? 0 - static_cast<uint64_t>(weights[k]) : static_cast<uint64_t>(weights[k])) * 255u;
+  if (bound > static_cast<unsigned __int128>(std::numeric_limits<int64_t>::max()))
+    return fail(e, SPX_ERR_ARG, "plugin weights: sum of |weight| * 255 over the scoring plugins exceeds int64 (a weighted total could overflow)");
   std::memcpy(e->plugin_weight, weights, sizeof e->plugin_weight);
   return SPX_OK;
 }

@@ -1180,6 +1180,10 @@ class Engine:
     def bind_score_table(self, plugin: int, dptr: int, row_stride: int, n_rows: int) -> None:
         self._ck(self._lib.spx_bind_score_table(self._h, plugin, C.c_void_p(dptr), row_stride, n_rows))
 
+    def bind_status_table(self, plugin: int, dptr: int, row_stride: int, n_rows: int) -> None:
+        """a Filter plugin's (NRT, NETOVERHEAD) uint8 status table in caller-owned memory, rows of the engine row stride; dptr 0 unbinds"""
+        self._ck(self._lib.spx_bind_status_table(self._h, plugin, C.c_void_p(dptr), row_stride, n_rows))
+
     def upload_feasible_mask(self, mask: Optional[np.ndarray]) -> None:
         """[n_pods][n_nodes] uint8, non-zero = the node passed the caller's other Filter plugins; None clears it."""
         if mask is None:

@@ -1,8 +1,14 @@
 """spx_decide: the per-pod decision (best node, weighted score, ties, feasible) computed without materialising score tables
-must equal spx_eval + spx_eval_best exactly — it is the same float32/float64 cell code with the argmax folded in."""
+must equal spx_eval + spx_eval_best exactly — it is the same float32/float64 cell code with the argmax folded in.
+
+That equality holds code under test to code under test: it rests on spx_eval_best being right.  The independent anchor is
+tests/test_gpu_best_edges.py, which holds spx_eval_best's kernels to a numpy int64 reference (tests/best_cases.py) on constructed
+tables; the threshold tests at the end of this file apply the same reference to the tables a separate spx_eval wrote, so that a
+disagreement names which of the three (spx_decide, spx_eval_best, the reference over spx_eval's bytes) is off."""
 import numpy as np
 import pytest
 
+from best_cases import reference
 from helpers import ALLOCATABLE, CAPACITY, LROC, LVRB, NETOVERHEAD, NRT, PEAKS, TLP
 from scheduler_plugins_amd import synth
 from scheduler_plugins_amd import SpxError
@@ -178,3 +184,91 @@ def test_decide_with_filter_plugins_falls_back_on_a_wide_allocatable_range(gpu_r
         for w, g in zip(want, got):
             assert (w == g).all()
         assert e.all_scores(ALLOCATABLE).shape == (60, 200)
+
+
+# ------------------------------------------------------------------ the dispatch thresholds, against the numpy reference
+def three_way(e, plugins, weights, filters=(), prefilter=None):
+    """(reference over the tables of a separate spx_eval, spx_eval_best, spx_decide) on one engine, every row; asserts all equal"""
+    mask = mask_of(*plugins)
+    e.set_plugin_weights(weights)
+    e.eval(mask)
+    e.sync()
+    scores = {p: e.all_scores(p) for p in plugins if p in weights}
+    statuses = [e.all_status(p) for p in filters]
+    rejected = (e.prefilter(prefilter) != 0) if prefilter is not None else None
+    want = reference(scores, weights, statuses, e.n_nodes, rejected)
+    e.eval_best(mask)
+    unfused = [x.copy() for x in e.best()]
+    e.decide(mask)
+    decided = e.best()
+    for name, w, u, d in zip(("node", "score", "ties", "feasible"), want, unfused, decided):
+        bad_u, bad_d = np.flatnonzero(u != w), np.flatnonzero(d != w)
+        assert len(bad_u) == 0, ("spx_eval_best differs from the reference", name, weights, bad_u[:5], u[bad_u[:5]], w[bad_u[:5]])
+        assert len(bad_d) == 0, ("spx_decide differs from the reference", name, weights, bad_d[:5], d[bad_d[:5]], w[bad_d[:5]])
+    return want
+
+
+@pytest.mark.parametrize("n_nodes,seed", [(1025, 4), (3000, 5)])
+# the weights of the mask sum to 8000: the last sum the fused sweep's 32-bit key admits (8000 << 11, the multiplier v_mad_u32_u24 takes,
+# is 2 % below 2^24); 8001 is the first sum that leaves the fused form
+@pytest.mark.parametrize("plugins,weights,fused", [
+    ((TLP,), {TLP: 8000}, True),
+    ((ALLOCATABLE, TLP, LVRB), {ALLOCATABLE: 3999, TLP: 4000, LVRB: 1}, True),
+    ((TLP, LVRB), {TLP: 1, LVRB: 7999}, True),
+    ((ALLOCATABLE, TLP), {ALLOCATABLE: 8000, TLP: 0}, True),
+    ((TLP,), {TLP: 8001}, False),
+])
+def test_decide_at_the_fused_sweeps_weight_limit(gpu_required, hdr, n_nodes, seed, plugins, weights, fused):
+    n_pods = 100
+    snap = synth.trimaran_snapshot(hdr, n_nodes, n_pods, seed=seed, round_frac=1.0)
+
+    def load(e):
+        e.load_trimaran_objects(snap["nodes"], snap["rc"], snap["pods"], snap["metrics"], snap["assigned"])
+
+    with Engine(0) as e:
+        load(e)
+        want = three_way(e, plugins, weights)
+    # rounded metrics: ties exist wherever the load-based plugins decide (Allocatable's normalised byte has one maximum among the
+    # generator's nodes, and with a weight in the thousands it separates the totals)
+    assert (want[2] > 1).any() or ALLOCATABLE in plugins
+    assert want[1].max() <= sum(weights.values()) * 100 and (want[3] == n_nodes).all()
+    with Engine(0) as e:   # which form ran: the fused sweep never writes TargetLoadPacking's table
+        load(e)
+        e.set_plugin_weights(weights)
+        e.decide(mask_of(*plugins))
+        for w, g in zip(want, e.best()):
+            assert (w == g).all()
+        if fused:
+            with pytest.raises(SpxError):
+                e.all_scores(TLP, 0, n_pods)
+        else:
+            assert e.all_scores(TLP, 0, n_pods).shape == (n_pods, n_nodes)
+
+
+@pytest.mark.parametrize("row_workgroup", [0, 1])
+def test_decide_with_filter_plugins_at_the_weight_thresholds(gpu_required, hdr, row_workgroup):
+    """k_decide_masked is admitted for weights < 2^23 with sum(weight * 255) < 2^31 (decide_masked_ok): just under the bound it
+    runs and leaves Allocatable's table unwritten; just over, and with a negative weight, spx_decide is spx_eval + spx_eval_best
+    through the general int64 argmax"""
+    from test_gpu_profile import ALL
+    tables, filters = (ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD), (NRT, NETOVERHEAD)
+    under = {ALLOCATABLE: 8388607, TLP: 32892, LVRB: 1, NRT: 1, NETOVERHEAD: 1}
+    over = {**under, TLP: 32898}
+    assert sum(under.values()) * 255 < 2 ** 31 <= sum(over.values()) * 255 and max(under.values()) < 2 ** 23
+    with Engine(0) as e:
+        e.set_option("ROW_WORKGROUP", row_workgroup)
+        _full(e, hdr, 300, 200, 1, under)
+        want = three_way(e, ALL, under, filters, CAPACITY)
+        assert (want[0] < 0).any() and (want[0] >= 0).any() and want[1].max() > 2 ** 29
+        with pytest.raises(SpxError):        # the fused form ran: nothing was written to Allocatable's table
+            e.all_scores(ALLOCATABLE)
+        three_way(e, ALL, over, filters, CAPACITY)
+        assert e.all_scores(ALLOCATABLE).shape == (200, 300)   # the unfused route: table written
+        e.set_plugin_weights(under)
+        e.decide(mask_of(*ALL))
+        with pytest.raises(SpxError):        # (and fused again under the bound, so that the next line says something)
+            e.all_scores(ALLOCATABLE)
+        negative = {ALLOCATABLE: -1, TLP: 2, LVRB: 1, NRT: 3, NETOVERHEAD: 2}
+        want = three_way(e, ALL, negative, filters, CAPACITY)
+        assert e.all_scores(ALLOCATABLE).shape == (200, 300)
+        assert (want[0] >= 0).any()
