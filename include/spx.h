@@ -862,6 +862,8 @@ typedef struct spx_net_commit_soa {
  *   spx_preempt_dry_run + spx_fetch_preempt_*  CapacityScheduling.PostFilter: SelectVictimsOnNode per (pod, node), pickOneNodeForPreemption
  *                                              capacity_scheduling.go:331-348, :486-677, :889-934
  *   spx_preempt_eligible                       preemptor.PodEligibleToPreemptOthers    capacity_scheduling.go:409-484
+ *   spx_preempt_sequential                     CapacityScheduling.PostFilter repeated over a batch, each pod against what the earlier ones
+ *                                              evicted, nominated and took out of their quotas' Used (deletePodIfPresent :778-792)
  *   spx_eval_best + spx_fetch_best             upstream prioritizeNodes + selectHost input (sum of weight x score over feasible nodes)
  *   spx_decide + spx_fetch_best                the same decision input without materialising the per-plugin tables
  *   spx_commit_sequential                      upstream scheduleOne repeated over the queue, with trimaran's bind-time bookkeeping
@@ -1064,6 +1066,52 @@ int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n
  * victim set stored at the step, as positions in the UPLOADED list of the node, most important first, and is SPX_ERR_ARG for any other
  * node (the state that cell saw is gone). */
 int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible, int64_t now_ns, const uint8_t* node_mask);
+
+/* CapacityScheduling's sequential preemption loop (kernels_preempt_seq.hip).  Tables, argument checks, limits, the
+ * memory pre-check and staleness are spx_preempt_dry_run's, plus the side table below; a pod row listed twice is SPX_ERR_ARG.
+ * spx_preempt_nominated_quota_soa: one entry per nominated record of the uploaded node table, in nom_ptr CSR order (n_nominated ==
+ * nom_ptr[N]): the pod's namespace and its computePodResourceRequest with the scalar-key mask (spx_flatten_preempt_nominated_quota
+ * forms all three).  spx_upload_preempt_nominated_quota: SPX_ERR_STATE before spx_upload_preempt_nodes; SPX_ERR_ARG when n_nominated
+ * differs from the node table's nominated count; it marks earlier results stale, and a later spx_upload_preempt_nodes drops the table.
+ * The loop needs it (SPX_ERR_STATE without) unless the node table has no nominated records.  Inside the loop PreFilter's two nominated
+ * sums (capacity_scheduling.go:226-265) are formed from THIS list and the loop's own nominations, not from spx_quota_soa's nom_* list:
+ * the device then has one list of nominated pods that it can clear and extend.  Precondition: both lists describe the same nominated
+ * pods (those on present nodes); then a one-row loop is spx_preempt_dry_run of that row, bit for bit.
+ * The rows are attempted once each, in list order.  Step i evaluates rows[i] on every unmasked present node (the dry run's
+ * SelectVictimsOnNode and pick) against the state that steps 0..i-1 left, then applies (T1-T3 only when a node n was picked; restated
+ * from upstream kube-scheduler — the nominator, prepareCandidate, the pod delete event reaching deletePod —, unpinned by a reference test):
+ *   T4  every uploaded nomination of rows[i] itself, on any node, is dropped, also when there is no candidate
+ *   T1  the victims of cell (i, n) leave n: Requested and the pod count shrink, nobody walks them again; for a victim of a quota'd
+ *       namespace deletePodIfPresent (capacity_scheduling.go:778-792, elasticquota.go:172-187): that quota's Used and the aggregate Used
+ *       shrink by the pod's quota request iff its SPX_PREEMPT_POD_IN_QUOTA_SET bit is set, scalar key presence OR-ed in (SetScalar)
+ *   T3  nominated pods of n with a priority BELOW rows[i]'s lose their nomination, uploaded ones and earlier rows of the loop alike:
+ *       they stop counting in the Filter's charge and in both PreFilter sums
+ *   T2  rows[i] becomes a pod nominated to n, with its namespace, priority, fit_req and quota request.  It does not enter Used
+ *       (Reserve's job)
+ * At its own step a row sees: nominatedPodsReqInEQWithPodReq = its request + the live nominated entries of its namespace with priority
+ * >= its own, other than itself; nominatedPodsReqWithPodReq = that + the live entries of other quota'd namespaces whose quota is not
+ * usedOverMin() on the CURRENT Used; usedOverMinWith(inEQ) on the current Used; the borrowed marks formed from the current Used,
+ * skipping the pods that left; the node's working Requested; the charge of the live nominated entries.  The sums are wrapping int64 adds.
+ * eligible[i] == 0 (NULL = all eligible): the row is evaluated at its own step, its pick is reported and nothing is applied (T4
+ * included).  There is no preempt_never column, as the capacity dry run has none: such rows arrive with eligible == 0.
+ * PDB DisruptionsAllowed stays as uploaded.  A row whose nomination T3 cleared is not attempted again; eligibility is not recomputed.
+ * The uploaded tables and marks are never written: a dry run of either kind after the loop gives what it gave before it, and a second
+ * loop starts from the uploaded state.
+ * Asynchronous on the engine stream, no host round trip between steps; spx_last_eval_ms reports the device time of the whole loop.
+ * Memory beyond the dry run's: 100 bytes per node, 37 bytes per row, 65 bytes per namespace, one byte per assigned pod and per
+ * nominated record (plus 69 per record for the side table).
+ * The fetches answer for the loop until the next dry run of either kind: spx_fetch_preempt_pick / _cells / _keys give row i's pick
+ * and cells as it saw them at its own step (column i of the cell buffer is written at step i and never again);
+ * spx_fetch_preempt_victims(i, node) answers for node == row i's picked node from the victim set stored at the step, as positions
+ * in the UPLOADED list of the node, most important first, and is SPX_ERR_ARG for any other node. */
+typedef struct spx_preempt_nominated_quota_soa {
+  int64_t n_nominated;
+  const int32_t* ns;
+  const int64_t* quota_req;          /* [n_nominated][8] */
+  const uint8_t* quota_req_present;
+} spx_preempt_nominated_quota_soa;
+int spx_upload_preempt_nominated_quota(spx_engine* e, const spx_preempt_nominated_quota_soa* t);
+int spx_preempt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask);
 
 /* optional per-(pod,node) feasibility mask for normalizing score plugins: uint8 [n_pods][n_nodes],
  * non-zero = node passed Filter for that pod (upstream scores feasible nodes only).  NULL clears it. */
@@ -1541,6 +1589,12 @@ int spx_flatten_quota(const spx_pod_objects* pods, const spx_resource_classes* r
 int spx_flatten_preempt_nodes(const spx_node_objects* nodes, const spx_resource_classes* rc, const spx_quota_objects* q, const spx_preempt_objects* o, int64_t* n_pods_out, int64_t* n_nom_out, int64_t* n_pdb_out, int64_t* bad_out, uint8_t* present, int64_t* allocatable, int64_t* requested, int32_t* pod_ptr, int32_t* pod_src, int32_t* pod_priority, int64_t* pod_start, int32_t* pod_ns, int64_t* pod_fit_req, int64_t* pod_quota_req, uint8_t* pod_quota_req_present, uint8_t* pod_flags, uint32_t* pod_pdb_mask, int32_t* pod_hi_order, int32_t* nom_ptr, int32_t* nom_priority, int64_t* nom_fit_req, int64_t* nom_pending_row, int32_t* pdb_ptr, int32_t* pdb_allowed);
 /* the checks spx_upload_preempt_nodes applies, host only: SPX_OK, or SPX_ERR_ARG with *bad_node_out = the first offending node */
 int spx_preempt_check(const spx_preempt_nodes_soa* t, int64_t* bad_node_out);
+/* The side table of CapacityScheduling's sequential loop: spx_preempt_nominated_quota_soa's columns for the nominated pods of
+ * `o`, in the record order of spx_flatten_preempt_nodes' table (node by node, the objects' order within a node; pods nominated to an
+ * absent node, or to node -1, are left out).  n_nom: that table's nominated count (*n_nom_out); SPX_ERR_ARG when it differs.  nom_src
+ * (may be NULL) [n_nom]: index of each record's pod in o->nominated.  ns: the object's namespace, whether it has a quota or not;
+ * quota_req / quota_req_present: computePodResourceRequest (:865-882) as spx_flatten_quota forms it.  Host only. */
+int spx_flatten_preempt_nominated_quota(const spx_node_objects* nodes, const spx_resource_classes* rc, const spx_quota_objects* q, const spx_preempt_objects* o, int64_t n_nom, int32_t* nom_src, int32_t* ns, int64_t* quota_req, uint8_t* quota_req_present);
 /* preemptor.PodEligibleToPreemptOthers (:409-484) for n pods: ns / priority / preempt_never of the pod, nominated_node (-1 = none, an
  * absent node answers eligible as a nil NodeInfo does), nominated_unresolvable = the nominated node's Filter status code was
  * UnschedulableAndUnresolvable, more_than_min = usedOverMinWith(nominatedPodsReqInEQWithPodReq) of the pod (read only when its

@@ -169,4 +169,7 @@ void launch_ptol_seq_step(const PtolSeqArgs& q, hipStream_t s) {
   if (q.step + 1 < q.t.n_rows) hipLaunchKernelGGL(k_ptol_seq_cells, dim3(q.n_dirty, blocks_for(q.t.n_rows, kBlock)), dim3(kBlock), 0, s, q);
 }
 
+// the pick of column q.step alone: CapacityScheduling's loop (kernels_preempt_seq.hip) picks over the same 32-byte cells
+void launch_ptol_seq_pick(const PtolSeqArgs& q, hipStream_t s) { hipLaunchKernelGGL(k_ptol_seq_pick, dim3(1), dim3(kPickBlock), 0, s, q); }
+
 }  // namespace spx

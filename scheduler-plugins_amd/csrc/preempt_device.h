@@ -1,8 +1,8 @@
 // preempt_device.h — the one copy of the device helpers that the preemption kernels share: kernels_preempt.hip (CapacityScheduling's
 // dry run), kernels_ptol.hip (PreemptionToleration's) and kernels_ptol_seq.hip (its sequential loop).  The launch shape (a wave per
 // node, a lane per preemptor, 256-bit sets over a node's pod list), the register helpers of the cell walks, NodeResourcesFit, and the
-// key pickOneNodeForPreemption orders candidates by.  What is one plugin's stays in its unit: cmp2 and the quota state in
-// kernels_preempt.hip, the toleration walk in ptol_cell.h.
+// key pickOneNodeForPreemption orders candidates by.  What is one plugin's stays with it: cmp2, the quota state and the capacity walk in
+// cap_cell.h (kernels_preempt.hip and kernels_preempt_seq.hip), the toleration walk in ptol_cell.h.
 //
 // Everything is in the anonymous namespace: each translation unit gets its own copy.  NodeResourcesFit (default args) and
 // pickOneNodeForPreemption restate upstream kube-scheduler code that is not in the reference tree.

@@ -263,7 +263,7 @@ struct spx_engine {
   DevBuf d_ptol_pods, d_ptol_meta, d_ptol_rec;
   bool ptol_table = false, pre_toleration = false;
   int64_t ptol_now = 0;
-  // The sequential loop (spx_preempt_toleration_sequential) is the third mode: pre_sequential implies pre_toleration.  d_pseq: the
+  // The sequential loop (spx_preempt_toleration_sequential) is the third mode: pre_sequential with pre_toleration.  d_pseq: the
   // overlay, the stored victim sets and the dirty lists, carved from one allocation; d_pseq_nom: the host-built CSR of each row's own
   // uploaded nominations.  pseq_victims: where the victim sets start.  h_pre_nom_*: host copies of the nominated records' node CSR and
   // pending rows, from which that CSR is built.
@@ -272,6 +272,12 @@ struct spx_engine {
   const uint32_t* pseq_victims = nullptr;
   std::vector<int32_t> h_pre_nom_ptr;
   std::vector<int64_t> h_pre_nom_row;
+  // CapacityScheduling's loop (spx_preempt_sequential) is the fourth mode: pre_sequential without pre_toleration.  It carves its
+  // overlay from d_pseq and puts its rows' own nominations into d_pseq_nom as the other loop does.  d_pre_nomq: the side table of
+  // spx_upload_preempt_nominated_quota, [ns int32 | quota_req 8 x int64 | present uint8] per nominated record, carved; pre_nomq: it
+  // describes the node table in place (spx_upload_preempt_nodes clears it).  d_pre_elig: the loop's eligible column.
+  DevBuf d_pre_nomq, d_pre_elig;
+  bool pre_nomq = false;
   // NetworkOverhead in the commit loop: per-pod effects + the workload pair lists rebuilt with room to grow
   std::vector<int32_t> h_pair_ptr, h_eff_ptr, h_eff_key;
   std::vector<uint8_t> h_key_flag;            // host copy of key_score_equally (spx_update_net_placed edits it)

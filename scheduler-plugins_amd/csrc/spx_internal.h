@@ -843,6 +843,38 @@ struct PtolSeqArgs {
 };
 void launch_ptol_seq_init(const PtolSeqArgs& q, hipStream_t s);
 void launch_ptol_seq_step(const PtolSeqArgs& q, hipStream_t s);
+void launch_ptol_seq_pick(const PtolSeqArgs& q, hipStream_t s);  // k_ptol_seq_pick alone: it reads t.n_nodes, t.row_stride, t.cells, step and pick
+
+// ---------------------------------------------------------------- CapacityScheduling: the sequential preemption loop (kernels_preempt_seq.hip)
+// The tables and results of the dry run, the side table of the nominated records' quota requests, and the overlay the loop keeps next
+// to the uploaded records.  Nothing is swept ahead: step i writes row i's record and column and nobody else's.
+struct CapSeqArgs {
+  PreemptArgs t;
+  int64_t step;                 // the row of the list this launch is about
+  const uint8_t* eligible;      // [n_rows] or NULL: 0 = evaluated at its step, nothing applied
+  // spx_preempt_nominated_quota_soa, parallel to t.noms
+  const int32_t* nom_ns;
+  const int64_t* nom_qreq;      // [nominated records][8]
+  const uint8_t* nom_qreq_present;
+  // the overlay
+  uint32_t* gone;               // [n_nodes][SPX_PREEMPT_MAX_NODE_PODS / 32]
+  int64_t* requested;           // [n_nodes][8]
+  int32_t* head;                // [n_nodes], -1 = no row nominated to the node
+  uint8_t* marks;               // [assigned pods]: the working copy of PreemptPod::marks
+  int64_t* used;                // [n_namespaces][8]
+  uint8_t* used_present;        // [n_namespaces]
+  int64_t* agg_used;            // [8]
+  uint32_t* agg_used_present;   // [1]
+  uint8_t* nom_cleared;         // [nominated records]
+  uint8_t* row_cleared;         // [row_stride]
+  int32_t* row_next;            // [row_stride]
+  uint32_t* victims;            // [row_stride][SPX_PREEMPT_MAX_NODE_PODS / 32]: the victim set of each row's picked cell
+  const int32_t* row_nom_ptr;   // [n_rows + 1]: per entry of the row list, the uploaded nominated records whose pending row it is (T4)
+  const int32_t* row_nom;       // index into t.noms
+};
+void launch_cap_seq_init(const CapSeqArgs& q, hipStream_t s);
+void launch_cap_seq_step(const CapSeqArgs& q, hipStream_t s);  // row record, marks, column cells; the pick is launch_ptol_seq_pick's; then launch_cap_seq_apply
+void launch_cap_seq_apply(const CapSeqArgs& q, hipStream_t s);
 
 // ---------------------------------------------------------------- sequential commit with Filter plugins (kernels_commit.hip)
 // Bookkeeping of ONE bound pod (row `pod`, node = best_node[pod]) on the engine's device tables: what the reference's Reserve /

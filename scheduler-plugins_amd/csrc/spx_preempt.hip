@@ -1,6 +1,7 @@
 // spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
-// spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_fetch_preempt_*): table checks and uploads, the launches of
-// kernels_preempt.hip, kernels_ptol.hip and kernels_ptol_seq.hip, and the fetches, which serve whichever of the three ran last.
+// spx_preempt_sequential, spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_fetch_preempt_*): table checks and
+// uploads, the launches of kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip and kernels_ptol_seq.hip, and the fetches,
+// which serve whichever of the four ran last.
 // State: spx_engine.h.
 #include "spx_engine.h"
 
@@ -222,7 +223,7 @@ int spx_upload_preempt_nodes(spx_engine* e, const spx_preempt_nodes_soa* t) {
   SPX_HIP(e, hipSetDevice(e->device));
   int rc = set_nodes(e, t->n_nodes);
   if (rc) return rc;
-  e->pre_nodes = e->pre_marks_valid = e->pre_valid = e->ptol_table = false;
+  e->pre_nodes = e->pre_marks_valid = e->pre_valid = e->ptol_table = e->pre_nomq = false;
   const size_t N = static_cast<size_t>(t->n_nodes), A = static_cast<size_t>(t->pod_ptr[N]), M = static_cast<size_t>(t->nom_ptr[N]), B = static_cast<size_t>(t->pdb_ptr[N]);
   // the columns as records: a wave reads a node and each of its pods through one base pointer
   std::vector<spx::PreemptNode> nodes(N);
@@ -303,6 +304,117 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
   spx::launch_preempt_rows(a, e->stream);
   spx::launch_preempt_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
   spx::launch_preempt_pick(a, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  e->timed = true;
+  e->pre_valid = true;
+  return SPX_OK;
+}
+
+int spx_upload_preempt_nominated_quota(spx_engine* e, const spx_preempt_nominated_quota_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  if (!e->pre_nodes) return fail(e, SPX_ERR_STATE, "preempt nominated quota: spx_upload_preempt_nodes not called");
+  const int64_t M = e->h_pre_nom_ptr.back();
+  if (t->n_nominated != M)
+    return fail(e, SPX_ERR_ARG, "preempt nominated quota: " + std::to_string(t->n_nominated) + " entries for the node table's " + std::to_string(M) + " nominated records");
+  if (M > 0 && (!t->ns || !t->quota_req || !t->quota_req_present)) return fail(e, SPX_ERR_ARG, "preempt nominated quota: NULL column in a non-empty table");
+  for (int64_t j = 0; j < M * S; ++j)
+    if (t->quota_req[j] < 0 || t->quota_req[j] >= kSumLimit) return fail(e, SPX_ERR_ARG, "preempt nominated quota: record " + std::to_string(j / S) + ": a request that is negative or 2^62 or more");
+  // one allocation: [quota_req | ns | present], the widest first so that each part is aligned
+  const size_t m = static_cast<size_t>(M);
+  std::vector<char> packed(m * (S * 8 + 4 + 1));
+  if (m) {
+    std::memcpy(packed.data(), t->quota_req, m * S * 8);
+    std::memcpy(packed.data() + m * S * 8, t->ns, m * 4);
+    std::memcpy(packed.data() + m * (S * 8 + 4), t->quota_req_present, m);
+  }
+  SPX_HIP(e, hipSetDevice(e->device));
+  e->pre_nomq = e->pre_valid = false;
+  if (int rc = upload(e, e->d_pre_nomq, packed.data(), packed.size())) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // the staged records live until the copy has landed
+  e->pre_nomq = true;
+  return SPX_OK;
+}
+
+int spx_preempt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask) {
+  if (!e) return SPX_ERR_ARG;
+  const std::string who = "sequential capacity preemption";
+  if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, who + ": the quota tables (spx_upload_quota with min) are not uploaded");
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  const int64_t N = e->n_nodes, M = e->h_pre_nom_ptr.back(), A = e->h_pre_pod_ptr.back(), NS = e->q_n_namespaces;
+  if (M > 0 && !e->pre_nomq) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nominated_quota since the last spx_upload_preempt_nodes");
+  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, who + ": empty row list");
+  if (int rc = rows_in_batch(e, who, rows, n_rows)) return rc;
+  // a row is attempted once; and the uploaded nominations each row came with (T4), as a CSR over the row list
+  std::unordered_map<int64_t, int64_t> at;  // pod row -> its index in the list
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (!at.emplace(rows[i], i).second) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is listed twice");
+  std::vector<int32_t> csr(static_cast<size_t>(n_rows) + 1, 0);
+  for (int64_t j = 0; j < M; ++j) {
+    const auto it = at.find(e->h_pre_nom_row[j]);
+    if (it != at.end()) ++csr[it->second + 1];
+  }
+  for (int64_t i = 0; i < n_rows; ++i) csr[i + 1] += csr[i];
+  std::vector<int32_t> fill(csr.begin(), csr.end() - 1);
+  csr.resize(static_cast<size_t>(n_rows) + 1 + static_cast<size_t>(csr[n_rows]));  // [ptr | record]
+  for (int64_t j = 0; j < M; ++j) {
+    const auto it = at.find(e->h_pre_nom_row[j]);
+    if (it != at.end()) csr[n_rows + 1 + fill[it->second]++] = static_cast<int32_t>(j);
+  }
+  // the overlay and the stored victim sets: one allocation, carved
+  const size_t R = static_cast<size_t>(spx::round_up(n_rows, 64));
+  constexpr size_t kSetBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
+  size_t total = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = total;
+    total += static_cast<size_t>(spx::round_up(static_cast<int64_t>(bytes), 256));
+    return o;
+  };
+  const size_t o_gone = carve(static_cast<size_t>(N) * kSetBytes), o_clear = carve(static_cast<size_t>(M)), o_rowclear = carve(R), zeroed = total;
+  const size_t o_head = carve(static_cast<size_t>(N) * 4), minus_one = total - o_head;
+  const size_t o_req = carve(static_cast<size_t>(N) * S * 8), o_next = carve(R * 4), o_vict = carve(R * kSetBytes), o_marks = carve(static_cast<size_t>(A)),
+               o_used = carve(static_cast<size_t>(NS) * S * 8), o_usedp = carve(static_cast<size_t>(NS)), o_agg = carve(S * 8), o_aggp = carve(4);
+  std::vector<Staged> more = {{&e->d_pseq, total, nullptr}, {&e->d_pseq_nom, csr.size() * 4, csr.data()}};
+  if (eligible) more.push_back({&e->d_pre_elig, static_cast<size_t>(n_rows), eligible});
+  if (int rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, more)) return rc;
+  e->pre_toleration = false;
+  char* const base = static_cast<char*>(e->d_pseq.p);
+  spx::CapSeqArgs q{};
+  q.t = preempt_args(e);
+  q.eligible = eligible ? static_cast<const uint8_t*>(e->d_pre_elig.p) : nullptr;
+  const char* const side = static_cast<const char*>(e->d_pre_nomq.p);  // (never read when M == 0)
+  q.nom_qreq = reinterpret_cast<const int64_t*>(side);
+  q.nom_ns = reinterpret_cast<const int32_t*>(side + static_cast<size_t>(M) * S * 8);
+  q.nom_qreq_present = reinterpret_cast<const uint8_t*>(side + static_cast<size_t>(M) * (S * 8 + 4));
+  q.gone = reinterpret_cast<uint32_t*>(base + o_gone);
+  q.nom_cleared = reinterpret_cast<uint8_t*>(base + o_clear);
+  q.row_cleared = reinterpret_cast<uint8_t*>(base + o_rowclear);
+  q.head = reinterpret_cast<int32_t*>(base + o_head);
+  q.requested = reinterpret_cast<int64_t*>(base + o_req);
+  q.row_next = reinterpret_cast<int32_t*>(base + o_next);
+  q.victims = reinterpret_cast<uint32_t*>(base + o_vict);
+  q.marks = reinterpret_cast<uint8_t*>(base + o_marks);
+  q.used = reinterpret_cast<int64_t*>(base + o_used);
+  q.used_present = reinterpret_cast<uint8_t*>(base + o_usedp);
+  q.agg_used = reinterpret_cast<int64_t*>(base + o_agg);
+  q.agg_used_present = reinterpret_cast<uint32_t*>(base + o_aggp);
+  q.row_nom_ptr = static_cast<const int32_t*>(e->d_pseq_nom.p);
+  q.row_nom = q.row_nom_ptr + n_rows + 1;
+  spx::PtolSeqArgs pick{};  // k_ptol_seq_pick reads the sizes, the cells, the step and the pick columns alone
+  pick.t.n_nodes = N, pick.t.row_stride = static_cast<int64_t>(R), pick.t.cells = q.t.cells, pick.pick = q.t.pick;
+  e->pre_sequential = true;
+  e->pseq_victims = q.victims;
+  // everything is enqueued here; each launch reads what the one before it left on the device, and nothing is read back in between
+  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  SPX_HIP(e, hipMemsetAsync(base, 0, zeroed, e->stream));
+  SPX_HIP(e, hipMemsetAsync(base + o_head, 0xFF, minus_one, e->stream));
+  spx::launch_cap_seq_init(q, e->stream);
+  for (q.step = 0; q.step < n_rows; ++q.step) {
+    pick.step = q.step;
+    spx::launch_cap_seq_step(q, e->stream);
+    spx::launch_ptol_seq_pick(pick, e->stream);
+    spx::launch_cap_seq_apply(q, e->stream);
+  }
   SPX_HIP(e, hipGetLastError());
   SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
   e->timed = true;

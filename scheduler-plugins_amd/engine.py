@@ -908,6 +908,8 @@ class Engine:
         f = self.flatten_preempt_nodes(t["nodes"], t["rc"], t["quota"], t["preempt"])
         self.upload_preempt_nodes(f)
         self.upload_preempt_pods(fq["cols"]["pod_req"].reshape(-1, 8))
+        f["nominated_quota"] = self.flatten_preempt_nominated_quota(t["nodes"], t["rc"], t["quota"], t["preempt"], len(f["nom_priority"]))
+        self.upload_preempt_nominated_quota(f["nominated_quota"])
         return f
 
     def preempt_nodes_table(self, f: dict) -> Table:
@@ -943,6 +945,48 @@ class Engine:
                 raise ValueError("node_mask must be [len(rows)][n_nodes]")
         self._ck(self._lib.spx_preempt_dry_run(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows),
                                                mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None))
+        self._preempt_rows = len(rows)
+
+    _PREEMPT_NOMQ_COLS = ("ns", "quota_req", "quota_req_present")
+
+    def flatten_preempt_nominated_quota(self, nodes: Table, rc: Optional[Table], quota: Table, objects: Table, n_nom: int) -> dict:
+        """the nominated pods of spx_preempt_objects in the record order of flatten_preempt_nodes' table (n_nom of them) -> the columns of
+        spx_preempt_nominated_quota_soa, plus "nom_src" (each record's index among the nominated-pod objects)
+        (spx_flatten_preempt_nominated_quota, host only)"""
+        out = {"nom_src": np.zeros(n_nom, np.int32), "ns": np.zeros(n_nom, np.int32), "quota_req": np.zeros((n_nom, 8), np.int64), "quota_req_present": np.zeros(n_nom, np.uint8)}
+        keep = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in out.items()}  # never hand C a NULL for an empty column
+        rc_ = self._lib.spx_flatten_preempt_nominated_quota(
+            nodes.ref(), rc.ref() if rc else None, quota.ref(), objects.ref(), n_nom, keep["nom_src"].ctypes.data_as(C.POINTER(C.c_int32)),
+            keep["ns"].ctypes.data_as(C.POINTER(C.c_int32)), keep["quota_req"].ctypes.data_as(C.POINTER(C.c_int64)), keep["quota_req_present"].ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc_ != 0:
+            raise self._err(rc_, f"preempt nominated flatten: refused (n_nom {n_nom} is not the node table's count, or a request it cannot hold)")
+        return out
+
+    def upload_preempt_nominated_quota(self, cols: dict) -> None:
+        """flatten_preempt_nominated_quota's columns, one entry per nominated record of the uploaded node table
+        (spx_upload_preempt_nominated_quota); earlier results become stale, and a later upload_preempt_nodes drops the table"""
+        cols = {"ns": np.ascontiguousarray(cols["ns"], dtype=np.int32), "quota_req": np.ascontiguousarray(cols["quota_req"], dtype=np.int64).reshape(-1, 8),
+                "quota_req_present": np.ascontiguousarray(cols["quota_req_present"], dtype=np.uint8)}
+        self._ck(self._lib.spx_upload_preempt_nominated_quota(self._h, Table(self._hdr, "spx_preempt_nominated_quota_soa", n_nominated=len(cols["ns"]), **cols).ref()))
+
+    def preempt_sequential(self, rows, eligible=None, node_mask=None) -> None:
+        """CapacityScheduling's sequential preemption loop (spx_preempt_sequential): the rows are attempted once each in list order, each
+        against the state the rows before it left (victims gone from their node and from their quota's Used, the preemptor nominated,
+        lower nominations cleared, its own old nomination dropped).  eligible: per entry of rows, 0 = evaluated at its step but nothing
+        applied (None = all).  The preempt_* fetches answer per row as it saw the state at its own step; preempt_victims answers for the
+        row's picked node alone."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        elig = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+        if elig is not None and len(elig) != len(rows):
+            raise ValueError("eligible must have one entry per row")
+        mask = None
+        if node_mask is not None:
+            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
+            if mask.shape != (len(rows), self.n_nodes):
+                raise ValueError("node_mask must be [len(rows)][n_nodes]")
+        u8 = C.POINTER(C.c_uint8)
+        self._ck(self._lib.spx_preempt_sequential(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows), elig.ctypes.data_as(u8) if elig is not None else None,
+                                                  mask.ctypes.data_as(u8) if mask is not None else None))
         self._preempt_rows = len(rows)
 
     def preempt_cells(self, i_begin: int = 0, i_end: Optional[int] = None):

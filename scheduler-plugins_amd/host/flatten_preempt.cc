@@ -178,6 +178,33 @@ extern "C" int spx_flatten_preempt_nodes(const spx_node_objects* nodes, const sp
   return SPX_OK;
 }
 
+// The nominated records of spx_flatten_preempt_nodes' table again, with what CapacityScheduling's sequential loop reads of them beyond
+// the node charge: the namespace and computePodResourceRequest.  Same order: node by node, the objects' order within a node.
+extern "C" int spx_flatten_preempt_nominated_quota(const spx_node_objects* nodes, const spx_resource_classes* rc, const spx_quota_objects* q, const spx_preempt_objects* o,
+                                                   int64_t n_nom, int32_t* nom_src, int32_t* ns, int64_t* quota_req, uint8_t* quota_req_present) {
+  if (!nodes || !q || !o || n_nom < 0 || nodes->n_nodes <= 0 || o->n_nominated < 0 || q->n_scalar_slots < 0 || q->n_scalar_slots > S - 4) return SPX_ERR_ARG;
+  if (o->n_nominated > 0 && (!o->nominated || !o->nominated_node)) return SPX_ERR_ARG;
+  if (n_nom > 0 && (!ns || !quota_req || !quota_req_present)) return SPX_ERR_ARG;
+  const int64_t N = nodes->n_nodes, M = o->n_nominated;
+  auto on_node = [&](int64_t n) { return n >= 0 && n < N && (!o->node_present || o->node_present[n]); };
+  std::vector<int32_t> at(static_cast<size_t>(N) + 1, 0);  // records per node, then where each node's records start
+  for (int64_t i = 0; i < M; ++i)
+    if (on_node(o->nominated_node[i])) ++at[o->nominated_node[i] + 1];
+  for (int64_t n = 0; n < N; ++n) at[n + 1] += at[n];
+  if (at[N] != n_nom) return SPX_ERR_ARG;
+  for (int64_t i = 0; i < M; ++i) {
+    if (!on_node(o->nominated_node[i])) continue;
+    const int64_t j = at[o->nominated_node[i]]++;
+    Vec r;
+    if (!pod_request(o->nominated, q, rc, i, r)) return SPX_ERR_ARG;
+    if (nom_src) nom_src[j] = static_cast<int32_t>(i);
+    ns[j] = o->nominated->ns[i];
+    std::memcpy(quota_req + j * S, r.v, sizeof r.v);
+    quota_req_present[j] = r.present;
+  }
+  return SPX_OK;
+}
+
 // PodEligibleToPreemptOthers, capacity_scheduling.go:409-484
 extern "C" int spx_preempt_eligible(const spx_preempt_nodes_soa* t, const spx_quota_objects* q, const uint8_t* over_min, int64_t n, const int32_t* ns,
                                     const int32_t* priority, const uint8_t* preempt_never, const int64_t* nominated_node, const uint8_t* nominated_unresolvable,
