@@ -55,7 +55,7 @@ __device__ __forceinline__ void cap_marks(const PreemptArgs& a, const CapSeqArgs
   const int p0 = a.nodes[node].pod_begin, p1 = a.nodes[node].pod_end;
   const int64_t* const used_tab = kOverlay ? q->used : a.used;
   const uint8_t* const usedp_tab = kOverlay ? q->used_present : a.used_present;
-  auto left = [&](int j) { return kOverlay && ((q->gone[node * kWords + ((j - p0) >> 5)] >> ((j - p0) & 31)) & 1u); };
+  auto left = [&](int j) { return kOverlay && seq_left(q->gone, node, j - p0); };
   auto mark_of = [&](int j) -> uint8_t { return kOverlay ? q->marks[j] : a.pods[j].marks; };
   for (int j = p0; j < p1; ++j) {
     if (left(j)) continue;
@@ -111,7 +111,7 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
   for (int i = 0; i < kWords; ++i) vict[i] = 0;
   const PreemptNode& nd = a.nodes[node];
   const PreemptPod* pods = a.pods + nd.pod_begin;  // position in the node's list -> record
-  auto left = [&](int k) { return kOverlay && ((q->gone[node * kWords + (k >> 5)] >> (k & 31)) & 1u); };  // wave-uniform: the skips are branches of the wave
+  auto left = [&](int k) { return kOverlay && seq_left(q->gone, node, k); };
   auto mark_at = [&](int k) -> uint8_t { return kOverlay ? q->marks[nd.pod_begin + k] : pods[k].marks; };
   bool live = want && nd.present && (!a.node_mask || a.node_mask[rr * a.n_nodes + node]);
 

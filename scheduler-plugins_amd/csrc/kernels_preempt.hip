@@ -85,39 +85,19 @@ __global__ __launch_bounds__(kBlock) void k_preempt_cells(PreemptArgs a) {
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_preempt_pick(PreemptArgs a) {
-  __shared__ PickKey s_key[kWaves][64];
-  __shared__ int32_t s_node[kWaves][64], s_cand[kWaves][64], s_ties[kWaves][64];
+__global__ __launch_bounds__(kBlock) void k_preempt_pick(PickArgs p) {
+  __shared__ PickAcc sh[kBlock];
   const int slice = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t R = a.row_stride, r = static_cast<int64_t>(blockIdx.x) * 64 + lane;  // r < R: the cells of the padding rows are never read below
-  PickKey best{0, 0, 0, 0, 0};
-  int32_t node = -1, cand = 0, ties = 0;
-  if (r < a.n_rows) {
-    for (int64_t n = slice; n < a.n_nodes; n += kWaves) {
-      const PreemptCell c = a.cells[n * R + r];
-      if (c.status != SPX_PREEMPT_ST_CANDIDATE) continue;
-      const PickKey key{c.n_violations, c.hi_prio, c.n_victims, c.prio_sum, -c.start};
-      const int o = cand ? cmp_key(key, best) : -1;
-      ++cand;
-      if (o < 0) best = key, node = static_cast<int32_t>(n), ties = 1;
-      else if (o == 0) ++ties;  // nodes ascend within a slice: the first one stays
-    }
-  }
-  s_key[slice][lane] = best, s_node[slice][lane] = node, s_cand[slice][lane] = cand, s_ties[slice][lane] = ties;
+  const int64_t R = p.row_stride, r = static_cast<int64_t>(blockIdx.x) * 64 + lane;  // r < R: the cells of the padding rows are never read below
+  PickAcc acc = kNoPick;
+  if (r < p.n_rows)
+    for (int64_t n = slice; n < p.n_nodes; n += kWaves) acc.take(p.cells[n * R + r], n);
+  sh[threadIdx.x] = acc;
   __syncthreads();
-  if (slice != 0 || r >= a.n_rows) return;
-  for (int w = 1; w < kWaves; ++w) {
-    if (s_cand[w][lane] == 0) continue;
-    const int o = cand ? cmp_key(s_key[w][lane], best) : -1;
-    cand += s_cand[w][lane];
-    if (o < 0) best = s_key[w][lane], node = s_node[w][lane], ties = s_ties[w][lane];
-    else if (o == 0) ties += s_ties[w][lane], node = min(node, s_node[w][lane]);
-  }
-  a.pick[0 * R + r] = node;
-  a.pick[1 * R + r] = node >= 0 ? best.n_vict : 0;
-  a.pick[2 * R + r] = node >= 0 ? best.viol : 0;
-  a.pick[3 * R + r] = cand;
-  a.pick[4 * R + r] = ties;
+  if (slice != 0 || r >= p.n_rows) return;
+  for (int w = 1; w < kWaves; ++w)
+    if (sh[w * 64 + lane].cand) acc.merge(sh[w * 64 + lane]);
+  acc.store(p.pick, R, r);
 }
 
 }  // namespace
@@ -136,8 +116,8 @@ void launch_preempt_cells(const PreemptArgs& a, unsigned n_nodes_launch, hipStre
     hipLaunchKernelGGL(k_preempt_cells, dim3(n_nodes_launch, blocks_for(a.n_rows, kBlock)), dim3(kBlock), 0, s, a);
 }
 
-void launch_preempt_pick(const PreemptArgs& a, hipStream_t s) {
-  if (a.n_rows > 0) hipLaunchKernelGGL(k_preempt_pick, dim3(blocks_for(a.n_rows, 64)), dim3(kBlock), 0, s, a);
+void launch_preempt_pick(const PickArgs& p, hipStream_t s) {
+  if (p.n_rows > 0) hipLaunchKernelGGL(k_preempt_pick, dim3(blocks_for(p.n_rows, 64)), dim3(kBlock), 0, s, p);
 }
 
 }  // namespace spx

@@ -2,18 +2,12 @@
 // each, in list order, and row i is evaluated against the state that rows 0..i-1 left.  A victim's removal moves its quota's Used, and
 // with it the over-min branch of every later preemptor, the borrowed marks of that namespace on every node and the aggregate gate: every
 // column is coupled to every other, so nothing is swept ahead.  At step i row i's record and its N cells are formed from the current
-// state, picked over and applied; only row i writes its column, at its own step.  The uploaded records are never written; what the loop
-// changes lives in an overlay next to them:
+// state, picked over and applied; only row i writes its column, at its own step.  The overlay is the one preempt_device.h describes (CapSeqArgs carries its
+// fields itself, spx_internal.h); next to it this loop keeps
 //
-//     gone [node][8]        256-bit set: positions of the node's uploaded list that an earlier row evicted (T1)
-//     requested [node][8]   the working copy of NodeInfo.Requested, less the evicted pods (T1)
 //     used [ns][8], used_present [ns], agg_used [8], agg_used_present
 //                           the working copies of every quota's Used and of the aggregate (T1, deletePodIfPresent)
 //     marks [pod]           the working copy of the pods' marks (cap_cell.h), recomputed from the working Used
-//     nom_cleared [nom]     an uploaded nominated record no longer counts (T3, T4)
-//     head [node], row_next [row], row_cleared [row]
-//                           the rows the loop nominated to the node (T2), newest first; the record of such a pod is the row's own
-//                           [field][row] record, and row_cleared takes it out again (T3).  The sums do not depend on the order.
 //
 // Every step is five launches on one stream, enqueued up front; each reads what the one before it left in device memory:
 //
@@ -156,32 +150,25 @@ __global__ __launch_bounds__(64) void k_cap_seq_apply(CapSeqArgs q) {
   __shared__ int16_t s_budget[kPdbs][64];
   const PreemptArgs& a = q.t;
   const int lane = threadIdx.x;
-  const int64_t R = a.row_stride, i = q.step;
+  const SeqOverlay o = q.overlay();
+  const int64_t R = a.row_stride, i = o.step;
   const int32_t n = a.pick[i];
   const uint32_t flags = static_cast<uint32_t>(a.row_rec[kFlags * R + i]);
   const int prio = static_cast<int>(a.row_rec[kPrio * R + i]);
 
-  // every lane computes the picked cell of row i; lane 0 keeps its victim set for spx_fetch_preempt_victims
-  uint32_t vict[kWords];
-#pragma unroll
-  for (int w = 0; w < kWords; ++w) vict[w] = 0;
+  // every lane computes the picked cell of row i
+  uint32_t vict[kWords] = {};
   if (n >= 0) (void)cap_cell<true>(a, &q, n, i, true, s_budget, lane, vict);
-  if (lane == 0) {
-#pragma unroll
-    for (int w = 0; w < kWords; ++w) q.victims[i * kWords + w] = vict[w];
-  }
+  seq_store_victims(o, i, vict, lane);
   if (flags & kHold) return;  // nothing moves
   // T4: the nominations row i came with are dropped wherever they sit
-  for (int32_t t = q.row_nom_ptr[i] + lane; t < q.row_nom_ptr[i + 1]; t += 64) q.nom_cleared[q.row_nom[t]] = 1;
+  for (int32_t t = o.row_nom_ptr[i] + lane; t < o.row_nom_ptr[i + 1]; t += 64) o.nom_cleared[o.row_nom[t]] = 1;
   if (n < 0) return;
   const PreemptNode& nd = a.nodes[n];
   const PreemptPod* pods = a.pods + nd.pod_begin;
   // T1: the victims leave the node, and deletePodIfPresent takes those that are in their quota's set out of its Used and of the
   // aggregate.  Lane s moves slot s, lane 0 the key masks: one wave, no two lanes on one word.
-  if (lane == 0) {
-#pragma unroll
-    for (int w = 0; w < kWords; ++w) q.gone[static_cast<int64_t>(n) * kWords + w] |= vict[w];
-  }
+  seq_evict(o, n, vict, lane);
   if (lane < S) {
     int64_t sub = 0;
     for (int k = 0; k < nd.pod_end - nd.pod_begin; ++k) {
@@ -194,18 +181,9 @@ __global__ __launch_bounds__(64) void k_cap_seq_apply(CapSeqArgs q) {
       q.agg_used[lane] = wsub(q.agg_used[lane], dq);
       if (lane == 0) q.used_present[pods[k].ns] |= pods[k].qreq_present, *q.agg_used_present |= pods[k].qreq_present;  // SetScalar
     }
-    q.requested[static_cast<int64_t>(n) * S + lane] -= sub;
+    o.requested[static_cast<int64_t>(n) * S + lane] -= sub;
   }
-  // T3: nominated pods of the node with a lower priority lose their nomination, the uploaded ones and the loop's alike
-  for (int j = nd.nom_begin + lane; j < nd.nom_end; j += 64)
-    if (a.noms[j].prio < prio) q.nom_cleared[j] = 1;
-  if (lane == 0) {
-    for (int k = q.head[n]; k >= 0; k = q.row_next[k])
-      if (static_cast<int>(a.row_rec[kPrio * R + k]) < prio) q.row_cleared[k] = 1;
-    // T2: row i is nominated to the node
-    q.row_next[i] = q.head[n];
-    q.head[n] = static_cast<int32_t>(i);
-  }
+  seq_nominate(o, nd, a.noms, n, i, prio, lane, a.row_rec + kPrio * R);  // T3, T2
 }
 
 }  // namespace

@@ -30,7 +30,7 @@ __device__ __forceinline__ int prio_of(int64_t meta) { return static_cast<int>(s
 // One cell per lane: row rr of the list on `node`, for the lanes with want set.  budget: the wave's [kPdbs][64] int16 in LDS.  vict
 // is all zero unless the cell is a CANDIDATE.
 // kOverlay off: the uploaded state; q (NULL) and frozen are not read.
-// kOverlay on: the sequential loop's state (kernels_ptol_seq.hip) from *q: Requested is the working copy, cleared nominations are not
+// kOverlay on: the sequential loop's state (kernels_ptol_seq.hip) from q->o: Requested is the working copy, cleared nominations are not
 // charged, the loop's own nominations are, and the positions in `gone` are skipped in every pass.  frozen (wave-uniform) switches all
 // of that off at run time: the untouched state, which a PreemptNever row sees.
 template <bool kOverlay>
@@ -53,7 +53,7 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
   const PreemptPod* pods = a.pods + nd.pod_begin;  // position in the node's list -> record
   const PtolPod* tol = a.tol + nd.pod_begin;
   const bool overlay = kOverlay && !frozen;  // false at compile time with the switch off: nothing below reads q then
-  auto left = [&](int k) { return overlay && ((q->gone[node * kWords + (k >> 5)] >> (k & 31)) & 1u); };  // wave-uniform: the skips are branches of the wave
+  auto left = [&](int k) { return overlay && seq_left(q->o.gone, node, k); };
   bool live = want && nd.present && (!a.node_mask || a.node_mask[rr * a.n_nodes + node]);
 
   if (__any(live)) {
@@ -61,16 +61,16 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
     // the lane's copy of the node, the nominated pods that outrank the preemptor charged once: they are re-added before every Filter run
     int64_t alloc[S], requested[S];
 #pragma unroll
-    for (int s = 0; s < S; ++s) alloc[s] = in_vgpr(nd.alloc[s]), requested[s] = overlay ? q->requested[node * S + s] : nd.requested[s];
+    for (int s = 0; s < S; ++s) alloc[s] = in_vgpr(nd.alloc[s]), requested[s] = overlay ? q->o.requested[node * S + s] : nd.requested[s];
     for (int j = nd.nom_begin; j < nd.nom_end; ++j) {
-      if (overlay && q->nom_cleared[j]) continue;
+      if (overlay && q->o.nom_cleared[j]) continue;
       const bool add = a.noms[j].prio >= prio && a.noms[j].row != pod_row;
 #pragma unroll
       for (int s = 0; s < S; ++s) requested[s] += add ? a.noms[j].fit[s] : 0;
     }
     if (overlay) {
-      for (int k = q->head[node]; k >= 0; k = q->row_next[k]) {  // the loop's own nominations: earlier rows, so never the lane's own
-        if (q->row_cleared[k]) continue;
+      for (int k = q->o.head[node]; k >= 0; k = q->o.row_next[k]) {  // the loop's own nominations: earlier rows, so never the lane's own
+        if (q->o.row_cleared[k]) continue;
         const bool add = prio_of(a.row_rec[kMeta * R + k]) >= prio;
 #pragma unroll
         for (int s = 0; s < S; ++s) requested[s] += add ? (s == 3 ? 1 : a.row_rec[(kFit + s) * R + k]) : 0;  // a pod counts once

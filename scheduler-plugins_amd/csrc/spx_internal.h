@@ -782,12 +782,20 @@ struct PreemptArgs {
   int64_t* row_rec;          // [kPreemptRowFields][row_stride]
   PreemptCell* cells;        // [grid.x][row_stride]
   uint32_t* victims_out;     // when set: n_rows == 1 and the lane writes the cell's 256-bit victim mask (bit = position in the node's list)
+  const int32_t* pick;       // PickArgs::pick, for k_cap_seq_apply: the picked node per row
+};
+struct PickArgs {  // pickOneNodeForPreemption over the 32-byte cells of either plugin: all that a pick kernel reads
+  int64_t n_nodes;
+  int64_t n_rows;
+  int64_t row_stride;
+  int64_t step;              // k_ptol_seq_pick: the one row of the list it picks for
+  const PreemptCell* cells;  // [n_nodes][row_stride]
   int32_t* pick;             // [5][row_stride]: node, n_victims, n_violations, n_candidates, n_ties
 };
 void launch_preempt_marks(const PreemptArgs& a, hipStream_t s);
 void launch_preempt_rows(const PreemptArgs& a, hipStream_t s);
 void launch_preempt_cells(const PreemptArgs& a, unsigned n_nodes_launch, hipStream_t s);
-void launch_preempt_pick(const PreemptArgs& a, hipStream_t s);
+void launch_preempt_pick(const PickArgs& p, hipStream_t s);  // every row of the list (k_preempt_pick)
 
 // ---------------------------------------------------------------- PreemptionToleration.PostFilter: its dry run (kernels_ptol.hip)
 // spx_preempt_toleration_soa as records parallel to PreemptPod: the pod at position k of a node's list is pods[k] and tol[k]
@@ -820,60 +828,70 @@ struct PtolArgs {
 void launch_ptol_rows(const PtolArgs& a, hipStream_t s);
 void launch_ptol_cells(const PtolArgs& a, unsigned n_nodes_launch, hipStream_t s);
 
-// ---------------------------------------------------------------- PreemptionToleration: the sequential preemption loop (kernels_ptol_seq.hip)
-// The tables and results of the dry run, plus the overlay the loop keeps next to the uploaded records.  row_nom*: per
-// entry of the row list, the uploaded nominated records whose pending row it is (T4), as a CSR built by the host.
-struct PtolSeqArgs {
-  PtolArgs t;
+// ---------------------------------------------------------------- the sequential preemption loops (kernels_ptol_seq.hip, kernels_preempt_seq.hip)
+// What both loops keep next to the uploaded records, which are never written (preempt_device.h describes it and holds the device code
+// that moves it).  row_nom*: per entry of the row list, the uploaded nominated records whose pending row it is (T4), as a CSR built by
+// the host.
+struct SeqOverlay {
   int64_t step;                 // the row of the list this launch is about
-  int32_t n_dirty;              // dirty slots per step: 1 + the most nominated records any one row of the list has
-  int32_t pad;
-  int32_t* pick;                // [5][row_stride], as PreemptArgs'
-  uint32_t* gone;               // [n_nodes][SPX_PREEMPT_MAX_NODE_PODS / 32]
-  int64_t* requested;           // [n_nodes][8]
   uint8_t* nom_cleared;         // [nominated records]
   uint8_t* row_cleared;         // [row_stride]
   int32_t* row_next;            // [row_stride]
+  uint32_t* gone;               // [n_nodes][SPX_PREEMPT_MAX_NODE_PODS / 32]
+  int64_t* requested;           // [n_nodes][8]
   int32_t* head;                // [n_nodes], -1 = no row nominated to the node
   const int32_t* row_nom_ptr;   // [n_rows + 1]
   const int32_t* row_nom;       // index into noms
-  const int32_t* row_nom_node;  // the node that record belongs to
   uint32_t* victims;            // [row_stride][SPX_PREEMPT_MAX_NODE_PODS / 32]: the victim set of each row's picked cell
+};
+void launch_ptol_seq_pick(const PickArgs& p, hipStream_t s);  // row p.step alone (k_ptol_seq_pick): the pick of both loops
+
+// PreemptionToleration's loop: the tables and results of the dry run, the overlay, and the dirty lists.
+struct PtolSeqArgs {
+  PtolArgs t;
+  SeqOverlay o;
+  int32_t n_dirty;              // dirty slots per step: 1 + the most nominated records any one row of the list has
+  const int32_t* pick;          // [row_stride] the picked node per row (PickArgs::pick's first column)
+  const int32_t* row_nom_node;  // parallel to o.row_nom: the node that record belongs to
   int32_t* dirty;               // [n_rows][n_dirty]: the nodes step i changed, -1 = unused slot
 };
 void launch_ptol_seq_init(const PtolSeqArgs& q, hipStream_t s);
-void launch_ptol_seq_step(const PtolSeqArgs& q, hipStream_t s);
-void launch_ptol_seq_pick(const PtolSeqArgs& q, hipStream_t s);  // k_ptol_seq_pick alone: it reads t.n_nodes, t.row_stride, t.cells, step and pick
+void launch_ptol_seq_step(const PtolSeqArgs& q, hipStream_t s);  // after launch_ptol_seq_pick: what row o.step changes, then the stale cells
 
-// ---------------------------------------------------------------- CapacityScheduling: the sequential preemption loop (kernels_preempt_seq.hip)
-// The tables and results of the dry run, the side table of the nominated records' quota requests, and the overlay the loop keeps next
-// to the uploaded records.  Nothing is swept ahead: step i writes row i's record and column and nobody else's.
+// CapacityScheduling's loop: the tables and results of the dry run, the side table of the nominated records' quota
+// requests, the overlay and the working quota state.  Nothing is swept ahead: step i writes row i's record and column and nobody else's.
+// The overlay's fields are this struct's own, at the offsets its kernels were first measured with: with `SeqOverlay o` nested, as in
+// PtolSeqArgs, k_cap_seq_cells took 248 to 254 us per launch instead of 242 in every field order tried (profiles/seq_shared/ab.md).
 struct CapSeqArgs {
   PreemptArgs t;
-  int64_t step;                 // the row of the list this launch is about
+  int64_t step;                 // SeqOverlay's
   const uint8_t* eligible;      // [n_rows] or NULL: 0 = evaluated at its step, nothing applied
   // spx_preempt_nominated_quota_soa, parallel to t.noms
   const int32_t* nom_ns;
   const int64_t* nom_qreq;      // [nominated records][8]
   const uint8_t* nom_qreq_present;
-  // the overlay
-  uint32_t* gone;               // [n_nodes][SPX_PREEMPT_MAX_NODE_PODS / 32]
-  int64_t* requested;           // [n_nodes][8]
-  int32_t* head;                // [n_nodes], -1 = no row nominated to the node
+  uint32_t* gone;               // SeqOverlay's, and requested and head
+  int64_t* requested;
+  int32_t* head;
   uint8_t* marks;               // [assigned pods]: the working copy of PreemptPod::marks
   int64_t* used;                // [n_namespaces][8]
   uint8_t* used_present;        // [n_namespaces]
   int64_t* agg_used;            // [8]
   uint32_t* agg_used_present;   // [1]
-  uint8_t* nom_cleared;         // [nominated records]
-  uint8_t* row_cleared;         // [row_stride]
-  int32_t* row_next;            // [row_stride]
-  uint32_t* victims;            // [row_stride][SPX_PREEMPT_MAX_NODE_PODS / 32]: the victim set of each row's picked cell
-  const int32_t* row_nom_ptr;   // [n_rows + 1]: per entry of the row list, the uploaded nominated records whose pending row it is (T4)
-  const int32_t* row_nom;       // index into t.noms
+  uint8_t* nom_cleared;         // SeqOverlay's from here on
+  uint8_t* row_cleared;
+  int32_t* row_next;
+  uint32_t* victims;
+  const int32_t* row_nom_ptr;
+  const int32_t* row_nom;
+  __host__ __device__ SeqOverlay overlay() const { return {step, nom_cleared, row_cleared, row_next, gone, requested, head, row_nom_ptr, row_nom, victims}; }
+  void overlay(const SeqOverlay& o) {
+    step = o.step, nom_cleared = o.nom_cleared, row_cleared = o.row_cleared, row_next = o.row_next, gone = o.gone, requested = o.requested, head = o.head;
+    row_nom_ptr = o.row_nom_ptr, row_nom = o.row_nom, victims = o.victims;
+  }
 };
 void launch_cap_seq_init(const CapSeqArgs& q, hipStream_t s);
-void launch_cap_seq_step(const CapSeqArgs& q, hipStream_t s);  // row record, marks, column cells; the pick is launch_ptol_seq_pick's; then launch_cap_seq_apply
+void launch_cap_seq_step(const CapSeqArgs& q, hipStream_t s);  // row record, marks, column cells; then launch_ptol_seq_pick and launch_cap_seq_apply
 void launch_cap_seq_apply(const CapSeqArgs& q, hipStream_t s);
 
 // ---------------------------------------------------------------- sequential commit with Filter plugins (kernels_commit.hip)

@@ -107,7 +107,7 @@ spx::PreemptArgs preempt_args(spx_engine* e) {
   a.pdb_allowed = static_cast<const int32_t*>(e->d_pre_pdb_allowed.p);
   a.row_rec = static_cast<int64_t*>(e->d_pre_rec.p);
   a.cells = static_cast<spx::PreemptCell*>(e->d_pre_cells.p);
-  a.pick = static_cast<int32_t*>(e->d_pre_pick.p);
+  a.pick = static_cast<const int32_t*>(e->d_pre_pick.p);
   return a;
 }
 
@@ -129,6 +129,11 @@ spx::PtolArgs ptol_args(spx_engine* e) {
   a.row_rec = static_cast<int64_t*>(e->d_ptol_rec.p);
   a.cells = static_cast<spx::PreemptCell*>(e->d_pre_cells.p);
   return a;
+}
+
+// What either pick kernel reads, whichever plugin wrote the cells.
+spx::PickArgs pick_args(spx_engine* e) {
+  return {e->n_nodes, e->pre_n_rows, e->pre_row_stride, 0, static_cast<const spx::PreemptCell*>(e->d_pre_cells.p), static_cast<int32_t*>(e->d_pre_pick.p)};
 }
 
 int preempt_results(spx_engine* e, int64_t i_begin, int64_t i_end) {
@@ -201,6 +206,81 @@ int ptol_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64
   if (int rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_ptol_rec, spx::kPtolRowFields, more)) return rc;
   e->pre_toleration = true;
   e->ptol_now = now_ns;
+  return SPX_OK;
+}
+
+struct SeqStaged {
+  spx::SeqOverlay o;
+  std::vector<char*> extra;     // the caller's regions of the carve, in the order it asked for them
+  int32_t n_dirty;              // 1 + the most uploaded nominations any one row of the list has
+  const int32_t* row_nom_node;  // parallel to o.row_nom: the node each record sits on
+};
+
+// What the two sequential loops stage once their state and arguments are checked.  A row is attempted once; the uploaded nominations
+// each row came with (T4) become a CSR over the row list, [ptr | record | node of the record]; the overlay, the stored victim sets and
+// the regions of extra_bytes(n_dirty) are carved from one allocation; stage(more) is the caller's staging with these two buffers
+// among `more`; then the overlay is addressed and its zero and -1 parts are set.
+template <class ExtraBytes, class Stage>
+int seq_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, ExtraBytes extra_bytes, Stage stage, SeqStaged* out) {
+  std::unordered_map<int64_t, int64_t> at;  // pod row -> its index in the list
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (!at.emplace(rows[i], i).second) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is listed twice");
+  const int64_t N = e->n_nodes, M = e->h_pre_nom_ptr.back();
+  std::vector<int32_t> csr(static_cast<size_t>(n_rows) + 1, 0);
+  for (int64_t j = 0; j < M; ++j) {
+    const auto it = at.find(e->h_pre_nom_row[j]);
+    if (it != at.end()) ++csr[it->second + 1];
+  }
+  out->n_dirty = 1;
+  for (int64_t i = 0; i < n_rows; ++i) out->n_dirty = std::max(out->n_dirty, 1 + csr[i + 1]), csr[i + 1] += csr[i];
+  const size_t own = static_cast<size_t>(csr[n_rows]);
+  std::vector<int32_t> fill(csr.begin(), csr.end() - 1);
+  csr.resize(static_cast<size_t>(n_rows) + 1 + 2 * own);
+  for (int64_t n = 0; n < N; ++n)  // node by node: the records of a row in ascending record index
+    for (int32_t j = e->h_pre_nom_ptr[n]; j < e->h_pre_nom_ptr[n + 1]; ++j) {
+      const auto it = at.find(e->h_pre_nom_row[j]);
+      if (it == at.end()) continue;
+      const size_t k = static_cast<size_t>(fill[it->second]++);
+      csr[n_rows + 1 + k] = j, csr[n_rows + 1 + own + k] = static_cast<int32_t>(n);
+    }
+  const size_t R = static_cast<size_t>(spx::round_up(n_rows, 64));
+  constexpr size_t kSetBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
+  size_t total = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = total;
+    total += static_cast<size_t>(spx::round_up(static_cast<int64_t>(bytes), 256));
+    return o;
+  };
+  const size_t o_gone = carve(static_cast<size_t>(N) * kSetBytes), o_clear = carve(static_cast<size_t>(M)), o_rowclear = carve(R), zeroed = total;
+  const size_t o_head = carve(static_cast<size_t>(N) * 4), minus_one = total - o_head;
+  const size_t o_req = carve(static_cast<size_t>(N) * S * 8), o_next = carve(R * 4), o_vict = carve(R * kSetBytes);
+  std::vector<size_t> o_extra;
+  for (size_t bytes : extra_bytes(out->n_dirty)) o_extra.push_back(carve(bytes));
+  if (int rc = stage(std::vector<Staged>{{&e->d_pseq, total, nullptr}, {&e->d_pseq_nom, csr.size() * 4, csr.data()}})) return rc;
+  char* const base = static_cast<char*>(e->d_pseq.p);
+  spx::SeqOverlay& o = out->o;
+  auto addr = [&](size_t off, auto*& p) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off); };
+  o.step = 0, addr(o_gone, o.gone), addr(o_clear, o.nom_cleared), addr(o_rowclear, o.row_cleared), addr(o_head, o.head), addr(o_req, o.requested);
+  addr(o_next, o.row_next), addr(o_vict, o.victims);
+  o.row_nom_ptr = static_cast<const int32_t*>(e->d_pseq_nom.p);
+  o.row_nom = o.row_nom_ptr + n_rows + 1;
+  out->row_nom_node = o.row_nom + own;
+  for (size_t x : o_extra) out->extra.push_back(base + x);
+  SPX_HIP(e, hipMemsetAsync(base, 0, zeroed, e->stream));
+  SPX_HIP(e, hipMemsetAsync(base + o_head, 0xFF, minus_one, e->stream));
+  e->pre_sequential = true, e->pseq_victims = o.victims;
+  return SPX_OK;
+}
+
+// The end of every entry point: what `launches` enqueues between the two events, and the run as the one the fetches answer for.
+// Everything is enqueued here; each launch reads what the one before it left on the device, and nothing is read back in between.
+template <class Launches>
+int preempt_launch(spx_engine* e, Launches launches) {
+  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  launches();
+  SPX_HIP(e, hipGetLastError());
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  e->timed = e->pre_valid = true;
   return SPX_OK;
 }
 
@@ -295,20 +375,16 @@ int spx_preempt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, cons
   int rc;
   if ((rc = rows_in_batch(e, who, rows, n_rows)) || (rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, {}))) return rc;
   e->pre_toleration = e->pre_sequential = false;
-  spx::PreemptArgs a = preempt_args(e);
-  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
-  if (!e->pre_marks_valid) {
-    spx::launch_preempt_marks(a, e->stream);
-    e->pre_marks_valid = true;
-  }
-  spx::launch_preempt_rows(a, e->stream);
-  spx::launch_preempt_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
-  spx::launch_preempt_pick(a, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
-  e->timed = true;
-  e->pre_valid = true;
-  return SPX_OK;
+  const spx::PreemptArgs a = preempt_args(e);
+  return preempt_launch(e, [&] {
+    if (!e->pre_marks_valid) {
+      spx::launch_preempt_marks(a, e->stream);
+      e->pre_marks_valid = true;
+    }
+    spx::launch_preempt_rows(a, e->stream);
+    spx::launch_preempt_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
+    spx::launch_preempt_pick(pick_args(e), e->stream);
+  });
 }
 
 int spx_upload_preempt_nominated_quota(spx_engine* e, const spx_preempt_nominated_quota_soa* t) {
@@ -341,85 +417,41 @@ int spx_preempt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, c
   const std::string who = "sequential capacity preemption";
   if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, who + ": the quota tables (spx_upload_quota with min) are not uploaded");
   if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
-  const int64_t N = e->n_nodes, M = e->h_pre_nom_ptr.back(), A = e->h_pre_pod_ptr.back(), NS = e->q_n_namespaces;
+  const int64_t M = e->h_pre_nom_ptr.back(), A = e->h_pre_pod_ptr.back(), NS = e->q_n_namespaces;
   if (M > 0 && !e->pre_nomq) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nominated_quota since the last spx_upload_preempt_nodes");
   if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, who + ": empty row list");
   if (int rc = rows_in_batch(e, who, rows, n_rows)) return rc;
-  // a row is attempted once; and the uploaded nominations each row came with (T4), as a CSR over the row list
-  std::unordered_map<int64_t, int64_t> at;  // pod row -> its index in the list
-  for (int64_t i = 0; i < n_rows; ++i)
-    if (!at.emplace(rows[i], i).second) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is listed twice");
-  std::vector<int32_t> csr(static_cast<size_t>(n_rows) + 1, 0);
-  for (int64_t j = 0; j < M; ++j) {
-    const auto it = at.find(e->h_pre_nom_row[j]);
-    if (it != at.end()) ++csr[it->second + 1];
-  }
-  for (int64_t i = 0; i < n_rows; ++i) csr[i + 1] += csr[i];
-  std::vector<int32_t> fill(csr.begin(), csr.end() - 1);
-  csr.resize(static_cast<size_t>(n_rows) + 1 + static_cast<size_t>(csr[n_rows]));  // [ptr | record]
-  for (int64_t j = 0; j < M; ++j) {
-    const auto it = at.find(e->h_pre_nom_row[j]);
-    if (it != at.end()) csr[n_rows + 1 + fill[it->second]++] = static_cast<int32_t>(j);
-  }
-  // the overlay and the stored victim sets: one allocation, carved
-  const size_t R = static_cast<size_t>(spx::round_up(n_rows, 64));
-  constexpr size_t kSetBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
-  size_t total = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t o = total;
-    total += static_cast<size_t>(spx::round_up(static_cast<int64_t>(bytes), 256));
-    return o;
+  SeqStaged st;
+  auto extra = [&](int32_t) { return std::vector<size_t>{static_cast<size_t>(A), static_cast<size_t>(NS) * S * 8, static_cast<size_t>(NS), S * 8, 4}; };
+  auto stage = [&](std::vector<Staged> more) {
+    if (eligible) more.push_back({&e->d_pre_elig, static_cast<size_t>(n_rows), eligible});
+    return preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, more);
   };
-  const size_t o_gone = carve(static_cast<size_t>(N) * kSetBytes), o_clear = carve(static_cast<size_t>(M)), o_rowclear = carve(R), zeroed = total;
-  const size_t o_head = carve(static_cast<size_t>(N) * 4), minus_one = total - o_head;
-  const size_t o_req = carve(static_cast<size_t>(N) * S * 8), o_next = carve(R * 4), o_vict = carve(R * kSetBytes), o_marks = carve(static_cast<size_t>(A)),
-               o_used = carve(static_cast<size_t>(NS) * S * 8), o_usedp = carve(static_cast<size_t>(NS)), o_agg = carve(S * 8), o_aggp = carve(4);
-  std::vector<Staged> more = {{&e->d_pseq, total, nullptr}, {&e->d_pseq_nom, csr.size() * 4, csr.data()}};
-  if (eligible) more.push_back({&e->d_pre_elig, static_cast<size_t>(n_rows), eligible});
-  if (int rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, more)) return rc;
+  if (int rc = seq_stage(e, who, rows, n_rows, extra, stage, &st)) return rc;
   e->pre_toleration = false;
-  char* const base = static_cast<char*>(e->d_pseq.p);
+  spx::PickArgs pick = pick_args(e);
   spx::CapSeqArgs q{};
   q.t = preempt_args(e);
+  q.overlay(st.o);
   q.eligible = eligible ? static_cast<const uint8_t*>(e->d_pre_elig.p) : nullptr;
   const char* const side = static_cast<const char*>(e->d_pre_nomq.p);  // (never read when M == 0)
   q.nom_qreq = reinterpret_cast<const int64_t*>(side);
   q.nom_ns = reinterpret_cast<const int32_t*>(side + static_cast<size_t>(M) * S * 8);
   q.nom_qreq_present = reinterpret_cast<const uint8_t*>(side + static_cast<size_t>(M) * (S * 8 + 4));
-  q.gone = reinterpret_cast<uint32_t*>(base + o_gone);
-  q.nom_cleared = reinterpret_cast<uint8_t*>(base + o_clear);
-  q.row_cleared = reinterpret_cast<uint8_t*>(base + o_rowclear);
-  q.head = reinterpret_cast<int32_t*>(base + o_head);
-  q.requested = reinterpret_cast<int64_t*>(base + o_req);
-  q.row_next = reinterpret_cast<int32_t*>(base + o_next);
-  q.victims = reinterpret_cast<uint32_t*>(base + o_vict);
-  q.marks = reinterpret_cast<uint8_t*>(base + o_marks);
-  q.used = reinterpret_cast<int64_t*>(base + o_used);
-  q.used_present = reinterpret_cast<uint8_t*>(base + o_usedp);
-  q.agg_used = reinterpret_cast<int64_t*>(base + o_agg);
-  q.agg_used_present = reinterpret_cast<uint32_t*>(base + o_aggp);
-  q.row_nom_ptr = static_cast<const int32_t*>(e->d_pseq_nom.p);
-  q.row_nom = q.row_nom_ptr + n_rows + 1;
-  spx::PtolSeqArgs pick{};  // k_ptol_seq_pick reads the sizes, the cells, the step and the pick columns alone
-  pick.t.n_nodes = N, pick.t.row_stride = static_cast<int64_t>(R), pick.t.cells = q.t.cells, pick.pick = q.t.pick;
-  e->pre_sequential = true;
-  e->pseq_victims = q.victims;
-  // everything is enqueued here; each launch reads what the one before it left on the device, and nothing is read back in between
-  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
-  SPX_HIP(e, hipMemsetAsync(base, 0, zeroed, e->stream));
-  SPX_HIP(e, hipMemsetAsync(base + o_head, 0xFF, minus_one, e->stream));
-  spx::launch_cap_seq_init(q, e->stream);
-  for (q.step = 0; q.step < n_rows; ++q.step) {
-    pick.step = q.step;
-    spx::launch_cap_seq_step(q, e->stream);
-    spx::launch_ptol_seq_pick(pick, e->stream);
-    spx::launch_cap_seq_apply(q, e->stream);
-  }
-  SPX_HIP(e, hipGetLastError());
-  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
-  e->timed = true;
-  e->pre_valid = true;
-  return SPX_OK;
+  q.marks = reinterpret_cast<uint8_t*>(st.extra[0]);
+  q.used = reinterpret_cast<int64_t*>(st.extra[1]);
+  q.used_present = reinterpret_cast<uint8_t*>(st.extra[2]);
+  q.agg_used = reinterpret_cast<int64_t*>(st.extra[3]);
+  q.agg_used_present = reinterpret_cast<uint32_t*>(st.extra[4]);
+  return preempt_launch(e, [&] {
+    spx::launch_cap_seq_init(q, e->stream);
+    for (; q.step < n_rows; ++q.step) {
+      pick.step = q.step;
+      spx::launch_cap_seq_step(q, e->stream);
+      spx::launch_ptol_seq_pick(pick, e->stream);
+      spx::launch_cap_seq_apply(q, e->stream);
+    }
+  });
 }
 
 int spx_upload_preempt_toleration(spx_engine* e, const spx_preempt_toleration_soa* t) {
@@ -452,16 +484,11 @@ int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n
     return rc;
   e->pre_sequential = false;
   const spx::PtolArgs a = ptol_args(e);
-  spx::PreemptArgs pick = preempt_args(e);  // k_preempt_pick reads the sizes, the cells and the pick columns alone
-  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
-  spx::launch_ptol_rows(a, e->stream);
-  spx::launch_ptol_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
-  spx::launch_preempt_pick(pick, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
-  e->timed = true;
-  e->pre_valid = true;
-  return SPX_OK;
+  return preempt_launch(e, [&] {
+    spx::launch_ptol_rows(a, e->stream);
+    spx::launch_ptol_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
+    spx::launch_preempt_pick(pick_args(e), e->stream);
+  });
 }
 
 int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
@@ -469,74 +496,28 @@ int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_
   if (!e) return SPX_ERR_ARG;
   const std::string who = "sequential preemption";
   if (int rc = ptol_check(e, who, rows, n_rows, priority, preempt_never, now_ns)) return rc;
-  // a row is attempted once; and the uploaded nominations each row came with (T4), as a CSR over the row list
-  std::unordered_map<int64_t, int64_t> at;  // pod row -> its index in the list
-  for (int64_t i = 0; i < n_rows; ++i)
-    if (!at.emplace(rows[i], i).second) return fail(e, SPX_ERR_ARG, who + ": rows[" + std::to_string(i) + "] is listed twice");
-  const int64_t N = e->n_nodes, M = e->h_pre_nom_ptr.back();
-  std::vector<int32_t> csr(static_cast<size_t>(n_rows) + 1, 0);
-  for (int64_t j = 0; j < M; ++j) {
-    const auto it = at.find(e->h_pre_nom_row[j]);
-    if (it != at.end()) ++csr[it->second + 1];
-  }
-  int32_t n_dirty = 1;
-  for (int64_t i = 0; i < n_rows; ++i) n_dirty = std::max(n_dirty, 1 + csr[i + 1]), csr[i + 1] += csr[i];
-  const size_t own = static_cast<size_t>(csr[n_rows]);
-  std::vector<int32_t> fill(csr.begin(), csr.end() - 1);
-  csr.resize(static_cast<size_t>(n_rows) + 1 + 2 * own);  // [ptr | record | node of the record]
-  for (int64_t n = 0; n < N; ++n)
-    for (int32_t j = e->h_pre_nom_ptr[n]; j < e->h_pre_nom_ptr[n + 1]; ++j) {
-      const auto it = at.find(e->h_pre_nom_row[j]);
-      if (it == at.end()) continue;
-      const size_t k = static_cast<size_t>(fill[it->second]++);
-      csr[n_rows + 1 + k] = j, csr[n_rows + 1 + own + k] = static_cast<int32_t>(n);
-    }
-  // the overlay, the stored victim sets and the dirty lists: one allocation, carved
-  const size_t R = static_cast<size_t>(spx::round_up(n_rows, 64));
-  constexpr size_t kSetBytes = SPX_PREEMPT_MAX_NODE_PODS / 8;
-  size_t total = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t o = total;
-    total += static_cast<size_t>(spx::round_up(static_cast<int64_t>(bytes), 256));
-    return o;
-  };
-  const size_t o_gone = carve(static_cast<size_t>(N) * kSetBytes), o_clear = carve(static_cast<size_t>(M)), o_rowclear = carve(R), zeroed = total;
-  const size_t o_head = carve(static_cast<size_t>(N) * 4), minus_one = total - o_head;
-  const size_t o_req = carve(static_cast<size_t>(N) * S * 8), o_next = carve(R * 4), o_vict = carve(R * kSetBytes),
-               o_dirty = carve(static_cast<size_t>(n_rows) * static_cast<size_t>(n_dirty) * 4);
-  if (int rc = ptol_stage(e, who, rows, n_rows, priority, preempt_never, eligible, now_ns, node_mask, {{&e->d_pseq, total, nullptr}, {&e->d_pseq_nom, csr.size() * 4, csr.data()}}))
-    return rc;
-  char* const base = static_cast<char*>(e->d_pseq.p);
+  SeqStaged st;
+  auto extra = [&](int32_t n_dirty) { return std::vector<size_t>{static_cast<size_t>(n_rows) * static_cast<size_t>(n_dirty) * 4}; };
+  auto stage = [&](std::vector<Staged> more) { return ptol_stage(e, who, rows, n_rows, priority, preempt_never, eligible, now_ns, node_mask, more); };
+  if (int rc = seq_stage(e, who, rows, n_rows, extra, stage, &st)) return rc;
+  spx::PickArgs pick = pick_args(e);
   spx::PtolSeqArgs q{};
   q.t = ptol_args(e);
-  q.n_dirty = n_dirty;
-  q.pick = static_cast<int32_t*>(e->d_pre_pick.p);
-  q.gone = reinterpret_cast<uint32_t*>(base + o_gone);
-  q.nom_cleared = reinterpret_cast<uint8_t*>(base + o_clear);
-  q.row_cleared = reinterpret_cast<uint8_t*>(base + o_rowclear);
-  q.head = reinterpret_cast<int32_t*>(base + o_head);
-  q.requested = reinterpret_cast<int64_t*>(base + o_req);
-  q.row_next = reinterpret_cast<int32_t*>(base + o_next);
-  q.victims = reinterpret_cast<uint32_t*>(base + o_vict);
-  q.dirty = reinterpret_cast<int32_t*>(base + o_dirty);
-  q.row_nom_ptr = static_cast<const int32_t*>(e->d_pseq_nom.p);
-  q.row_nom = q.row_nom_ptr + n_rows + 1;
-  q.row_nom_node = q.row_nom + own;
-  e->pre_sequential = true;
-  e->pseq_victims = q.victims;
-  // everything is enqueued here; each step reads what the one before it left on the device, and nothing is read back in between
-  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
-  SPX_HIP(e, hipMemsetAsync(base, 0, zeroed, e->stream));
-  SPX_HIP(e, hipMemsetAsync(base + o_head, 0xFF, minus_one, e->stream));
-  spx::launch_ptol_seq_init(q, e->stream);
-  spx::launch_ptol_rows(q.t, e->stream);
-  spx::launch_ptol_cells(q.t, static_cast<unsigned>(N), e->stream);  // the untouched state: no row of the list has moved anything yet
-  for (q.step = 0; q.step < n_rows; ++q.step) spx::launch_ptol_seq_step(q, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
-  e->timed = true;
-  e->pre_valid = true;
-  return SPX_OK;
+  q.o = st.o;
+  q.n_dirty = st.n_dirty;
+  q.pick = pick.pick;
+  q.row_nom_node = st.row_nom_node;
+  q.dirty = reinterpret_cast<int32_t*>(st.extra[0]);
+  return preempt_launch(e, [&] {
+    spx::launch_ptol_seq_init(q, e->stream);
+    spx::launch_ptol_rows(q.t, e->stream);
+    spx::launch_ptol_cells(q.t, static_cast<unsigned>(e->n_nodes), e->stream);  // the untouched state: no row of the list has moved anything yet
+    for (; q.o.step < n_rows; ++q.o.step) {
+      pick.step = q.o.step;
+      spx::launch_ptol_seq_pick(pick, e->stream);
+      spx::launch_ptol_seq_step(q, e->stream);
+    }
+  });
 }
 
 }  // extern "C"
@@ -553,6 +534,18 @@ int fetch_cells(spx_engine* e, int64_t i_begin, int64_t i_end, std::vector<spx::
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   SPX_HIP(e, hipMemcpy2D(h.data(), n * sizeof(spx::PreemptCell), static_cast<const spx::PreemptCell*>(e->d_pre_cells.p) + i_begin, R * sizeof(spx::PreemptCell),
                          n * sizeof(spx::PreemptCell), N, hipMemcpyDeviceToHost));
+  return SPX_OK;
+}
+
+// put(i * n_nodes + node, cell) for every fetched cell
+template <class Put>
+int each_cell(spx_engine* e, int64_t i_begin, int64_t i_end, Put put) {
+  if (!e) return SPX_ERR_ARG;
+  std::vector<spx::PreemptCell> h;
+  if (int rc = fetch_cells(e, i_begin, i_end, h)) return rc;
+  const size_t n = static_cast<size_t>(i_end - i_begin), N = static_cast<size_t>(e->n_nodes);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t node = 0; node < N; ++node) put(i * N + node, h[node * n + i]);
   return SPX_OK;
 }
 
@@ -576,33 +569,19 @@ int victims_in_order(spx_engine* e, int64_t node, const uint32_t* mask, int32_t*
 extern "C" {
 
 int spx_fetch_preempt_cells(spx_engine* e, int64_t i_begin, int64_t i_end, uint8_t* status, int32_t* n_victims, int32_t* n_violations) {
-  if (!e) return SPX_ERR_ARG;
-  std::vector<spx::PreemptCell> h;
-  if (int rc = fetch_cells(e, i_begin, i_end, h)) return rc;
-  const size_t n = static_cast<size_t>(i_end - i_begin), N = static_cast<size_t>(e->n_nodes);
-  for (size_t i = 0; i < n; ++i)
-    for (size_t node = 0; node < N; ++node) {
-      const spx::PreemptCell& c = h[node * n + i];
-      if (status) status[i * N + node] = static_cast<uint8_t>(c.status);
-      if (n_victims) n_victims[i * N + node] = c.n_victims;
-      if (n_violations) n_violations[i * N + node] = c.n_violations;
-    }
-  return SPX_OK;
+  return each_cell(e, i_begin, i_end, [&](size_t at, const spx::PreemptCell& c) {
+    if (status) status[at] = static_cast<uint8_t>(c.status);
+    if (n_victims) n_victims[at] = c.n_victims;
+    if (n_violations) n_violations[at] = c.n_violations;
+  });
 }
 
 int spx_fetch_preempt_keys(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* hi_priority, int64_t* priority_sum, int64_t* start) {
-  if (!e) return SPX_ERR_ARG;
-  std::vector<spx::PreemptCell> h;
-  if (int rc = fetch_cells(e, i_begin, i_end, h)) return rc;
-  const size_t n = static_cast<size_t>(i_end - i_begin), N = static_cast<size_t>(e->n_nodes);
-  for (size_t i = 0; i < n; ++i)
-    for (size_t node = 0; node < N; ++node) {
-      const spx::PreemptCell& c = h[node * n + i];
-      if (hi_priority) hi_priority[i * N + node] = c.hi_prio;
-      if (priority_sum) priority_sum[i * N + node] = c.prio_sum;
-      if (start) start[i * N + node] = c.start;
-    }
-  return SPX_OK;
+  return each_cell(e, i_begin, i_end, [&](size_t at, const spx::PreemptCell& c) {
+    if (hi_priority) hi_priority[at] = c.hi_prio;
+    if (priority_sum) priority_sum[at] = c.prio_sum;
+    if (start) start[at] = c.start;
+  });
 }
 
 int spx_fetch_preempt_pick(spx_engine* e, int64_t i_begin, int64_t i_end, int32_t* node, int32_t* n_victims, int32_t* n_violations, int32_t* n_candidates,

@@ -934,18 +934,27 @@ class Engine:
         self._ck(self._lib.spx_upload_preempt_pods(self._h, Table(self._hdr, "spx_preempt_pods_soa", n_pods=len(fit), fit_req=fit).ref()))
         self.n_pods = len(fit)
 
-    def preempt_dry_run(self, rows, node_mask=None) -> None:
-        """SelectVictimsOnNode for the pod rows `rows` x all nodes and the pick per row (spx_preempt_dry_run); node_mask [len(rows)][n_nodes],
-        0 = excluded.  Asynchronous; the fetches below address a row by its index in `rows`."""
+    def _preempt_row_list(self, rows, node_mask, eligible=None, per_row=(), names="eligible"):
+        """What the four preemption runs take per entry of `rows`, converted and checked: (len(rows), rows, eligible, node_mask) as C
+        pointers, None staying NULL.  per_row: the caller's own columns, which like eligible must have one entry per row (`names`)."""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
+        elig = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+        if any(len(v) != len(rows) for v in (*per_row, *(() if elig is None else (elig,)))):
+            raise ValueError(f"{names} must have one entry per row")
         mask = None
         if node_mask is not None:
             mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
             if mask.shape != (len(rows), self.n_nodes):
                 raise ValueError("node_mask must be [len(rows)][n_nodes]")
-        self._ck(self._lib.spx_preempt_dry_run(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows),
-                                               mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None))
-        self._preempt_rows = len(rows)
+        u8 = lambda v: None if v is None else v.ctypes.data_as(C.POINTER(C.c_uint8))  # (the pointer keeps its array alive)
+        return len(rows), rows.ctypes.data_as(C.POINTER(C.c_int64)), u8(elig), u8(mask)
+
+    def preempt_dry_run(self, rows, node_mask=None) -> None:
+        """SelectVictimsOnNode for the pod rows `rows` x all nodes and the pick per row (spx_preempt_dry_run); node_mask [len(rows)][n_nodes],
+        0 = excluded.  Asynchronous; the fetches below address a row by its index in `rows`."""
+        n, rows_p, _, mask_p = self._preempt_row_list(rows, node_mask)
+        self._ck(self._lib.spx_preempt_dry_run(self._h, rows_p, n, mask_p))
+        self._preempt_rows = n
 
     _PREEMPT_NOMQ_COLS = ("ns", "quota_req", "quota_req_present")
 
@@ -975,19 +984,9 @@ class Engine:
         lower nominations cleared, its own old nomination dropped).  eligible: per entry of rows, 0 = evaluated at its step but nothing
         applied (None = all).  The preempt_* fetches answer per row as it saw the state at its own step; preempt_victims answers for the
         row's picked node alone."""
-        rows = np.ascontiguousarray(rows, dtype=np.int64)
-        elig = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
-        if elig is not None and len(elig) != len(rows):
-            raise ValueError("eligible must have one entry per row")
-        mask = None
-        if node_mask is not None:
-            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
-            if mask.shape != (len(rows), self.n_nodes):
-                raise ValueError("node_mask must be [len(rows)][n_nodes]")
-        u8 = C.POINTER(C.c_uint8)
-        self._ck(self._lib.spx_preempt_sequential(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows), elig.ctypes.data_as(u8) if elig is not None else None,
-                                                  mask.ctypes.data_as(u8) if mask is not None else None))
-        self._preempt_rows = len(rows)
+        n, rows_p, elig_p, mask_p = self._preempt_row_list(rows, node_mask, eligible)
+        self._ck(self._lib.spx_preempt_sequential(self._h, rows_p, n, elig_p, mask_p))
+        self._preempt_rows = n
 
     def preempt_cells(self, i_begin: int = 0, i_end: Optional[int] = None):
         """(status uint8, n_victims, n_violations), each [i_end - i_begin][n_nodes] (spx_fetch_preempt_cells)"""
@@ -1073,40 +1072,22 @@ class Engine:
         """PreemptionToleration's SelectVictimsOnNode for the pod rows `rows` x all nodes and the pick per row
         (spx_preempt_toleration_dry_run); priority / preempt_never per entry of rows, now_ns the plugin's clock.  The preempt_* fetches
         answer for this run until the next dry run of either kind."""
-        rows = np.ascontiguousarray(rows, dtype=np.int64)
         prio, never = np.ascontiguousarray(priority, dtype=np.int32), np.ascontiguousarray(preempt_never, dtype=np.uint8)
-        if not len(rows) == len(prio) == len(never):
-            raise ValueError("priority and preempt_never must have one entry per row")
-        mask = None
-        if node_mask is not None:
-            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
-            if mask.shape != (len(rows), self.n_nodes):
-                raise ValueError("node_mask must be [len(rows)][n_nodes]")
-        self._ck(self._lib.spx_preempt_toleration_dry_run(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows), prio.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                          never.ctypes.data_as(C.POINTER(C.c_uint8)), int(now_ns),
-                                                          mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None))
-        self._preempt_rows = len(rows)
+        n, rows_p, _, mask_p = self._preempt_row_list(rows, node_mask, per_row=(prio, never), names="priority and preempt_never")
+        self._ck(self._lib.spx_preempt_toleration_dry_run(self._h, rows_p, n, prio.ctypes.data_as(C.POINTER(C.c_int32)), never.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                          int(now_ns), mask_p))
+        self._preempt_rows = n
 
     def preempt_toleration_sequential(self, rows, priority, preempt_never, now_ns: int, eligible=None, node_mask=None) -> None:
         """The sequential preemption loop (spx_preempt_toleration_sequential): the rows are attempted once each in list order, each against
         the state the rows before it left (victims gone, the preemptor nominated, lower nominations cleared, its own old nomination
         dropped).  eligible: per entry of rows, 0 = evaluated at its step but nothing applied (None = all).  The preempt_* fetches
         answer per row as it saw the state at its own step; preempt_victims answers for the row's picked node alone."""
-        rows = np.ascontiguousarray(rows, dtype=np.int64)
         prio, never = np.ascontiguousarray(priority, dtype=np.int32), np.ascontiguousarray(preempt_never, dtype=np.uint8)
-        elig = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
-        if not len(rows) == len(prio) == len(never) or (elig is not None and len(elig) != len(rows)):
-            raise ValueError("priority, preempt_never and eligible must have one entry per row")
-        mask = None
-        if node_mask is not None:
-            mask = np.ascontiguousarray(node_mask, dtype=np.uint8)
-            if mask.shape != (len(rows), self.n_nodes):
-                raise ValueError("node_mask must be [len(rows)][n_nodes]")
-        u8 = C.POINTER(C.c_uint8)
-        self._ck(self._lib.spx_preempt_toleration_sequential(self._h, rows.ctypes.data_as(C.POINTER(C.c_int64)), len(rows), prio.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                             never.ctypes.data_as(u8), elig.ctypes.data_as(u8) if elig is not None else None, int(now_ns),
-                                                             mask.ctypes.data_as(u8) if mask is not None else None))
-        self._preempt_rows = len(rows)
+        n, rows_p, elig_p, mask_p = self._preempt_row_list(rows, node_mask, eligible, per_row=(prio, never), names="priority, preempt_never and eligible")
+        self._ck(self._lib.spx_preempt_toleration_sequential(self._h, rows_p, n, prio.ctypes.data_as(C.POINTER(C.c_int32)), never.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                             elig_p, int(now_ns), mask_p))
+        self._preempt_rows = n
 
     def preempt_toleration_eligible(self, f: dict, priority, preempt_never, nominated_node, nominated_unresolvable) -> np.ndarray:
         """PreemptionToleration's PodEligibleToPreemptOthers per pod (spx_preempt_toleration_eligible, host only)"""
