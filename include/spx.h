@@ -1206,7 +1206,8 @@ int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t r
  * for the row range first (LVRB carries no commit state, so the loop reads those rows).  Synchronous. */
 int spx_commit_sequential(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end, int32_t* node_idx, int64_t* weighted_score, int32_t* n_ties, int64_t* tlp_missing_out);
 
-/* duration in ms of the last spx_eval's kernels measured with HIP events on the engine stream */
+/* duration in ms of the last spx_eval's kernels measured with HIP events on the engine stream.  It waits for those kernels but is not a
+ * synchronisation point for their tables (the events carry no system-scope fence): spx_sync and the fetches are. */
 int spx_last_eval_ms(spx_engine* e, float* ms);
 
 /* Per-engine options (no process-wide state: two profiles in one scheduler process may differ).  Unknown option or value

@@ -35,8 +35,12 @@ int spx_create(int device_id, spx_engine** out) {
   if (device_id < 0 || device_id >= count) return fail(nullptr, SPX_ERR_ARG, "device_id out of range");
   spx_engine* e = new spx_engine();
   e->device = device_id;
+  // ev0 / ev1 only time (spx_last_eval_ms, spx_multi's per-rank figures): nothing is read on the strength of them, so their packets carry
+  // no system-scope fence — of the 0.0074 ms that the two packets between two sweeps cost the headline step, 0.0030 is the fences'
+  // (tools/micro/evgap.hip, profiles/tlp_pairs/tlp_pairs_ab.md)
   if ((st = hipSetDevice(device_id)) != hipSuccess || (st = hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking)) != hipSuccess ||
-      (st = hipEventCreate(&e->ev0)) != hipSuccess || (st = hipEventCreate(&e->ev1)) != hipSuccess) {
+      (st = hipEventCreateWithFlags(&e->ev0, hipEventDisableSystemFence)) != hipSuccess ||
+      (st = hipEventCreateWithFlags(&e->ev1, hipEventDisableSystemFence)) != hipSuccess) {
     std::string msg = std::string("engine init: ") + hipGetErrorString(st);
     delete e;
     return fail(nullptr, SPX_ERR_HIP, msg);

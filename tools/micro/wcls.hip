@@ -8,7 +8,8 @@
 //   (c) the wave start: sixteen float4 loads of node constants and the chain order -> pod value -> ambiguity word (three dependent
 //       loads), or with the values kept next to the order (two);
 //   (d) the chunk order: ascending value, heaviest (most evaluated positions) first, heavy / light interleaved;
-//   (e) the same held to 4 waves per SIMD by LDS size, against 8.
+//   (e) the same held to 4 waves per SIMD by LDS size, against 8;
+//   (f) two or four chunks of one tile per wave, a heavy one paired with a light one (k_cls_multi).
 // Prints mean and best of 5 x 20 launches per variant.  Plain stores; no inline assembly.
 // usage: wcls INPUT [--plain-ms 0.24] [--stride 10112]
 #include <hip/hip_runtime.h>
@@ -93,19 +94,95 @@ __global__ __launch_bounds__(256) void k_cls(Args a) {
   }
 }
 
+// (f) NCH chunks of one tile per wave, one after the other: pair index f = u * NCH / 2 + t / 2 takes chunk f from the front of the launch
+// order (even t) and chunk n_chunks - 1 - f from its back (odd t), so with the heaviest chunks first every wave carries about the same
+// number of evaluated positions.  The constants are loaded once; the order -> value -> ambiguity chains of all NCH chunks are issued
+// together, before the first row loop; the chunk loop stays rolled (its records rotate through registers).  A chunk that the front and
+// the back would both take (an odd count's middle one) runs once: the later trip has no rows.
+template <int NCH>
+__global__ __launch_bounds__(256) void k_cls_multi(Args a) {
+  extern __shared__ uint32_t lds[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + wave;
+  const int tile = static_cast<int>(unit % a.n_tiles);
+  const int64_t u = unit / a.n_tiles;
+  const int64_t n_chunks = (a.rows + 63) / 64;
+  if (u * NCH >= n_chunks) return;  // wave-uniform
+  auto chunk_rows = [&](int t, int64_t* pos0) -> int {  // rows of trip t (0: none), scalar
+    const int64_t f = u * (NCH / 2) + t / 2, b = n_chunks - 1 - f;
+    const bool valid = (t & 1) ? b > f : f <= b;
+    const int64_t c = (t & 1) ? b : f;
+    *pos0 = valid ? c * 64 : 0;
+    return valid ? static_cast<int>(c * 64 + 64 < a.rows ? 64 : a.rows - c * 64) : 0;
+  };
+  F32x2 acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = F32x2{1.0f + lane, 2.0f + j};
+  {
+    const float4* tab = a.consts + static_cast<int64_t>(tile) * 16 * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float4 c = tab[j * 64];
+      acc[j >> 1] += F32x2{c.x + c.z, c.y + c.w};
+    }
+  }
+  int rec_row[NCH];
+  uint32_t rec_copy[NCH], rec_word[NCH];
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    int64_t pos0;
+    const bool live = lane < chunk_rows(t, &pos0);
+    rec_row[t] = live ? min(static_cast<uint32_t>(a.perm[pos0 + lane]), static_cast<uint32_t>(a.rows - 1)) : 0;  // (clamped: no store leaves the table)
+    rec_copy[t] = live && lane > 0 ? a.copy[pos0 + lane] : 0u;
+  }
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int64_t v = a.val_row[rec_row[t]];
+    rec_word[t] = a.amb[static_cast<uint32_t>(v) & (kAmb - 1)];
+  }
+  const int64_t col = (static_cast<int64_t>(tile) * 64 + lane) * 16;
+  const bool active = col < a.stride;
+  if (a.stride < 0) lds[threadIdx.x] = 1;  // never: keeps the dynamic LDS referenced
+  const F32x2 m{1.0001f, 0.9999f}, d{0.5f, 0.25f};
+  uint4 v{1u, 2u, 3u, static_cast<unsigned>(tile)};
+#pragma unroll 1
+  for (int t = 0; t < NCH; ++t) {
+    int64_t pos0;
+    const int n_rows = chunk_rows(t, &pos0);
+    const int my_row = rec_row[0];
+    const uint64_t copies = __ballot(rec_copy[0] != 0);
+    v.w = static_cast<unsigned>(tile) + (__ballot(lane < n_rows && ((rec_word[0] >> (tile & 31)) & 1u) != 0) != 0 ? 1u : 0u);
+#pragma unroll
+    for (int k = 0; k + 1 < NCH; ++k) rec_row[k] = rec_row[k + 1], rec_copy[k] = rec_copy[k + 1], rec_word[k] = rec_word[k + 1];
+    for (int r = 0; r < n_rows; ++r) {
+      const int64_t row = __builtin_amdgcn_readlane(my_row, r);
+      if (((copies >> r) & 1ull) == 0) {
+        for (int k = 0; k < a.k; k += 8) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] = __builtin_elementwise_fma(acc[j], m, d);
+        }
+        v.x = __float_as_uint(acc[0].x + acc[1].y + acc[2].x + acc[3].y);
+        v.y = __float_as_uint(acc[4].x + acc[5].y + acc[6].x + acc[7].y);
+      }
+      if (active) *reinterpret_cast<uint4*>(a.out + row * a.stride + col) = v;
+    }
+  }
+}
+
 struct Timing { float mean, best; };
-template <bool EVAL, int START>
-static Timing run(const Args& a, unsigned blocks, size_t lds_bytes) {
+template <typename Launch>
+static Timing run_launch(Launch launch) {
   float best = 1e30f, sum = 0.0f;
   const int reps = 5, per = 20;
-  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((k_cls<EVAL, START>), dim3(blocks), dim3(256), lds_bytes, 0, a);
+  for (int i = 0; i < 3; ++i) launch();
   CHECK(hipDeviceSynchronize());
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
   for (int rep = 0; rep < reps; ++rep) {
     CHECK(hipEventRecord(e0));
-    for (int i = 0; i < per; ++i) hipLaunchKernelGGL((k_cls<EVAL, START>), dim3(blocks), dim3(256), lds_bytes, 0, a);
+    for (int i = 0; i < per; ++i) launch();
     CHECK(hipEventRecord(e1));
     CHECK(hipEventSynchronize(e1));
     float ms;
@@ -117,6 +194,16 @@ static Timing run(const Args& a, unsigned blocks, size_t lds_bytes) {
   CHECK(hipEventDestroy(e0));
   CHECK(hipEventDestroy(e1));
   return {sum / reps, best};
+}
+template <int NCH>
+static Timing run_multi(const Args& a, size_t lds_bytes) {
+  const int64_t n_chunks = (a.rows + 63) / 64, units = (n_chunks + NCH - 1) / NCH;
+  const unsigned blocks = static_cast<unsigned>((units * a.n_tiles + 3) / 4);
+  return run_launch([&] { hipLaunchKernelGGL((k_cls_multi<NCH>), dim3(blocks), dim3(256), lds_bytes, 0, a); });
+}
+template <bool EVAL, int START>
+static Timing run(const Args& a, unsigned blocks, size_t lds_bytes) {
+  return run_launch([&] { hipLaunchKernelGGL((k_cls<EVAL, START>), dim3(blocks), dim3(256), lds_bytes, 0, a); });
 }
 
 int main(int argc, char** argv) {
@@ -242,6 +329,12 @@ int main(int argc, char** argv) {
     report(std::string("(d) ") + o.first + ", two-load chain, 4 waves per SIMD", run<true, 2>(a, blocks, kLds4));
     report(std::string("(d) ") + o.first + ", no wave start, 4 waves per SIMD", run<true, 0>(a, blocks, kLds4));
   }
+  // (f) several chunks per wave, heaviest-first order, beside the one-chunk form measured again next to them
+  upload(heavy, false);
+  report("(f) heaviest first, one chunk per wave (= (d)), 4 waves per SIMD", run<true, 1>(a, blocks, kLds4));
+  report("(f) heaviest first, two chunks per wave (q, n-1-q), 4 waves per SIMD", run_multi<2>(a, kLds4));
+  report("(f) heaviest first, four chunks per wave (q, n-1-q, q+1, n-2-q), 4 waves per SIMD", run_multi<4>(a, kLds4));
+  report("(f) heaviest first, one chunk per wave, again", run<true, 1>(a, blocks, kLds4));
   CHECK(hipFree(a.out));
   return 0;
 }
