@@ -202,8 +202,11 @@ __global__ __launch_bounds__(64 * kMaxRowWaves) void k_alloc_masked(ProfileArgs 
   const uint64_t range = static_cast<uint64_t>(hi) - static_cast<uint64_t>(lo);
   // (s - lo) * 100 / range with a wave-uniform range: below 2^42 the quotient is floor(d * b) for
   // b = RN(100 / range) * (1 + 2^-49) — the float64 product lies in [x, x + 2^-42) and frac(x) <= 1 - 1/range, so the
-  // floor is exact (same argument as kernels_nrt_fast.hip); wider ranges keep the int64 division
+  // floor is exact (same argument as kernels_nrt_fast.hip); wider ranges keep the int64 division.  From floor(2^63 / 100) + 1 on
+  // d * 100 can reach 2^63 (and from 2^63 on the range itself is negative as an int64): such rows take the reference's own
+  // sequence — the wrapping int64 product, divided, truncating, by the int64 range, clamped as k_alloc_prepare clamps
   const bool small = hi >= lo && range < (1ull << 42);
+  const bool wraps = range > static_cast<uint64_t>(INT64_MAX / 100);
   const double b = small && range ? (100.0 / static_cast<double>(range)) * (1.0 + 0x1p-49) : 0.0;
   for (int64_t t = wave; t < tiles; t += n_waves) {
     const int64_t n0 = (t * 64 + lane) * kNpl;
@@ -220,9 +223,13 @@ __global__ __launch_bounds__(64 * kMaxRowWaves) void k_alloc_masked(ProfileArgs 
         if (small) {
           const double df = __builtin_fma(static_cast<double>(static_cast<uint32_t>(d >> 32)), 0x1p32, static_cast<double>(static_cast<uint32_t>(d)));
           v = static_cast<uint32_t>(df * b);
-        } else {
+        } else if (!wraps) {
           const uint64_t q = div_le100(d * 100ull, range);
           v = q > 255 ? 255u : static_cast<uint32_t>(q);
+        } else {
+          const int64_t num = static_cast<int64_t>(d * 100ull), den = static_cast<int64_t>(range);
+          const int64_t q = den == -1 ? static_cast<int64_t>(0 - static_cast<uint64_t>(num)) : num / den;  // (Go: MinInt64 / -1 wraps)
+          v = q < 0 ? 0u : (q > 255 ? 255u : static_cast<uint32_t>(q));
         }
         w |= v << (8 * j);
       }

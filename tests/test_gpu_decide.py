@@ -4,7 +4,8 @@ must equal spx_eval + spx_eval_best exactly — it is the same float32/float64 c
 That equality holds code under test to code under test: it rests on spx_eval_best being right.  The independent anchor is
 tests/test_gpu_best_edges.py, which holds spx_eval_best's kernels to a numpy int64 reference (tests/best_cases.py) on constructed
 tables; the threshold tests at the end of this file apply the same reference to the tables a separate spx_eval wrote, so that a
-disagreement names which of the three (spx_decide, spx_eval_best, the reference over spx_eval's bytes) is off."""
+disagreement names which of the three (spx_decide, spx_eval_best, the reference over spx_eval's bytes) is off.
+The masked normalisation folded into k_decide_masked has its own anchor on constructed tables: tests/test_gpu_alloc_norm_edges.py."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,7 @@
 """Full profile on the GPU (CapacityScheduling PreFilter + Allocatable + NRT + trimaran + network-aware):
 Filter plugins feed the feasibility set of the normalising Score plugins exactly as upstream's framework does
-(Score/NormalizeScore run on nodes that passed every Filter), and the per-pod weighted argmax."""
+(Score/NormalizeScore run on nodes that passed every Filter), and the per-pod weighted argmax.
+The independent anchor of Allocatable's masked normalisation, at its edges, is tests/test_gpu_alloc_norm_edges.py."""
 import numpy as np
 import pytest
 
