@@ -1067,6 +1067,57 @@ int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n
  * node (the state that cell saw is gone). */
 int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible, int64_t now_ns, const uint8_t* node_mask);
 
+/* PreemptionToleration's dry run with NodeResourceTopologyMatch's single-NUMA Filter in the refit (kernels_ptol_nrt.hip, DESIGN.md
+ * 3.9g).  SelectVictimsOnNode runs every Filter through RunFilterPluginsWithNominatedPods; NRT's sees the pods removed so far as its
+ * preemption stack (prefilter.go:66-102), simulates their eviction on the node's zone table (filter.go:205-220, preemption.go:39-157)
+ * and runs the single-NUMA handler on the result.  The refit of the walk becomes NodeResourcesFit-with-nominated && F; everything else is
+ * spx_preempt_toleration_dry_run's, and a failing F is SPX_PREEMPT_ST_NOT_FIT.  F(p, n, stack), in this order: p BestEffort without a
+ * non-native request: pass; the node's NRT not fresh: fail; no NRT: pass; with preemption_mode, a non-empty stack and placement info
+ * that holds containers the simulation runs: no contributing pod on the stack: fail, a zone's available + releases above its
+ * allocatable: fail; then a policy other than single-numa-node: pass; else the pod-scope or container-scope handler on available +
+ * releases.  preemption_mode == 0 (prefilter.go:52): the stack is never kept and F is the ordinary Filter on the live table.  NRT
+ * ignores nominated pods.  The NodeMaybeOverReserved mark of a failing Filter outside the preemption flow is control-plane state and is
+ * not modelled.
+ * spx_preempt_nrt_soa is a side table of the preemption tables, indexed by their node index, their assigned-pod CSR order and their
+ * pod rows; it does not read spx_upload_nrt_*'s tables.  Host row-major:
+ *   slots            the NRT slot table, n_res <= SPX_NRT_MAX_RES
+ *   node_flags [N]   SPX_NRT_F_* | SPX_PNRT_F_PLACEMENT (placement info present and Containers() != 0)
+ *   n_zones [N], zone_id [N][8], zone_present [N][8] (bit = slot), node_present [N]: as spx_nrt_nodes_soa's columns
+ *   zone_avail / zone_headroom [N][8][n_res]: available, and allocatable - available (>= 0)
+ *   pod_contributes [n_assigned]: the pod, once on the stack, gives the simulation something to add (whether or not the node has the
+ *                    zone or the resource); rel_ptr [n_assigned + 1], rel_zone / rel_slot / rel_qty: its releases mapped to the node's
+ *                    zone list (position, slot, quantity > 0; zero quantities are dropped: with available <= allocatable they cannot fail)
+ *   pods             the preemptors' NRT records, one per pod row of spx_upload_preempt_pods (n_pods equal, n_res the slots')
+ * spx_upload_preempt_nrt: SPX_ERR_STATE before spx_upload_preempt_nodes / spx_upload_preempt_pods; SPX_ERR_ARG, naming the node or pod,
+ * for a size that differs from theirs, more than 8 slots, zones or containers of a preemptor (wide tables and long rows are declined),
+ * negative headroom (a zone with available > allocatable: malformed, a documented limit), a release that is negative, outside the
+ * node's zones or slots, or a node whose releases sum to 2^62 or more in a slot.  It marks earlier results stale; a later
+ * spx_upload_preempt_nodes or spx_upload_preempt_pods drops the table.
+ * spx_preempt_toleration_nrt_dry_run: the arguments of spx_preempt_toleration_dry_run and preemption_mode; SPX_ERR_STATE without the
+ * toleration table or this side table.  The spx_fetch_preempt_* calls answer for it while it is the last run; the victims fetch
+ * recomputes the cell with the same kernel. */
+#define SPX_PNRT_F_PLACEMENT 16
+typedef struct spx_preempt_nrt_soa {
+  int64_t n_nodes;
+  const spx_nrt_slots* slots;
+  const uint8_t* node_flags;
+  const uint8_t* n_zones;
+  const uint8_t* zone_id;
+  const uint8_t* zone_present;
+  const uint8_t* node_present;
+  const int64_t* zone_avail;
+  const int64_t* zone_headroom;
+  int64_t n_assigned;
+  const uint8_t* pod_contributes;
+  const int32_t* rel_ptr;
+  const uint8_t* rel_zone;
+  const uint8_t* rel_slot;
+  const int64_t* rel_qty;
+  const spx_nrt_pods_soa* pods;
+} spx_preempt_nrt_soa;
+int spx_upload_preempt_nrt(spx_engine* e, const spx_preempt_nrt_soa* t);
+int spx_preempt_toleration_nrt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns, const uint8_t* node_mask, int32_t preemption_mode);
+
 /* CapacityScheduling's sequential preemption loop (kernels_preempt_seq.hip).  Tables, argument checks, limits, the
  * memory pre-check and staleness are spx_preempt_dry_run's, plus the side table below; a pod row listed twice is SPX_ERR_ARG.
  * spx_preempt_nominated_quota_soa: one entry per nominated record of the uploaded node table, in nom_ptr CSR order (n_nominated ==
@@ -1624,6 +1675,22 @@ int spx_flatten_preempt_toleration(const spx_priority_classes* classes, int64_t 
  * nominated node (-1 = none) was UnschedulableAndUnresolvable or is absent; false when a terminating pod of lower priority sits on it;
  * else true.  Reads pod_ptr, pod_priority, pod_flags & SPX_PREEMPT_POD_TERMINATING and present.  Host only. */
 int spx_preempt_toleration_eligible(const spx_preempt_nodes_soa* t, int64_t n, const int32_t* priority, const uint8_t* preempt_never, const int64_t* nominated_node, const uint8_t* nominated_unresolvable, uint8_t* eligible_out);
+/* The side table of spx_upload_preempt_nrt from the objects (host/flatten_preempt_nrt.cc).  nodes / nrt / slots as
+ * spx_flatten_nrt_nodes takes them (nrt->zres_allocatable is required); o->assigned are the pods of the preemption tables (their QoS
+ * class is computed here) and ctr_numa holds one entry per container of o->assigned in CSR order, in the encoding of
+ * spx_nrt_post_eviction (NUMA id, -1 = no affinity, SPX_EVICT_CTR_UNKNOWN); placement_present / placement_containers [N] per node.
+ * pod_src [n_pods] = spx_flatten_preempt_nodes' column: the per-pod outputs are in the node table's CSR order.  The per-pod release rule
+ * is spx_nrt_post_eviction's (one copy, host/nrt_release.hpp): for any set of victims of one node, available + the sum of their releases
+ * and the three verdicts (nothing to add / exceeds allocatable / ok) are what that function gives.  rel_cap: the capacity of the rel_*
+ * arrays; *n_rel_out receives the count.  SPX_ERR_ARG with *bad_out = the node (>= 0) or -1 - the assigned pod: more than 8 slots or
+ * zones, a zone whose name parses to a NUMA id but that the Filter does not list (not of type Node, or an id above 63), a resource
+ * listed twice in a zone, available > allocatable, a negative release, a node's releases summing to 2^62 or more in a slot, rel_cap too
+ * small; *bad_out = INT64_MIN for a NULL or inconsistent argument.  The preemptors' records are spx_flatten_nrt_pods' on the same slots.
+ * spx_flatten_preempt_nrt_check: the limits that can be read off the flattened table (what spx_upload_preempt_nrt runs first, before
+ * it adds up a node's releases against the node table's CSR): *kind_out = 0 and SPX_OK, or SPX_ERR_ARG with 1 = node *bad_out, 2 =
+ * assigned pod *bad_out (CSR order), 3 = pod row *bad_out, 4 = a NULL column or sizes that contradict each other. */
+int spx_flatten_preempt_nrt(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_nrt_slots* slots, const spx_preempt_objects* o, const int32_t* ctr_numa, const uint8_t* placement_present, const int32_t* placement_containers, int64_t n_pods, const int32_t* pod_src, int64_t rel_cap, int64_t* n_rel_out, int64_t* bad_out, uint8_t* node_flags, uint8_t* n_zones, uint8_t* zone_id, uint8_t* zone_present, uint8_t* node_present, int64_t* zone_avail, int64_t* zone_headroom, uint8_t* pod_contributes, int32_t* rel_ptr, uint8_t* rel_zone, uint8_t* rel_slot, int64_t* rel_qty);
+int spx_flatten_preempt_nrt_check(const spx_preempt_nrt_soa* t, int32_t* kind_out, int64_t* bad_out);
 
 /* ------------------------------------------------------------------ wire format -> object tables (first slice)
  *

@@ -11,6 +11,9 @@
 // The node's pod list arrives through wave-uniform (scalar) loads and every lane walks the same trip count under its own predicate.
 // Per lane, in registers: the node's Requested (8 int64) and three 256-bit sets (potential victims, PDB-violating, victims); the PDB
 // budgets are 32 int16 per lane in LDS.  Integer vector code only; every sum is bounded by the upload's 2^62 check.
+//
+// The refit (RunFilterPluginsWithNominatedPods, :250 and :268) is NodeResourcesFit and whatever the Refit policy adds to it: FitOnly
+// nothing, kernels_ptol_nrt.hip's NodeResourceTopologyMatch's Filter, which sees the pods removed so far.
 #pragma once
 
 #include "preempt_device.h"
@@ -27,15 +30,24 @@ constexpr int64_t kHold = int64_t{1} << 33;   // and "not eligible" (the sequent
 
 __device__ __forceinline__ int prio_of(int64_t meta) { return static_cast<int>(static_cast<uint32_t>(meta)); }
 
+// What the walk asks of a refit policy, in walk order: begin() once per cell, by the whole wave; moved() whenever the pod at index j of
+// the pod records leaves (add false) or rejoins (add true) the copy of the node of the lanes with pred set, by the whole wave; ok()
+// wherever the refit is asked, by the lanes that ask, so it holds no cross-lane operation.
+struct FitOnly {
+  __device__ __forceinline__ void begin(int64_t, int64_t, int) {}
+  __device__ __forceinline__ void moved(int, bool, bool) {}
+  __device__ __forceinline__ bool ok() { return true; }
+};
+
 // One cell per lane: row rr of the list on `node`, for the lanes with want set.  budget: the wave's [kPdbs][64] int16 in LDS.  vict
 // is all zero unless the cell is a CANDIDATE.
 // kOverlay off: the uploaded state; q (NULL) and frozen are not read.
 // kOverlay on: the sequential loop's state (kernels_ptol_seq.hip) from q->o: Requested is the working copy, cleared nominations are not
 // charged, the loop's own nominations are, and the positions in `gone` are skipped in every pass.  frozen (wave-uniform) switches all
 // of that off at run time: the untouched state, which a PreemptNever row sees.
-template <bool kOverlay>
+template <bool kOverlay, class Refit = FitOnly>
 __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSeqArgs* q, int64_t node, int64_t rr, bool want, bool frozen, int16_t (*budget)[64], int lane,
-                                                 uint32_t* vict) {
+                                                 uint32_t* vict, Refit rf = Refit{}) {
   const int64_t R = a.row_stride;
   int64_t fit[S];
 #pragma unroll
@@ -58,6 +70,7 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
 
   if (__any(live)) {
     const int L = nd.pod_end - nd.pod_begin;
+    rf.begin(node, rr, lane);
     // the lane's copy of the node, the nominated pods that outrank the preemptor charged once: they are re-added before every Filter run
     int64_t alloc[S], requested[S];
 #pragma unroll
@@ -83,6 +96,7 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
         const int64_t f = pods[k].fit[s];
         requested[s] += pred ? (add ? f : -f) : 0;
       }
+      rf.moved(nd.pod_begin + k, pred, add);
     };
 
     // step 1 (:218-236): every lower-priority pod still on the node that is not exempted is a potential victim and is removed
@@ -108,7 +122,7 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
     if (live) {
       if (class_error) out.status = SPX_PREEMPT_ST_CLASS_ERROR, live = false;
       else if (n_pot == 0) out.status = SPX_PREEMPT_ST_NO_VICTIMS, live = false;
-      else if (!fits(fit, alloc, requested)) out.status = SPX_PREEMPT_ST_NOT_FIT, live = false;
+      else if (!fits(fit, alloc, requested) || !rf.ok()) out.status = SPX_PREEMPT_ST_NOT_FIT, live = false;
     }
     if (__any(live)) {
       // step 4: filterPodsWithPDBViolation over the potential victims, most important first; the budgets are the uploaded ones, in the
@@ -144,7 +158,7 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
           const bool pv = live && get_bit(pot, pos) && (get_bit(viol, pos) == (pass == 0));
           if (!__any(pv)) continue;
           move_pod(pos, pv, true);
-          const bool victim = pv && !fits(fit, alloc, requested);
+          const bool victim = pv && !(fits(fit, alloc, requested) && rf.ok());
           move_pod(pos, victim, false);
           set_bit(vict, pos, victim);
           if (victim) {

@@ -278,6 +278,16 @@ struct spx_engine {
   // describes the node table in place (spx_upload_preempt_nodes clears it).  d_pre_elig: the loop's eligible column.
   DevBuf d_pre_nomq, d_pre_elig;
   bool pre_nomq = false;
+  // The toleration dry run with NRT's Filter in the refit (spx_preempt_toleration_nrt_dry_run) is the fifth mode: pre_toleration with
+  // pre_nrt.  d_pnrt_*: spx_upload_preempt_nrt's side table as spx::PnrtNode / PnrtRel records and the preemptors' columns carved from
+  // one allocation (pnrt_pod_off: qos, non_native, n_ctr, ctr_kind, ctr_present, pod_present, ctr_req, pod_req); pnrt_table: it
+  // describes the node and pod tables in place (an upload of either clears it); pnrt_mode: the last run's preemption mode, for the
+  // victims fetch.
+  DevBuf d_pnrt_nodes, d_pnrt_contrib, d_pnrt_rel_ptr, d_pnrt_rel, d_pnrt_pods, d_pnrt_rec;
+  bool pnrt_table = false, pre_nrt = false;
+  int32_t pnrt_n_res = 0, pnrt_mode = 0, pnrt_max_zones = 0;
+  uint64_t pnrt_slot_flags = 0;
+  size_t pnrt_pod_off[8] = {0};
   // NetworkOverhead in the commit loop: per-pod effects + the workload pair lists rebuilt with room to grow
   std::vector<int32_t> h_pair_ptr, h_eff_ptr, h_eff_key;
   std::vector<uint8_t> h_key_flag;            // host copy of key_score_equally (spx_update_net_placed edits it)

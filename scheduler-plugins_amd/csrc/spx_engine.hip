@@ -89,7 +89,8 @@ int spx_destroy(spx_engine* e) {
                     &e->d_cs_snode, &e->d_cs_scum, &e->d_cs_walk, &e->d_cs_pass, &e->d_cs_open, &e->d_cs_gap, &e->d_cs_exists, &e->d_cs_minm, &e->d_cs_hasres,
                     &e->d_cs_backoff, &e->d_cs_permit, &e->d_cs_listed, &e->d_cs_gated, &e->d_cs_pod_group, &e->d_cs_status,
                     &e->d_pre_nodes, &e->d_pre_podrec, &e->d_pre_noms, &e->d_pre_pdb_allowed, &e->d_pre_pod_fit, &e->d_pre_rows, &e->d_pre_mask, &e->d_pre_rec, &e->d_pre_cells,
-                    &e->d_pre_pick, &e->d_pre_one, &e->d_ptol_pods, &e->d_ptol_meta, &e->d_ptol_rec, &e->d_pseq, &e->d_pseq_nom};
+                    &e->d_pre_pick, &e->d_pre_one, &e->d_ptol_pods, &e->d_ptol_meta, &e->d_ptol_rec, &e->d_pseq, &e->d_pseq_nom,
+                    &e->d_pnrt_nodes, &e->d_pnrt_contrib, &e->d_pnrt_rel_ptr, &e->d_pnrt_rel, &e->d_pnrt_pods, &e->d_pnrt_rec};
   for (DevBuf* b : bufs)
     if (b->p && !b->external) (void)hipFree(b->p);
   for (int i = 0; i < SPX_NUM_PLUGINS; ++i) {

@@ -828,6 +828,51 @@ struct PtolArgs {
 void launch_ptol_rows(const PtolArgs& a, hipStream_t s);
 void launch_ptol_cells(const PtolArgs& a, unsigned n_nodes_launch, hipStream_t s);
 
+// ---------------------------------------------------------------- the same dry run with NRT's single-NUMA Filter in the refit (kernels_ptol_nrt.hip)
+// spx_preempt_nrt_soa as records: a wave reads its node's zone table and each pod's releases through wave-uniform loads.
+struct PnrtNode {
+  int64_t avail[SPX_NRT_MAX_ZONES][SPX_NRT_MAX_RES];     // zone_avail, slots >= n_res zero
+  int64_t headroom[SPX_NRT_MAX_ZONES][SPX_NRT_MAX_RES];  // zone_headroom
+  uint8_t zone_id[SPX_NRT_MAX_ZONES];
+  uint8_t zone_present[SPX_NRT_MAX_ZONES];
+  uint8_t flags;         // SPX_NRT_F_* | SPX_PNRT_F_PLACEMENT
+  uint8_t n_zones;
+  uint8_t node_present;
+  uint8_t pad[5];
+};
+struct PnrtRel {
+  int64_t qty;
+  int32_t entry;  // zone position * SPX_NRT_MAX_RES + slot
+  int32_t pad;
+};
+static_assert(sizeof(PnrtNode) == 1048 && sizeof(PnrtRel) == 16, "record layouts");
+// int64 columns of the per-preemptor NRT record, [field][row_stride] (k_pnrt_rows): 0 = qos | non_native << 8 | n_ctr << 16 |
+// pod_present << 24, 1 = the containers' kinds, 2 = their presence masks (8 bits each), 3.. = pod_req [8], 11.. = ctr_req [8][8]
+constexpr int kPnrtRowFields = 3 + SPX_NRT_MAX_RES + SPX_NRT_MAX_CTRS * SPX_NRT_MAX_RES;
+struct PnrtArgs {
+  PtolArgs t;
+  int32_t n_res;
+  int32_t mode;                 // preemption mode enabled: the Filter sees the removed pods as its stack
+  int32_t max_zones;            // the most zones any node lists: with n_res, the LDS a wave's release sums take
+  uint64_t slot_flags;          // SPX_NRT_SLOT_* of slot r in bits 8r..8r+7 (AFFINE and HOST_LEVEL are what the Filter reads)
+  const PnrtNode* nodes;
+  const uint8_t* contributes;   // [assigned pods]
+  const int32_t* rel_ptr;       // [assigned pods + 1]
+  const PnrtRel* rel;
+  // the uploaded spx_nrt_pods_soa columns, by pod row
+  const uint8_t* qos;
+  const uint8_t* non_native;
+  const uint8_t* n_ctr;
+  const uint8_t* ctr_kind;
+  const uint8_t* ctr_present;
+  const int64_t* ctr_req;
+  const uint8_t* pod_present;
+  const int64_t* pod_req;
+  int64_t* nrt_rec;             // [kPnrtRowFields][row_stride]
+};
+void launch_pnrt_rows(const PnrtArgs& a, hipStream_t s);
+void launch_pnrt_cells(const PnrtArgs& a, unsigned n_nodes_launch, hipStream_t s);
+
 // ---------------------------------------------------------------- the sequential preemption loops (kernels_ptol_seq.hip, kernels_preempt_seq.hip)
 // What both loops keep next to the uploaded records, which are never written (preempt_device.h describes it and holds the device code
 // that moves it).  row_nom*: per entry of the row list, the uploaded nominated records whose pending row it is (T4), as a CSR built by

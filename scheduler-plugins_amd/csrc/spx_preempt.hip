@@ -1,7 +1,8 @@
 // spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
-// spx_preempt_sequential, spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_fetch_preempt_*): table checks and
-// uploads, the launches of kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip and kernels_ptol_seq.hip, and the fetches,
-// which serve whichever of the four ran last.
+// spx_preempt_sequential, spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_upload_preempt_nrt,
+// spx_preempt_toleration_nrt_dry_run, spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip,
+// kernels_preempt_seq.hip, kernels_ptol.hip, kernels_ptol_seq.hip and kernels_ptol_nrt.hip, and the fetches, which serve whichever of
+// the five ran last.
 // State: spx_engine.h.
 #include "spx_engine.h"
 
@@ -131,6 +132,22 @@ spx::PtolArgs ptol_args(spx_engine* e) {
   return a;
 }
 
+spx::PnrtArgs pnrt_args(spx_engine* e) {
+  spx::PnrtArgs a{};
+  a.t = ptol_args(e);
+  a.n_res = e->pnrt_n_res, a.mode = e->pnrt_mode, a.max_zones = e->pnrt_max_zones, a.slot_flags = e->pnrt_slot_flags;
+  a.nodes = static_cast<const spx::PnrtNode*>(e->d_pnrt_nodes.p);
+  a.contributes = static_cast<const uint8_t*>(e->d_pnrt_contrib.p);
+  a.rel_ptr = static_cast<const int32_t*>(e->d_pnrt_rel_ptr.p);
+  a.rel = static_cast<const spx::PnrtRel*>(e->d_pnrt_rel.p);
+  const char* const pods = static_cast<const char*>(e->d_pnrt_pods.p);
+  auto col = [&](int k) { return reinterpret_cast<const uint8_t*>(pods + e->pnrt_pod_off[k]); };
+  a.qos = col(0), a.non_native = col(1), a.n_ctr = col(2), a.ctr_kind = col(3), a.ctr_present = col(4), a.pod_present = col(5);
+  a.ctr_req = reinterpret_cast<const int64_t*>(col(6)), a.pod_req = reinterpret_cast<const int64_t*>(col(7));
+  a.nrt_rec = static_cast<int64_t*>(e->d_pnrt_rec.p);
+  return a;
+}
+
 // What either pick kernel reads, whichever plugin wrote the cells.
 spx::PickArgs pick_args(spx_engine* e) {
   return {e->n_nodes, e->pre_n_rows, e->pre_row_stride, 0, static_cast<const spx::PreemptCell*>(e->d_pre_cells.p), static_cast<int32_t*>(e->d_pre_pick.p)};
@@ -185,7 +202,7 @@ int preempt_stage(spx_engine* e, const std::string& who, const int64_t* rows, in
       return fail(e, SPX_ERR_ARG, who + ": " + std::to_string(n_rows) + " rows x " + std::to_string(N) + " nodes need " + std::to_string(grow) +
                                       " bytes of cell records, the device has " + std::to_string(free_b) + " free: split the row list");
   }
-  e->pre_valid = false;
+  e->pre_valid = e->pre_nrt = false;
   for (const Staged& w : want)
     if (int rc = w.src ? upload(e, *w.buf, w.src, w.bytes) : ensure(e, *w.buf, w.bytes)) return rc;
   SPX_HIP(e, hipStreamSynchronize(e->stream));  // what was uploaded is only borrowed for the call
@@ -303,7 +320,7 @@ int spx_upload_preempt_nodes(spx_engine* e, const spx_preempt_nodes_soa* t) {
   SPX_HIP(e, hipSetDevice(e->device));
   int rc = set_nodes(e, t->n_nodes);
   if (rc) return rc;
-  e->pre_nodes = e->pre_marks_valid = e->pre_valid = e->ptol_table = e->pre_nomq = false;
+  e->pre_nodes = e->pre_marks_valid = e->pre_valid = e->ptol_table = e->pre_nomq = e->pnrt_table = false;
   const size_t N = static_cast<size_t>(t->n_nodes), A = static_cast<size_t>(t->pod_ptr[N]), M = static_cast<size_t>(t->nom_ptr[N]), B = static_cast<size_t>(t->pdb_ptr[N]);
   // the columns as records: a wave reads a node and each of its pods through one base pointer
   std::vector<spx::PreemptNode> nodes(N);
@@ -359,7 +376,7 @@ int spx_upload_preempt_pods(spx_engine* e, const spx_preempt_pods_soa* t) {
   SPX_HIP(e, hipSetDevice(e->device));
   int rc = set_pods(e, t->n_pods);
   if (rc) return rc;
-  e->pre_pods = e->pre_valid = false;
+  e->pre_pods = e->pre_valid = e->pnrt_table = false;
   if ((rc = upload(e, e->d_pre_pod_fit, t->fit_req, static_cast<size_t>(t->n_pods) * S * 8))) return rc;
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   e->pre_pods = true;
@@ -487,6 +504,101 @@ int spx_preempt_toleration_dry_run(spx_engine* e, const int64_t* rows, int64_t n
   return preempt_launch(e, [&] {
     spx::launch_ptol_rows(a, e->stream);
     spx::launch_ptol_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
+    spx::launch_preempt_pick(pick_args(e), e->stream);
+  });
+}
+
+int spx_upload_preempt_nrt(spx_engine* e, const spx_preempt_nrt_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  const std::string who = "preempt nrt";
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  int32_t kind = 0;
+  int64_t bad = -1;
+  if (spx_flatten_preempt_nrt_check(t, &kind, &bad) != SPX_OK) {
+    static const char* const what[] = {"", "node ", "assigned pod ", "pod row ", ""};
+    const char* const why[] = {"", "more than 8 zones, a NUMA id above 63, a slot outside the slot table, or available > allocatable",
+                               "a release that is negative, 2^62 or more, or outside the zone and slot tables", "more than SPX_NRT_MAX_CTRS containers (a long row)",
+                               "a NULL column, more than SPX_NRT_MAX_RES slots, or sizes that contradict each other"};
+    return fail(e, SPX_ERR_ARG, who + ": " + what[kind] + (kind < 4 ? std::to_string(bad) + ": " : std::string()) + why[kind]);
+  }
+  const int64_t N = e->n_nodes, A = e->h_pre_pod_ptr.back(), P = e->n_pods;
+  const int R = t->slots->n_res;
+  if (t->n_nodes != N) return fail(e, SPX_ERR_ARG, who + ": " + std::to_string(t->n_nodes) + " nodes for the node table's " + std::to_string(N));
+  if (t->n_assigned != A) return fail(e, SPX_ERR_ARG, who + ": " + std::to_string(t->n_assigned) + " entries for the node table's " + std::to_string(A) + " pods");
+  if (t->pods->n_pods != P) return fail(e, SPX_ERR_ARG, who + ": " + std::to_string(t->pods->n_pods) + " pod rows for the pod table's " + std::to_string(P));
+  constexpr int Z = SPX_NRT_MAX_ZONES, RM = SPX_NRT_MAX_RES, CM = SPX_NRT_MAX_CTRS;
+  std::vector<spx::PnrtNode> nodes(static_cast<size_t>(N));
+  std::vector<spx::PnrtRel> rel(static_cast<size_t>(t->rel_ptr[A]));
+  for (int64_t n = 0; n < N; ++n) {
+    spx::PnrtNode& r = nodes[n];
+    std::memset(&r, 0, sizeof r);
+    r.flags = t->node_flags[n], r.n_zones = t->n_zones[n], r.node_present = t->node_present[n];
+    for (int z = 0; z < r.n_zones; ++z) {
+      r.zone_id[z] = t->zone_id[n * Z + z], r.zone_present[z] = t->zone_present[n * Z + z];
+      for (int s = 0; s < R; ++s) r.avail[z][s] = t->zone_avail[(n * Z + z) * R + s], r.headroom[z][s] = t->zone_headroom[(n * Z + z) * R + s];
+    }
+    // what a lane can add up: every release of the node's pods, per slot
+    uint64_t total[RM] = {0};
+    for (int64_t j = e->h_pre_pod_ptr[n]; j < e->h_pre_pod_ptr[n + 1]; ++j)
+      for (int32_t k = t->rel_ptr[j]; k < t->rel_ptr[j + 1]; ++k) {
+        const int z = t->rel_zone[k], s = t->rel_slot[k];
+        if (z >= r.n_zones || !((r.zone_present[z] >> s) & 1u))
+          return fail(e, SPX_ERR_ARG, who + ": assigned pod " + std::to_string(j) + ": a release outside the zones and resources of node " + std::to_string(n));
+        if ((total[s] += static_cast<uint64_t>(t->rel_qty[k])) >= static_cast<uint64_t>(kSumLimit))
+          return fail(e, SPX_ERR_ARG, who + ": node " + std::to_string(n) + ": the releases of slot " + std::to_string(s) + " sum to 2^62 or more");
+        rel[k] = spx::PnrtRel{t->rel_qty[k], z * RM + s, 0};
+      }
+  }
+  // the preemptors' columns, the 8-byte ones last so that each part is aligned
+  const spx_nrt_pods_soa* p = t->pods;
+  const size_t np = static_cast<size_t>(P);
+  const size_t bytes[8] = {np, np, np, np * CM, np * CM, np, np * CM * R * 8, np * R * 8};
+  const void* const src[8] = {p->qos, p->non_native, p->n_ctr, p->ctr_kind, p->ctr_present, p->pod_present, p->ctr_req, p->pod_req};
+  size_t off = 0;
+  for (int k = 0; k < 8; ++k) {
+    if (k == 6) off = static_cast<size_t>(spx::round_up(static_cast<int64_t>(off), 8));
+    e->pnrt_pod_off[k] = off, off += bytes[k];
+  }
+  std::vector<char> packed(off);
+  for (int k = 0; k < 8; ++k)
+    if (bytes[k]) std::memcpy(packed.data() + e->pnrt_pod_off[k], src[k], bytes[k]);
+  SPX_HIP(e, hipSetDevice(e->device));
+  e->pnrt_table = e->pre_valid = false;
+  struct Drain {  // the staged records live until the copies have landed
+    spx_engine* e;
+    ~Drain() { (void)hipStreamSynchronize(e->stream); }
+  } drain{e};
+  int rc;
+  if ((rc = upload(e, e->d_pnrt_nodes, nodes.data(), nodes.size() * sizeof(spx::PnrtNode))) || (rc = upload(e, e->d_pnrt_contrib, t->pod_contributes, static_cast<size_t>(A))) ||
+      (rc = upload(e, e->d_pnrt_rel_ptr, t->rel_ptr, static_cast<size_t>(A + 1) * 4)) || (rc = upload(e, e->d_pnrt_rel, rel.data(), rel.size() * sizeof(spx::PnrtRel))) ||
+      (rc = upload(e, e->d_pnrt_pods, packed.data(), packed.size())))
+    return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->pnrt_n_res = R;
+  e->pnrt_max_zones = 0;
+  for (int64_t n = 0; n < N; ++n) e->pnrt_max_zones = std::max<int32_t>(e->pnrt_max_zones, t->n_zones[n]);
+  e->pnrt_slot_flags = 0;
+  for (int s = 0; s < R; ++s) e->pnrt_slot_flags |= static_cast<uint64_t>(t->slots->slot_flags[s]) << (8 * s);
+  e->pnrt_table = true;
+  return SPX_OK;
+}
+
+int spx_preempt_toleration_nrt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns,
+                                       const uint8_t* node_mask, int32_t preemption_mode) {
+  if (!e) return SPX_ERR_ARG;
+  const std::string who = "preemption toleration dry run with NRT";
+  if (int rc = ptol_check(e, who, rows, n_rows, priority, preempt_never, now_ns)) return rc;
+  if (!e->pnrt_table) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nrt since the last spx_upload_preempt_nodes / spx_upload_preempt_pods");
+  if (n_rows > int64_t{65535} * 64) return fail(e, SPX_ERR_ARG, who + ": more than 65535 x 64 rows (a workgroup is one wave here): split the row list");
+  const size_t rec = static_cast<size_t>(spx::round_up(n_rows, 64)) * spx::kPnrtRowFields * 8;
+  if (int rc = ptol_stage(e, who, rows, n_rows, priority, preempt_never, nullptr, now_ns, node_mask, {{&e->d_pnrt_rec, rec, nullptr}})) return rc;
+  e->pre_sequential = false;
+  e->pre_nrt = true, e->pnrt_mode = preemption_mode != 0;
+  const spx::PnrtArgs a = pnrt_args(e);
+  return preempt_launch(e, [&] {
+    spx::launch_ptol_rows(a.t, e->stream);
+    spx::launch_pnrt_rows(a, e->stream);
+    spx::launch_pnrt_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
     spx::launch_preempt_pick(pick_args(e), e->stream);
   });
 }
@@ -629,7 +741,12 @@ int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* p
     a.victims_out = d_mask;
     return a;
   };
-  if (e->pre_toleration) spx::launch_ptol_cells(one_cell(ptol_args(e)), 1, e->stream);
+  if (e->pre_toleration && e->pre_nrt) {
+    spx::PnrtArgs a = pnrt_args(e);
+    a.t = one_cell(a.t);
+    a.nrt_rec += i;
+    spx::launch_pnrt_cells(a, 1, e->stream);
+  } else if (e->pre_toleration) spx::launch_ptol_cells(one_cell(ptol_args(e)), 1, e->stream);
   else spx::launch_preempt_cells(one_cell(preempt_args(e)), 1, e->stream);
   SPX_HIP(e, hipGetLastError());
   struct {

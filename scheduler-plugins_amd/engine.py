@@ -1099,6 +1099,79 @@ class Engine:
                                                                   nn.ctypes.data_as(i64), un.ctypes.data_as(u8), out.ctypes.data_as(u8)))
         return out.astype(bool)
 
+    # ------------------------------------------------------------------ the toleration dry run with NRT's single-NUMA Filter in the refit
+    _PNRT_NODE_COLS = ("node_flags", "n_zones", "zone_id", "zone_present", "node_present", "zone_avail", "zone_headroom")
+    _PNRT_POD_COLS = ("pod_contributes", "rel_ptr", "rel_zone", "rel_slot", "rel_qty")
+
+    def flatten_preempt_nrt(self, nodes: Table, nrt: Table, rc: Optional[Table], pods: Table, objects: Table, pod_src, ctr_numa, placement_present,
+                            placement_containers, params: Optional[Table] = None) -> dict:
+        """the NRT side table of the preemption tables (spx_flatten_nrt_slots, spx_flatten_preempt_nrt, spx_flatten_nrt_pods; host only):
+        `pods` the pending batch, `objects` the spx_preempt_objects of flatten_preempt_nodes and pod_src its column; ctr_numa per container
+        of the assigned pods (NUMA id, -1, SPX_EVICT_CTR_UNKNOWN), placement_present / placement_containers per node.  Returns "slots",
+        "R", the node and assigned-pod columns of spx_preempt_nrt_soa and "pods" (the preemptors' records).  SpxError(SPX_ERR_ARG) names
+        the node or the assigned pod the flattener refuses."""
+        L, H = self._lib, self._hdr
+        u8p, i32p, i64p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        n_res, slot_res, slot_flags, slot_weight = C.c_int32(), np.zeros(8, np.int32), np.zeros(8, np.uint8), np.zeros(8, np.int64)
+        rc_p = rc.ref() if rc else None
+        rc_ = L.spx_flatten_nrt_slots(pods.ref(), nrt.ref(), rc_p, params.ref() if params else None, C.byref(n_res), slot_res.ctypes.data_as(i32p),
+                                      slot_flags.ctypes.data_as(u8p), slot_weight.ctypes.data_as(i64p))
+        if rc_ != 0:
+            raise self._err(rc_, "preempt nrt flatten: more than SPX_NRT_MAX_RES resource slots (the wide tables are not taken here)")
+        R = n_res.value
+        slots = Table(H, "spx_nrt_slots", n_res=R, slot_res=slot_res, slot_flags=slot_flags, slot_weight=slot_weight)
+        arr = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
+        src, numa, pp, pcnt = arr(pod_src, np.int32), arr(ctr_numa, np.int32), arr(placement_present, np.uint8), arr(placement_containers, np.int32)
+        N, A = int(nodes.struct.n_nodes), len(src)
+        if len(pp) != N or len(pcnt) != N:
+            raise ValueError("placement_present / placement_containers must have one entry per node")
+        cols = dict(node_flags=np.zeros(N, np.uint8), n_zones=np.zeros(N, np.uint8), zone_id=np.zeros((N, 8), np.uint8), zone_present=np.zeros((N, 8), np.uint8),
+                    node_present=np.zeros(N, np.uint8), zone_avail=np.zeros((N, 8, max(R, 1)), np.int64), zone_headroom=np.zeros((N, 8, max(R, 1)), np.int64),
+                    pod_contributes=np.zeros(A, np.uint8), rel_ptr=np.zeros(A + 1, np.int32))
+        ptr = lambda v, t: (v if v.size else np.zeros(1, v.dtype)).ctypes.data_as(t)  # never hand C a NULL for an empty column
+        n_rel, bad, cap = C.c_int64(), C.c_int64(), 64
+        while True:
+            rel = dict(rel_zone=np.zeros(cap, np.uint8), rel_slot=np.zeros(cap, np.uint8), rel_qty=np.zeros(cap, np.int64))
+            rc_ = L.spx_flatten_preempt_nrt(nodes.ref(), nrt.ref(), rc_p, slots.ref(), objects.ref(), ptr(numa, i32p), ptr(pp, u8p), ptr(pcnt, i32p), A, ptr(src, i32p), cap,
+                                            C.byref(n_rel), C.byref(bad), *[ptr(cols[k], t) for k, t in zip(cols, (u8p, u8p, u8p, u8p, u8p, i64p, i64p, u8p, i32p))],
+                                            rel["rel_zone"].ctypes.data_as(u8p), rel["rel_slot"].ctypes.data_as(u8p), rel["rel_qty"].ctypes.data_as(i64p))
+            if rc_ == 0 or n_rel.value <= cap:
+                break
+            cap = int(n_rel.value)
+        if rc_ != 0:
+            b = int(bad.value)
+            what = f"node {b}" if b >= 0 else f"assigned pod {-1 - b}" if b > -(1 << 63) else "its arguments"
+            raise self._err(rc_, f"preempt nrt flatten: refused at {what}")
+        cols.update({k: v[:n_rel.value] for k, v in rel.items()})
+        return {"slots": slots, "R": R, "N": N, **cols, "pods": self.flatten_nrt_pods(pods, rc, slots)}
+
+    def preempt_nrt_table(self, f: dict) -> Table:
+        pc = f["pods"]
+        pods = Table(self._hdr, "spx_nrt_pods_soa", n_pods=len(pc["qos"]), n_res=f["R"], **{k: pc[k] for k in pc})
+        return Table(self._hdr, "spx_preempt_nrt_soa", n_nodes=f["N"], slots=f["slots"], n_assigned=len(f["pod_contributes"]), pods=pods,
+                     **{k: f[k] for k in self._PNRT_NODE_COLS + self._PNRT_POD_COLS})
+
+    def preempt_nrt_check(self, f: dict):
+        """(kind, index) of spx_flatten_preempt_nrt_check: (0, -1) when the table is within the device's limits, else what it names"""
+        kind, bad = C.c_int32(), C.c_int64()
+        self._lib.spx_flatten_preempt_nrt_check(self.preempt_nrt_table(f).ref(), C.byref(kind), C.byref(bad))
+        return int(kind.value), int(bad.value)
+
+    def upload_preempt_nrt(self, f: dict) -> None:
+        """flatten_preempt_nrt's table, for the node and pod tables in place (spx_upload_preempt_nrt); earlier results become stale, and a
+        later upload_preempt_nodes or upload_preempt_pods drops the table"""
+        self._ck(self._lib.spx_upload_preempt_nrt(self._h, self.preempt_nrt_table(f).ref()))
+
+    def preempt_toleration_nrt_dry_run(self, rows, priority, preempt_never, now_ns: int, node_mask=None, preemption_mode: bool = True) -> None:
+        """preempt_toleration_dry_run with NodeResourceTopologyMatch's Filter in the refit (spx_preempt_toleration_nrt_dry_run): the
+        Filter sees the pods removed so far as its preemption stack; preemption_mode False: it never does, and is the ordinary Filter.
+        The preempt_* fetches answer for this run until the next dry run of any kind."""
+        prio, never = np.ascontiguousarray(priority, dtype=np.int32), np.ascontiguousarray(preempt_never, dtype=np.uint8)
+        n, rows_p, _, mask_p = self._preempt_row_list(rows, node_mask, per_row=(prio, never), names="priority and preempt_never")
+        self._ck(self._lib.spx_preempt_toleration_nrt_dry_run(self._h, rows_p, n, prio.ctypes.data_as(C.POINTER(C.c_int32)), never.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                              int(now_ns), mask_p, 1 if preemption_mode else 0))
+        self._preempt_rows = n
+
     def status(self, plugin: int, pod_row: int) -> np.ndarray:
         out = np.empty(self.n_nodes, dtype=np.uint8)
         self._ck(self._lib.spx_fetch_status(self._h, plugin, pod_row, out.ctypes.data_as(C.POINTER(C.c_uint8))))

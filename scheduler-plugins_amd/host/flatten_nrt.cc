@@ -17,6 +17,7 @@
 #include <atomic>
 
 #include "../../include/spx.h"
+#include "nrt_release.hpp"
 #include "parallel.hpp"
 
 namespace {
@@ -38,37 +39,6 @@ inline int slot_of(const spx_nrt_slots* s, int32_t res) {
   for (int i = 0; i < s->n_res; ++i)
     if (s->slot_res[i] == res) return i;
   return -1;
-}
-
-// v1qos.ComputePodQOS restated for the fields the hot path reads (cpu, memory; zero quantities ignored)
-int pod_qos(const spx_pod_objects* p, int64_t pod) {
-  int64_t req[2] = {0, 0}, lim[2] = {0, 0};
-  bool has_req[2] = {false, false}, has_lim[2] = {false, false};
-  bool guaranteed = true;
-  for (int32_t c = p->ctr_ptr[pod]; c < p->ctr_ptr[pod + 1]; ++c) {
-    for (int32_t i = p->req_ptr[c]; i < p->req_ptr[c + 1]; ++i) {
-      const int32_t r = p->req_res[i];
-      if ((r == SPX_RES_CPU || r == SPX_RES_MEMORY) && p->req_qty[i] > 0) {
-        req[r] += p->req_qty[i];
-        has_req[r] = true;
-      }
-    }
-    bool found[2] = {false, false};
-    for (int32_t i = p->lim_ptr[c]; i < p->lim_ptr[c + 1]; ++i) {
-      const int32_t r = p->lim_res[i];
-      if ((r == SPX_RES_CPU || r == SPX_RES_MEMORY) && p->lim_qty[i] > 0) {
-        lim[r] += p->lim_qty[i];
-        has_lim[r] = found[r] = true;
-      }
-    }
-    if (!(found[0] && found[1])) guaranteed = false;
-  }
-  if (!has_req[0] && !has_req[1] && !has_lim[0] && !has_lim[1]) return SPX_QOS_BESTEFFORT;
-  if (guaranteed)
-    for (int r = 0; r < 2; ++r)
-      if (has_req[r] && (!has_lim[r] || lim[r] != req[r])) guaranteed = false;
-  if (guaranteed && (int(has_req[0]) + int(has_req[1])) == (int(has_lim[0]) + int(has_lim[1]))) return SPX_QOS_GUARANTEED;
-  return SPX_QOS_BURSTABLE;
 }
 
 struct KV {
@@ -399,7 +369,7 @@ extern "C" int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resou
     const int32_t c0 = pods->ctr_ptr[i], c1 = pods->ctr_ptr[i + 1];
     // more containers than the dense columns hold: a long row (its containers go to spx_flatten_nrt_long_pods' table)
     const bool is_long = c1 - c0 > CM;
-    qos[i] = static_cast<uint8_t>(pod_qos(pods, i));
+    qos[i] = static_cast<uint8_t>(spx_host::nrt_pod_qos(pods, i));
     bool nn = false;
     n_ctr[i] = static_cast<uint8_t>(is_long ? SPX_NRT_CTRS_LONG : c1 - c0);
     for (int32_t c = c0; c < c1; ++c) {
@@ -519,7 +489,7 @@ extern "C" int spx_flatten_nrt_pods_wide(const spx_pod_objects* pods, const spx_
       }
       pmask[static_cast<size_t>(i)] = m;
       if (!count_only) {
-        qos[i] = static_cast<uint8_t>(pod_qos(pods, i));
+        qos[i] = static_cast<uint8_t>(spx_host::nrt_pod_qos(pods, i));
         non_native[i] = nn ? 1 : 0;
       }
     }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/spx.h"
+#include "nrt_release.hpp"
 
 namespace {
 
@@ -23,14 +24,6 @@ struct Give {
   int32_t res;
   int64_t qty;
 };
-
-inline bool native(const spx_resource_classes* rc, int32_t res) {
-  if (res == SPX_RES_CPU || res == SPX_RES_MEMORY || res == SPX_RES_EPHEMERAL || res == SPX_RES_PODS || res == SPX_RES_STORAGE) return true;
-  return rc != nullptr && res >= 0 && res < rc->n_res && (rc->flags[res] & SPX_RC_NATIVE) != 0;
-}
-inline bool hugepage(const spx_resource_classes* rc, int32_t res) {
-  return rc != nullptr && res >= SPX_RES_FIRST_DYNAMIC && res < rc->n_res && (rc->flags[res] & SPX_RC_HUGEPAGE) != 0;
-}
 
 }  // namespace
 
@@ -60,38 +53,15 @@ extern "C" int spx_nrt_post_eviction(const spx_nrt_objects* nrt, const spx_resou
     return false;
   };
   std::vector<Give> gives;  // one entry per (numa, resource), quantities summed
-  for (int64_t v = 0; v < victims->n_pods; ++v) {
-    const int qos = victim_qos[v];
-    bool non_native = false;  // resourcerequests.IncludeNonNative: any container, init ones included
-    for (int32_t c = victims->ctr_ptr[v]; c < victims->ctr_ptr[v + 1] && !non_native; ++c)
-      for (int32_t i = victims->req_ptr[c]; i < victims->req_ptr[c + 1]; ++i)
-        if (!native(rc, victims->req_res[i])) {
-          non_native = true;
-          break;
+  for (int64_t v = 0; v < victims->n_pods; ++v)  // (a pod that contributes leaves an entry)
+    spx_host::nrt_pod_releases(rc, victims, v, victim_qos[v], ctr_numa, reported, [&](int32_t numa, int32_t res, int64_t q) {
+      for (Give& g : gives)
+        if (g.numa == numa && g.res == res) {
+          g.qty += q;
+          return;
         }
-    if (qos != SPX_QOS_GUARANTEED && !non_native) continue;
-    for (int32_t c = victims->ctr_ptr[v]; c < victims->ctr_ptr[v + 1]; ++c) {
-      if (victims->ctr_kind[c] != SPX_CTR_APP || ctr_numa[c] < 0) continue;
-      for (int32_t i = victims->req_ptr[c]; i < victims->req_ptr[c + 1]; ++i) {
-        const int32_t res = victims->req_res[i];
-        const int64_t q = victims->req_qty[i];
-        bool exclusive;
-        if (!native(rc, res)) exclusive = reported(res);
-        else if (qos != SPX_QOS_GUARANTEED) exclusive = false;
-        else if (res == SPX_RES_CPU) exclusive = q > 0 && q % 1000 == 0;
-        else exclusive = (res == SPX_RES_MEMORY || hugepage(rc, res)) && q > 0;
-        if (!exclusive) continue;
-        bool merged = false;
-        for (Give& g : gives)
-          if (g.numa == ctr_numa[c] && g.res == res) {
-            g.qty += q;
-            merged = true;
-            break;
-          }
-        if (!merged) gives.push_back(Give{ctr_numa[c], res, q});
-      }
-    }
-  }
+      gives.push_back(Give{numa, res, q});
+    });
   if (gives.empty()) return done(SPX_EVICT_NOTHING_TO_ADD);
   for (int32_t z = z0; z < z1; ++z) {
     const int32_t id = nrt->zone_numa_id[z];

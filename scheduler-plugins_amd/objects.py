@@ -523,9 +523,15 @@ def _preempt_fields(r: dict) -> dict:
 
 
 def _preempt_pod(p: dict) -> dict:
-    """a pod of the model as a one-container v1.Pod whose computePodResourceRequest is p["req"]"""
+    """a pod of the model as a one-container v1.Pod whose computePodResourceRequest is p["req"]; a pod that carries its own "containers"
+    (and "init_containers": {"requests", "limits"} in canonical units, cpu in millicores), as the NRT decoration of the model does, is
+    built from those, and p["req"] must be their request"""
     r = p["req"]
     _preempt_fields(r)
+    if "containers" in p:
+        rl = lambda d: {k: (f"{v}m" if k == "cpu" else v) for k, v in d.items()}
+        ctr = lambda c: container(rl(c["requests"]), rl(c.get("limits", {})))
+        return pod([ctr(c) for c in p["containers"]], [ctr(c) for c in p.get("init_containers", ())], priority=p["prio"], ns=p["ns"])
     req = {"cpu": f"{r['v'][0]}m", "memory": r["v"][1], "ephemeral-storage": r["v"][2]}
     req.update({PREEMPT_SCALARS[s - 4]: r["v"][s] for s in range(4, QUOTA_SLOTS) if (r["p"] >> s) & 1})
     return pod([container(req)], priority=p["prio"], ns=p["ns"])
