@@ -1118,6 +1118,23 @@ typedef struct spx_preempt_nrt_soa {
 int spx_upload_preempt_nrt(spx_engine* e, const spx_preempt_nrt_soa* t);
 int spx_preempt_toleration_nrt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, int64_t now_ns, const uint8_t* node_mask, int32_t preemption_mode);
 
+/* CapacityScheduling's dry run with the same Filter in the refit (kernels_preempt_nrt.hip).  Its SelectVictimsOnNode
+ * makes the same calls: removePod (capacity_scheduling.go:513) and addPod (:523) run the PreFilter extensions that push and pop NRT's
+ * preemption stack, and both Filter runs (:607 after the potential victims are gone, :636 inside reprievePod) run NRT's Filter on it.
+ * The refit of the walk becomes NodeResourcesFit-with-nominated && F, with F exactly as stated above for
+ * spx_preempt_toleration_nrt_dry_run (the same six steps in the same order; NRT ignores nominated pods); everything else is
+ * spx_preempt_dry_run's.  A failing F is SPX_PREEMPT_ST_NOT_FIT; no new status.  The order of :596-619 is kept: SPX_PREEMPT_ST_NO_VICTIMS,
+ * then the refit (SPX_PREEMPT_ST_NOT_FIT), then the quota test (SPX_PREEMPT_ST_QUOTA): a cell the reference ends at :607 is never reported
+ * as QUOTA.  A pod that fits but is removed again for the quota (:646-649) goes back onto NRT's stack, and every later reprieve's F
+ * sees it there.  The borrowed marks (:572) depend on no Filter.
+ * Arguments, argument checks, limits, the memory pre-check and staleness are spx_preempt_dry_run's, plus preemption_mode as in
+ * spx_preempt_toleration_nrt_dry_run and at most 65 535 x 64 rows per call (SPX_ERR_ARG beyond).  SPX_ERR_STATE without the quota tables
+ * (with min), without spx_upload_preempt_nodes / spx_upload_preempt_pods, or without the side table of spx_upload_preempt_nrt (which a
+ * later spx_upload_preempt_nodes or spx_upload_preempt_pods drops); the toleration table is not needed.  Every upload of a preemption
+ * table marks the results stale.  The spx_fetch_preempt_* calls answer for it while it is the last run; the victims fetch recomputes
+ * the cell with the same kernel. */
+int spx_preempt_nrt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* node_mask, int32_t preemption_mode);
+
 /* CapacityScheduling's sequential preemption loop (kernels_preempt_seq.hip).  Tables, argument checks, limits, the
  * memory pre-check and staleness are spx_preempt_dry_run's, plus the side table below; a pod row listed twice is SPX_ERR_ARG.
  * spx_preempt_nominated_quota_soa: one entry per nominated record of the uploaded node table, in nom_ptr CSR order (n_nominated ==

@@ -12,6 +12,10 @@
 // (the removal shrank Used iff the bit was set), after the reprieve's add-back it is in (Used grows in any case), and a second
 // removal always shrinks Used.  Key presence of a scalar in Used only grows (SetScalar).
 //
+// The refit (RunFilterPluginsWithNominatedPods, :607 and :636) is NodeResourcesFit and whatever the Refit policy adds to it
+// (preempt_device.h states the three calls): FitOnly nothing, nrt_refit.h's NrtRefit NodeResourceTopologyMatch's Filter, which sees the
+// pods removed so far (kernels_preempt_nrt.hip).  The borrowed marks depend on no Filter.
+//
 // cmp2 is restated from kernels_capacity.hip, whose machine code stays as it is.  Integer vector code only; every sum is bounded by the
 // upload's 2^62 check.
 #pragma once
@@ -87,8 +91,9 @@ __device__ __forceinline__ void cap_marks(const PreemptArgs& a, const CapSeqArgs
 // kOverlay on: the sequential loop's state (kernels_preempt_seq.hip) from *q: Requested, every quota's Used, the aggregate and the marks
 // are the working copies, cleared nominations are not charged, the loop's own nominations are, and the positions in `gone` are
 // skipped in every pass.
-template <bool kOverlay>
-__device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapSeqArgs* q, int64_t node, int64_t rr, bool want, int16_t (*budget)[64], int lane, uint32_t* vict) {
+template <bool kOverlay, class Refit = FitOnly>
+__device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapSeqArgs* q, int64_t node, int64_t rr, bool want, int16_t (*budget)[64], int lane, uint32_t* vict,
+                                                Refit rf = Refit{}) {
   const int64_t R = a.row_stride;
   // the preemptor
   int64_t req[S], in_eq[S], total[S], fit[S];
@@ -117,6 +122,7 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
 
   if (__any(live)) {
     const int L = nd.pod_end - nd.pod_begin;
+    rf.begin(node, rr, lane);
     // the lane's copy of the node, the nominated pods that outrank the preemptor charged once: they are re-added before every Filter run
     int64_t alloc[S], requested[S];
 #pragma unroll
@@ -153,7 +159,8 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
       for (int s = 0; s < S; ++s) sum[s] = wadd(agg[s], y[s]);
       return cmp2(x, xp, own, mx, mx_p, INT64_MAX) || cmp2(sum, agg_p | yp, nullptr, agg_min, a.agg_min_present, 0);
     };
-    // RemovePod / AddPod of the pod at position k on the lane's copies; `quota`: the pod's ElasticQuotaInfo moves too
+    // RemovePod / AddPod of the pod at position k on the lane's copies; `quota`: the pod's ElasticQuotaInfo moves too.  Every one of them
+    // runs the PreFilter extensions (:513, :523), the removal for the quota (:646-649) included: that pod is on the policy's stack from then on.
     auto move_pod = [&](int k, bool pred, bool quota, bool add) {
       const uint32_t qp = pods[k].qreq_present;
 #pragma unroll
@@ -165,6 +172,7 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
         own[s] += more ? dq : 0;  // a victim shares the preemptor's quota exactly when the preemptor is over its min (:558)
       }
       if (pred && quota) agg_p |= qp, own_p |= more ? qp : 0u;
+      rf.moved(nd.pod_begin + k, pred, add);
     };
 
     // step b: the potential victims, least important first, each removed
@@ -187,7 +195,7 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
     // steps c, d, e
     if (live) {
       if (n_pot == 0) out.status = SPX_PREEMPT_ST_NO_VICTIMS, live = false;
-      else if (!fits(fit, alloc, requested)) out.status = SPX_PREEMPT_ST_NOT_FIT, live = false;
+      else if (!fits(fit, alloc, requested) || !rf.ok()) out.status = SPX_PREEMPT_ST_NOT_FIT, live = false;
       else if (pq && quota_over(req, req_p, req, req_p)) out.status = SPX_PREEMPT_ST_QUOTA, live = false;
     }
     if (__any(live)) {
@@ -224,7 +232,7 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
           const bool pv = live && get_bit(pot, pos) && (get_bit(viol, pos) == (pass == 0));
           if (!__any(pv)) continue;
           move_pod(pos, pv, pq, true);
-          const bool gone = pv && !fits(fit, alloc, requested);
+          const bool gone = pv && !(fits(fit, alloc, requested) && rf.ok());
           move_pod(pos, gone, pq, false);
           const bool over = pv && pq && quota_over(in_eq, in_p, total, total_p);
           if (over && gone) out.status = SPX_PREEMPT_ST_REMOVE_TWICE, live = false;

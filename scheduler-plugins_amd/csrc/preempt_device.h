@@ -1,5 +1,5 @@
 // preempt_device.h — the one copy of the device helpers that the preemption kernels share: kernels_preempt.hip (CapacityScheduling's
-// dry run), kernels_ptol.hip (PreemptionToleration's) and the two sequential loops.  The launch shape (a wave per node, a lane per
+// dry run), kernels_ptol.hip (PreemptionToleration's), each one's variant with NRT's Filter and the two sequential loops.  The launch shape (a wave per node, a lane per
 // preemptor, 256-bit sets over a node's pod list), the register helpers of the cell walks, NodeResourcesFit, the accumulator both
 // pick kernels fold cells into, and the overlay of the two loops with the code that moves it.  What is one plugin's stays with it: cmp2,
 // the quota state and the capacity walk in cap_cell.h (kernels_preempt.hip and kernels_preempt_seq.hip), the toleration walk in ptol_cell.h.
@@ -49,6 +49,17 @@ __device__ __forceinline__ bool fits(const int64_t* fit, const int64_t* alloc, c
     if (s != 3) ok &= !(fit[s] > 0 && fit[s] > alloc[s] - requested[s]);
   return ok;
 }
+
+// The refit of a cell walk (RunFilterPluginsWithNominatedPods) is NodeResourcesFit and whatever its Refit policy adds to it.  What a walk
+// (ptol_cell.h, cap_cell.h) asks of the policy, in walk order: begin() once per cell, by the whole wave; moved() whenever the pod at index
+// j of the pod records leaves (add false) or rejoins (add true) the copy of the node of the lanes with pred set, by the whole wave; ok()
+// wherever the refit is asked, by the lanes that ask, so it holds no cross-lane operation.  FitOnly adds nothing and compiles to nothing;
+// nrt_refit.h's NrtRefit is NodeResourceTopologyMatch's Filter, which sees the pods removed so far.
+struct FitOnly {
+  __device__ __forceinline__ void begin(int64_t, int64_t, int) {}
+  __device__ __forceinline__ void moved(int, bool, bool) {}
+  __device__ __forceinline__ bool ok() { return true; }
+};
 
 // pickOneNodeForPreemption over a set of cells of one row: the best candidate's keys, the lowest node that has them, and the candidate
 // and tie counts.  40 bytes without padding: the pick kernels merge their threads' sets through an array of these in LDS.

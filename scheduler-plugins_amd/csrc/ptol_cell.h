@@ -12,8 +12,9 @@
 // Per lane, in registers: the node's Requested (8 int64) and three 256-bit sets (potential victims, PDB-violating, victims); the PDB
 // budgets are 32 int16 per lane in LDS.  Integer vector code only; every sum is bounded by the upload's 2^62 check.
 //
-// The refit (RunFilterPluginsWithNominatedPods, :250 and :268) is NodeResourcesFit and whatever the Refit policy adds to it: FitOnly
-// nothing, kernels_ptol_nrt.hip's NodeResourceTopologyMatch's Filter, which sees the pods removed so far.
+// The refit (RunFilterPluginsWithNominatedPods, :250 and :268) is NodeResourcesFit and whatever the Refit policy adds to it
+// (preempt_device.h states the three calls): FitOnly nothing, nrt_refit.h's NrtRefit NodeResourceTopologyMatch's Filter, which sees the
+// pods removed so far.
 #pragma once
 
 #include "preempt_device.h"
@@ -29,15 +30,6 @@ constexpr int64_t kNever = int64_t{1} << 32;  // kMeta: the priority in the low 
 constexpr int64_t kHold = int64_t{1} << 33;   // and "not eligible" (the sequential loop: evaluated at its step, nothing applied)
 
 __device__ __forceinline__ int prio_of(int64_t meta) { return static_cast<int>(static_cast<uint32_t>(meta)); }
-
-// What the walk asks of a refit policy, in walk order: begin() once per cell, by the whole wave; moved() whenever the pod at index j of
-// the pod records leaves (add false) or rejoins (add true) the copy of the node of the lanes with pred set, by the whole wave; ok()
-// wherever the refit is asked, by the lanes that ask, so it holds no cross-lane operation.
-struct FitOnly {
-  __device__ __forceinline__ void begin(int64_t, int64_t, int) {}
-  __device__ __forceinline__ void moved(int, bool, bool) {}
-  __device__ __forceinline__ bool ok() { return true; }
-};
 
 // One cell per lane: row rr of the list on `node`, for the lanes with want set.  budget: the wave's [kPdbs][64] int16 in LDS.  vict
 // is all zero unless the cell is a CANDIDATE.

@@ -279,7 +279,8 @@ struct spx_engine {
   DevBuf d_pre_nomq, d_pre_elig;
   bool pre_nomq = false;
   // The toleration dry run with NRT's Filter in the refit (spx_preempt_toleration_nrt_dry_run) is the fifth mode: pre_toleration with
-  // pre_nrt.  d_pnrt_*: spx_upload_preempt_nrt's side table as spx::PnrtNode / PnrtRel records and the preemptors' columns carved from
+  // pre_nrt; CapacityScheduling's with it (spx_preempt_nrt_dry_run) the sixth: pre_nrt alone.  Every staging clears pre_nrt and the two
+  // entry points set it.  d_pnrt_*: spx_upload_preempt_nrt's side table as spx::PnrtNode / PnrtRel records and the preemptors' columns carved from
   // one allocation (pnrt_pod_off: qos, non_native, n_ctr, ctr_kind, ctr_present, pod_present, ctr_req, pod_req); pnrt_table: it
   // describes the node and pod tables in place (an upload of either clears it); pnrt_mode: the last run's preemption mode, for the
   // victims fetch.

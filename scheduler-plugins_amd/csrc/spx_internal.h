@@ -849,8 +849,9 @@ static_assert(sizeof(PnrtNode) == 1048 && sizeof(PnrtRel) == 16, "record layouts
 // int64 columns of the per-preemptor NRT record, [field][row_stride] (k_pnrt_rows): 0 = qos | non_native << 8 | n_ctr << 16 |
 // pod_present << 24, 1 = the containers' kinds, 2 = their presence masks (8 bits each), 3.. = pod_req [8], 11.. = ctr_req [8][8]
 constexpr int kPnrtRowFields = 3 + SPX_NRT_MAX_RES + SPX_NRT_MAX_CTRS * SPX_NRT_MAX_RES;
-struct PnrtArgs {
-  PtolArgs t;
+// What the Filter reads (nrt_refit.h), and nothing of either plugin: the side table, the preemptors' columns and their record.  The row
+// list (rows, n_rows, row_stride) is the plugin's, in the `t` a kernel's arguments hold beside this.
+struct NrtRefitArgs {
   int32_t n_res;
   int32_t mode;                 // preemption mode enabled: the Filter sees the removed pods as its stack
   int32_t max_zones;            // the most zones any node lists: with n_res, the LDS a wave's release sums take
@@ -870,8 +871,21 @@ struct PnrtArgs {
   const int64_t* pod_req;
   int64_t* nrt_rec;             // [kPnrtRowFields][row_stride]
 };
+struct PnrtArgs {
+  PtolArgs t;
+  NrtRefitArgs n;
+};
 void launch_pnrt_rows(const PnrtArgs& a, hipStream_t s);
 void launch_pnrt_cells(const PnrtArgs& a, unsigned n_nodes_launch, hipStream_t s);
+
+// ---------------------------------------------------------------- CapacityScheduling's dry run with the same Filter in the refit (kernels_preempt_nrt.hip)
+// The row record, the marks and the pick are kernels_preempt.hip's; the NRT record is written next to the row record.
+struct CnrtArgs {
+  PreemptArgs t;
+  NrtRefitArgs n;
+};
+void launch_cnrt_rows(const CnrtArgs& a, hipStream_t s);
+void launch_cnrt_cells(const CnrtArgs& a, unsigned n_nodes_launch, hipStream_t s);
 
 // ---------------------------------------------------------------- the sequential preemption loops (kernels_ptol_seq.hip, kernels_preempt_seq.hip)
 // What both loops keep next to the uploaded records, which are never written (preempt_device.h describes it and holds the device code

@@ -1,8 +1,8 @@
 // spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
 // spx_preempt_sequential, spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_upload_preempt_nrt,
-// spx_preempt_toleration_nrt_dry_run, spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip,
-// kernels_preempt_seq.hip, kernels_ptol.hip, kernels_ptol_seq.hip and kernels_ptol_nrt.hip, and the fetches, which serve whichever of
-// the five ran last.
+// spx_preempt_toleration_nrt_dry_run, spx_preempt_nrt_dry_run, spx_fetch_preempt_*): table checks and uploads, the launches of
+// kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip, kernels_ptol_seq.hip, kernels_ptol_nrt.hip and kernels_preempt_nrt.hip,
+// and the fetches, which serve whichever of the six ran last.
 // State: spx_engine.h.
 #include "spx_engine.h"
 
@@ -132,9 +132,9 @@ spx::PtolArgs ptol_args(spx_engine* e) {
   return a;
 }
 
-spx::PnrtArgs pnrt_args(spx_engine* e) {
-  spx::PnrtArgs a{};
-  a.t = ptol_args(e);
+// The NRT side table and the preemptors' columns, for either plugin's walk.
+spx::NrtRefitArgs nrt_refit_args(spx_engine* e) {
+  spx::NrtRefitArgs a{};
   a.n_res = e->pnrt_n_res, a.mode = e->pnrt_mode, a.max_zones = e->pnrt_max_zones, a.slot_flags = e->pnrt_slot_flags;
   a.nodes = static_cast<const spx::PnrtNode*>(e->d_pnrt_nodes.p);
   a.contributes = static_cast<const uint8_t*>(e->d_pnrt_contrib.p);
@@ -147,6 +147,9 @@ spx::PnrtArgs pnrt_args(spx_engine* e) {
   a.nrt_rec = static_cast<int64_t*>(e->d_pnrt_rec.p);
   return a;
 }
+
+spx::PnrtArgs pnrt_args(spx_engine* e) { return {ptol_args(e), nrt_refit_args(e)}; }
+spx::CnrtArgs cnrt_args(spx_engine* e) { return {preempt_args(e), nrt_refit_args(e)}; }
 
 // What either pick kernel reads, whichever plugin wrote the cells.
 spx::PickArgs pick_args(spx_engine* e) {
@@ -603,6 +606,32 @@ int spx_preempt_toleration_nrt_dry_run(spx_engine* e, const int64_t* rows, int64
   });
 }
 
+int spx_preempt_nrt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* node_mask, int32_t preemption_mode) {
+  if (!e) return SPX_ERR_ARG;
+  const std::string who = "preemption dry run with NRT";
+  if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, who + ": the quota tables (spx_upload_quota with min) are not uploaded");
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  if (!e->pnrt_table) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nrt since the last spx_upload_preempt_nodes / spx_upload_preempt_pods");
+  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, who + ": empty row list");
+  if (int rc = rows_in_batch(e, who, rows, n_rows)) return rc;
+  if (n_rows > int64_t{65535} * 64) return fail(e, SPX_ERR_ARG, who + ": more than 65535 x 64 rows (a workgroup is one wave here): split the row list");
+  const size_t rec = static_cast<size_t>(spx::round_up(n_rows, 64)) * spx::kPnrtRowFields * 8;
+  if (int rc = preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, {{&e->d_pnrt_rec, rec, nullptr}})) return rc;
+  e->pre_toleration = e->pre_sequential = false;
+  e->pre_nrt = true, e->pnrt_mode = preemption_mode != 0;
+  const spx::CnrtArgs a = cnrt_args(e);
+  return preempt_launch(e, [&] {
+    if (!e->pre_marks_valid) {
+      spx::launch_preempt_marks(a.t, e->stream);
+      e->pre_marks_valid = true;
+    }
+    spx::launch_preempt_rows(a.t, e->stream);
+    spx::launch_cnrt_rows(a, e->stream);
+    spx::launch_cnrt_cells(a, static_cast<unsigned>(e->n_nodes), e->stream);
+    spx::launch_preempt_pick(pick_args(e), e->stream);
+  });
+}
+
 int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
                                       int64_t now_ns, const uint8_t* node_mask) {
   if (!e) return SPX_ERR_ARG;
@@ -744,8 +773,13 @@ int spx_fetch_preempt_victims(spx_engine* e, int64_t i, int64_t node, int32_t* p
   if (e->pre_toleration && e->pre_nrt) {
     spx::PnrtArgs a = pnrt_args(e);
     a.t = one_cell(a.t);
-    a.nrt_rec += i;
+    a.n.nrt_rec += i;
     spx::launch_pnrt_cells(a, 1, e->stream);
+  } else if (e->pre_nrt) {
+    spx::CnrtArgs a = cnrt_args(e);
+    a.t = one_cell(a.t);
+    a.n.nrt_rec += i;
+    spx::launch_cnrt_cells(a, 1, e->stream);
   } else if (e->pre_toleration) spx::launch_ptol_cells(one_cell(ptol_args(e)), 1, e->stream);
   else spx::launch_preempt_cells(one_cell(preempt_args(e)), 1, e->stream);
   SPX_HIP(e, hipGetLastError());

@@ -1172,6 +1172,15 @@ class Engine:
                                                               int(now_ns), mask_p, 1 if preemption_mode else 0))
         self._preempt_rows = n
 
+    def preempt_nrt_dry_run(self, rows, node_mask=None, preemption_mode: bool = True) -> None:
+        """preempt_dry_run with NodeResourceTopologyMatch's Filter in the refit (spx_preempt_nrt_dry_run), on the quota and preemption
+        tables and upload_preempt_nrt's side table: the Filter sees the pods removed so far, those taken for the quota included, as its
+        preemption stack; preemption_mode False: it never does, and is the ordinary Filter.  The preempt_* fetches answer for this run
+        until the next dry run of any kind."""
+        n, rows_p, _, mask_p = self._preempt_row_list(rows, node_mask)
+        self._ck(self._lib.spx_preempt_nrt_dry_run(self._h, rows_p, n, mask_p, 1 if preemption_mode else 0))
+        self._preempt_rows = n
+
     def status(self, plugin: int, pod_row: int) -> np.ndarray:
         out = np.empty(self.n_nodes, dtype=np.uint8)
         self._ck(self._lib.spx_fetch_status(self._h, plugin, pod_row, out.ctypes.data_as(C.POINTER(C.c_uint8))))
