@@ -1135,6 +1135,25 @@ int spx_preempt_toleration_nrt_dry_run(spx_engine* e, const int64_t* rows, int64
  * the cell with the same kernel. */
 int spx_preempt_nrt_dry_run(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* node_mask, int32_t preemption_mode);
 
+/* PreemptionToleration's sequential preemption loop with the same Filter in the refit (kernels_ptol_nrt_seq.hip).  The
+ * contract is spx_preempt_toleration_sequential's in full (T1-T4, preempt_never, eligible, rows listed once, PDB budgets as uploaded,
+ * results through the same fetches, spx_fetch_preempt_victims(i, node) for the picked node only) with the refit of
+ * spx_preempt_toleration_nrt_dry_run: NodeResourcesFit-with-nominated && F.  One more rule:
+ *   T5  the zone table, the placement info and the per-pod releases of spx_preempt_nrt_soa stay as uploaded at every step.  A pod that
+ *       left at an earlier step contributes no release and is not counted in the stack size or the contributing count: it is gone from
+ *       NodeInfo, nobody calls RemovePod for it again, so it is never on NRT's preemption stack again.  NRT ignores nominated pods, so T2
+ *       and T3 do not touch F.  Unlike T1-T4 this is pinned by reference source: NRT's caches have no pod-delete path
+ *       (pkg/noderesourcetopology/cache/passthrough.go, discardreserved.go, overreserve.go change on an NRT update, a Reserve / Unreserve
+ *       or a resync only), so between two PostFilter calls of one batch the zone table is what the node agent last reported.
+ * A preempt_never row is answered on the uploaded state with F: what spx_preempt_toleration_nrt_dry_run writes for it, bit for bit.
+ * With preemption_mode == 0, F is the ordinary Filter on the live table at every step.
+ * Argument checks, limits, the memory pre-check (which counts the NRT row record of 75 int64 per row as well) and staleness are the
+ * union of the two: SPX_ERR_STATE without spx_upload_preempt_nodes / _pods, the toleration table or the side table of
+ * spx_upload_preempt_nrt (which a later spx_upload_preempt_nodes or spx_upload_preempt_pods drops); SPX_ERR_ARG for an empty list, a row
+ * outside the batch or listed twice, now_ns == INT64_MAX, or more than 65 535 x 64 rows.  The uploaded tables are never written: either
+ * dry run and spx_preempt_toleration_sequential give after this loop what they gave before it. */
+int spx_preempt_toleration_nrt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible, int64_t now_ns, const uint8_t* node_mask, int32_t preemption_mode);
+
 /* CapacityScheduling's sequential preemption loop (kernels_preempt_seq.hip).  Tables, argument checks, limits, the
  * memory pre-check and staleness are spx_preempt_dry_run's, plus the side table below; a pod row listed twice is SPX_ERR_ARG.
  * spx_preempt_nominated_quota_soa: one entry per nominated record of the uploaded node table, in nom_ptr CSR order (n_nominated ==

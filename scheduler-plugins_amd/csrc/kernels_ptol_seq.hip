@@ -7,7 +7,8 @@
 //                      the candidate and tie counts of k_preempt_pick; the step waits for it, so it is as wide as a workgroup gets.
 //                      CapacityScheduling's loop (kernels_preempt_seq.hip) picks with it over the same 32-byte cells
 //   k_ptol_seq_apply   one wave: cell (i, picked node) again for its victim set, which is stored (32 B per row); then T1-T4 and the
-//                      ids of the nodes whose state moved (the picked node and the nodes a dropped nomination sat on; -1 = unused slot)
+//                      ids of the nodes whose state moved (the picked node and the nodes a dropped nomination sat on; -1 = unused slot):
+//                      ptol_cell.h's ptol_seq_apply_tail, which the loop with NRT's Filter (kernels_ptol_nrt_seq.hip) ends its step with too
 //   k_ptol_seq_cells   dirty slots x ceil(rows / 256): the column of each dirty node for the rows after i, ptol_cell.h's walk with
 //                      the overlay on.  Rows <= i store nothing, so the cells of row i stay what row i saw at its own step.
 //
@@ -53,47 +54,14 @@ __global__ __launch_bounds__(64) void k_ptol_seq_apply(PtolSeqArgs q) {
   __shared__ int16_t s_budget[kPdbs][64];
   const PtolArgs& a = q.t;
   const int lane = threadIdx.x;
-  const SeqOverlay& o = q.o;
-  const int64_t R = a.row_stride, i = o.step;
+  const int64_t R = a.row_stride, i = q.o.step;
   const int32_t n = q.pick[i];
   const int64_t meta = a.row_rec[kMeta * R + i];
-  const int prio = prio_of(meta);
-  const bool never = meta & kNever;
-  int32_t* const dirty = q.dirty + i * q.n_dirty;
 
   // every lane computes the picked cell of row i
   uint32_t vict[kWords] = {};
-  if (n >= 0) (void)ptol_cell<true>(a, &q, n, i, true, never, s_budget, lane, vict);
-  seq_store_victims(o, i, vict, lane);
-  if (meta & (kNever | kHold)) {  // nothing moves
-    for (int k = lane; k < q.n_dirty; k += 64) dirty[k] = -1;
-    return;
-  }
-  if (lane == 0) {
-    // T4: the nominations row i came with are dropped wherever they sit; with T1-T3 below, these are the nodes whose cells are stale
-    int n_dirty = 0;
-    if (n >= 0) dirty[n_dirty++] = n;
-    for (int32_t t = o.row_nom_ptr[i]; t < o.row_nom_ptr[i + 1]; ++t) {
-      const int32_t j = o.row_nom[t], m = q.row_nom_node[t];
-      if (o.nom_cleared[j]) continue;
-      o.nom_cleared[j] = 1;
-      bool listed = false;
-      for (int k = 0; k < n_dirty; ++k) listed |= dirty[k] == m;
-      if (!listed) dirty[n_dirty++] = m;
-    }
-    for (; n_dirty < q.n_dirty; ++n_dirty) dirty[n_dirty] = -1;
-  }
-  if (n < 0) return;
-  const PreemptNode& nd = a.nodes[n];
-  // T1: the victims leave the node and its Requested
-  seq_evict(o, n, vict, lane);
-  if (lane < S) {
-    const PreemptPod* pods = a.pods + nd.pod_begin;
-    int64_t sub = 0;
-    for (int k = 0; k < nd.pod_end - nd.pod_begin; ++k) sub += get_bit(vict, k) ? pods[k].fit[lane] : 0;
-    o.requested[static_cast<int64_t>(n) * S + lane] -= sub;
-  }
-  seq_nominate(o, nd, a.noms, n, i, prio, lane, a.row_rec + kMeta * R);  // T3, T2
+  if (n >= 0) (void)ptol_cell<true>(a, &q, n, i, true, meta & kNever, s_budget, lane, vict);
+  ptol_seq_apply_tail(q, n, i, meta, vict, lane);
 }
 
 __global__ __launch_bounds__(kBlock) void k_ptol_seq_cells(PtolSeqArgs q) {

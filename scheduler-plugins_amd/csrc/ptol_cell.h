@@ -1,6 +1,8 @@
 // ptol_cell.h — PreemptionToleration's SelectVictimsOnNode (pkg/preemptiontoleration/preemption_toleration.go:188-299) for one
 // (preemptor, node) cell per lane, and the row record it reads: the one copy of the walk that kernels_ptol.hip (k_ptol_cells, on the
-// uploaded state) and kernels_ptol_seq.hip (k_ptol_seq_apply and k_ptol_seq_cells, on the state the loop's earlier rows left) run.
+// uploaded state) and kernels_ptol_seq.hip (k_ptol_seq_apply and k_ptol_seq_cells, on the state the loop's earlier rows left) run, and
+// with nrt_refit.h's Filter in the refit kernels_ptol_nrt.hip and kernels_ptol_nrt_seq.hip; and the end of a loop's step, which the two
+// apply kernels share (ptol_seq_apply_tail).
 //
 // The walk is DefaultPreemption's with one more predicate per (preemptor, lower-priority pod) pair, ExemptedFromPreemption (:129-181).
 // What of it depends on the pod alone is folded into the PtolPod record by the host (flatten_ptol.cc): the class lookup, the parsed
@@ -36,7 +38,8 @@ __device__ __forceinline__ int prio_of(int64_t meta) { return static_cast<int>(s
 // kOverlay off: the uploaded state; q (NULL) and frozen are not read.
 // kOverlay on: the sequential loop's state (kernels_ptol_seq.hip) from q->o: Requested is the working copy, cleared nominations are not
 // charged, the loop's own nominations are, and the positions in `gone` are skipped in every pass.  frozen (wave-uniform) switches all
-// of that off at run time: the untouched state, which a PreemptNever row sees.
+// of that off at run time: the untouched state, which a PreemptNever row sees.  A skipped position never reaches move_pod, so the
+// refit policy never hears of a pod that left at an earlier step.
 template <bool kOverlay, class Refit = FitOnly>
 __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSeqArgs* q, int64_t node, int64_t rr, bool want, bool frozen, int16_t (*budget)[64], int lane,
                                                  uint32_t* vict, Refit rf = Refit{}) {
@@ -175,6 +178,48 @@ __device__ __forceinline__ PreemptCell ptol_cell(const PtolArgs& a, const PtolSe
     for (int i = 0; i < kWords; ++i) vict[i] = 0;
   }
   return out;
+}
+
+// The end of step i in the apply kernel of a PreemptionToleration loop (k_ptol_seq_apply, k_pnrt_seq_apply), called by all lanes of its
+// one wave once the picked cell (i, n) is computed again: the victim set is stored (32 B per row); then T4, T1, T3 + T2 and the ids of
+// the nodes whose state moved (the picked node and the nodes a dropped nomination sat on; -1 = unused slot).  n: the pick, -1 = no
+// candidate; meta: row i's kMeta field; vict: all zero without a pick.
+__device__ __forceinline__ void ptol_seq_apply_tail(const PtolSeqArgs& q, int32_t n, int64_t i, int64_t meta, const uint32_t* vict, int lane) {
+  const PtolArgs& a = q.t;
+  const SeqOverlay& o = q.o;
+  const int64_t R = a.row_stride;
+  const int prio = prio_of(meta);
+  int32_t* const dirty = q.dirty + i * q.n_dirty;
+  seq_store_victims(o, i, vict, lane);
+  if (meta & (kNever | kHold)) {  // nothing moves
+    for (int k = lane; k < q.n_dirty; k += 64) dirty[k] = -1;
+    return;
+  }
+  if (lane == 0) {
+    // T4: the nominations row i came with are dropped wherever they sit; with T1-T3 below, these are the nodes whose cells are stale
+    int n_dirty = 0;
+    if (n >= 0) dirty[n_dirty++] = n;
+    for (int32_t t = o.row_nom_ptr[i]; t < o.row_nom_ptr[i + 1]; ++t) {
+      const int32_t j = o.row_nom[t], m = q.row_nom_node[t];
+      if (o.nom_cleared[j]) continue;
+      o.nom_cleared[j] = 1;
+      bool listed = false;
+      for (int k = 0; k < n_dirty; ++k) listed |= dirty[k] == m;
+      if (!listed) dirty[n_dirty++] = m;
+    }
+    for (; n_dirty < q.n_dirty; ++n_dirty) dirty[n_dirty] = -1;
+  }
+  if (n < 0) return;
+  const PreemptNode& nd = a.nodes[n];
+  // T1: the victims leave the node and its Requested
+  seq_evict(o, n, vict, lane);
+  if (lane < S) {
+    const PreemptPod* pods = a.pods + nd.pod_begin;
+    int64_t sub = 0;
+    for (int k = 0; k < nd.pod_end - nd.pod_begin; ++k) sub += get_bit(vict, k) ? pods[k].fit[lane] : 0;
+    o.requested[static_cast<int64_t>(n) * S + lane] -= sub;
+  }
+  seq_nominate(o, nd, a.noms, n, i, prio, lane, a.row_rec + kMeta * R);  // T3, T2
 }
 
 }  // namespace

@@ -283,7 +283,8 @@ struct spx_engine {
   // entry points set it.  d_pnrt_*: spx_upload_preempt_nrt's side table as spx::PnrtNode / PnrtRel records and the preemptors' columns carved from
   // one allocation (pnrt_pod_off: qos, non_native, n_ctr, ctr_kind, ctr_present, pod_present, ctr_req, pod_req); pnrt_table: it
   // describes the node and pod tables in place (an upload of either clears it); pnrt_mode: the last run's preemption mode, for the
-  // victims fetch.
+  // victims fetch.  The toleration loop with that Filter (spx_preempt_toleration_nrt_sequential) is the seventh mode: pre_toleration,
+  // pre_nrt and pre_sequential; the fetches branch on pre_sequential first, so its victims are the stored sets of the third mode.
   DevBuf d_pnrt_nodes, d_pnrt_contrib, d_pnrt_rel_ptr, d_pnrt_rel, d_pnrt_pods, d_pnrt_rec;
   bool pnrt_table = false, pre_nrt = false;
   int32_t pnrt_n_res = 0, pnrt_mode = 0, pnrt_max_zones = 0;

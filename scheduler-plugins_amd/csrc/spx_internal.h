@@ -917,6 +917,16 @@ struct PtolSeqArgs {
 void launch_ptol_seq_init(const PtolSeqArgs& q, hipStream_t s);
 void launch_ptol_seq_step(const PtolSeqArgs& q, hipStream_t s);  // after launch_ptol_seq_pick: what row o.step changes, then the stale cells
 
+// The same loop with NRT's single-NUMA Filter in the refit (kernels_ptol_nrt_seq.hip): the loop's arguments with the
+// Filter's beside them.  The zone table, the placement info and the releases are read as uploaded at every step (T5), so the overlay is
+// the loop's and nothing of NRT's is carried.  The pick, the overlay's init and the sweep of the untouched state are launch_ptol_seq_pick,
+// launch_ptol_seq_init and launch_ptol_rows + launch_pnrt_rows + launch_pnrt_cells.
+struct PnrtSeqArgs {
+  PtolSeqArgs q;
+  NrtRefitArgs n;
+};
+void launch_pnrt_seq_step(const PnrtSeqArgs& p, hipStream_t s);  // as launch_ptol_seq_step
+
 // CapacityScheduling's loop: the tables and results of the dry run, the side table of the nominated records' quota
 // requests, the overlay and the working quota state.  Nothing is swept ahead: step i writes row i's record and column and nobody else's.
 // The overlay's fields are this struct's own, at the offsets its kernels were first measured with: with `SeqOverlay o` nested, as in

@@ -1,8 +1,8 @@
 // spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
 // spx_preempt_sequential, spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_upload_preempt_nrt,
-// spx_preempt_toleration_nrt_dry_run, spx_preempt_nrt_dry_run, spx_fetch_preempt_*): table checks and uploads, the launches of
-// kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip, kernels_ptol_seq.hip, kernels_ptol_nrt.hip and kernels_preempt_nrt.hip,
-// and the fetches, which serve whichever of the six ran last.
+// spx_preempt_toleration_nrt_dry_run, spx_preempt_nrt_dry_run, spx_preempt_toleration_nrt_sequential, spx_fetch_preempt_*): table checks
+// and uploads, the launches of kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip, kernels_ptol_seq.hip, kernels_ptol_nrt.hip,
+// kernels_preempt_nrt.hip and kernels_ptol_nrt_seq.hip, and the fetches, which serve whichever of the seven ran last.
 // State: spx_engine.h.
 #include "spx_engine.h"
 
@@ -657,6 +657,45 @@ int spx_preempt_toleration_sequential(spx_engine* e, const int64_t* rows, int64_
       pick.step = q.o.step;
       spx::launch_ptol_seq_pick(pick, e->stream);
       spx::launch_ptol_seq_step(q, e->stream);
+    }
+  });
+}
+
+int spx_preempt_toleration_nrt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const int32_t* priority, const uint8_t* preempt_never, const uint8_t* eligible,
+                                          int64_t now_ns, const uint8_t* node_mask, int32_t preemption_mode) {
+  if (!e) return SPX_ERR_ARG;
+  const std::string who = "sequential preemption with NRT";
+  if (int rc = ptol_check(e, who, rows, n_rows, priority, preempt_never, now_ns)) return rc;
+  if (!e->pnrt_table) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nrt since the last spx_upload_preempt_nodes / spx_upload_preempt_pods");
+  if (n_rows > int64_t{65535} * 64) return fail(e, SPX_ERR_ARG, who + ": more than 65535 x 64 rows (a workgroup is one wave here): split the row list");
+  const size_t rec = static_cast<size_t>(spx::round_up(n_rows, 64)) * spx::kPnrtRowFields * 8;
+  SeqStaged st;
+  auto extra = [&](int32_t n_dirty) { return std::vector<size_t>{static_cast<size_t>(n_rows) * static_cast<size_t>(n_dirty) * 4}; };
+  auto stage = [&](std::vector<Staged> more) {
+    more.push_back({&e->d_pnrt_rec, rec, nullptr});  // the memory pre-check counts the NRT row record too
+    return ptol_stage(e, who, rows, n_rows, priority, preempt_never, eligible, now_ns, node_mask, more);
+  };
+  if (int rc = seq_stage(e, who, rows, n_rows, extra, stage, &st)) return rc;
+  e->pre_nrt = true, e->pnrt_mode = preemption_mode != 0;
+  spx::PickArgs pick = pick_args(e);
+  spx::PnrtSeqArgs p{};
+  p.q.t = ptol_args(e);
+  p.q.o = st.o;
+  p.q.n_dirty = st.n_dirty;
+  p.q.pick = pick.pick;
+  p.q.row_nom_node = st.row_nom_node;
+  p.q.dirty = reinterpret_cast<int32_t*>(st.extra[0]);
+  p.n = nrt_refit_args(e);
+  const spx::PnrtArgs sweep{p.q.t, p.n};
+  return preempt_launch(e, [&] {
+    spx::launch_ptol_seq_init(p.q, e->stream);
+    spx::launch_ptol_rows(p.q.t, e->stream);
+    spx::launch_pnrt_rows(sweep, e->stream);
+    spx::launch_pnrt_cells(sweep, static_cast<unsigned>(e->n_nodes), e->stream);  // the untouched state with F: no row of the list has moved anything yet
+    for (; p.q.o.step < n_rows; ++p.q.o.step) {
+      pick.step = p.q.o.step;
+      spx::launch_ptol_seq_pick(pick, e->stream);
+      spx::launch_pnrt_seq_step(p, e->stream);
     }
   });
 }

@@ -1172,6 +1172,17 @@ class Engine:
                                                               int(now_ns), mask_p, 1 if preemption_mode else 0))
         self._preempt_rows = n
 
+    def preempt_toleration_nrt_sequential(self, rows, priority, preempt_never, now_ns: int, eligible=None, node_mask=None, preemption_mode: bool = True) -> None:
+        """preempt_toleration_sequential with NodeResourceTopologyMatch's Filter in the refit (spx_preempt_toleration_nrt_sequential), on
+        upload_preempt_nrt's side table, which stays as uploaded at every step: a pod evicted at an earlier step is never on the Filter's
+        stack again.  preemption_mode False: the ordinary Filter at every step.  The preempt_* fetches answer as after
+        preempt_toleration_sequential."""
+        prio, never = np.ascontiguousarray(priority, dtype=np.int32), np.ascontiguousarray(preempt_never, dtype=np.uint8)
+        n, rows_p, elig_p, mask_p = self._preempt_row_list(rows, node_mask, eligible, per_row=(prio, never), names="priority, preempt_never and eligible")
+        self._ck(self._lib.spx_preempt_toleration_nrt_sequential(self._h, rows_p, n, prio.ctypes.data_as(C.POINTER(C.c_int32)), never.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                                 elig_p, int(now_ns), mask_p, 1 if preemption_mode else 0))
+        self._preempt_rows = n
+
     def preempt_nrt_dry_run(self, rows, node_mask=None, preemption_mode: bool = True) -> None:
         """preempt_dry_run with NodeResourceTopologyMatch's Filter in the refit (spx_preempt_nrt_dry_run), on the quota and preemption
         tables and upload_preempt_nrt's side table: the Filter sees the pods removed so far, those taken for the quota included, as its
