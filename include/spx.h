@@ -1200,6 +1200,31 @@ typedef struct spx_preempt_nominated_quota_soa {
 int spx_upload_preempt_nominated_quota(spx_engine* e, const spx_preempt_nominated_quota_soa* t);
 int spx_preempt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask);
 
+/* CapacityScheduling's sequential preemption loop with NodeResourceTopologyMatch's Filter in the refit (kernels_preempt_nrt_seq.hip,
+ * DESIGN.md 3.9j).  The contract is spx_preempt_sequential's in full (T1-T4, eligible, rows listed once, PDB budgets as uploaded,
+ * PreFilter's sums from the nominated side table and the loop's own nominations, results through the same fetches,
+ * spx_fetch_preempt_victims(i, node) for the picked node only) with the refit of spx_preempt_nrt_dry_run: NodeResourcesFit-with-nominated
+ * && F at :607 and :636, the status order SPX_PREEMPT_ST_NO_VICTIMS, then the refit (SPX_PREEMPT_ST_NOT_FIT), then the quota test
+ * (SPX_PREEMPT_ST_QUOTA), and a pod removed again for the quota (:646-649) on F's stack from then on.  One more rule, taken over from
+ * spx_preempt_toleration_nrt_sequential:
+ *   T5  the zone table, the placement info and the per-pod releases of spx_preempt_nrt_soa stay as uploaded at every step.  A pod that
+ *       left at an earlier step contributes no release and is not counted in the stack size or the contributing count: it is gone from
+ *       NodeInfo, nobody calls RemovePod for it again, so it is never on NRT's preemption stack again.  NRT ignores nominated pods, so T2
+ *       and T3 do not touch F.  Unlike T1-T4 this is pinned by reference source: NRT's caches have no pod-delete path
+ *       (pkg/noderesourcetopology/cache/passthrough.go, discardreserved.go, overreserve.go change on an NRT update, a Reserve / Unreserve
+ *       or a resync only), so between two PostFilter calls of one batch the zone table is what the node agent last reported.
+ *       A victim that F alone kept (NodeResourcesFit would have reprieved it) leaves its quota through T1 like any other victim: its
+ *       quota's Used and the aggregate move, and with them the borrowed marks and over-min branches of later rows on every node.
+ * With preemption_mode == 0, F is the ordinary Filter on the uploaded zone table at every step.
+ * Argument checks, limits, the memory pre-check (which counts the NRT row record of 75 int64 per row, rounded up to 64 rows, as well)
+ * and staleness are the union of the two: SPX_ERR_STATE without the quota tables (with min), without spx_upload_preempt_nodes / _pods,
+ * without spx_upload_preempt_nominated_quota when the node table has nominated records, or without the side table of
+ * spx_upload_preempt_nrt (which a later spx_upload_preempt_nodes or spx_upload_preempt_pods drops); SPX_ERR_ARG for an empty list or a
+ * row outside the batch or listed twice.  The column of a step is launched by nodes, one wave each, so spx_preempt_nrt_dry_run's
+ * limit of 65 535 x 64 rows does not apply here.  The uploaded tables and marks are never written: every dry run and every other loop
+ * gives after this loop what it gave before it, and a second run of this loop starts from the uploaded state. */
+int spx_preempt_nrt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask, int32_t preemption_mode);
+
 /* optional per-(pod,node) feasibility mask for normalizing score plugins: uint8 [n_pods][n_nodes],
  * non-zero = node passed Filter for that pod (upstream scores feasible nodes only).  NULL clears it. */
 int spx_upload_feasible_mask(spx_engine* e, const uint8_t* mask, int64_t n_pods, int64_t n_nodes);

@@ -1,7 +1,9 @@
 // cap_cell.h — CapacityScheduling's SelectVictimsOnNode (pkg/capacityscheduling/capacity_scheduling.go:486-677) for one (preemptor,
 // node) cell per lane, the borrowed marks of a node's pods, and the row record both read: the one copy of the walk that
 // kernels_preempt.hip (k_preempt_cells and k_preempt_marks, on the uploaded state) and kernels_preempt_seq.hip (the sequential loop,
-// on the state its earlier rows left) run.
+// on the state its earlier rows left) run, and with nrt_refit.h's Filter in the refit kernels_preempt_nrt.hip and
+// kernels_preempt_nrt_seq.hip; and the end of a loop's step (cap_seq_apply_tail), which k_cnrt_seq_apply calls and k_cap_seq_apply keeps
+// written out, so that its machine code stays what it was.
 //
 // The node's pod list arrives through wave-uniform (scalar) loads and every lane walks the same trip count under its own predicate.
 // Per lane, in registers: the node's Requested, the preemptor quota's Used, the aggregate Used (8 int64 each) with their scalar-key
@@ -90,7 +92,8 @@ __device__ __forceinline__ void cap_marks(const PreemptArgs& a, const CapSeqArgs
 // kOverlay off: the uploaded state; q (NULL) is not read.
 // kOverlay on: the sequential loop's state (kernels_preempt_seq.hip) from *q: Requested, every quota's Used, the aggregate and the marks
 // are the working copies, cleared nominations are not charged, the loop's own nominations are, and the positions in `gone` are
-// skipped in every pass.
+// skipped in every pass.  A skipped position never reaches move_pod, so the refit policy never hears of a pod that left at an earlier
+// step.
 template <bool kOverlay, class Refit = FitOnly>
 __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapSeqArgs* q, int64_t node, int64_t rr, bool want, int16_t (*budget)[64], int lane, uint32_t* vict,
                                                 Refit rf = Refit{}) {
@@ -262,6 +265,42 @@ __device__ __forceinline__ PreemptCell cap_cell(const PreemptArgs& a, const CapS
     for (int i = 0; i < kWords; ++i) vict[i] = 0;
   }
   return out;
+}
+
+// The end of step i in the apply kernel of a CapacityScheduling loop (k_cnrt_seq_apply; k_cap_seq_apply ends with the same lines, written
+// out there: DESIGN.md 3.9j says why), called by all lanes of its one wave once the picked cell (i, n) is computed again: the victim set
+// is stored (32 B per row); then T4, T1 with the movement of the victims' quotas' Used and of the aggregate, T3 and T2.  n: the pick,
+// -1 = no candidate; flags, prio: row i's kFlags and kPrio fields; vict: all zero without a pick.  Whatever the refit kept a victim
+// for, it leaves its quota here like any other.
+__device__ __forceinline__ void cap_seq_apply_tail(const CapSeqArgs& q, int32_t n, int64_t i, uint32_t flags, int prio, const uint32_t* vict, int lane) {
+  const PreemptArgs& a = q.t;
+  const SeqOverlay o = q.overlay();
+  const int64_t R = a.row_stride;
+  seq_store_victims(o, i, vict, lane);
+  if (flags & kHold) return;  // nothing moves
+  // T4: the nominations row i came with are dropped wherever they sit
+  for (int32_t t = o.row_nom_ptr[i] + lane; t < o.row_nom_ptr[i + 1]; t += 64) o.nom_cleared[o.row_nom[t]] = 1;
+  if (n < 0) return;
+  const PreemptNode& nd = a.nodes[n];
+  const PreemptPod* pods = a.pods + nd.pod_begin;
+  // T1: the victims leave the node, and deletePodIfPresent takes those that are in their quota's set out of its Used and of the
+  // aggregate.  Lane s moves slot s, lane 0 the key masks: one wave, no two lanes on one word.
+  seq_evict(o, n, vict, lane);
+  if (lane < S) {
+    int64_t sub = 0;
+    for (int k = 0; k < nd.pod_end - nd.pod_begin; ++k) {
+      if (!get_bit(vict, k)) continue;
+      sub += pods[k].fit[lane];
+      const uint8_t m = q.marks[nd.pod_begin + k];
+      if ((m & (kMarkQuota | kMarkInSet)) != (kMarkQuota | kMarkInSet)) continue;
+      const int64_t dq = pods[k].qreq[lane];
+      q.used[static_cast<int64_t>(pods[k].ns) * S + lane] = wsub(q.used[static_cast<int64_t>(pods[k].ns) * S + lane], dq);
+      q.agg_used[lane] = wsub(q.agg_used[lane], dq);
+      if (lane == 0) q.used_present[pods[k].ns] |= pods[k].qreq_present, *q.agg_used_present |= pods[k].qreq_present;  // SetScalar
+    }
+    o.requested[static_cast<int64_t>(n) * S + lane] -= sub;
+  }
+  seq_nominate(o, nd, a.noms, n, i, prio, lane, a.row_rec + kPrio * R);  // T3, T2
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 //   k_cap_seq_cells   a wave per node, four nodes per workgroup: cell (i, node), every lane the same cell, lane 0 stores
 //   k_ptol_seq_pick   (kernels_ptol_seq.hip) one workgroup of 1024 threads over the N cells of column i
 //   k_cap_seq_apply   one wave: cell (i, picked node) again for its victim set, which is stored (32 B per row); then T4, T1, T3, T2
+//                     (what cap_cell.h's cap_seq_apply_tail says for the loop with NRT's Filter, kernels_preempt_nrt_seq.hip)
 //
 // The walk, the marks and the row record are cap_cell.h's, shared with kernels_preempt.hip.  Integer vector code only; every sum is
 // bounded by the upload's 2^62 check (the loop only ever moves requests between sums), and the nominated sums wrap as int64, so any
@@ -159,6 +160,8 @@ __global__ __launch_bounds__(64) void k_cap_seq_apply(CapSeqArgs q) {
   // every lane computes the picked cell of row i
   uint32_t vict[kWords] = {};
   if (n >= 0) (void)cap_cell<true>(a, &q, n, i, true, s_budget, lane, vict);
+  // The end of the step, written out here although cap_cell.h's cap_seq_apply_tail says the same: with the call in its place this kernel's
+  // machine code moves (107 SGPR spills for 104), and the loop then timed outside the parent's own spread in one run of two
   seq_store_victims(o, i, vict, lane);
   if (flags & kHold) return;  // nothing moves
   // T4: the nominations row i came with are dropped wherever they sit
@@ -197,10 +200,16 @@ void launch_cap_seq_init(const CapSeqArgs& q, hipStream_t s) {
   hipLaunchKernelGGL(k_cap_seq_marks, dim3(blocks_for(q.t.n_nodes, kBlock)), dim3(kBlock), 0, s, all);
 }
 
-// step q.step of the loop up to the pick: the row's record, the marks it reads, its column
-void launch_cap_seq_step(const CapSeqArgs& q, hipStream_t s) {
+// the start of step q.step, which depends on no Filter: the row's record and the marks it reads.  The loop with NRT's Filter
+// (kernels_preempt_nrt_seq.hip) starts its step with it too.
+void launch_cap_seq_row(const CapSeqArgs& q, hipStream_t s) {
   hipLaunchKernelGGL(k_cap_seq_row, dim3(1), dim3(kBlock), 0, s, q);
   hipLaunchKernelGGL(k_cap_seq_marks, dim3(blocks_for(q.t.n_nodes, kBlock)), dim3(kBlock), 0, s, q);
+}
+
+// step q.step of the loop up to the pick: the row's record, the marks it reads, its column
+void launch_cap_seq_step(const CapSeqArgs& q, hipStream_t s) {
+  launch_cap_seq_row(q, s);
   hipLaunchKernelGGL(k_cap_seq_cells, dim3(blocks_for(q.t.n_nodes, kWaves)), dim3(kBlock), 0, s, q);
 }
 

@@ -285,6 +285,9 @@ struct spx_engine {
   // describes the node and pod tables in place (an upload of either clears it); pnrt_mode: the last run's preemption mode, for the
   // victims fetch.  The toleration loop with that Filter (spx_preempt_toleration_nrt_sequential) is the seventh mode: pre_toleration,
   // pre_nrt and pre_sequential; the fetches branch on pre_sequential first, so its victims are the stored sets of the third mode.
+  // CapacityScheduling's loop with it (spx_preempt_nrt_sequential) is the eighth: pre_nrt and pre_sequential without pre_toleration, its
+  // victims the stored sets likewise.  Every run's staging (preempt_stage) clears pre_nrt, so a loop without the Filter after one
+  // with it is not taken for an NRT result.
   DevBuf d_pnrt_nodes, d_pnrt_contrib, d_pnrt_rel_ptr, d_pnrt_rel, d_pnrt_pods, d_pnrt_rec;
   bool pnrt_table = false, pre_nrt = false;
   int32_t pnrt_n_res = 0, pnrt_mode = 0, pnrt_max_zones = 0;

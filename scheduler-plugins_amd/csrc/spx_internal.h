@@ -960,8 +960,20 @@ struct CapSeqArgs {
   }
 };
 void launch_cap_seq_init(const CapSeqArgs& q, hipStream_t s);
+void launch_cap_seq_row(const CapSeqArgs& q, hipStream_t s);   // row record, marks: the part of a step no Filter touches
 void launch_cap_seq_step(const CapSeqArgs& q, hipStream_t s);  // row record, marks, column cells; then launch_ptol_seq_pick and launch_cap_seq_apply
 void launch_cap_seq_apply(const CapSeqArgs& q, hipStream_t s);
+
+// The same loop with NRT's single-NUMA Filter in the refit (kernels_preempt_nrt_seq.hip): the loop's arguments, flat and
+// at their offsets, with the Filter's beside them.  The zone table, the placement info and the releases are read as uploaded at every
+// step (T5), so the overlay is the loop's and nothing of NRT's is carried.  The overlay's init, the row record with the marks and the
+// pick are launch_cap_seq_init, launch_cap_seq_row and launch_ptol_seq_pick; the NRT row record is launch_cnrt_rows' on {q.t, n}, once.
+struct CnrtSeqArgs {
+  CapSeqArgs q;
+  NrtRefitArgs n;
+};
+void launch_cnrt_seq_cells(const CnrtSeqArgs& p, hipStream_t s);  // the column of row q.step, after launch_cap_seq_row
+void launch_cnrt_seq_apply(const CnrtSeqArgs& p, hipStream_t s);  // after launch_ptol_seq_pick, as launch_cap_seq_apply
 
 // ---------------------------------------------------------------- sequential commit with Filter plugins (kernels_commit.hip)
 // Bookkeeping of ONE bound pod (row `pod`, node = best_node[pod]) on the engine's device tables: what the reference's Reserve /

@@ -1,8 +1,9 @@
 // spx_preempt.hip — the preemption dry runs' entry points (include/spx.h: spx_upload_preempt_*, spx_preempt_dry_run,
 // spx_preempt_sequential, spx_preempt_toleration_dry_run, spx_preempt_toleration_sequential, spx_upload_preempt_nrt,
-// spx_preempt_toleration_nrt_dry_run, spx_preempt_nrt_dry_run, spx_preempt_toleration_nrt_sequential, spx_fetch_preempt_*): table checks
-// and uploads, the launches of kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip, kernels_ptol_seq.hip, kernels_ptol_nrt.hip,
-// kernels_preempt_nrt.hip and kernels_ptol_nrt_seq.hip, and the fetches, which serve whichever of the seven ran last.
+// spx_preempt_toleration_nrt_dry_run, spx_preempt_nrt_dry_run, spx_preempt_toleration_nrt_sequential, spx_preempt_nrt_sequential,
+// spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip,
+// kernels_ptol_seq.hip, kernels_ptol_nrt.hip, kernels_preempt_nrt.hip, kernels_ptol_nrt_seq.hip and kernels_preempt_nrt_seq.hip, and the
+// fetches, which serve whichever of the eight ran last.
 // State: spx_engine.h.
 #include "spx_engine.h"
 
@@ -292,6 +293,52 @@ int seq_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_
   return SPX_OK;
 }
 
+// What CapacityScheduling's two loops check before anything moves: state first, then the arguments.
+// nrt: the loop reads spx_upload_preempt_nrt's side table too.
+int cap_seq_check(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, bool nrt) {
+  if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, who + ": the quota tables (spx_upload_quota with min) are not uploaded");
+  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
+  if (e->h_pre_nom_ptr.back() > 0 && !e->pre_nomq) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nominated_quota since the last spx_upload_preempt_nodes");
+  if (nrt && !e->pnrt_table) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nrt since the last spx_upload_preempt_nodes / spx_upload_preempt_pods");
+  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, who + ": empty row list");
+  return rows_in_batch(e, who, rows, n_rows);
+}
+
+// Their staging: seq_stage around preempt_stage with the working marks, Used and aggregate among the carve-outs (SeqStaged::extra, in
+// that order), `eligible` and the caller's `more` among the staged buffers.  The run is a CapacityScheduling loop from here on.
+int cap_seq_stage(spx_engine* e, const std::string& who, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask, std::vector<Staged> mine,
+                  SeqStaged* st) {
+  const int64_t A = e->h_pre_pod_ptr.back(), NS = e->q_n_namespaces;
+  auto extra = [&](int32_t) { return std::vector<size_t>{static_cast<size_t>(A), static_cast<size_t>(NS) * S * 8, static_cast<size_t>(NS), S * 8, 4}; };
+  auto stage = [&](std::vector<Staged> more) {
+    more.insert(more.end(), mine.begin(), mine.end());
+    if (eligible) more.push_back({&e->d_pre_elig, static_cast<size_t>(n_rows), eligible});
+    return preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, more);
+  };
+  if (int rc = seq_stage(e, who, rows, n_rows, extra, stage, st)) return rc;
+  e->pre_toleration = false;
+  return SPX_OK;
+}
+
+// Their arguments at step 0, once cap_seq_stage has carved the overlay.
+spx::CapSeqArgs cap_seq_args(spx_engine* e, const SeqStaged& st, const uint8_t* eligible) {
+  const size_t M = static_cast<size_t>(e->h_pre_nom_ptr.back());
+  spx::CapSeqArgs q{};
+  q.t = preempt_args(e);
+  q.overlay(st.o);
+  q.eligible = eligible ? static_cast<const uint8_t*>(e->d_pre_elig.p) : nullptr;
+  const char* const side = static_cast<const char*>(e->d_pre_nomq.p);  // (never read when M == 0)
+  q.nom_qreq = reinterpret_cast<const int64_t*>(side);
+  q.nom_ns = reinterpret_cast<const int32_t*>(side + M * S * 8);
+  q.nom_qreq_present = reinterpret_cast<const uint8_t*>(side + M * (S * 8 + 4));
+  q.marks = reinterpret_cast<uint8_t*>(st.extra[0]);
+  q.used = reinterpret_cast<int64_t*>(st.extra[1]);
+  q.used_present = reinterpret_cast<uint8_t*>(st.extra[2]);
+  q.agg_used = reinterpret_cast<int64_t*>(st.extra[3]);
+  q.agg_used_present = reinterpret_cast<uint32_t*>(st.extra[4]);
+  return q;
+}
+
 // The end of every entry point: what `launches` enqueues between the two events, and the run as the one the fetches answer for.
 // Everything is enqueued here; each launch reads what the one before it left on the device, and nothing is read back in between.
 template <class Launches>
@@ -435,34 +482,11 @@ int spx_upload_preempt_nominated_quota(spx_engine* e, const spx_preempt_nominate
 int spx_preempt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask) {
   if (!e) return SPX_ERR_ARG;
   const std::string who = "sequential capacity preemption";
-  if (!e->quota || !e->q_has_min) return fail(e, SPX_ERR_STATE, who + ": the quota tables (spx_upload_quota with min) are not uploaded");
-  if (!e->pre_nodes || !e->pre_pods) return fail(e, SPX_ERR_STATE, who + ": spx_upload_preempt_nodes / spx_upload_preempt_pods not called");
-  const int64_t M = e->h_pre_nom_ptr.back(), A = e->h_pre_pod_ptr.back(), NS = e->q_n_namespaces;
-  if (M > 0 && !e->pre_nomq) return fail(e, SPX_ERR_STATE, who + ": no spx_upload_preempt_nominated_quota since the last spx_upload_preempt_nodes");
-  if (!rows || n_rows <= 0) return fail(e, SPX_ERR_ARG, who + ": empty row list");
-  if (int rc = rows_in_batch(e, who, rows, n_rows)) return rc;
+  if (int rc = cap_seq_check(e, who, rows, n_rows, false)) return rc;
   SeqStaged st;
-  auto extra = [&](int32_t) { return std::vector<size_t>{static_cast<size_t>(A), static_cast<size_t>(NS) * S * 8, static_cast<size_t>(NS), S * 8, 4}; };
-  auto stage = [&](std::vector<Staged> more) {
-    if (eligible) more.push_back({&e->d_pre_elig, static_cast<size_t>(n_rows), eligible});
-    return preempt_stage(e, who, rows, n_rows, node_mask, e->d_pre_rec, spx::kPreemptRowFields, more);
-  };
-  if (int rc = seq_stage(e, who, rows, n_rows, extra, stage, &st)) return rc;
-  e->pre_toleration = false;
+  if (int rc = cap_seq_stage(e, who, rows, n_rows, eligible, node_mask, {}, &st)) return rc;
   spx::PickArgs pick = pick_args(e);
-  spx::CapSeqArgs q{};
-  q.t = preempt_args(e);
-  q.overlay(st.o);
-  q.eligible = eligible ? static_cast<const uint8_t*>(e->d_pre_elig.p) : nullptr;
-  const char* const side = static_cast<const char*>(e->d_pre_nomq.p);  // (never read when M == 0)
-  q.nom_qreq = reinterpret_cast<const int64_t*>(side);
-  q.nom_ns = reinterpret_cast<const int32_t*>(side + static_cast<size_t>(M) * S * 8);
-  q.nom_qreq_present = reinterpret_cast<const uint8_t*>(side + static_cast<size_t>(M) * (S * 8 + 4));
-  q.marks = reinterpret_cast<uint8_t*>(st.extra[0]);
-  q.used = reinterpret_cast<int64_t*>(st.extra[1]);
-  q.used_present = reinterpret_cast<uint8_t*>(st.extra[2]);
-  q.agg_used = reinterpret_cast<int64_t*>(st.extra[3]);
-  q.agg_used_present = reinterpret_cast<uint32_t*>(st.extra[4]);
+  spx::CapSeqArgs q = cap_seq_args(e, st, eligible);
   return preempt_launch(e, [&] {
     spx::launch_cap_seq_init(q, e->stream);
     for (; q.step < n_rows; ++q.step) {
@@ -470,6 +494,29 @@ int spx_preempt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, c
       spx::launch_cap_seq_step(q, e->stream);
       spx::launch_ptol_seq_pick(pick, e->stream);
       spx::launch_cap_seq_apply(q, e->stream);
+    }
+  });
+}
+
+int spx_preempt_nrt_sequential(spx_engine* e, const int64_t* rows, int64_t n_rows, const uint8_t* eligible, const uint8_t* node_mask, int32_t preemption_mode) {
+  if (!e) return SPX_ERR_ARG;
+  const std::string who = "sequential capacity preemption with NRT";
+  if (int rc = cap_seq_check(e, who, rows, n_rows, true)) return rc;
+  const size_t rec = static_cast<size_t>(spx::round_up(n_rows, 64)) * spx::kPnrtRowFields * 8;
+  SeqStaged st;
+  if (int rc = cap_seq_stage(e, who, rows, n_rows, eligible, node_mask, {{&e->d_pnrt_rec, rec, nullptr}}, &st)) return rc;  // the memory pre-check counts the NRT row record too
+  e->pre_nrt = true, e->pnrt_mode = preemption_mode != 0;
+  spx::PickArgs pick = pick_args(e);
+  spx::CnrtSeqArgs p{cap_seq_args(e, st, eligible), nrt_refit_args(e)};
+  return preempt_launch(e, [&] {
+    spx::launch_cap_seq_init(p.q, e->stream);
+    spx::launch_cnrt_rows(spx::CnrtArgs{p.q.t, p.n}, e->stream);  // a function of the preemptors' uploaded columns alone: once, for every row
+    for (; p.q.step < n_rows; ++p.q.step) {
+      pick.step = p.q.step;
+      spx::launch_cap_seq_row(p.q, e->stream);
+      spx::launch_cnrt_seq_cells(p, e->stream);
+      spx::launch_ptol_seq_pick(pick, e->stream);
+      spx::launch_cnrt_seq_apply(p, e->stream);
     }
   });
 }

@@ -1192,6 +1192,16 @@ class Engine:
         self._ck(self._lib.spx_preempt_nrt_dry_run(self._h, rows_p, n, mask_p, 1 if preemption_mode else 0))
         self._preempt_rows = n
 
+    def preempt_nrt_sequential(self, rows, eligible=None, node_mask=None, preemption_mode: bool = True) -> None:
+        """preempt_sequential with NodeResourceTopologyMatch's Filter in the refit (spx_preempt_nrt_sequential), on the quota and
+        preemption tables, the nominated-quota side table and upload_preempt_nrt's side table, which stays as uploaded at every step: a
+        pod evicted at an earlier step is never on the Filter's stack again, and a victim the Filter alone kept leaves its quota's Used
+        like any other.  preemption_mode False: the ordinary Filter at every step.  The preempt_* fetches answer as after
+        preempt_sequential."""
+        n, rows_p, elig_p, mask_p = self._preempt_row_list(rows, node_mask, eligible)
+        self._ck(self._lib.spx_preempt_nrt_sequential(self._h, rows_p, n, elig_p, mask_p, 1 if preemption_mode else 0))
+        self._preempt_rows = n
+
     def status(self, plugin: int, pod_row: int) -> np.ndarray:
         out = np.empty(self.n_nodes, dtype=np.uint8)
         self._ck(self._lib.spx_fetch_status(self._h, plugin, pod_row, out.ctypes.data_as(C.POINTER(C.c_uint8))))

@@ -1,0 +1,315 @@
+"""GPU parity (through the C ABI) for CapacityScheduling's sequential preemption loop with NodeResourceTopologyMatch's single-NUMA
+Filter in the refit (spx_preempt_nrt_sequential) with the literal loop of tests/preempt_nrt_seq_oracle.py, at tolerance
+0 and through ptol_seq_cases.assert_sequential's fields: every row's pick, candidate and tie counts, every cell's status, counts and
+five keys as the row saw them at its own step, and the stored victim list of every picked cell.  Models: the seven shapes of the NRT dry
+run's suite (257 x 3 has more rows than a wave, "lists" the 0 / 1 / 31 / 32 / 33 / 256-pod lists at the word edges of the 256-bit sets,
+64 x 64 eight zones x eight slots x eight containers, the largest dynamic LDS) and the five retuned models of the capacity loop's suite,
+decorated, where the quota coupling is live (200 x 257 crosses a 256-row block of the cell buffer).  The oracle's answers are computed
+once per case and shared (preempt_nrt_seq_cases.expected)."""
+import numpy as np
+import pytest
+
+import preempt_nrt_cases as CC
+import preempt_nrt_oracle as CO
+import preempt_nrt_seq_cases as NSC
+import preempt_nrt_seq_oracle as NSO
+import preempt_seq_cases as SC
+import preempt_seq_oracle as SO
+import ptol_nrt_cases as NC
+import ptol_nrt_seq_cases as TNSC
+import ptol_nrt_seq_oracle as TNSO
+import scheduler_plugins_amd as spx
+from preempt_cases import model_position
+from scheduler_plugins_amd import SpxError
+from scheduler_plugins_amd.engine import Engine
+from test_gpu_preempt_nrt import both_plugins_model
+from test_oracle_ptol_nrt import without_nrt
+
+K = spx.header().consts
+ST = CO.ST
+STATE, ARG = K["SPX_ERR_STATE"], K["SPX_ERR_ARG"]
+
+
+def raises(code, fn):
+    with pytest.raises(SpxError) as err:
+        fn()
+    assert err.value.code == code, err.value
+    return err.value.msg
+
+
+def snapshot(e):
+    """everything the fetches give, the victims of every picked cell included"""
+    cells, keys, pick = e.preempt_cells(), e.preempt_keys(), e.preempt_pick()
+    victims = [e.preempt_victims(i, int(n)) for i, n in enumerate(pick["node"]) if n >= 0]
+    return [a.tolist() for a in (*cells, *keys, *pick.values())] + [(s, v.tolist()) for s, v in victims]
+
+
+def cell(e, f, t, i, n):
+    """(status, victims) of cell (i, n) as the fetches give them after a loop: the victims of the picked cell alone are stored"""
+    status = int(e.preempt_cells()[0][i, n])
+    if status != ST["CANDIDATE"] or int(e.preempt_pick()["node"][i]) != n:
+        return (status, [])
+    got, pos = e.preempt_victims(i, n)
+    return (got, [model_position(f, t, n, p) for p in pos])
+
+
+# ---------------------------------------------------------------------------------------------------------------- parity
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,name", [("shape", "1x1")] + NSC.MODELS)
+def test_parity_with_the_literal_loop(gpu_required, kind, name):
+    t = NSC.tables(kind, name)
+    want, counters = NSC.expected(kind, name)
+    if (kind, name) == ("retuned", "200x257"):
+        assert len(want) == 257 and counters["used_moved"] > 50 and counters["untouched_cells_differ"] > 1000
+    if (kind, name) == ("shape", "lists"):
+        assert {len(n["pods"]) for n in NSC.model(kind, name)["nodes"]} >= {0, 1, 31, 32, 33, 256}
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, want)
+        assert e.last_eval_ms() > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,name", [("shape", "64x64"), ("retuned", "63x65")])
+def test_mode_off_is_the_ordinary_filter_at_every_step(gpu_required, kind, name):
+    t = NSC.tables(kind, name)
+    on, off = NSC.expected(kind, name)[0], NSC.expected(kind, name, mode=False)[0]
+    assert NSC.differing_rows(on, off) > 0
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        NSC.run(e, t, mode=False)
+        NSC.assert_sequential(e, f, t, off)
+        NSC.run(e, t, mode=True)
+        NSC.assert_sequential(e, f, t, on)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the constructed models
+@pytest.mark.gpu
+def test_the_cross_node_model(gpu_required):
+    """the Filter decides who leaves node A, that moves quota 0's Used, and that decides the cell on node B, which no step touched; the
+    fit-only loop, the loop with mode off and the frozen NRT batch give their other answers on the same upload"""
+    m, mask = NSC.cross_node_model()
+    want = NSC.CROSS_NODE
+    t = CC.build_tables(m)
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        cells = lambda: (cell(e, f, t, 0, NSC.A), cell(e, f, t, 1, NSC.B))
+        loop = NSO.run(m, m["pending"], mask)
+        assert (NSC.end(loop[0], NSC.A), NSC.end(loop[1], NSC.B)) == want["loop"]
+        NSC.run(e, t, mask=mask)
+        NSC.assert_sequential(e, f, t, loop)
+        assert cells() == want["loop"]
+        SC.run(e, t, mask=mask)  # spx_preempt_sequential
+        SC.assert_sequential(e, f, t, SO.run(m, m["pending"], mask))
+        assert cells() == want["fit_only"]
+        NSC.run(e, t, mask=mask, mode=False)
+        NSC.assert_sequential(e, f, t, NSO.run(m, m["pending"], mask, mode=False))
+        assert cells() == want["mode_off"]
+        CC.run(e, t, mask=mask)  # spx_preempt_nrt_dry_run
+        CC.assert_dry_run(e, f, t, CO.dry_run(m, m["pending"], mask))
+        frozen = tuple((got[0], [model_position(f, t, n, p) for p in got[1]]) for n, got in ((NSC.A, e.preempt_victims(0, NSC.A)), (NSC.B, e.preempt_victims(1, NSC.B))))
+        assert frozen == want["frozen"]
+
+
+@pytest.mark.gpu
+def test_the_second_visit_pins_t5(gpu_required):
+    """a pod evicted at an earlier step releases nothing at a later one; the fit-only loop, the frozen NRT batch and the loop with mode
+    off give their other answers on the same upload"""
+    m = NSC.second_visit_model()
+    want = NSC.SECOND_VISIT
+    t = CC.build_tables(m)
+
+    def end(i):  # (pick, status, victims) of row i as the fetches give them
+        n = int(e.preempt_pick()["node"][i])
+        if n < 0:
+            return (n, int(e.preempt_cells()[0][i, 0]), [])
+        status, pos = e.preempt_victims(i, n)
+        return (n, status, [model_position(f, t, n, p) for p in pos])
+
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        loop = NSO.run(m, m["pending"])
+        assert [NSC.row_end(r) for r in loop] == want["loop"]
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, loop)
+        assert [end(0), end(1)] == want["loop"]
+        SC.run(e, t)  # spx_preempt_sequential
+        SC.assert_sequential(e, f, t, SO.run(m, m["pending"]))
+        assert end(1) == want["fit_only_p1"]
+        CC.run(e, t)  # spx_preempt_nrt_dry_run
+        CC.assert_dry_run(e, f, t, CO.dry_run(m, m["pending"]))
+        assert end(1) == want["frozen_p1"]
+        NSC.run(e, t, mode=False)
+        NSC.assert_sequential(e, f, t, NSO.run(m, m["pending"], mode=False))
+        assert [end(0), end(1)] == want["mode_off"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- row handling
+@pytest.mark.gpu
+def test_rows_out_of_order_with_a_node_mask(gpu_required):
+    kind, name = "retuned", "65x63"
+    rows = (40, 3, 62, 0, 17, 18, 5, 61, 33, 2, 50, 9)
+    mask = CC.node_mask(len(rows), SC.RETUNED[name]["n_nodes"], 11)
+    assert (mask == 0).any()
+    t = NSC.tables(kind, name)
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        NSC.run(e, t, rows)
+        NSC.assert_sequential(e, f, t, NSC.expected(kind, name, rows=rows)[0])
+        NSC.run(e, t, rows, mask)
+        want, counters = NSC.expected(kind, name, rows=rows, mask_seed=11)
+        assert counters["applied"] == len(rows) and sum(r["pick"][0] >= 0 for r in want) > 1
+        NSC.assert_sequential(e, f, t, want)
+
+
+@pytest.mark.gpu
+def test_rows_that_are_not_eligible_are_evaluated_and_move_nothing(gpu_required):
+    kind, name = "retuned", "64x64"
+    t = NSC.tables(kind, name)
+    eligible = NSC.eligible_column(SC.RETUNED[name]["n_pending"], 21)
+    assert 0 < eligible.sum() < len(eligible)
+    want, counters = NSC.expected(kind, name, eligible_seed=21)
+    assert counters["applied"] == eligible.sum() < NSC.expected(kind, name)[1]["applied"]
+    assert [r["pick"] for r in want] != [r["pick"] for r in NSC.expected(kind, name)[0]]
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        NSC.run(e, t, eligible=eligible)
+        NSC.assert_sequential(e, f, t, want)
+
+
+# ---------------------------------------------------------------------------------------------------------------- next to the runs the tree had
+@pytest.mark.gpu
+def test_every_row_alone_is_the_nrt_dry_run_of_that_row(gpu_required):
+    """a one-row loop is spx_preempt_nrt_dry_run of that row, bit for bit"""
+    kw = CC.SHAPES["63x65"]
+    t = CC.tables(**kw)
+    with Engine(0) as e:
+        CC.load(e, t)
+        picked = 0
+        for r in range(kw["n_pending"]):
+            e.preempt_nrt_dry_run([r])
+            batch = snapshot(e)
+            e.preempt_nrt_sequential([r])
+            assert snapshot(e) == batch, r
+            picked += batch[6][0] >= 0
+        assert picked > 10
+
+
+@pytest.mark.gpu
+def test_without_any_nrt_it_is_the_fit_only_loop_byte_for_byte(gpu_required):
+    m = without_nrt(NSC.model("retuned", "63x65"))
+    t = CC.build_tables(m)
+    want, counters = SO.run(m, m["pending"]), {}
+    SO.run(m, m["pending"], counters=counters)
+    assert counters["used_moved"] > 0
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        assert not (f["nrt"]["node_flags"] & K["SPX_NRT_F_HAS_NRT"]).any()
+        SC.run(e, t)
+        old = snapshot(e)
+        SC.assert_sequential(e, f, t, want)
+        for mode in (True, False):
+            NSC.run(e, t, mode=mode)
+            assert snapshot(e) == old
+
+
+# ---------------------------------------------------------------------------------------------------------------- state
+@pytest.mark.gpu
+def test_the_uploaded_tables_and_marks_are_never_written(gpu_required):
+    """NRT dry run -> loop -> NRT dry run, and fit-only capacity loop -> this loop -> fit-only capacity loop, with identical results;
+    a second run of the loop equals the first"""
+    kind, name = "retuned", "65x63"
+    t = NSC.tables(kind, name)
+    want = NSC.expected(kind, name)[0]
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        CC.run(e, t)
+        batch = snapshot(e)
+        CC.assert_dry_run(e, f, t, NSC.frozen(kind, name))
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, want)
+        mine = snapshot(e)
+        assert mine != batch
+        CC.run(e, t)
+        assert snapshot(e) == batch
+        SC.run(e, t)
+        plain = snapshot(e)
+        SC.assert_sequential(e, f, t, NSC.fit_only(kind, name))  # a fit-only loop is not taken for an NRT result
+        NSC.run(e, t)  # the loop starts from the uploaded state every time
+        assert snapshot(e) == mine != plain
+        SC.run(e, t)
+        assert snapshot(e) == plain
+        SC.assert_sequential(e, f, t, NSC.fit_only(kind, name))
+
+
+@pytest.mark.gpu
+def test_the_toleration_loop_with_the_filter_is_the_same_before_and_after(gpu_required):
+    """PreemptionToleration's NRT loop -> this loop -> PreemptionToleration's NRT loop on one engine"""
+    m = both_plugins_model(**CC.SHAPES["63x65"])
+    assert m["quotas"]
+    hdr = spx.header()
+    t = spx.objects.build_preempt_toleration_tables(hdr, m)
+    t.update(NC.nrt_tables(hdr, m))
+    twant, want = TNSO.run(m, m["pending"]), NSO.run(m, m["pending"])
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        e.upload_preempt_toleration(e.flatten_preempt_toleration(t["classes"], t["pod_class"], t["pod_scheduled"], t["pod_scheduled_at_ns"], f["pod_src"]))
+        TNSC.run(e, t)
+        TNSC.assert_sequential(e, f, t, twant)
+        toleration = snapshot(e)
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, want)
+        assert snapshot(e) != toleration
+        TNSC.run(e, t)
+        assert snapshot(e) == toleration
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, want)
+
+
+@pytest.mark.gpu
+def test_refusals_and_staleness(gpu_required):
+    kind, name = "retuned", "63x65"
+    t = NSC.tables(kind, name)
+    want, _ = NSC.expected(kind, name)
+    n_pending = SC.RETUNED[name]["n_pending"]
+    fetches = lambda e: (e.preempt_cells, e.preempt_pick, e.preempt_keys, lambda: e.preempt_victims(0, 0))
+    with Engine(0) as e:
+        raises(STATE, lambda: NSC.run(e, t))  # no tables
+        f = e.load_preempt_objects(t)
+        side, M = f["nominated_quota"], len(f["nom_priority"])
+        assert M > 0
+        g = NC.flatten_nrt(e, t, f)
+        assert "spx_upload_preempt_nrt" in raises(STATE, lambda: NSC.run(e, t))  # no side table yet
+        e.upload_preempt_nrt(g)
+        raises(ARG, lambda: e.preempt_nrt_sequential([n_pending]))  # no row of the batch
+        assert "twice" in raises(ARG, lambda: e.preempt_nrt_sequential([3, 7, 3]))  # a row listed twice
+        raises(ARG, lambda: e.preempt_nrt_sequential([]))  # an empty list
+        fq = e.flatten_quota(t["pods"], t["rc"], t["quota"])
+        used = fq["ns"]["used"].reshape(-1, 8)
+        fit = fq["cols"]["pod_req"].reshape(-1, 8)
+        uploads = (lambda: e.upload_preempt_nrt(g), lambda: e.upload_preempt_nominated_quota(side), lambda: (e.upload_preempt_pods(fit), e.upload_preempt_nrt(g)),
+                   lambda: e.upload_quota(fq),
+                   lambda: e.update_quota_used([0], used[0], fq["ns"]["used_present"][:1], fq["cols"]["agg_used"], fq["cols"]["agg_used_present"]),
+                   lambda: e.upload_preempt_nodes(f))
+        for again in uploads:  # every upload marks the results stale
+            NSC.run(e, t)
+            e.preempt_pick()
+            again()
+            for fetch in fetches(e):
+                raises(STATE, fetch)
+        # the nodes were uploaded again: neither the nominated-quota side table nor the NRT side table is in place
+        assert "spx_upload_preempt_nominated_quota" in raises(STATE, lambda: NSC.run(e, t))
+        e.upload_preempt_nominated_quota(side)
+        assert "spx_upload_preempt_nrt" in raises(STATE, lambda: NSC.run(e, t))
+        SC.run(e, t)  # the fit-only loop needs no NRT side table
+        e.upload_preempt_nrt(g)
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, want)
+        # the victims of a cell other than the picked one: the state it saw is gone
+        i = next(i for i, r in enumerate(want) if r["pick"][0] >= 0 and r["pick"][1] > 1)
+        other = next(n for n, c in enumerate(want[i]["cells"]) if c["status"] == ST["CANDIDATE"] and n != want[i]["pick"][0])
+        raises(ARG, lambda: e.preempt_victims(i, other))
+        none = next(i for i, r in enumerate(want) if r["pick"][0] < 0)
+        raises(ARG, lambda: e.preempt_victims(none, 0))
+        assert e.preempt_victims(i, want[i]["pick"][0])[0] == ST["CANDIDATE"]  # the refusals left the results in place
