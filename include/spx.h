@@ -536,7 +536,13 @@ typedef struct spx_cosched_soa {
 
 /* NodeResourceTopologyMatch.  Resources are renumbered into dense "slots" 0..n_res-1 (the union of
  * what pods request and zones report; slot_res gives the canonical id).  Limits of this build:
- * NUMA zones per node <= 8 (flatten fails beyond them).  The dense tables below (spx_nrt_nodes_soa,
+ * NUMA zones per node <= SPX_NRT_TALL_MAX_ZONES = 64 with ids 0..63 (flatten fails beyond them).  The dense
+ * node table holds up to SPX_NRT_MAX_ZONES = 8 zones per node; a node with 9 to 64 zones is a "tall node" —
+ * n_zones = SPX_NRT_ZONES_TALL, zone quantities zero, flags those of a node without an NRT object — whose
+ * zones travel in spx_nrt_tall_nodes and are evaluated by kernels_nrt_tall.hip after the dense sweep.  With
+ * LeastNUMANodes a tall node may list up to SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA = 16 zones (65 535 subsets).
+ * Tall nodes are declined, by an error that says so, in spx_commit_sequential with NodeResourceTopologyMatch,
+ * in spx_update_nrt_nodes and in a wide snapshot.  The dense tables below (spx_nrt_nodes_soa,
  * spx_nrt_pods_soa) hold n_res <= SPX_NRT_MAX_RES = 8 slots, and spx_flatten_nrt_slots fails beyond 8.
  * A snapshot with up to SPX_NRT_MAX_RES_WIDE = 32 slots travels in the wide tables (spx_nrt_nodes_wide,
  * spx_nrt_pods_wide; spx_flatten_nrt_slots_wide), which spx_load_nrt takes by itself above 8 slots; a wide
@@ -549,6 +555,9 @@ typedef struct spx_cosched_soa {
 #define SPX_NRT_MAX_RES_WIDE 32
 #define SPX_NRT_WIDE_MAX_CTRS 64
 #define SPX_NRT_MAX_ZONES 8
+#define SPX_NRT_ZONES_TALL 255
+#define SPX_NRT_TALL_MAX_ZONES 64
+#define SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA 16
 #define SPX_NRT_MAX_CTRS 8
 #define SPX_NRT_CTRS_LONG 255
 #define SPX_NRT_F_HAS_NRT 1
@@ -615,6 +624,28 @@ typedef struct spx_nrt_long_pods {
   const uint8_t* ctr_present;
   const int64_t* ctr_req;
 } spx_nrt_long_pods;
+
+/* The tall nodes of an spx_nrt_nodes_soa table (n_zones = SPX_NRT_ZONES_TALL), host row-major: tall node k is node node_idx[k]
+ * (ascending); zone_stride = the most zones any of them lists, shorter nodes padded (zone_id / zone_present / zone_avail 0, zone_cost
+ * 255, min_avg_dist 255).  flags / max_numa / node_present / n_zones [n_tall] are the node's own (flags with SPX_NRT_F_HAS_NRT as the
+ * snapshot has it); zone_id / zone_present / min_avg_dist [n_tall*zone_stride], zone_avail [n_tall*zone_stride*n_res], zone_cost
+ * [n_tall*zone_stride*zone_stride] by list position (255 where Costs has no entry).  min_avg_dist[k*zone_stride + s-1] is
+ * minAvgDistanceInCombinations for subsets of size s, filled for nodes of at most SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA zones (255 above). */
+typedef struct spx_nrt_tall_nodes {
+  int64_t n_tall;
+  int32_t n_res;
+  int32_t zone_stride;
+  const int32_t* node_idx;
+  const uint8_t* flags;
+  const int32_t* max_numa;
+  const uint8_t* node_present;
+  const uint8_t* n_zones;
+  const uint8_t* zone_id;
+  const uint8_t* zone_present;
+  const int64_t* zone_avail;
+  const int32_t* zone_cost;
+  const float* min_avg_dist;
+} spx_nrt_tall_nodes;
 
 /* The wide NRT node table (up to SPX_NRT_MAX_RES_WIDE slots): the columns of spx_nrt_nodes_soa, host row-major, with uint32 presence
  * masks (bit s = slot s).  zone_id / zone_present / min_avg_dist [N*8], zone_avail [N*8*n_res], zone_cost [N*64], node_present [N]. */
@@ -938,6 +969,14 @@ int spx_upload_nrt_pods(spx_engine* e, const spx_nrt_pods_soa* t);
 int spx_upload_nrt_long_pods(spx_engine* e, const spx_nrt_long_pods* t);
 /* *n_out = long rows the last NodeResourceTopologyMatch sweep of spx_eval evaluated (those inside its row range; 0 = none / no sweep yet) */
 int spx_nrt_long_rows(const spx_engine* e, int64_t* n_out);
+/* the zones of the node table's tall nodes (after spx_upload_nrt_nodes; t->node_idx must list exactly the rows whose n_zones is
+ * SPX_NRT_ZONES_TALL, else SPX_ERR_ARG; a table with n_tall = 0 for a node table without tall nodes is accepted).  Until it arrives an
+ * NRT spx_eval / spx_decide / spx_fetch_raw fails with SPX_ERR_STATE.  A later spx_upload_nrt_nodes or slot upload drops it.  With
+ * tall nodes in place spx_commit_sequential with NodeResourceTopologyMatch and spx_update_nrt_nodes fail with SPX_ERR_STATE, and an
+ * evaluation with LeastNUMANodes fails with SPX_ERR_STATE when a tall node lists more than SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA zones. */
+int spx_upload_nrt_tall_nodes(spx_engine* e, const spx_nrt_tall_nodes* t);
+/* *n_out = tall nodes the last NodeResourceTopologyMatch sweep of spx_eval evaluated (0 = none / no sweep yet / an empty row range) */
+int spx_nrt_tall_count(const spx_engine* e, int64_t* n_out);
 /* The wide NRT tables (up to SPX_NRT_MAX_RES_WIDE slots), evaluated by kernels_nrt_wide.hip; order: slots, nodes, pods.  The wide
  * slot table replaces the dense NRT tables (and a later spx_upload_nrt_slots the wide ones): an engine holds one form at a time.
  * On a wide engine spx_commit_sequential with NodeResourceTopologyMatch and spx_update_nrt_nodes fail with SPX_ERR_STATE. */
@@ -1628,6 +1667,17 @@ int spx_flatten_nrt_pods(const spx_pod_objects* pods, const spx_resource_classes
  * pod_row / ctr_ptr must hold long_cap / long_cap + 1 entries and ctr_kind / ctr_present / ctr_req ctr_cap / ctr_cap / ctr_cap x n_res,
  * and a table larger than that is SPX_ERR_ARG (the counts are written first, so the caller can resize and call again). */
 int spx_flatten_nrt_long_pods(const spx_pod_objects* pods, const spx_resource_classes* rc, const spx_nrt_slots* slots, int64_t long_cap, int64_t ctr_cap, int64_t* n_long_out, int64_t* n_ctr_out, int32_t* pod_row, int32_t* ctr_ptr, uint8_t* ctr_kind, uint8_t* ctr_present, int64_t* ctr_req);
+/* the zones of the nodes with 9 to SPX_NRT_TALL_MAX_ZONES zones (the tall nodes spx_flatten_nrt_nodes marks), as spx_nrt_tall_nodes.
+ * *n_tall_out / *zone_stride_out receive the counts; with every output array NULL the call only counts.  Otherwise tall_cap nodes and
+ * stride_cap zones per node must hold them (SPX_ERR_ARG if not); the arrays are laid out by the counts themselves (zone_stride =
+ * *zone_stride_out, the most zones any tall node lists), not by the caps.  Assumed pods are subtracted and duplicate ids' costs
+ * resolved as in spx_flatten_nrt_nodes.  SPX_ERR_ARG for a node with a 65th zone or with id 64 on a counted zone, and for a slot table
+ * of more than SPX_NRT_MAX_RES slots (tall nodes in a wide snapshot stay refused). */
+int spx_flatten_nrt_tall_nodes(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, int64_t tall_cap, int32_t stride_cap, int64_t* n_tall_out, int32_t* zone_stride_out, int32_t* node_idx, uint8_t* flags, int32_t* max_numa, uint8_t* node_present, uint8_t* n_zones, uint8_t* zone_id, uint8_t* zone_present, int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist);
+/* SPX_OK and the first node (or -1) with more than SPX_NRT_MAX_ZONES zones of type Node with ids 0..64, and its zone count; SPX_ERR_ARG
+ * and the first node beyond this build's limits (a 65th zone, or id 64 on a tall node) when there is one: what a loader names when
+ * it refuses a snapshot.  Host only. */
+int spx_nrt_first_tall_node(const spx_nrt_objects* nrt, int64_t* node_out, int32_t* n_zones_out);
 /* The wide forms (up to SPX_NRT_MAX_RES_WIDE slots).  spx_flatten_nrt_slots_wide: the numbering of spx_flatten_nrt_slots (ascending
  * resource id) for up to cap <= SPX_NRT_MAX_RES_WIDE slots; *n_res_out receives the count even when it exceeds cap (SPX_ERR_ARG). */
 int spx_flatten_nrt_slots_wide(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_nrt_params* p, int32_t cap, int32_t* n_res_out, int32_t* slot_res, uint8_t* slot_flags, int64_t* slot_weight);

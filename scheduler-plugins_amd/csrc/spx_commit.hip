@@ -186,6 +186,9 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
   if (N && e->nrt_wide)
     return fail(e, SPX_ERR_STATE, "NRT: spx_commit_sequential does not take a wide snapshot (more than 8 resource slots, or SPX_OPT_NRT_WIDE)");
   if (N && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
+  if (N && !e->h_nrt_tall_nodes.empty())
+    return fail(e, SPX_ERR_STATE, "NRT: spx_commit_sequential does not take nodes with more than 8 NUMA zones (node " + std::to_string(e->h_nrt_tall_nodes[0]) +
+                                      " is the first): the loop's zone updates cover the dense node table only");
   if (N && !e->nrt_long_ok)
     return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
   if (W && !(e->net_nodes && e->net_topo && e->net_pods && e->net_commit))

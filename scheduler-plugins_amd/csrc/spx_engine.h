@@ -175,6 +175,16 @@ struct spx_engine {
   bool nrt_long_ok = true;               // the long table describes those rows (trivially true without any)
   int64_t nrt_long_last = 0;             // spx_nrt_long_rows
   DevBuf d_nrtl_row, d_nrtl_ptr, d_nrtl_kind, d_nrtl_pres, d_nrtl_req, d_nrtl_map;
+  // tall nodes (more than SPX_NRT_MAX_ZONES zones): their zones in a side table (spx_upload_nrt_tall_nodes), evaluated by
+  // kernels_nrt_tall.hip after the dense sweep and the long rows
+  std::vector<int32_t> h_nrt_tall_nodes;  // nodes of the uploaded table whose n_zones is SPX_NRT_ZONES_TALL, ascending
+  bool nrt_tall_ok = true;                // the side table describes those nodes (trivially true without any)
+  int64_t nrt_tall_last = 0;              // spx_nrt_tall_count
+  int32_t nrt_tall_stride = 0;            // the side table's zone_stride
+  int32_t nrt_tall_ln_node = -1, nrt_tall_ln_zones = 0;  // the first tall node with more zones than LeastNUMANodes takes, its count
+  DevBuf d_nrtt_idx, d_nrtt_flags, d_nrtt_max, d_nrtt_np, d_nrtt_nz, d_nrtt_zid, d_nrtt_zp, d_nrtt_avail, d_nrtt_cost, d_nrtt_minavg;
+  DevBuf d_nrtt_work, d_nrtt_cmask, d_nrtt_cstart;  // the waves' working copies; LeastNUMANodes' subset table (built when first needed)
+  bool nrt_tall_combos = false;
   // the wide NRT tables (more than SPX_NRT_MAX_RES slots, or SPX_OPT_NRT_WIDE; kernels_nrt_wide.hip).  nrt_wide: they, not the dense
   // tables above, are the engine's NRT state (spx_upload_nrt_slots_wide sets it, spx_upload_nrt_slots clears it)
   bool nrt_wide = false;
@@ -830,6 +840,115 @@ int launch_nrt_long_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begi
   return SPX_OK;
 }
 
+// combin.Combinations(n, k) for n = 9 .. 16 as 16-bit masks over list positions, size-major then lexicographic (the 16-bit sibling
+// of nrt_combinations; 131 064 masks, built once on the host and uploaded: the 64 KB constant segment does not hold them)
+struct NrtTallCombos {
+  std::vector<uint16_t> mask;
+  uint32_t start[8][SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA + 1];
+};
+inline NrtTallCombos make_nrt_tall_combos() {
+  NrtTallCombos t;
+  for (int n = 9; n <= SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA; ++n) {
+    for (int k = 1; k <= SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA; ++k) {
+      t.start[n - 9][k - 1] = static_cast<uint32_t>(t.mask.size());
+      if (k > n) continue;
+      int c[SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA];
+      for (int i = 0; i < k; ++i) c[i] = i;
+      while (true) {
+        unsigned m = 0;
+        for (int i = 0; i < k; ++i) m |= 1u << c[i];
+        t.mask.push_back(static_cast<uint16_t>(m));
+        int i = k - 1;
+        while (i >= 0 && c[i] == n - k + i) --i;
+        if (i < 0) break;
+        ++c[i];
+        for (int j = i + 1; j < k; ++j) c[j] = c[j - 1] + 1;
+      }
+    }
+    t.start[n - 9][SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA] = static_cast<uint32_t>(t.mask.size());
+  }
+  return t;
+}
+
+int ensure_nrt_creq(spx_engine* e, bool force = false);
+
+// what an NRT evaluation of an engine with tall nodes needs before its first launch, from host state alone: the side table, and with
+// LeastNUMANodes no tall node above that strategy's zone limit.  spx_eval and spx_fetch_raw ask before they write anything.
+int nrt_tall_ready(spx_engine* e) {
+  if (e->h_nrt_tall_nodes.empty()) return SPX_OK;
+  if (!e->nrt_tall_ok)
+    return fail(e, SPX_ERR_STATE, "NRT: the node table has nodes with more than 8 NUMA zones: call spx_upload_nrt_tall_nodes after spx_upload_nrt_nodes");
+  if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && e->nrt_tall_ln_node >= 0) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "NRT: LeastNUMANodes takes nodes of up to %d NUMA zones; node %d lists %d", SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA,
+                  e->nrt_tall_ln_node, e->nrt_tall_ln_zones);
+    return fail(e, SPX_ERR_STATE, buf);
+  }
+  return SPX_OK;
+}
+
+// the tall nodes' columns of rows [row_begin, row_end) (kernels_nrt_tall.hip) after the dense sweep `na` and the long rows wrote them as
+// those of a node without an NRT object: status and score are overwritten (or, with na.out_raw, the raw row's entries).  It runs for
+// every row of the range — class copies, short and long rows — in reference arithmetic, whatever form the dense sweep took.  No launch
+// and no allocation without tall nodes.
+int launch_nrt_tall_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begin, int64_t row_end) {
+  e->nrt_tall_last = 0;
+  const std::vector<int32_t>& tall = e->h_nrt_tall_nodes;
+  if (tall.empty()) return SPX_OK;
+  if (e->row_indirect) return fail(e, SPX_ERR_STATE, "NRT: the sequential commit loop does not take nodes with more than 8 NUMA zones");
+  int rc;
+  if ((rc = nrt_tall_ready(e))) return rc;  // (the callers checked before their first launch; a direct call must not get past it either)
+  if (row_end <= row_begin) return SPX_OK;
+  spx::NrtTallArgs t{};
+  t.n_nodes = na.n_nodes, t.n_pods = na.n_pods, t.row_stride = na.row_stride, t.n_res = na.n_res, t.strategy = na.strategy;
+  std::memcpy(t.slot_flags, na.slot_flags, sizeof t.slot_flags);
+  std::memcpy(t.slot_weight, na.slot_weight, sizeof t.slot_weight);
+  t.n_tall = static_cast<int32_t>(tall.size());
+  t.zone_stride = e->nrt_tall_stride;
+  t.node_idx = static_cast<const int32_t*>(e->d_nrtt_idx.p);
+  t.flags = static_cast<const uint8_t*>(e->d_nrtt_flags.p);
+  t.max_numa = static_cast<const int32_t*>(e->d_nrtt_max.p);
+  t.node_present = static_cast<const uint8_t*>(e->d_nrtt_np.p);
+  t.n_zones = static_cast<const uint8_t*>(e->d_nrtt_nz.p);
+  t.zone_id = static_cast<const uint8_t*>(e->d_nrtt_zid.p);
+  t.zone_present = static_cast<const uint8_t*>(e->d_nrtt_zp.p);
+  t.zone_avail = static_cast<const int64_t*>(e->d_nrtt_avail.p);
+  t.zone_cost = static_cast<const int32_t*>(e->d_nrtt_cost.p);
+  t.min_avg = static_cast<const float*>(e->d_nrtt_minavg.p);
+  // the per-container request column: a batch the float64 formulation takes does not ship it, and the dense sweep that just ran did
+  // not need it (ensure_nrt_creq) — this kernel reads it whatever form the dense sweep took, so it is rebuilt from the record stream here
+  if ((rc = ensure_nrt_creq(e, true))) return rc;
+  t.qos = na.qos, t.non_native = na.non_native, t.n_ctr = na.n_ctr, t.ctr_kind = na.ctr_kind, t.ctr_present = na.ctr_present;
+  t.ctr_req = static_cast<const int64_t*>(e->d_nrt_creq.p);
+  t.pod_present = na.pod_present, t.pod_req = na.pod_req;
+  if (!e->h_nrt_long_rows.empty()) {
+    t.long_of_row = static_cast<const int32_t*>(e->d_nrtl_map.p);
+    t.long_ptr = static_cast<const int32_t*>(e->d_nrtl_ptr.p);
+    t.long_kind = static_cast<const uint8_t*>(e->d_nrtl_kind.p);
+    t.long_present = static_cast<const uint8_t*>(e->d_nrtl_pres.p);
+    t.long_req = static_cast<const int64_t*>(e->d_nrtl_req.p);
+  }
+  t.row_begin = row_begin, t.row_end = row_end;
+  if (na.strategy == SPX_NRT_LEAST_NUMA_NODES) {
+    if (!e->nrt_tall_combos) {
+      const NrtTallCombos c = make_nrt_tall_combos();
+      if ((rc = upload(e, e->d_nrtt_cmask, c.mask.data(), c.mask.size() * sizeof(uint16_t))) || (rc = upload(e, e->d_nrtt_cstart, c.start, sizeof c.start))) return rc;
+      SPX_HIP(e, hipStreamSynchronize(e->stream));  // (a local table)
+      e->nrt_tall_combos = true;
+    }
+    t.combo_mask = static_cast<const uint16_t*>(e->d_nrtt_cmask.p);
+    t.combo_start = static_cast<const uint32_t*>(e->d_nrtt_cstart.p);
+  }
+  t.n_waves = spx::nrt_tall_waves(row_end - row_begin, t.n_tall, t.zone_stride, t.n_res);
+  if ((rc = ensure(e, e->d_nrtt_work, static_cast<size_t>(spx::nrt_tall_work_bytes(t.zone_stride, t.n_res, t.n_waves))))) return rc;
+  t.work = static_cast<int64_t*>(e->d_nrtt_work.p);
+  t.out_status = na.out_status, t.out_score = na.out_score, t.out_raw = na.out_raw;
+  spx::launch_nrt_tall(t, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  e->nrt_tall_last = static_cast<int64_t>(tall.size());
+  return SPX_OK;
+}
+
 // NodeResourceTopologyMatch over the wide tables, rows [row_begin, row_end) into the status / score tables (or, with out_raw, the one
 // row's raw scores).  Replaces the whole dense machinery: no pod classes, rank stream, fused walk, redo lists or long rows.
 int launch_nrt_wide_rows(spx_engine* e, int64_t row_begin, int64_t row_end, int64_t* out_raw) {
@@ -872,10 +991,11 @@ int launch_nrt_wide_rows(spx_engine* e, int64_t row_begin, int64_t row_end, int6
 }
 
 // the reference-arithmetic NRT kernel's request column, when the coming launch may take that kernel and the batch did not ship it
-int ensure_nrt_creq(spx_engine* e) {
+// (`force`: whatever form the dense sweep takes — the tall nodes' kernel reads the column in every case)
+int ensure_nrt_creq(spx_engine* e, bool force) {
   const bool fast = e->nrt_fast_slots && e->nrt_fast_nodes && e->nrt_fast_pods && !forced_reference(e, SPX_PLUGIN_NRT) &&
                     !(e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && !(e->nrt_ln_ok && e->nrt_ln_built));
-  if (fast || e->nrt_creq_valid) return SPX_OK;
+  if ((fast && !force) || e->nrt_creq_valid) return SPX_OK;
   const size_t bytes = static_cast<size_t>(e->n_pods) * SPX_NRT_MAX_CTRS * static_cast<size_t>(e->nrt_n_res) * sizeof(int64_t);
   int rc = ensure(e, e->d_nrt_creq, bytes);
   if (rc) return rc;

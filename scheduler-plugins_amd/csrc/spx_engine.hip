@@ -278,6 +278,7 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
   if (N && !e->nrt_wide && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
   if (N && !e->nrt_wide && !e->nrt_long_ok)
     return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
+  if (N && !e->nrt_wide && (rc = nrt_tall_ready(e))) return rc;
   if (A && (rc = prepare_alloc(e))) return rc;
   const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD);
   if (W && !(e->net_nodes && e->net_topo && e->net_pods)) return fail(e, SPX_ERR_STATE, "NetworkOverhead node/topology/pod tables not uploaded");
@@ -428,6 +429,7 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     if ((rc = launch_nrt_wide_rows(e, row_begin, row_end, nullptr))) return rc;
     e->last_nrt_filter = 4;
     e->nrt_long_last = 0;
+    e->nrt_tall_last = 0;
   } else if (N) {
     if (e->score_stride[SPX_PLUGIN_NRT] != e->row_stride)
       return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
@@ -558,6 +560,8 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     // the long rows overwrite what the sweep above wrote from their pod-level request, before NetworkOverhead and Allocatable's
     // masked normalisation read the NRT status table (a long row is a class of its own: no copy of it was made above)
     if ((rc = launch_nrt_long_rows(e, na, row_begin, row_end))) return rc;
+    // then the tall nodes' columns of every row of the range (class copies and long rows included), still ahead of those readers
+    if ((rc = launch_nrt_tall_rows(e, na, row_begin, row_end))) return rc;
   }
   if (W) {
     if (e->score_stride[SPX_PLUGIN_NETOVERHEAD] != e->row_stride)
@@ -762,6 +766,12 @@ int spx_nrt_long_rows(const spx_engine* e, int64_t* n_out) {
   return SPX_OK;
 }
 
+int spx_nrt_tall_count(const spx_engine* e, int64_t* n_out) {
+  if (!e || !n_out) return SPX_ERR_ARG;
+  *n_out = e->nrt_tall_last;
+  return SPX_OK;
+}
+
 int spx_nrt_packed_score_slots(const spx_engine* e) {
   if (!e) return SPX_ERR_ARG;
   NrtPacked pk;
@@ -889,6 +899,7 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
   if (plugin == SPX_PLUGIN_NRT) {  // TopologyMatch has no NormalizeScore (score.go:104-106)
     if (!(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
     if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
+    if ((rc = nrt_tall_ready(e))) return rc;
     if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
     if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && (rc = build_ln_tab(e))) return rc;
     if ((rc = ensure_nrt_creq(e))) return rc;
@@ -901,6 +912,10 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
     const int64_t swept = e->nrt_long_last;  // (spx_nrt_long_rows reports spx_eval's sweeps, not this row)
     rc = launch_nrt_long_rows(e, na, pod_row, pod_row + 1);
     e->nrt_long_last = swept;
+    if (rc) return rc;
+    const int64_t swept_tall = e->nrt_tall_last;
+    rc = launch_nrt_tall_rows(e, na, pod_row, pod_row + 1);
+    e->nrt_tall_last = swept_tall;
     if (rc) return rc;
     SPX_HIP(e, hipGetLastError());
     SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));

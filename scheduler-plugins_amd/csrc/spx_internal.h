@@ -541,6 +541,57 @@ struct NrtLongArgs {
 };
 void launch_nrt_long(const NrtLongArgs& a, hipStream_t s);
 
+// NodeResourceTopologyMatch's tall nodes (more than SPX_NRT_MAX_ZONES zones; kernels_nrt_tall.hip): the side table of
+// spx_upload_nrt_tall_nodes node-major over the compacted index t (element e of tall node t at [e * n_tall + t]), the pod columns of
+// NrtArgs and, for the batch's long rows, the CSR of NrtLongArgs
+struct NrtTallArgs {
+  int64_t n_nodes;
+  int64_t n_pods;
+  int64_t row_stride;
+  int32_t n_res;
+  int32_t strategy;
+  uint8_t slot_flags[SPX_NRT_MAX_RES];
+  int64_t slot_weight[SPX_NRT_MAX_RES];
+  int32_t n_tall;
+  int32_t zone_stride;           // the most zones any tall node lists
+  const int32_t* node_idx;       // [n_tall] the node (column of the tables) of each tall node, ascending
+  const uint8_t* flags;          // [n_tall]
+  const int32_t* max_numa;       // [n_tall]
+  const uint8_t* node_present;   // [n_tall]
+  const uint8_t* n_zones;        // [n_tall]
+  const uint8_t* zone_id;        // [zone_stride][n_tall]
+  const uint8_t* zone_present;   // [zone_stride][n_tall]
+  const int64_t* zone_avail;     // [zone_stride][n_res][n_tall]
+  const int32_t* zone_cost;      // [zone_stride][zone_stride][n_tall]
+  const float* min_avg;          // [zone_stride][n_tall]
+  const uint8_t* qos;            // [P]
+  const uint8_t* non_native;     // [P]
+  const uint8_t* n_ctr;          // [P] (0 for a long row)
+  const uint8_t* ctr_kind;       // [P][8]
+  const uint8_t* ctr_present;    // [P][8]
+  const int64_t* ctr_req;        // [P][8][n_res]
+  const uint8_t* pod_present;    // [P]
+  const int64_t* pod_req;        // [P][n_res]
+  const int32_t* long_of_row;    // [P] long row of a batch row or -1; NULL: the batch has no long rows
+  const int32_t* long_ptr;       // [n_long + 1]
+  const uint8_t* long_kind;
+  const uint8_t* long_present;
+  const int64_t* long_req;
+  int64_t row_begin, row_end;
+  const uint16_t* combo_mask;    // LeastNUMANodes: combin.Combinations(n, k) for n = 9..16 (NrtTallCombos)
+  const uint32_t* combo_start;   // [8][17]: row n - 9, subsets of size k at [k - 1] .. [k]
+  int64_t* work;                 // [n_waves][zone_stride][n_res][64] the waves' working copies
+  int32_t n_waves;               // the grid, a multiple of 4 (nrt_tall_waves)
+  uint8_t* out_status;           // [P][row_stride]
+  uint8_t* out_score;            // [P][row_stride]
+  int64_t* out_raw;              // when set: raw int64 scores of the one row row_begin at the tall nodes' columns, no table writes
+};
+constexpr int64_t kNrtTallWorkBytes = int64_t{64} << 20;
+constexpr int64_t kNrtTallMaxWaves = 4096;
+int64_t nrt_tall_work_bytes(int32_t zone_stride, int32_t n_res, int n_waves);
+int nrt_tall_waves(int64_t rows, int32_t n_tall, int32_t zone_stride, int32_t n_res);
+void launch_nrt_tall(const NrtTallArgs& a, hipStream_t s);
+
 // NodeResourceTopologyMatch over the wide tables (up to SPX_NRT_MAX_RES_WIDE slots; kernels_nrt_wide.hip): node-major columns as
 // NrtArgs' with uint32 presence masks, the pod table in CSR (spx_nrt_pods_wide)
 struct NrtWideArgs {

@@ -83,6 +83,43 @@ int spx_load_sysched(spx_engine* e, const spx_sysched_objects* o) {
 }  // extern "C"
 
 namespace {
+// why a node flattener refused the snapshot, when its zone counts are the reason: the node and its count by name
+int fail_nrt_nodes(spx_engine* e, const spx_nrt_objects* nrt, bool wide, const char* plain) {
+  int64_t node = -1;
+  int32_t nz = 0;
+  const int rc = spx_nrt_first_tall_node(nrt, &node, &nz);
+  char buf[240];
+  if (rc != SPX_OK && node >= 0) {
+    std::snprintf(buf, sizeof buf, "NRT: node %lld lists %d NUMA zones of type Node (or one with id 64); this build takes up to %d zones with ids 0..63",
+                  static_cast<long long>(node), nz, SPX_NRT_TALL_MAX_ZONES);
+    return fail(e, SPX_ERR_ARG, buf);
+  }
+  if (wide && node >= 0) {
+    std::snprintf(buf, sizeof buf, "NRT: node %lld lists %d NUMA zones; a wide snapshot (more than 8 resource slots, or SPX_OPT_NRT_WIDE) takes up to %d per node",
+                  static_cast<long long>(node), nz, SPX_NRT_MAX_ZONES);
+    return fail(e, SPX_ERR_ARG, buf);
+  }
+  return fail(e, SPX_ERR_ARG, plain);
+}
+
+// the side table of the node table's tall nodes (more than 8 zones), flattened and uploaded after spx_upload_nrt_nodes marked them
+int load_nrt_tall(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots& slots) {
+  int64_t n_tall = 0;
+  int32_t zs = 0;
+  if (spx_flatten_nrt_tall_nodes(nodes, nrt, &slots, 0, 0, &n_tall, &zs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != SPX_OK)
+    return fail_nrt_nodes(e, nrt, false, "spx_flatten_nrt_tall_nodes failed");
+  const size_t T = static_cast<size_t>(n_tall), S = static_cast<size_t>(zs), R = static_cast<size_t>(slots.n_res > 0 ? slots.n_res : 1);
+  std::vector<int32_t> idx(T), mx(T), cost(T * S * S);
+  std::vector<uint8_t> fl(T), np(T), nz(T), zid(T * S), zp(T * S);
+  std::vector<int64_t> av(T * S * R);
+  std::vector<float> mavg(T * S);
+  if (spx_flatten_nrt_tall_nodes(nodes, nrt, &slots, n_tall, zs, &n_tall, &zs, idx.data(), fl.data(), mx.data(), np.data(), nz.data(), zid.data(), zp.data(), av.data(),
+                                 cost.data(), mavg.data()) != SPX_OK)
+    return fail(e, SPX_ERR_ARG, "spx_flatten_nrt_tall_nodes failed");
+  const spx_nrt_tall_nodes tt{n_tall, slots.n_res, zs, idx.data(), fl.data(), mx.data(), np.data(), nz.data(), zid.data(), zp.data(), av.data(), cost.data(), mavg.data()};
+  return spx_upload_nrt_tall_nodes(e, &tt);
+}
+
 // spx_load_nrt's wide route: slot numbering done, the node and pod halves flattened and uploaded side by side as in the dense route
 int load_nrt_wide(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_resource_classes* rc, const spx_pod_objects* pods,
                   const spx_nrt_params* params, const spx_nrt_slots& slots) {
@@ -120,7 +157,7 @@ int load_nrt_wide(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_ob
     std::vector<float> minavg(N * Z);
     if (spx_flatten_nrt_nodes_wide(nodes, nrt, &slots, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(),
                                    minavg.data(), np.data()) != SPX_OK) {
-      rc_nodes = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_nodes_wide failed");
+      rc_nodes = fail_nrt_nodes(e, nrt, true, "spx_flatten_nrt_nodes_wide failed");
     } else {
       const spx_nrt_nodes_wide ns{nodes->n_nodes, slots.n_res, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(),
                                   minavg.data(), np.data()};
@@ -203,12 +240,13 @@ int spx_load_nrt(spx_engine* e, const spx_node_objects* nodes, const spx_nrt_obj
     std::vector<float> minavg(N * Z);
     if (spx_flatten_nrt_nodes(nodes, nrt, &slots, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(), minavg.data(), np.data()) !=
         SPX_OK) {
-      rc_nodes = fail(e, SPX_ERR_ARG, "spx_flatten_nrt_nodes failed");
+      rc_nodes = fail_nrt_nodes(e, nrt, false, "spx_flatten_nrt_nodes failed");
     } else {
       e->load_nrt_ms[1] = since(t1);  // 1: node columns allocated + spx_flatten_nrt_nodes
       const auto t2 = clk::now();
       const spx_nrt_nodes_soa ns{nodes->n_nodes, n_res, nflags.data(), max_numa.data(), nz.data(), zid.data(), zp.data(), zavail.data(), zcost.data(), minavg.data(), np.data()};
       rc_nodes = spx_upload_nrt_nodes(e, &ns);
+      if (rc_nodes == SPX_OK && !e->nrt_tall_ok) rc_nodes = load_nrt_tall(e, nodes, nrt, slots);  // nodes with more than 8 zones: their side table
       e->load_nrt_ms[4] = since(t2);  // 4: spx_upload_nrt_nodes (precondition checks, window-local node order, one blob, derived columns on the device)
     }
   }

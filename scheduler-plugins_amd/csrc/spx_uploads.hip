@@ -423,12 +423,17 @@ int spx_update_nrt_nodes(spx_engine* e, const int64_t* idx, const spx_nrt_nodes_
   if (e->nrt_wide)
     return fail(e, SPX_ERR_STATE, "NRT node delta: the engine holds a wide snapshot (more than 8 resource slots, or SPX_OPT_NRT_WIDE): load it again instead");
   if (!e->nrt_nodes || !e->nrt_slots) return fail(e, SPX_ERR_STATE, "NRT node delta: upload the slot and node tables first");
+  if (!e->h_nrt_tall_nodes.empty())
+    return fail(e, SPX_ERR_STATE, "NRT node delta: the engine holds nodes with more than 8 NUMA zones (spx_upload_nrt_tall_nodes): load the snapshot again instead");
   if (t->n_res != e->nrt_n_res) return fail(e, SPX_ERR_ARG, "NRT node delta: n_res differs from the slot table");
   const int64_t n = t->n_nodes;
   if (n == 0) return SPX_OK;
   if (!t->flags || !t->max_numa || !t->n_zones || !t->zone_id || !t->zone_present || !t->zone_cost || !t->min_avg_dist || !t->node_present ||
       (!t->zone_avail && t->n_res))
     return fail(e, SPX_ERR_ARG, "NULL column in table");
+  for (int64_t i = 0; i < n; ++i)
+    if (t->n_zones[i] == SPX_NRT_ZONES_TALL)
+      return fail(e, SPX_ERR_STATE, "NRT node delta: row " + std::to_string(i) + " is a node with more than 8 NUMA zones (n_zones = SPX_NRT_ZONES_TALL): load the snapshot again instead");
   std::vector<int32_t> ix;
   int rc = delta_indices(e, idx, n, ix);
   if (rc) return rc;
@@ -800,6 +805,9 @@ int spx_upload_nrt_slots(spx_engine* e, const spx_nrt_slots* t) {
   e->nrt_slots = true;
   ++e->nrt_items_gen;
   e->nrt_nodes = e->nrt_pods = false;  // tables are laid out by slot count
+  e->h_nrt_tall_nodes.clear();         // (the tall nodes' side table too)
+  e->nrt_tall_ok = true;
+  e->nrt_tall_last = 0;
   // float64 formulation: weight-subset table, cpu slot, weight range
   SPX_HIP(e, hipSetDevice(e->device));
   NrtSlotWeights w = nrt_slot_weights(t);
@@ -822,6 +830,24 @@ int spx_upload_nrt_nodes(spx_engine* e, const spx_nrt_nodes_soa* t) {
   if (!t->flags || !t->max_numa || !t->n_zones || !t->zone_id || !t->zone_present || !t->zone_cost || !t->min_avg_dist || !t->node_present ||
       (!t->zone_avail && R))
     return fail(e, SPX_ERR_ARG, "NULL column in table");
+  // tall nodes (n_zones = SPX_NRT_ZONES_TALL): their zones come with spx_upload_nrt_tall_nodes; the dense sweeps see them as nodes without
+  // zones (every column of this call holds 0 for them), and kernels_nrt_tall.hip overwrites their columns afterwards.  An older side
+  // table goes with the node table it described.
+  e->h_nrt_tall_nodes.clear();
+  for (int64_t i = 0; i < n; ++i)
+    if (t->n_zones[i] == SPX_NRT_ZONES_TALL) e->h_nrt_tall_nodes.push_back(static_cast<int32_t>(i));
+  e->nrt_tall_ok = e->h_nrt_tall_nodes.empty();
+  e->nrt_tall_last = 0;
+  e->nrt_tall_stride = 0;
+  e->nrt_tall_ln_node = -1, e->nrt_tall_ln_zones = 0;
+  std::vector<uint8_t> nz_dense;
+  spx_nrt_nodes_soa dense = *t;
+  if (!e->h_nrt_tall_nodes.empty()) {
+    nz_dense.assign(t->n_zones, t->n_zones + n);
+    for (const int32_t i : e->h_nrt_tall_nodes) nz_dense[static_cast<size_t>(i)] = 0;
+    dense.n_zones = nz_dense.data();
+    t = &dense;
+  }
   // Round 4: the full upload takes the delta's road (ship_nrt_rows) with every node listed — the rows as they are into ONE pinned
   // blob, one DMA, and the device derives the rest (the derived columns used to be computed here, on the host, into five freshly
   // allocated vectors that were then copied from pageable memory: 12.6 of the 24 ms a full snapshot load took at 20 000 nodes).
@@ -1176,6 +1202,58 @@ int spx_upload_nrt_long_pods(spx_engine* e, const spx_nrt_long_pods* t) {
   return SPX_OK;
 }
 
+int spx_upload_nrt_tall_nodes(spx_engine* e, const spx_nrt_tall_nodes* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (e->nrt_wide) return fail(e, SPX_ERR_STATE, "NRT: a wide snapshot (more than 8 resource slots) takes no nodes with more than 8 NUMA zones");
+  if (!e->nrt_nodes) return fail(e, SPX_ERR_STATE, "NRT: upload the node table (spx_upload_nrt_nodes) before its tall nodes");
+  if (t->n_tall < 0 || t->n_res != e->nrt_n_res) return fail(e, SPX_ERR_ARG, "NRT tall nodes: n_tall < 0 or n_res differs from the slot table");
+  const std::vector<int32_t>& tall = e->h_nrt_tall_nodes;
+  const char* const listing = "NRT tall nodes: the table must list exactly the nodes whose n_zones is SPX_NRT_ZONES_TALL";
+  if (static_cast<size_t>(t->n_tall) != tall.size()) return fail(e, SPX_ERR_ARG, listing);
+  if (t->n_tall == 0) {
+    e->nrt_tall_ok = true;
+    return SPX_OK;
+  }
+  const int64_t T = t->n_tall, S = t->zone_stride, R = t->n_res;
+  if (!t->node_idx || !t->flags || !t->max_numa || !t->node_present || !t->n_zones || !t->zone_id || !t->zone_present || !t->zone_cost ||
+      !t->min_avg_dist || (!t->zone_avail && R))
+    return fail(e, SPX_ERR_ARG, "NULL column in table");
+  if (S <= SPX_NRT_MAX_ZONES || S > SPX_NRT_TALL_MAX_ZONES) return fail(e, SPX_ERR_ARG, "NRT tall nodes: zone_stride must lie in 9..64");
+  e->nrt_tall_ok = false;
+  int32_t ln_node = -1, ln_zones = 0;
+  for (int64_t k = 0; k < T; ++k) {
+    if (t->node_idx[k] != tall[static_cast<size_t>(k)]) return fail(e, SPX_ERR_ARG, listing);
+    const int nz = t->n_zones[k];
+    if (nz <= SPX_NRT_MAX_ZONES || nz > S)
+      return fail(e, SPX_ERR_ARG, "NRT tall nodes: node " + std::to_string(t->node_idx[k]) + " lists " + std::to_string(nz) + " zones; a tall node holds 9 to zone_stride");
+    for (int z = 0; z < nz; ++z)
+      if (t->zone_id[k * S + z] > 63) return fail(e, SPX_ERR_ARG, "NRT tall nodes: node " + std::to_string(t->node_idx[k]) + " carries a NUMA id above 63");
+    if (nz > SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA && ln_node < 0) ln_node = t->node_idx[k], ln_zones = nz;
+  }
+  int rc;
+  if ((rc = upload(e, e->d_nrtt_idx, t->node_idx, static_cast<size_t>(T) * 4)) || (rc = upload(e, e->d_nrtt_flags, t->flags, static_cast<size_t>(T))) ||
+      (rc = upload(e, e->d_nrtt_max, t->max_numa, static_cast<size_t>(T) * 4)) || (rc = upload(e, e->d_nrtt_np, t->node_present, static_cast<size_t>(T))) ||
+      (rc = upload(e, e->d_nrtt_nz, t->n_zones, static_cast<size_t>(T))) || (rc = upload_transposed(e, e->d_nrtt_zid, t->zone_id, T, S)) ||
+      (rc = upload_transposed(e, e->d_nrtt_zp, t->zone_present, T, S)) || (rc = upload_transposed(e, e->d_nrtt_cost, t->zone_cost, T, S * S)) ||
+      (rc = upload_transposed(e, e->d_nrtt_minavg, t->min_avg_dist, T, S)))
+    return rc;
+  if (R) {
+    if ((rc = upload_transposed(e, e->d_nrtt_avail, t->zone_avail, T, S * R))) return rc;
+  } else if ((rc = ensure(e, e->d_nrtt_avail, 16))) {
+    return rc;
+  }
+  // the dense table's n_zones column holds 0 for these nodes already (spx_upload_nrt_nodes wrote it so)
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->nrt_tall_stride = static_cast<int32_t>(S);
+  e->nrt_tall_ln_node = ln_node, e->nrt_tall_ln_zones = ln_zones;
+  e->nrt_tall_last = 0;
+  e->nrt_tall_ok = true;
+  e->evaluated = 0;
+  e->best_valid = false;
+  return SPX_OK;
+}
+
 // The wide form replaces the dense NRT state: its tables and every cache keyed on them (the fused walk's items, the packed Score's
 // table, the windows' sorted quantities, the long rows) are invalidated; spx_upload_nrt_slots does the same the other way round.
 int spx_upload_nrt_slots_wide(spx_engine* e, const spx_nrt_slots* t) {
@@ -1190,6 +1268,9 @@ int spx_upload_nrt_slots_wide(spx_engine* e, const spx_nrt_slots* t) {
   e->h_nrt_long_rows.clear();
   e->nrt_long_ok = true;
   e->nrt_long_last = 0;
+  e->h_nrt_tall_nodes.clear();
+  e->nrt_tall_ok = true;
+  e->nrt_tall_last = 0;
   e->nrt_wide = true;
   e->nrtw_slots = e->nrtw_nodes = e->nrtw_pods = false;
   const size_t R = static_cast<size_t>(t->n_res);

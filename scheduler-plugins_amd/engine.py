@@ -530,7 +530,11 @@ class Engine:
                   zone_avail=np.zeros(N * 8 * max(R, 1), np.int64), zone_cost=np.zeros(N * 64, np.int32),
                   min_avg_dist=np.zeros(N * 8, np.float32), node_present=np.zeros(N, np.uint8))
         fn = L.spx_flatten_nrt_nodes
-        self._ck(fn(nodes.ref(), nrt.ref(), slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(nc.values(), fn.argtypes[3:])]))
+        rc_ = fn(nodes.ref(), nrt.ref(), slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(nc.values(), fn.argtypes[3:])])
+        if rc_ != 0:
+            self._raise_nrt_zones(nrt)
+            self._ck(rc_)  # (another reason: the flattener's own code, as before)
+        tall = self.flatten_nrt_tall_nodes(nodes, nrt, slots)
         pc = dict(qos=np.zeros(P, np.uint8), non_native=np.zeros(P, np.uint8), n_ctr=np.zeros(P, np.uint8),
                   ctr_kind=np.zeros(P * 8, np.uint8), ctr_present=np.zeros(P * 8, np.uint8),
                   ctr_req=np.zeros(P * 8 * max(R, 1), np.int64), pod_present=np.zeros(P, np.uint8),
@@ -539,7 +543,19 @@ class Engine:
         self._ck(fn(pods.ref(), rc.ref() if rc else None, slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(pc.values(), fn.argtypes[3:])]))
         pc = NrtPods(pc)
         pc.long = self.flatten_nrt_long_pods(pods, rc, slots)
-        return {"params": params, "slots": slots, "nodes": nc, "pods": pc, "long": pc.long, "N": N, "P": P, "R": R}
+        return {"params": params, "slots": slots, "nodes": nc, "pods": pc, "long": pc.long, "tall": tall, "N": N, "P": P, "R": R}
+
+    def _raise_nrt_zones(self, nrt: Table, wide: bool = False) -> None:
+        """raises when a node's zone count is why a node flattener refused the snapshot, naming the node (spx_nrt_first_tall_node);
+        returns when it is not, and the caller reports the flattener's own code"""
+        from . import SpxError
+        node, nz = C.c_int64(), C.c_int32()
+        rc = self._lib.spx_nrt_first_tall_node(nrt.ref(), C.byref(node), C.byref(nz))
+        err = self._hdr.consts["SPX_ERR_ARG"]
+        if rc != 0 and node.value >= 0:
+            raise SpxError(err, f"NRT: node {node.value} lists {nz.value} NUMA zones of type Node (or one with id 64); this build takes up to 64 zones with ids 0..63")
+        if wide and node.value >= 0:
+            raise SpxError(err, f"NRT: node {node.value} lists {nz.value} NUMA zones; a wide snapshot (more than 8 resource slots, or the NRT_WIDE option) takes up to 8 per node")
 
     def nrt_slots_wide(self, nrt: Table, rc: Optional[Table], pods: Table, params: Table, cap: int = 32):
         """(count, status, slot_res, slot_flags, slot_weight) of spx_flatten_nrt_slots_wide with `cap` slots; the count is the snapshot's
@@ -565,7 +581,10 @@ class Engine:
                   zone_avail=np.zeros(N * 8 * max(R, 1), np.int64), zone_cost=np.zeros(N * 64, np.int32),
                   min_avg_dist=np.zeros(N * 8, np.float32), node_present=np.zeros(N, np.uint32))
         fn = L.spx_flatten_nrt_nodes_wide
-        self._ck_static(fn(nodes.ref(), nrt.ref(), slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(nc.values(), fn.argtypes[3:])]))
+        rc_ = fn(nodes.ref(), nrt.ref(), slots.ref(), *[v.ctypes.data_as(t) for v, t in zip(nc.values(), fn.argtypes[3:])])
+        if rc_ != 0:
+            self._raise_nrt_zones(nrt, wide=True)
+            self._ck_static(rc_)
         return {"wide": True, "params": params, "slots": slots, "nodes": nc, "pods": self.flatten_nrt_pods_wide(pods, rc, slots),
                 "N": N, "P": P, "R": R}
 
@@ -614,6 +633,43 @@ class Engine:
             lt = dict(n_long=0)
         cols = {k: lt[k] for k in ("pod_row", "ctr_ptr", "ctr_kind", "ctr_present", "ctr_req") if k in lt and len(lt[k])}
         self._ck(self._lib.spx_upload_nrt_long_pods(self._h, Table(self._hdr, "spx_nrt_long_pods", n_long=int(lt["n_long"]), n_res=n_res, **cols).ref()))
+
+    TALL_COLS = ("node_idx", "flags", "max_numa", "node_present", "n_zones", "zone_id", "zone_present", "zone_avail", "zone_cost", "min_avg_dist")
+
+    def flatten_nrt_tall_nodes(self, nodes: Table, nrt: Table, slots: Table) -> dict:
+        """the zones of the nodes with more than 8 NUMA zones (spx_flatten_nrt_tall_nodes): n_tall, zone_stride and the columns of
+        spx_nrt_tall_nodes, host row-major (zone_id [n_tall * zone_stride], zone_avail [n_tall * zone_stride * n_res], ...)"""
+        L = self._lib
+        R = int(slots.struct.n_res)
+        n_tall, zs = C.c_int64(), C.c_int32()
+        args = (nodes.ref(), nrt.ref(), slots.ref())
+        rc_ = L.spx_flatten_nrt_tall_nodes(*args, 0, 0, C.byref(n_tall), C.byref(zs), *([None] * 10))
+        if rc_ != 0:
+            self._raise_nrt_zones(nrt)
+            self._ck_static(rc_)
+        T, S = n_tall.value, zs.value
+        tt = dict(n_tall=T, zone_stride=S, node_idx=np.zeros(T, np.int32), flags=np.zeros(T, np.uint8), max_numa=np.zeros(T, np.int32),
+                  node_present=np.zeros(T, np.uint8), n_zones=np.zeros(T, np.uint8), zone_id=np.zeros(T * S, np.uint8),
+                  zone_present=np.zeros(T * S, np.uint8), zone_avail=np.zeros(T * S * max(R, 1), np.int64),
+                  zone_cost=np.zeros(T * S * S, np.int32), min_avg_dist=np.zeros(T * S, np.float32))
+        if T:
+            fn = L.spx_flatten_nrt_tall_nodes
+            self._ck_static(fn(*args, T, S, C.byref(n_tall), C.byref(zs), *[tt[k].ctypes.data_as(t) for k, t in zip(self.TALL_COLS, fn.argtypes[7:])]))
+        return tt
+
+    def upload_nrt_tall_nodes(self, tt: Optional[dict], n_res: int) -> None:
+        """the tall nodes' zones (spx_upload_nrt_tall_nodes), after the node table they belong to; None = an empty table"""
+        if tt is None:
+            tt = dict(n_tall=0, zone_stride=0)
+        cols = {k: tt[k] for k in self.TALL_COLS if k in tt and len(tt[k])}
+        self._ck(self._lib.spx_upload_nrt_tall_nodes(self._h, Table(self._hdr, "spx_nrt_tall_nodes", n_tall=int(tt["n_tall"]), n_res=n_res,
+                                                                    zone_stride=int(tt.get("zone_stride", 0)), **cols).ref()))
+
+    def nrt_tall_nodes(self) -> int:
+        """tall nodes (more than 8 NUMA zones) the last NRT sweep of eval evaluated (spx_nrt_tall_count)"""
+        n = C.c_int64()
+        self._ck(self._lib.spx_nrt_tall_count(self._h, C.byref(n)))
+        return n.value
 
     def nrt_long_rows(self) -> int:
         """long rows (pods with more than 8 containers) the last NRT sweep of eval evaluated (spx_nrt_long_rows)"""
@@ -741,6 +797,8 @@ class Engine:
         self._ck(L.spx_set_nrt_params(self._h, f["params"].ref()))
         self._ck(L.spx_upload_nrt_slots(self._h, f["slots"].ref()))
         self._ck(L.spx_upload_nrt_nodes(self._h, Table(H, "spx_nrt_nodes_soa", n_nodes=f["N"], n_res=f["R"], **f["nodes"]).ref()))
+        if f.get("tall") is not None:
+            self.upload_nrt_tall_nodes(f["tall"], f["R"])
         pc = _rows(f["pods"], f["P"], rows)
         P = f["P"] if rows is None else rows[1] - rows[0]
         if P > 0:

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <climits>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -163,6 +164,20 @@ int flatten_slots(const spx_pod_objects* pods, const spx_nrt_objects* nrt, const
   return SPX_OK;
 }
 
+// the zones createNUMANodeList keeps of node i (type Node, id 0..64); *id64: one of them carries id 64, beyond the 64-bit masks
+inline int count_zones(const spx_nrt_objects* nrt, int64_t i, bool* id64) {
+  int n = 0;
+  if (!nrt->has_nrt[i]) return 0;
+  for (int32_t z = nrt->zone_ptr[i]; z < nrt->zone_ptr[i + 1]; ++z) {
+    if (!nrt->zone_is_node[z]) continue;
+    const int id = nrt->zone_numa_id[z];
+    if (id < 0 || id > 64) continue;
+    if (id == 64) *id64 = true;
+    ++n;
+  }
+  return n;
+}
+
 // node i of the object tables -> row j of the SoA columns; PM is the presence mask type (uint8_t: dense, uint32_t: wide)
 template <typename PM>
 int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, int64_t i, int64_t j,
@@ -191,6 +206,20 @@ int flatten_nrt_node(const spx_node_objects* nodes, const spx_nrt_objects* nrt, 
       if (has) np |= static_cast<PM>(1u << s);
     }
     node_present[j] = np;
+    // ---- more zones than the dense columns hold: a tall node (its zones go to spx_flatten_nrt_tall_nodes' table).  The dense row is
+    // a placeholder the dense sweeps meet in every snapshot: no NRT object, no zones
+    {
+      bool id64 = false;
+      const int total = count_zones(nrt, i, &id64);
+      if (total > Z) {
+        if (id64 || total > SPX_NRT_TALL_MAX_ZONES || sizeof(PM) != 1) return SPX_ERR_ARG;  // (the wide tables keep their 8 zones)
+        flags[j] = static_cast<uint8_t>(flags[j] & ~SPX_NRT_F_HAS_NRT);
+        n_zones[j] = SPX_NRT_ZONES_TALL;
+        for (int k = 0; k < Z * Z; ++k) zone_cost[j * Z * Z + k] = 255;
+        for (int k = 0; k < Z; ++k) min_avg_dist[j * Z + k] = 255.0f;
+        return SPX_OK;
+      }
+    }
     // ---- NUMA node list (list order = zone order), with assumed pods subtracted from every zone
     int nz = 0;
     int32_t zsrc[Z];
@@ -346,6 +375,180 @@ extern "C" int spx_flatten_nrt_node_rows(const spx_node_objects* nodes, const sp
     const int rc = flatten_nrt_node(nodes, nrt, slots, idx[j], j, flags, max_numa, n_zones, zone_id, zone_present, zone_avail, zone_cost, min_avg_dist, node_present);
     if (rc != SPX_OK) return rc;
   }
+  return SPX_OK;
+}
+
+extern "C" int spx_nrt_first_tall_node(const spx_nrt_objects* nrt, int64_t* node_out, int32_t* n_zones_out) {
+  if (!nrt || !node_out || !n_zones_out) return SPX_ERR_ARG;
+  *node_out = -1;
+  *n_zones_out = 0;
+  for (int64_t i = 0; i < nrt->n_nodes; ++i) {
+    bool id64 = false;
+    const int total = count_zones(nrt, i, &id64);
+    if (total > SPX_NRT_TALL_MAX_ZONES || (id64 && total > Z)) {
+      *node_out = i, *n_zones_out = total;
+      return SPX_ERR_ARG;
+    }
+    if (total > Z && *node_out < 0) *node_out = i, *n_zones_out = total;
+  }
+  return SPX_OK;
+}
+
+namespace {
+// minAvgDistanceInCombinations for every subset size of one (zone count, cost matrix) key of nz <= 16 zones — key = {nz, the nz x nz
+// costs by list position} — float32 exactly as the dense flattener: every subset once, its pair sum grown from the subset without
+// its lowest member (2^nz ints on the heap).  65 535 subsets at 16 zones, about a millisecond of one host thread.
+std::vector<float> tall_min_avg(const std::vector<int32_t>& key) {
+  const int nz = key[0];
+  const int32_t* c = key.data() + 1;
+  std::vector<int> pair_sum(size_t{1} << nz);
+  int least[SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA];
+  for (int k = 0; k < nz; ++k) least[k] = INT32_MAX;
+  pair_sum[0] = 0;
+  for (unsigned m = 1; m < (1u << nz); ++m) {
+    const int z = __builtin_ctz(m);
+    const unsigned rest = m & (m - 1);
+    int accu = pair_sum[rest] + c[z * nz + z];
+    for (unsigned r = rest; r; r &= r - 1) {
+      const int j = __builtin_ctz(r);
+      accu += c[z * nz + j] + c[j * nz + z];
+    }
+    pair_sum[m] = accu;
+    const int k = __builtin_popcount(m);
+    if (accu < least[k - 1]) least[k - 1] = accu;
+  }
+  std::vector<float> best(static_cast<size_t>(nz), 255.0f);
+  for (int k = 1; k <= nz; ++k) {
+    const float d = static_cast<float>(least[k - 1]) / static_cast<float>(k * k);
+    if (d < best[k - 1]) best[k - 1] = d;
+  }
+  return best;
+}
+}  // namespace
+
+extern "C" int spx_flatten_nrt_tall_nodes(const spx_node_objects* nodes, const spx_nrt_objects* nrt, const spx_nrt_slots* slots, int64_t tall_cap,
+                                          int32_t stride_cap, int64_t* n_tall_out, int32_t* zone_stride_out, int32_t* node_idx, uint8_t* flags,
+                                          int32_t* max_numa, uint8_t* node_present, uint8_t* n_zones, uint8_t* zone_id, uint8_t* zone_present,
+                                          int64_t* zone_avail, int32_t* zone_cost, float* min_avg_dist) {
+  if (!nodes || !nrt || !slots || !n_tall_out || !zone_stride_out || nrt->n_nodes != nodes->n_nodes) return SPX_ERR_ARG;
+  const bool count_only = !node_idx && !flags && !max_numa && !node_present && !n_zones && !zone_id && !zone_present && !zone_avail && !zone_cost && !min_avg_dist;
+  if (!count_only && (!node_idx || !flags || !max_numa || !node_present || !n_zones || !zone_id || !zone_present || !zone_cost || !min_avg_dist ||
+                      (!zone_avail && slots->n_res) || tall_cap < 0 || stride_cap < 0))
+    return SPX_ERR_ARG;
+  const int R = slots->n_res;
+  if (R < 0 || R > RM) return SPX_ERR_ARG;  // (tall nodes in a wide snapshot stay refused)
+  int64_t n_tall = 0;
+  int32_t zs = 0;
+  for (int64_t i = 0; i < nrt->n_nodes; ++i) {
+    bool id64 = false;
+    const int total = count_zones(nrt, i, &id64);
+    if (total <= Z) continue;
+    if (id64 || total > SPX_NRT_TALL_MAX_ZONES) return SPX_ERR_ARG;
+    ++n_tall;
+    zs = total > zs ? total : zs;
+  }
+  *n_tall_out = n_tall;
+  *zone_stride_out = zs;
+  if (count_only) return SPX_OK;
+  if (n_tall > tall_cap || zs > stride_cap || n_tall > INT32_MAX) return SPX_ERR_ARG;
+  const size_t T = static_cast<size_t>(n_tall), S = static_cast<size_t>(zs);
+  std::memset(zone_id, 0, T * S);
+  std::memset(zone_present, 0, T * S);
+  if (R) std::memset(zone_avail, 0, T * S * static_cast<size_t>(R) * sizeof(int64_t));
+  for (size_t q = 0; q < T * S * S; ++q) zone_cost[q] = 255;
+  for (size_t q = 0; q < T * S; ++q) min_avg_dist[q] = 255.0f;
+  // the distance minima are kept per (zone count, cost matrix): the machines of one model share a key and cost one enumeration
+  std::map<std::vector<int32_t>, size_t> key_of;
+  std::vector<const std::vector<int32_t>*> keys;
+  std::vector<int64_t> key_at(T, -1);
+  int64_t k = 0;
+  for (int64_t i = 0; i < nrt->n_nodes; ++i) {
+    bool id64 = false;
+    if (count_zones(nrt, i, &id64) <= Z) continue;
+    node_idx[k] = static_cast<int32_t>(i);
+    // the node's own record: the dense row's flags (with HAS_NRT as the snapshot has it), max_numa and key set, from the dense walk
+    {
+      uint8_t f = 0, nzd = 0, np = 0, zid[Z] = {0}, zp[Z] = {0};
+      int32_t mx = 0, cost[Z * Z];
+      float mavg[Z];
+      int64_t av[Z * RM] = {0};
+      const int rc = flatten_nrt_node<uint8_t>(nodes, nrt, slots, i, 0, &f, &mx, &nzd, zid, zp, av, cost, mavg, &np);
+      if (rc != SPX_OK) return rc;
+      flags[k] = static_cast<uint8_t>(f | SPX_NRT_F_HAS_NRT);
+      max_numa[k] = mx;
+      node_present[k] = np;
+    }
+    int nz = 0;
+    int32_t zsrc[SPX_NRT_TALL_MAX_ZONES];
+    for (int32_t z = nrt->zone_ptr[i]; z < nrt->zone_ptr[i + 1]; ++z) {
+      if (!nrt->zone_is_node[z]) continue;
+      const int id = nrt->zone_numa_id[z];
+      if (id < 0 || id > 64) continue;
+      zsrc[nz] = z;
+      zone_id[k * zs + nz] = static_cast<uint8_t>(id);
+      uint8_t present = 0;
+      for (int32_t e = nrt->zres_ptr[z]; e < nrt->zres_ptr[z + 1]; ++e) {
+        const int s = slot_of(slots, nrt->zres_res[e]);
+        if (s < 0) return SPX_ERR_ARG;
+        int64_t avail = nrt->zres_avail[e];
+        if (nrt->assumed_ptr)
+          for (int32_t a = nrt->assumed_ptr[i]; a < nrt->assumed_ptr[i + 1]; ++a)
+            for (int32_t q = nrt->arl_ptr[a]; q < nrt->arl_ptr[a + 1]; ++q)
+              if (nrt->arl_res[q] == nrt->zres_res[e]) avail = avail < nrt->arl_qty[q] ? 0 : avail - nrt->arl_qty[q];
+        present |= static_cast<uint8_t>(1u << s);
+        zone_avail[(k * zs + nz) * R + s] = avail;
+      }
+      zone_present[k * zs + nz] = present;
+      ++nz;
+    }
+    n_zones[k] = static_cast<uint8_t>(nz);
+    // distance matrix by list position, 255 where Costs has no entry; duplicate ids as in the dense flattener: with unique ids the
+    // last entry for an id wins, else every zone with that id takes the entry
+    int32_t* row = zone_cost + static_cast<size_t>(k) * S * S;
+    if (nrt->zcost_ptr) {
+      int8_t pos_of[64];
+      std::memset(pos_of, -1, sizeof pos_of);
+      bool unique = true;
+      for (int b = 0; b < nz; ++b) {
+        const int id = zone_id[k * zs + b];
+        unique &= pos_of[id] < 0;
+        pos_of[id] = static_cast<int8_t>(b);
+      }
+      if (unique) {
+        for (int a = 0; a < nz; ++a)
+          for (int32_t e = nrt->zcost_ptr[zsrc[a]]; e < nrt->zcost_ptr[zsrc[a] + 1]; ++e) {
+            const int32_t id = nrt->zcost_numa_id[e];
+            if (id >= 0 && id < 64 && pos_of[id] >= 0) row[a * zs + pos_of[id]] = static_cast<int32_t>(nrt->zcost_value[e]);
+          }
+      } else {
+        for (int a = 0; a < nz; ++a)
+          for (int b = 0; b < nz; ++b) {
+            const int want = zone_id[k * zs + b];
+            for (int32_t e = nrt->zcost_ptr[zsrc[a]]; e < nrt->zcost_ptr[zsrc[a] + 1]; ++e)
+              if (nrt->zcost_numa_id[e] == want) row[a * zs + b] = static_cast<int32_t>(nrt->zcost_value[e]);
+          }
+      }
+    }
+    if (nz <= SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA) {
+      std::vector<int32_t> key;
+      key.reserve(static_cast<size_t>(nz) * nz + 1);
+      key.push_back(nz);
+      for (int a = 0; a < nz; ++a)
+        for (int b = 0; b < nz; ++b) key.push_back(row[a * zs + b]);
+      const auto at = key_of.emplace(std::move(key), keys.size());
+      if (at.second) keys.push_back(&at.first->first);
+      key_at[static_cast<size_t>(k)] = static_cast<int64_t>(at.first->second);
+    }
+    ++k;
+  }
+  // the distinct keys on the host threads (a snapshot of 5 000 tall nodes with a matrix each is 5 000 enumerations, a few seconds of one
+  // thread), then every node takes its key's row
+  std::vector<std::vector<float>> minima(keys.size());
+  spx_host::parallel_rows(static_cast<int64_t>(keys.size()), [&](int64_t k0, int64_t k1) {
+    for (int64_t q = k0; q < k1; ++q) minima[static_cast<size_t>(q)] = tall_min_avg(*keys[static_cast<size_t>(q)]);
+  }, 1);
+  for (size_t q = 0; q < T; ++q)
+    if (key_at[q] >= 0) std::copy(minima[static_cast<size_t>(key_at[q])].begin(), minima[static_cast<size_t>(key_at[q])].end(), min_avg_dist + q * S);
   return SPX_OK;
 }
 

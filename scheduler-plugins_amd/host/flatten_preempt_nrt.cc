@@ -105,6 +105,13 @@ extern "C" int spx_flatten_preempt_nrt(const spx_node_objects* nodes, const spx_
       }
       return SPX_ERR_ARG;
     }
+    // a node with more than 8 zones (spx_flatten_nrt_nodes marks it, its zones travel in a side table the refits do not read): refused
+    // by name before any walk over its zones — this table keeps its 8 zones per node
+    for (int64_t n = 0; n < N; ++n)
+      if (n_zones[n] == SPX_NRT_ZONES_TALL) {
+        *bad_out = n;
+        return SPX_ERR_ARG;
+      }
   }
   std::memset(zone_headroom, 0, static_cast<size_t>(N) * Z * (R ? R : 1) * sizeof(int64_t));
   auto slot_of = [&](int32_t res) {

@@ -387,7 +387,8 @@ def nrt_resource_classes(hdr: Header, wide: bool = False, extra_res: int = 0) ->
     return Table(hdr, "spx_resource_classes", n_res=len(flags), flags=flags)
 
 
-def synth_nrt(hdr: Header, nodes: Table, seed: int = SEED, n_zones: int = 8, vary: bool = True, wide: bool = False):
+def synth_nrt(hdr: Header, nodes: Table, seed: int = SEED, n_zones: int = 8, vary: bool = True, wide: bool = False,
+              tall_frac: float = 0.0, tall_zones=(9, 16), tall_control: bool = False):
     """NRT objects for the given nodes: Z NUMA zones per node with ids == list positions,
     per-zone available = alloc/Z x U[0.1,1] for {cpu, memory, hugepages-2Mi, device}; distances 10 on the
     diagonal and {12,20,32} off it; single-numa-node policy, container scope 70% / pod scope 30%,
@@ -464,7 +465,7 @@ def synth_nrt(hdr: Header, nodes: Table, seed: int = SEED, n_zones: int = 8, var
     arl_ptr = np.arange(na + 1, dtype=np.int32) * 2
     arl_res = np.tile(np.array([0, 1], dtype=np.int32), na)
     arl_qty = np.stack([rng.integers(500, 4000, na), rng.integers(1, 16, na) * GiB], axis=1).reshape(-1)
-    return Table(
+    out = Table(
         hdr, "spx_nrt_objects", n_nodes=N, has_nrt=has.astype(np.uint8), fresh=fresh.astype(np.uint8),
         legacy_policy=legacy, attr_scope=attr_scope, attr_policy=attr_policy, attr_max_numa=attr_max,
         zone_ptr=zone_ptr, zone_is_node=np.ones(nzt, dtype=np.uint8), zone_numa_id=zpos.astype(np.int32),
@@ -472,15 +473,109 @@ def synth_nrt(hdr: Header, nodes: Table, seed: int = SEED, n_zones: int = 8, var
         zcost_ptr=cost_ptr, zcost_numa_id=tgt.reshape(-1)[csel], zcost_value=cval.reshape(-1)[csel].astype(np.int64),
         assumed_ptr=assumed_ptr, arl_ptr=arl_ptr, arl_res=arl_res, arl_qty=arl_qty.astype(np.int64),
     )
+    # `tall_frac`: that share of the nodes gets tall_zones[0]..tall_zones[1] zones (heighten_nrt, its own stream); 0 leaves the objects
+    # as they always were.  `tall_control`: the same nodes lose their NRT object instead.
+    return heighten_nrt(hdr, nodes, out, tall_frac, tall_zones, seed, drop_nrt=tall_control) if tall_frac > 0 else out
+
+
+def heighten_nrt(hdr: Header, nodes: Table, nrt: Table, frac: float = 0.0, zones=(9, 16), seed: int = SEED, rows=None, drop_nrt: bool = False) -> Table:
+    """The NRT objects with a share `frac` of the nodes that have an NRT object (or the nodes `rows`) made "tall" for
+    NodeResourceTopologyMatch: zones[0]..zones[1] zones each (more than the dense NRT table's 8) reporting cpu, memory,
+    hugepages-2Mi and — on 85 % of the zones — the device, available = alloc / Z x U[0.1, 1]; distances 10 on the diagonal and
+    {12, 20, 32} off it with 5 % of the entries missing; on a third of the tall nodes the ids are a permutation of the positions.
+    Policies, freshness and assumed pods stay the node's own.  The draws come from their own stream, so the other nodes' objects
+    are those of the input.  `drop_nrt`: the chosen nodes lose their NRT object instead (the control a tall snapshot is compared to)."""
+    rng = np.random.default_rng(seed + 404)
+    N = nrt.struct.n_nodes
+    has = nrt.array("has_nrt").astype(bool)
+    if rows is None:
+        pick = has & (rng.random(N) < frac)
+    else:
+        pick = np.zeros(N, bool)
+        pick[np.asarray(rows, dtype=np.int64)] = True
+    tz = np.where(pick, rng.integers(zones[0], zones[1] + 1, N), 0)
+    if drop_nrt:
+        tz[:] = 0
+    zone_ptr = nrt.array("zone_ptr")
+    old_cnt = np.where(pick, 0, zone_ptr[1:] - zone_ptr[:-1])
+    keep = np.flatnonzero(~pick[np.repeat(np.arange(N), zone_ptr[1:] - zone_ptr[:-1])])  # old zones that stay
+    # the tall nodes' zones
+    nt = int(tz.sum())
+    t_node = np.repeat(np.arange(N), tz)
+    t_first = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(tz, out=t_first[1:])
+    t_pos = np.arange(nt) - t_first[t_node]
+    t_cnt = tz[t_node]
+    t_id = t_pos.copy()
+    for n in np.flatnonzero(tz > 0):
+        if rng.random() < 1 / 3:
+            t_id[t_first[n]:t_first[n + 1]] = rng.permutation(int(tz[n]))
+    fr = rng.uniform(0.1, 1.0, (nt, 2))
+    z_cpu = (nodes.array("alloc_cpu_milli")[t_node] / np.maximum(t_cnt, 1) * fr[:, 0]).astype(np.int64)
+    z_cpu = np.where(rng.random(nt) < 0.5, (z_cpu // 1000) * 1000, z_cpu)
+    z_mem = (nodes.array("alloc_mem")[t_node] / np.maximum(t_cnt, 1) * fr[:, 1]).astype(np.int64)
+    z_hp = (rng.integers(0, 513, nt) * (2 << 20)).astype(np.int64)
+    z_dev = rng.integers(0, 5, nt).astype(np.int64)
+    t_mask = np.stack([np.ones(nt, bool), np.ones(nt, bool), np.ones(nt, bool), rng.random(nt) < 0.85], axis=1)
+    t_rptr, t_rsel = _csr_from_mask(t_mask)
+    t_res = np.tile(np.array([0, 1, RES_HUGEPAGES_2MI, RES_DEVICE], dtype=np.int32), (nt, 1)).reshape(-1)[t_rsel]
+    t_qty = np.stack([z_cpu, z_mem, z_hp, z_dev], axis=1).reshape(-1)[t_rsel]
+    zmax = int(zones[1])
+    col = np.arange(zmax)[None, :]
+    t_cmask = (col < t_cnt[:, None]) & (rng.random((nt, zmax)) >= 0.05)
+    off = rng.choice(np.array([12, 20, 32]), (nt, zmax))
+    t_cval = np.where(col == t_pos[:, None], 10, off)
+    t_ctgt = np.zeros((nt, zmax), dtype=np.int32)
+    for n in np.flatnonzero(tz > 0):  # column c of a zone's costs names the id of the zone at position c
+        k = int(tz[n])
+        t_ctgt[t_first[n]:t_first[n + 1], :k] = t_id[t_first[n]:t_first[n + 1]][None, :]
+    t_cptr, t_csel = _csr_from_mask(t_cmask)
+    # merged zone order: node-major, a node's zones in list order
+    new_cnt = old_cnt + tz
+    new_ptr = np.zeros(N + 1, dtype=np.int32)
+    np.cumsum(new_cnt, out=new_ptr[1:])
+    n_keep = len(keep)
+    key_node = np.concatenate([np.repeat(np.arange(N), old_cnt), t_node])
+    order = np.argsort(key_node, kind="stable")  # (a node has kept zones or tall zones, never both: list order survives)
+    src_old = order < n_keep
+
+    def merge_zone(old_vals, tall_vals):
+        return np.concatenate([old_vals[keep], tall_vals])[order]
+
+    def merge_csr(old_ptr, old_cols, tall_ptr, tall_cols):
+        optr, opos = _gather_csr(old_ptr, keep)
+        cnt = np.concatenate([optr[1:] - optr[:-1], tall_ptr[1:] - tall_ptr[:-1]])
+        both_ptr = np.zeros(len(cnt) + 1, dtype=np.int32)
+        np.cumsum(cnt, out=both_ptr[1:])
+        nptr, pos = _gather_csr(both_ptr, order)
+        return nptr, [np.concatenate([oc[opos], tc])[pos] for oc, tc in zip(old_cols, tall_cols)]
+
+    zres_ptr, (zres_res, zres_avail) = merge_csr(nrt.array("zres_ptr"), [nrt.array("zres_res"), nrt.array("zres_avail")], t_rptr, [t_res, t_qty])
+    zcost_ptr, (zcost_id, zcost_val) = merge_csr(nrt.array("zcost_ptr"), [nrt.array("zcost_numa_id"), nrt.array("zcost_value")], t_cptr,
+                                                 [t_ctgt.reshape(-1)[t_csel], t_cval.reshape(-1)[t_csel].astype(np.int64)])
+    del src_old
+    has_new = has & ~pick if drop_nrt else has
+    return Table(
+        hdr, "spx_nrt_objects", n_nodes=N, has_nrt=has_new.astype(np.uint8), fresh=nrt.array("fresh"),
+        legacy_policy=nrt.array("legacy_policy"), attr_scope=nrt.array("attr_scope"), attr_policy=nrt.array("attr_policy"),
+        attr_max_numa=nrt.array("attr_max_numa"), zone_ptr=new_ptr, zone_is_node=merge_zone(nrt.array("zone_is_node"), np.ones(nt, np.uint8)),
+        zone_numa_id=merge_zone(nrt.array("zone_numa_id"), t_id.astype(np.int32)),
+        zres_ptr=zres_ptr, zres_res=zres_res.astype(np.int32), zres_avail=zres_avail.astype(np.int64),
+        zcost_ptr=zcost_ptr, zcost_numa_id=zcost_id.astype(np.int32), zcost_value=zcost_val.astype(np.int64),
+        assumed_ptr=nrt.array("assumed_ptr"), arl_ptr=nrt.array("arl_ptr"), arl_res=nrt.array("arl_res"), arl_qty=nrt.array("arl_qty"),
+    )
 
 
 def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary: bool = True, wide: bool = False,
-                 long_frac: float = 0.0, long_ctrs=(9, 40), extra_res: int = 0, extra_req_frac: float = 0.15) -> Dict[str, Table]:
+                 long_frac: float = 0.0, long_ctrs=(9, 40), extra_res: int = 0, extra_req_frac: float = 0.15,
+                 tall_frac: float = 0.0, tall_zones=(9, 16), tall_control: bool = False) -> Dict[str, Table]:
     """Object tables for BASELINE.json config #3 (NRT Filter+Score, 8 NUMA zones).  `wide`: six resource slots (cpu, memory,
     hugepages-2Mi, hugepages-1Gi, two extended resources) instead of four — the kernels' 8-slot instantiations.  `long_frac`: that
     share of the pods gets long_ctrs[0]..long_ctrs[1] containers (lengthen_pods); 0 leaves the snapshot as it always was.
     `extra_res`: that many more resources (ids RES_EXTRA0.., hugepage sizes and extended device pools) reported by a random subset of
-    node allocatables and zones and requested by a share extra_req_frac of the pods (_widen_nrt); 0 leaves the snapshot unchanged."""
+    node allocatables and zones and requested by a share extra_req_frac of the pods (_widen_nrt); 0 leaves the snapshot unchanged.
+    `tall_frac`: that share of the nodes lists tall_zones[0]..tall_zones[1] NUMA zones (heighten_nrt; `tall_control`: they have no NRT
+    object instead); 0 leaves the snapshot unchanged."""
     nodes = synth_nodes(hdr, n_nodes, seed, device_res=RES_DEVICE)
     # node-level allocatable must list hugepages too (util.ResourceList key check, filter.go:110-116)
     rng = np.random.default_rng(seed + 6)
@@ -501,7 +596,7 @@ def nrt_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, vary:
     if long_frac > 0:
         pods = lengthen_pods(hdr, pods, long_frac, seed, *long_ctrs)
     scalar = (ptr, res.reshape(-1)[sel], qty.reshape(-1)[sel])
-    nrt = synth_nrt(hdr, nodes, seed, vary=vary, wide=wide)
+    nrt = synth_nrt(hdr, nodes, seed, vary=vary, wide=wide, tall_frac=tall_frac, tall_zones=tall_zones, tall_control=tall_control)
     if extra_res > 0:
         scalar, nrt, pods = _widen_nrt(hdr, scalar, nrt, pods, extra_res, seed, extra_req_frac)
     nodes = Table(hdr, "spx_node_objects", n_nodes=N, alloc_cpu_milli=nodes.array("alloc_cpu_milli"),
