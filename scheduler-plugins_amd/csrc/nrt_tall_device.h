@@ -69,11 +69,18 @@ __device__ bool tall_fits_any(const A& a, const TallNode& nd, const AvView& av, 
   return ok && bitmask != 0;
 }
 
-// subtractResourcesFromNUMANodeList numaresources.go:145-182 on the wave's working copy: every zone that carries the id is charged
+// what the Filter's status cell holds where the reference returns fwk.Error instead of Unschedulable (the oracle's -1 as a byte; the
+// value NetworkOverhead's PreFilter error travels as)
+constexpr uint32_t kTallStError = 0xffu;
+
+// subtractResourcesFromNUMANodeList numaresources.go:145-182 on the wave's working copy: every zone that carries the id is charged.
+// False when a charge leaves a zone below zero — two zones share the id and only one of them holds the request; the reference stops
+// there with "inconsistent resource accounting" (numaresources.go:172-175, filter.go:73-77)
 template <class A>
-__device__ void tall_charge(const A& a, const TallNode& nd, int64_t* work, bool non_guaranteed, uint32_t present,
+__device__ bool tall_charge(const A& a, const TallNode& nd, int64_t* work, bool non_guaranteed, uint32_t present,
                             const int64_t* __restrict__ req, uint32_t numa_id) {
   const int R = a.n_res;
+  bool ok = true;
   for (int z = 0; z < nd.nz; ++z) {
     if (tall_id(a, nd, z) != numa_id) continue;
     const uint32_t zp = tall_zp(a, nd, z);
@@ -82,9 +89,13 @@ __device__ void tall_charge(const A& a, const TallNode& nd, int64_t* work, bool 
       if (non_guaranteed && (a.slot_flags[r] & SPX_NRT_SLOT_AFFINE)) continue;
       const int64_t q = req[r];
       if (q == 0) continue;
-      work[(static_cast<int64_t>(z) * R + r) * 64] -= q;
+      int64_t* cell = work + (static_cast<int64_t>(z) * R + r) * 64;
+      const int64_t left = *cell - q;
+      ok &= left >= 0;
+      *cell = left;
     }
   }
+  return ok;
 }
 
 // one zone's strategy score, as nrt_ref_device.h's zone_score

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import nrt_tall_cases as TC
+import nrt_tall_edge_cases as EC
 from helpers import NRT
 
 
@@ -18,9 +19,10 @@ def _oracle(oracle, hdr, c, strategy="LeastAllocated"):
 
 def test_id_patterns():
     for n in (9, 16, 17, 32, 33, 64):
-        for pat in TC.ID_PATTERNS:
+        for pat in TC.ID_PATTERNS + EC.SHARED_PATTERNS:
             ids = pat(n)
-            assert len(ids) == n and len(set(ids)) == n and 0 <= min(ids) and max(ids) <= 63
+            assert len(ids) == n and 0 <= min(ids) and max(ids) <= 63
+            assert (len(set(ids)) == n) == (pat in TC.ID_PATTERNS)    # the duplicate-free patterns are; the shared ones are not
         assert TC.ids_permuted(n)[-1] == 0 and TC.ids_sparse(n)[-1] == min(TC.ids_sparse(n)) and max(TC.ids_sparse(n)) == 63
 
 
