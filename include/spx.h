@@ -577,6 +577,9 @@ typedef struct spx_cosched_soa {
 #define SPX_NRT_ST_SIDECAR_CONTAINER 3/* "cannot align sidecar container"  filter.go:55  */
 #define SPX_NRT_ST_CONTAINER 4        /* "cannot align container"          filter.go:67  */
 #define SPX_NRT_ST_POD 5              /* "cannot align pod"                filter.go:172 */
+/* fwk.Error, not Unschedulable: "inconsistent resource accounting" filter.go:73-77 — a container fits one of several zones that share
+ * a NUMA id, is charged to every one of them, and a smaller one goes below zero (numaresources.go:145-182).  Infeasible like 1..5 */
+#define SPX_NRT_ST_ERROR 255
 
 typedef struct spx_nrt_slots {
   int32_t n_res;

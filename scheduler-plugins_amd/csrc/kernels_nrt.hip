@@ -113,9 +113,11 @@ __global__ __launch_bounds__(256, 2) void k_nrt(NrtArgs a, int n_tiles) {
           for (int c = 0; c < n_ctr; ++c) {
             if (ckind[c] != SPX_CTR_APP) continue;
             uint32_t id;
-            const bool ok = fits_any(ns, a, non_g, cpres[c], creq + c * R, &id);
+            bool negative;
+            const bool ok = fits_any(ns, a, non_g, cpres[c], creq + c * R, &id, &negative);
             const bool live = status == 0;
             if (live && !ok) status = SPX_NRT_ST_CONTAINER;
+            if (live && negative) status = SPX_NRT_ST_ERROR;  // ends the walk (fwk.Error); its charge is applied and undone like any other
             const bool apply = live && ok;
             adjust_numa(ns, a, non_g, cpres[c], creq + c * R, id, apply, -1);
             chosen |= static_cast<uint64_t>(apply ? id : 0u) << (8 * c);
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void k_nrt(NrtArgs a, int n_tiles) {
         } else {
           bool is_min;
           const uint32_t m = numa_nodes_required(ns, a, n, pod_present, preq, &is_min);
-          score = m ? normalize_score(__builtin_popcount(m), is_min, ns.max_numa) : 0;
+          score = m ? normalize_score(__builtin_popcountll(ids_of(ns, m)), is_min, ns.max_numa) : 0;  // (the count is of NUMA ids)
         }
       } else {  // leastNUMAContainerScopeScore
         int max_count = 0;
@@ -157,9 +159,10 @@ __global__ __launch_bounds__(256, 2) void k_nrt(NrtArgs a, int n_tiles) {
             continue;
           }
           all_min &= is_min;
-          const int cnt = __builtin_popcount(m);
+          const uint64_t ids = ids_of(ns, m);
+          const int cnt = __builtin_popcountll(ids);  // numaNodes.Count(): distinct NUMA ids, not zones
           max_count = cnt > max_count ? cnt : max_count;
-          subtract_from_numas(ns, a, cpres[c], creq + c * R, ids_of(ns, m));
+          subtract_from_numas(ns, a, cpres[c], creq + c * R, ids);
           dirty = true;
         }
         score = failed ? 0 : (max_count == 0 ? 100 : normalize_score(max_count, all_min, ns.max_numa));

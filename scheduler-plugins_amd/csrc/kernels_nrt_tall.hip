@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_nrt_tall(NrtTallArgs a, int tiles) {
               for (int e = 0; e < nd.nz * R; ++e) work[static_cast<int64_t>(e) * 64] = table.p[static_cast<int64_t>(e) * T];
               copied = true;
             }
-            if (!tall_charge(a, nd, work, non_g, cpres[c], q, id)) status = kTallStError;  // (ends the walk: fwk.Error)
+            if (!tall_charge(a, nd, work, non_g, cpres[c], q, id)) status = SPX_NRT_ST_ERROR;  // (ends the walk: fwk.Error)
           }
         }
       }

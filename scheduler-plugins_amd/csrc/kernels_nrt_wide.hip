@@ -113,11 +113,15 @@ __device__ __forceinline__ void cur_avail(int64_t (&v)[kZ], const WideNode& ns, 
   }
 }
 
-// resourcesAvailableInAnyNUMANodes filter.go:93-163
+// resourcesAvailableInAnyNUMANodes filter.go:93-163.  *negative (kFilterReplay): charging the list to the id it fits, as
+// subtractResourcesFromNUMANodeList does to every zone that carries the id, would leave one of them below zero — a twin of the zone
+// that fits holds less than the request (numaresources.go:172-175: an error, filter.go:73-77: fwk.Error).  The quantities are the ones
+// the fit was decided on, so the sign test costs no second replay.
 template <int MODE>
 __device__ __forceinline__ bool fits_any(const WideNode& ns, const NrtWideArgs& a, const WList& l, const Hist& h, const uint8_t (*rec)[kBlock],
-                                         uint32_t* numa_id) {
+                                         uint32_t* numa_id, bool* negative = nullptr) {
   uint64_t bitmask = ~0ull;
+  uint64_t short_ids = 0;  // ids of reporting zones that hold less than a quantity the charge takes
   bool ok = true;
   for (int e = 0; e < l.n; ++e) {
     const int s = l.slot[e];
@@ -141,10 +145,12 @@ __device__ __forceinline__ bool fits_any(const WideNode& ns, const NrtWideArgs& 
       const bool rep = ns.reports(z, s);
       has_affinity |= rep;
       if (rep && (always || v[z] >= q)) rb |= 1ull << ns.id(z);
+      else if (MODE == kFilterReplay && rep) short_ids |= 1ull << ns.id(z);  // (never under `always`: such a slot is not charged)
     }
     if (!(!has_affinity && host_level)) bitmask &= rb;
   }
   *numa_id = bitmask ? static_cast<uint32_t>(__builtin_ctzll(bitmask)) : 0u;
+  if constexpr (MODE == kFilterReplay) *negative = ok && bitmask != 0 && ((short_ids >> *numa_id) & 1ull);
   return ok && bitmask != 0;
 }
 
@@ -311,6 +317,15 @@ __device__ __forceinline__ uint32_t ids_of(const WideNode& ns, uint32_t pos_mask
   return bits;
 }
 
+// numaNodes.Count() of a chosen subset: the distinct NUMA ids its zones carry (twins count once)
+__device__ __forceinline__ int id_count(const WideNode& ns, uint32_t pos_mask) {
+  uint64_t bits = 0;
+#pragma unroll
+  for (int z = 0; z < kZ; ++z)
+    if ((pos_mask >> z) & 1u) bits |= 1ull << ns.id(z);
+  return __builtin_popcountll(bits);
+}
+
 __device__ __forceinline__ WList ctr_list(const NrtWideArgs& a, int32_t c) {
   const int32_t e0 = a.ent_ptr[c];
   return WList{a.ent_slot + e0, a.ent_qty + e0, a.ent_ptr[c + 1] - e0};
@@ -377,9 +392,11 @@ __global__ __launch_bounds__(kBlock, 2) void k_nrt_wide(NrtWideArgs a, int group
         for (int c = 0; c < n_ctr; ++c) {  // app containers: each charged to the NUMA id it fits before the next is tested
           if (a.ctr_kind[c0 + c] != SPX_CTR_APP) continue;
           uint32_t id;
-          const bool ok = fits_any<kFilterReplay>(ns, a, ctr_list(a, c0 + c), Hist{c0, c, non_g}, rec, &id);
+          bool negative;
+          const bool ok = fits_any<kFilterReplay>(ns, a, ctr_list(a, c0 + c), Hist{c0, c, non_g}, rec, &id, &negative);
           const bool live = status == 0;
           if (live && !ok) status = SPX_NRT_ST_CONTAINER;
+          if (live && negative) status = SPX_NRT_ST_ERROR;  // ends the walk: no later container is charged on this lane
           rec[c][threadIdx.x] = static_cast<uint8_t>(live && ok ? (kApplied | id) : 0u);
         }
       }
@@ -399,7 +416,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_nrt_wide(NrtWideArgs a, int group
       } else {
         bool is_min;
         const uint32_t m = numa_nodes_required<kNoReplay>(ns, a, preq, none, rec, &is_min);
-        score = m ? normalize_score(__builtin_popcount(m), is_min, max_numa) : 0;
+        score = m ? normalize_score(id_count(ns, m), is_min, max_numa) : 0;
       }
     } else {  // leastNUMAContainerScopeScore
       int max_count = 0;
@@ -414,7 +431,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_nrt_wide(NrtWideArgs a, int group
             failed = true;
           } else {
             all_min &= is_min;
-            const int cnt = __builtin_popcount(m);
+            const int cnt = id_count(ns, m);
             max_count = cnt > max_count ? cnt : max_count;
             r = ids_of(ns, m);
           }

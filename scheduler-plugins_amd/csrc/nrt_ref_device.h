@@ -128,10 +128,16 @@ __device__ __forceinline__ void load_avail(N<RM>& ns, const A& a, int64_t n, boo
 }
 
 // resourcesAvailableInAnyNUMANodes filter.go:93-163.  req/present are wave-uniform.
+// negative (asked for by the app containers' walk only): charging the request to the id it fits — which
+// subtractResourcesFromNUMANodeList does to EVERY zone that carries the id — would leave one of them below zero: a twin of the zone
+// that fits reports the resource and holds less than the quantity.  The reference stops there with an error (numaresources.go:172-175)
+// that filter.go:73-77 turns into fwk.Error; the caller ends the row with SPX_NRT_ST_ERROR.  The test reads the quantities the fit
+// is decided on, in the loop that decides it: folded into the charge loop (adjust_numa) it cost k_nrt scratch, here it costs none.
 template <int RM, template <int> class N, class A>
 __device__ __forceinline__ bool fits_any(const N<RM>& ns, const A& a, bool non_guaranteed, uint32_t present,
-                                         const int64_t* __restrict__ req, uint32_t* numa_id) {
+                                         const int64_t* __restrict__ req, uint32_t* numa_id, bool* negative = nullptr) {
   uint64_t bitmask = ~0ull;
+  uint64_t short_ids = 0;  // ids of reporting zones that hold less than a quantity the charge takes
   bool ok = true;
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
@@ -148,14 +154,18 @@ __device__ __forceinline__ bool fits_any(const N<RM>& ns, const A& a, bool non_g
       const bool rep = z < ns.nz && ((ns.zp(z) >> r) & 1u);
       has_affinity |= rep;
       if (rep && (always || ns.avail[z][r] >= q)) rb |= 1ull << ns.id(z);
+      else if (negative && rep) short_ids |= 1ull << ns.id(z);  // (never under `always`: such a slot is not charged)
     }
     if (!(!has_affinity && host_level)) bitmask &= rb;
   }
   *numa_id = bitmask ? static_cast<uint32_t>(__builtin_ctzll(bitmask)) : 0u;
+  if (negative) *negative = ok && bitmask != 0 && ((short_ids >> *numa_id) & 1ull);
   return ok && bitmask != 0;
 }
 
-// subtractResourcesFromNUMANodeList numaresources.go:145-182 (sign = -1) and its exact inverse (+1)
+// subtractResourcesFromNUMANodeList numaresources.go:145-182 (sign = -1) and its exact inverse (+1).  Every zone that carries the id
+// is charged, also where fits_any reports that one of them goes below zero: the whole charge is applied, so that the inverse
+// restores the table whatever the outcome.
 template <int RM, template <int> class N, class A>
 __device__ __forceinline__ void adjust_numa(N<RM>& ns, const A& a, bool non_guaranteed, uint32_t present,
                                             const int64_t* __restrict__ req, uint32_t numa_id, bool apply, int sign) {

@@ -139,17 +139,26 @@ struct NrtRefit {
     return ok && bitmask != 0;
   }
 
-  // subtractResourcesFromNUMANodeList (numaresources.go:145-182) on the lane's table (sign -1), and its exact inverse (+1)
-  __device__ __forceinline__ void adjust(uint32_t present, int base, bool non_g, uint32_t numa_id, bool apply, int sign) const {
+  // subtractResourcesFromNUMANodeList (numaresources.go:145-182) on the lane's table (sign -1), and its exact inverse (+1).  True when
+  // a charge leaves a zone below zero (two zones share the id, only one holds the request): the reference returns an error there
+  // (:172-175) and the Filter fwk.Error (filter.go:73-77), which is a Filter that did not succeed.  The whole charge is applied all the
+  // same, so that the inverse restores the table.
+  __device__ __forceinline__ bool adjust(uint32_t present, int base, bool non_g, uint32_t numa_id, bool apply, int sign) const {
     const int nz = nd->n_zones;
+    bool negative = false;
     for (int r = 0; r < a->n_res; ++r) {
       const int64_t q = a->nrt_rec[(base + r) * R + rr];
       const bool take = apply && ((present >> r) & 1u) && !(non_g && slot_is(r, SPX_NRT_SLOT_AFFINE)) && q != 0;
       for (int z = 0; z < nz; ++z) {
         if (!((nd->zone_present[z] >> r) & 1u)) continue;
-        if (take && nd->zone_id[z] == numa_id) at(z, r) += sign * q;
+        if (take && nd->zone_id[z] == numa_id) {
+          const int64_t now = at(z, r) + sign * q;
+          at(z, r) = now;
+          negative |= sign < 0 && nd->avail[z][r] + now < 0;
+        }
       }
     }
+    return negative;
   }
 
   // filter.go:179-245 on the lane's stack
@@ -179,7 +188,7 @@ struct NrtRefit {
       const bool ok = fits_any(cp, kCtrReq + c * kR, non_g, &id);
       const bool apply = mine && pass && ok;
       pass &= !(mine && !ok);
-      adjust(cp, kCtrReq + c * kR, non_g, id, apply, -1);
+      pass &= !adjust(cp, kCtrReq + c * kR, non_g, id, apply, -1);  // "inconsistent resource accounting": no later container is placed
       chosen |= static_cast<uint64_t>(apply ? id : 0u) << (8 * c);
       placed |= (apply ? 1u : 0u) << c;
     }

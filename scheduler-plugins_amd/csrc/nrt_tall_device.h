@@ -69,9 +69,8 @@ __device__ bool tall_fits_any(const A& a, const TallNode& nd, const AvView& av, 
   return ok && bitmask != 0;
 }
 
-// what the Filter's status cell holds where the reference returns fwk.Error instead of Unschedulable (the oracle's -1 as a byte; the
-// value NetworkOverhead's PreFilter error travels as)
-constexpr uint32_t kTallStError = 0xffu;
+// Where the reference returns fwk.Error instead of Unschedulable the Filter's status cell holds SPX_NRT_ST_ERROR (spx.h: the oracle's
+// -1 as a byte; the value NetworkOverhead's PreFilter error travels as).
 
 // subtractResourcesFromNUMANodeList numaresources.go:145-182 on the wave's working copy: every zone that carries the id is charged.
 // False when a charge leaves a zone below zero — two zones share the id and only one of them holds the request; the reference stops

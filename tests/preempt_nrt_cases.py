@@ -102,6 +102,15 @@ DIRECTIONS = {
 }
 
 
+# ---------------------------------------------------------------------------------------------------------------- zones that share a NUMA id
+def twin_models():
+    """ptol_nrt_cases.twin_models() for CapacityScheduling: every pod in namespace 2, which has no quota, next to namespace 1's lending
+    one (as one_node's), so that the Filter alone decides"""
+    res = lambda cpu, mem: {"v": [cpu, mem, 0, 0, 0, 0, 0, 0], "p": 0}
+    lending = {1: {"min": res(BIG, BIG), "max": res(BIG, BIG), "used": res(0, 0), "pods": set()}}
+    return NC.twin_models(ns=2, n_namespaces=3, quotas=lending)
+
+
 def load(e, t):
     """the quota tables, the preemption tables and the NRT side table onto the engine; flatten_preempt_nodes' columns plus "nrt\""""
     f = e.load_preempt_objects(t)

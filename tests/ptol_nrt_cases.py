@@ -131,6 +131,58 @@ def model(zones=(2,), max_ctrs=3, extra=False, one_slot=False, **kw):
     return decorate(TC.model(**kw), kw.get("seed", 0), zones, max_ctrs, extra, one_slot)
 
 
+# ---------------------------------------------------------------------------------------------------------------- zones that share a NUMA id
+# decorate() never writes one NUMA id twice (sorted(set(ids))), and the seeded shapes keep their tables.  These hand-built models do:
+# every node lists "node-0" twice (twins), container scope, placement present.  A container is charged to both twins
+# (subtractResourcesFromNUMANodeList), a victim's release lands on both (GetNRTPostPodsEviction walks every zone of the id), and where the
+# smaller twin goes below zero the Filter ends with fwk.Error "inconsistent resource accounting" — a Filter that did not succeed: the node
+# is no candidate, a victim is not reprieved.
+def twin_pod(key, prio, cpus, start=1000, row=-1, ns=0):
+    """a Guaranteed pod with one container per entry of `cpus` (millicores), 1 GiB each"""
+    total = sum(cpus)
+    mem = GiB * len(cpus)
+    ctrs = [{"name": f"c{j}", "requests": {"cpu": q, "memory": GiB}, "limits": {"cpu": q, "memory": GiB}} for j, q in enumerate(cpus)]
+    return {"key": key, "ns": ns, "prio": prio, "start": start, "fit": [total, mem, 0, 1, 0, 0, 0, 0], "req": {"v": [total, mem, 0, 0, 0, 0, 0, 0], "p": 0},
+            "pdbs": [], "terminating": False, "row": row, "pc": "", "scheduled_at": None, "never": False, "init_containers": [], "containers": ctrs}
+
+
+def twin_node(avail, pods, ids=(0, 0)):
+    """zones named by `ids` with 4 000 millicores allocatable and avail[z] available, 64 GiB with 32 available; every container of
+    every pod placed on NUMA id 0"""
+    zones = [{"name": f"node-{i}", "resources": [("cpu", 4000, a), ("memory", 64 * GiB, 32 * GiB)]} for i, a in zip(ids, avail)]
+    return {"present": True, "alloc": [16000, 128 * GiB, 0, 110, 0, 0, 0, 0], "pods": pods, "nominated": [], "alloc_names": {"cpu", "memory", "ephemeral-storage", "pods"},
+            "nrt": {"zones": zones, "policy": "single-numa-node", "scope": "container"}, "nrt_fresh": True,
+            "placement": {(p["key"], c["name"]): 0 for p in pods for c in p["containers"]}}
+
+
+def twin_model(ns=0, n_namespaces=1, quotas=None):
+    """nodes (the node's totals, 16 cpus, always take the preemptor; only the zones decide):
+      0 uneven     3 000 and 500 available, v (1 cpu).  With v gone the twins hold 4 000 and 1 500: a 3-cpu container fits the larger,
+                   is charged to both, and the smaller goes to -1 500 — the Error; a reading without the sign test lets it pass, and
+                   reprieves v as well
+      1 even       2 000 and 2 000, v (2 cpus): its release lands on both twins, 4 000 and 4 000, and two 2-cpu containers take both
+      2 reprieve   1 000 and 0, v1 (2 cpus, priority 10) and v2 (1 cpu, priority 20).  With both gone, 4 000 and 3 000 take 3 cpus.
+                   Re-adding v2 leaves 3 000 and 2 000: the larger holds the 3 cpus, the smaller goes below zero, v2 stays evicted
+      3 free       node 0's sizes under the ids 0 and 1: the duplicate-free twin
+    rows: p0 3 cpus, p1 2 + 2 cpus, p2 3 cpus (priority 100, 90, 80): in the loops p2 meets the nodes p0 and p1 have changed"""
+    P = lambda key, prio, cpus, start=1000, row=-1: twin_pod(key, prio, cpus, start, row, ns)
+    nodes = [twin_node([3000, 500], [P("u-v", 10, [1000])]),
+             twin_node([2000, 2000], [P("e-v", 10, [2000])]),
+             twin_node([1000, 0], [P("r-v1", 10, [2000], 1000), P("r-v2", 20, [1000], 2000)]),
+             twin_node([3000, 500], [P("f-v", 10, [1000])], ids=(0, 1))]
+    pending = [P("p0", 100, [3000], row=0), P("p1", 90, [2000, 2000], row=1), P("p2", 80, [3000], row=2)]
+    return {"n_namespaces": n_namespaces, "quotas": dict(quotas or {}), "pdbs": [], "nodes": nodes, "pending": pending, "classes": {}, "now": TC.GOLDEN_NOW}
+
+
+def twin_models(**kw):
+    """name -> model: all four nodes (the even twins and the release on both twins are decided next to the Error there); the uneven node
+    with its duplicate-free twin; the reprieve node alone"""
+    return {name: dict(twin_model(**kw), nodes=[twin_model(**kw)["nodes"][n] for n in cols]) for name, cols in TWIN_MODELS.items()}
+
+
+TWIN_MODELS = {"twins": (0, 1, 2, 3), "uneven": (0, 3), "reprieve": (2,)}
+
+
 def quantity(name, v):
     return f"{v}m" if name == "cpu" else v
 

@@ -225,3 +225,20 @@ def test_refusals_and_staleness(gpu_required):
         e.upload_preempt_nrt(g)
         CC.run(e, t)
         CC.assert_dry_run(e, f, t, CC.expected(**kw))
+
+
+# ---------------------------------------------------------------------------------------------------------------- zones that share a NUMA id
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(NC.TWIN_MODELS))
+def test_twin_zones_and_the_accounting_error(gpu_required, name):
+    """nodes that list one NUMA id twice: the charge and the release land on both twins, and a twin charged below zero is the Filter's
+    fwk.Error — no candidate, no reprieve (tests/test_nrt_refit_twins_host.py shows the models hold that edge)"""
+    m = CC.twin_models()[name]
+    trace = set()
+    want = CO.dry_run(m, m["pending"], trace=trace)
+    assert "accounting-error" in trace
+    t = CC.build_tables(m)
+    with Engine(0) as e:
+        f = CC.load(e, t)
+        CC.run(e, t)
+        CC.assert_dry_run(e, f, t, want)

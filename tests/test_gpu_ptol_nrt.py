@@ -248,3 +248,20 @@ def test_refusals_and_staleness(gpu_required):
         e.upload_preempt_nrt(g)
         NC.run(e, t)
         NC.assert_dry_run(e, f, t, NC.expected(**kw))
+
+
+# ---------------------------------------------------------------------------------------------------------------- zones that share a NUMA id
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(NC.TWIN_MODELS))
+def test_twin_zones_and_the_accounting_error(gpu_required, name):
+    """nodes that list one NUMA id twice: the charge and the release land on both twins, and a twin charged below zero is the Filter's
+    fwk.Error — no candidate, no reprieve (tests/test_nrt_refit_twins_host.py shows the models hold that edge)"""
+    m = NC.twin_models()[name]
+    trace = set()
+    want = NO.dry_run(m, m["pending"], trace=trace)
+    assert "accounting-error" in trace
+    t = NC.build_tables(m)
+    with Engine(0) as e:
+        f = NC.load(e, t)
+        NC.run(e, t)
+        NC.assert_dry_run(e, f, t, want)

@@ -235,3 +235,18 @@ def test_refusals_and_staleness(gpu_required):
         none = next(i for i, r in enumerate(want) if r["pick"][0] < 0)
         raises(ARG, lambda: e.preempt_victims(none, 0))
         assert e.preempt_victims(i, want[i]["pick"][0])[0] == ST["CANDIDATE"]  # the refusals left the results in place
+
+
+# ---------------------------------------------------------------------------------------------------------------- zones that share a NUMA id
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(NC.TWIN_MODELS))
+def test_twin_zones_and_the_accounting_error(gpu_required, name):
+    """the loop over nodes that list one NUMA id twice: a twin charged below zero is the Filter's fwk.Error at every step, and a later
+    row meets the node an earlier one changed"""
+    m = NC.twin_models()[name]
+    want = NSO.run(m, m["pending"])
+    t = NC.build_tables(m)
+    with Engine(0) as e:
+        f = NC.load(e, t)
+        NSC.run(e, t)
+        NSC.assert_sequential(e, f, t, want)
