@@ -67,7 +67,7 @@ int commit_coop(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t 
     for (int64_t i = row_begin; i < row_end; ++i)
       if (e->h_eff_ptr[static_cast<size_t>(i) + 1] - e->h_eff_ptr[static_cast<size_t>(i)] > spx::kCoopMaxEffects) return SPX_OK;
   }
-  const size_t P = static_cast<size_t>(e->n_pods), Nn = static_cast<size_t>(e->n_nodes);
+  const size_t Nn = static_cast<size_t>(e->n_nodes);
   spx::CoopArgs c{};
   c.use = plugin_mask;
   for (int k = 0; k < SPX_NUM_PLUGINS; ++k) c.w[k] = static_cast<int32_t>(e->plugin_weight[k]);
@@ -142,11 +142,9 @@ int commit_coop(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t 
     c.net_priv_node = static_cast<int32_t*>(e->d_coop_node.p);
     c.net_priv_max = static_cast<int64_t*>(e->d_coop_max.p);
   }
-  if ((rc = ensure(e, e->d_best, P * 20))) return rc;
-  c.best_score = static_cast<int64_t*>(e->d_best.p);
-  c.best_node = reinterpret_cast<int32_t*>(c.best_score + P);
-  c.best_ties = c.best_node + P;
-  c.best_feasible = c.best_ties + P;
+  BestRows best;
+  if ((rc = ensure_best(e, &best))) return rc;
+  c.best_score = best.score, c.best_node = best.node, c.best_ties = best.ties, c.best_feasible = best.feasible;
   if (tlp_missing_out && T) {
     if ((rc = ensure(e, e->d_commit, Nn * 8))) return rc;
     c.missing_out = static_cast<int64_t*>(e->d_commit.p);
@@ -195,7 +193,7 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
     return fail(e, SPX_ERR_STATE, "NetworkOverhead in a sequential commit needs spx_upload_net_commit (after the NetworkOverhead pod table)");
   if (Q && !(e->quota && e->q_has_min)) return fail(e, SPX_ERR_STATE, "CapacityScheduling in a sequential commit needs spx_quota_soa.min / min_present");
   if (e->ext_mask) return fail(e, SPX_ERR_STATE, "a caller feasibility mask is a frozen-snapshot input: clear it for the sequential commit");
-  const size_t Nn = static_cast<size_t>(e->n_nodes), P = static_cast<size_t>(e->n_pods), R = static_cast<size_t>(e->nrt_n_res);
+  const size_t Nn = static_cast<size_t>(e->n_nodes), R = static_cast<size_t>(e->nrt_n_res);
   const size_t NS = static_cast<size_t>(e->q_n_namespaces), S = SPX_QUOTA_SLOTS, K = static_cast<size_t>(e->net_n_keys);
   int rc;
   // ---- NetworkOverhead: pair lists with the slack the effects of this batch can fill
@@ -289,11 +287,12 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
   for (const Saved& sv : saved)
     SPX_HIP(e, hipMemcpyAsync(static_cast<char*>(e->d_commit_save.p) + sv.off, sv.buf->p, sv.bytes, hipMemcpyDeviceToDevice, e->stream));
   // ---- the loop
-  if ((rc = ensure(e, e->d_best, P * 20))) return rc;
+  BestRows best;
+  if ((rc = ensure_best(e, &best))) return rc;
   spx::CommitApplyArgs ca{};
   ca.n_nodes = e->n_nodes;
   ca.n_pods = e->n_pods;
-  ca.best_node = reinterpret_cast<const int32_t*>(static_cast<const int64_t*>(e->d_best.p) + P);
+  ca.best_node = best.node;
   la.best_node = ca.best_node;
   if (T) {
     ca.tlp_missing = static_cast<int64_t*>(e->d_tlp_missing.p);
@@ -422,11 +421,9 @@ int commit_with_filters(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, 
     return rc;
   }
   const size_t rows = static_cast<size_t>(row_end - row_begin);
-  const int64_t* ds = static_cast<const int64_t*>(e->d_best.p);
-  const int32_t* dn = reinterpret_cast<const int32_t*>(ds + P);
-  SPX_HIP(e, hipMemcpyAsync(weighted_score, ds + row_begin, rows * 8, hipMemcpyDeviceToHost, e->stream));
-  SPX_HIP(e, hipMemcpyAsync(node_idx, dn + row_begin, rows * 4, hipMemcpyDeviceToHost, e->stream));
-  if (n_ties) SPX_HIP(e, hipMemcpyAsync(n_ties, dn + P + row_begin, rows * 4, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(weighted_score, best.score + row_begin, rows * 8, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(node_idx, best.node + row_begin, rows * 4, hipMemcpyDeviceToHost, e->stream));
+  if (n_ties) SPX_HIP(e, hipMemcpyAsync(n_ties, best.ties + row_begin, rows * 4, hipMemcpyDeviceToHost, e->stream));
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   if (tlp_missing_out && !T) std::memset(tlp_missing_out, 0, Nn * 8);
   return SPX_OK;

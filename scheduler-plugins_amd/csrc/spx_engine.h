@@ -46,9 +46,7 @@ struct spx_engine {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool hold_ev0 = false;  // spx_decide times its preparatory spx_eval together with its own sweep
-  bool skip_alloc_masked = false;  // spx_decide folds Allocatable's masked normalisation into its argmax kernel
-  bool alloc_compact = false;      // k_alloc_prepare found the raw scores spanning less than 2^32 (AllocPrepArgs.rel is valid)
+  bool alloc_compact = false;     // k_alloc_prepare found the raw scores spanning less than 2^32 (AllocPrepArgs.rel is valid)
   bool timed = false;
   // last error: the engine's own copy (whoever failed last) under a lock; every thread also keeps the text of ITS last failure
   // (spx_last_error returns thread-local storage: concurrent readers may fail concurrently)
@@ -463,13 +461,28 @@ int tlp_build_order(spx_engine* e) {
 // something other than the unmasked broadcast wrote (or may have written) into Allocatable's score table, or the buffer changed
 void alloc_table_dirty(spx_engine* e) { e->alloc_kept = spx_engine::AllocKept{}; }
 
+// The checks of a plugin's tables that write nothing (spx_eval makes them all before its first allocation): a table the caller bound
+// must hold n_pods x row_stride ...
+int score_table_fits(const spx_engine* e, int plugin) {
+  if (e->score[plugin].external && (e->score_rows[plugin] < e->n_pods || e->score_stride[plugin] < e->row_stride))
+    return fail(e, SPX_ERR_STATE, "bound score table is smaller than n_pods x row_stride");
+  return SPX_OK;
+}
+int status_table_fits(const spx_engine* e, int plugin) {
+  if (e->status[plugin].external && e->status[plugin].bytes < static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride))
+    return fail(e, SPX_ERR_STATE, "bound status table is smaller than n_pods x row_stride");
+  return SPX_OK;
+}
+// ... and use the engine's row stride (an engine-owned table has it by construction: ensure_score_table)
+int score_table_stride(const spx_engine* e, int plugin) {
+  if (e->score[plugin].external && e->score_stride[plugin] != e->row_stride)
+    return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
+  return SPX_OK;
+}
+
 int ensure_score_table(spx_engine* e, int plugin) {
   DevBuf& b = e->score[plugin];
-  if (b.external) {
-    if (e->score_rows[plugin] < e->n_pods || e->score_stride[plugin] < e->row_stride)
-      return fail(e, SPX_ERR_STATE, "bound score table is smaller than n_pods x row_stride");
-    return SPX_OK;
-  }
+  if (b.external) return score_table_fits(e, plugin);
   const size_t had = b.p ? b.bytes : 0;
   int rc = ensure(e, b, static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride));
   if (plugin == SPX_PLUGIN_ALLOCATABLE && (rc || b.bytes != had)) alloc_table_dirty(e);  // (a new allocation may come back at the old address)
@@ -486,6 +499,36 @@ constexpr uint32_t kNormalizingPlugins =
 // plugins that own a uint8 score table
 constexpr bool plugin_has_score(int k) { return k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS || k == SPX_PLUGIN_SYSCHED; }
 
+// The status tables that narrow a pod's node list when `mask` is evaluated or summed: {NRT's, NetworkOverhead's, the caller's mask},
+// NULL = not in play (the layout of ProfileArgs.status and the scorers' other_status; NetworkOverhead's own sweep takes [0] and [2])
+void feasibility_status(const spx_engine* e, uint32_t mask, const uint8_t* out[3]) {
+  out[0] = (mask & (1u << SPX_PLUGIN_NRT)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
+  out[1] = (mask & (1u << SPX_PLUGIN_NETOVERHEAD)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
+  out[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
+}
+
+// d_best's four columns, [score int64 P | node int32 P | ties int32 P | feasible int32 P]
+struct BestRows {
+  int64_t* score;
+  int32_t *node, *ties, *feasible;
+};
+BestRows best_rows(const spx_engine* e) {
+  int64_t* score = static_cast<int64_t*>(e->d_best.p);
+  int32_t* node = reinterpret_cast<int32_t*>(score + e->n_pods);
+  return BestRows{score, node, node + e->n_pods, node + 2 * e->n_pods};
+}
+int ensure_best(spx_engine* e, BestRows* out) {
+  int rc = ensure(e, e->d_best, static_cast<size_t>(e->n_pods) * 20);
+  if (rc == SPX_OK) *out = best_rows(e);
+  return rc;
+}
+
+// What one evaluation is asked for besides its mask and rows (spx_decide's preparatory sweeps; spx_eval itself passes the defaults)
+struct EvalCall {
+  bool hold_ev0 = false;           // the caller has recorded ev0 and times this evaluation together with its own sweep
+  bool skip_alloc_masked = false;  // the caller folds Allocatable's masked normalisation into its argmax kernel: the table is not written
+};
+
 // rows [b, e) of `plugin` hold results of an spx_eval
 int rows_evaluated(const spx_engine* e, int plugin, int64_t b, int64_t en) {
   const spx_engine::EvalInfo& i = e->eval_info[plugin];
@@ -497,21 +540,24 @@ int rows_evaluated(const spx_engine* e, int plugin, int64_t b, int64_t en) {
 
 int ensure_status_table(spx_engine* e, int plugin) {
   DevBuf& b = e->status[plugin];
-  const size_t need = static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride);
-  if (b.external) {
-    if (b.bytes < need) return fail(e, SPX_ERR_STATE, "bound status table is smaller than n_pods x row_stride");
-    return SPX_OK;
-  }
-  return ensure(e, b, need);
+  if (b.external) return status_table_fits(e, plugin);
+  return ensure(e, b, static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride));
 }
 
-int prepare_alloc(spx_engine* e) {
+// what prepare_alloc refuses, from host state alone
+int alloc_check(const spx_engine* e) {
   if (e->alloc_ready) return SPX_OK;
   if (!e->d_alloc.p) return fail(e, SPX_ERR_STATE, "Allocatable: spx_upload_alloc_nodes not called");
   if (e->alloc_n_res != static_cast<int32_t>(e->alloc_res.size()))
     return fail(e, SPX_ERR_STATE, "Allocatable: uploaded table has a different resource count than the params");
-  int rc = upload(e, e->d_alloc_w, e->alloc_weight.data(), e->alloc_weight.size() * sizeof(int64_t));
+  return SPX_OK;
+}
+
+int prepare_alloc(spx_engine* e) {
+  if (e->alloc_ready) return SPX_OK;
+  int rc = alloc_check(e);
   if (rc) return rc;
+  if ((rc = upload(e, e->d_alloc_w, e->alloc_weight.data(), e->alloc_weight.size() * sizeof(int64_t)))) return rc;
   if ((rc = ensure(e, e->d_alloc_raw, static_cast<size_t>(e->n_nodes) * sizeof(int64_t)))) return rc;
   if ((rc = ensure(e, e->d_alloc_rel, static_cast<size_t>(e->row_stride + 4) * sizeof(uint32_t)))) return rc;
   // (The comparison is a launch of its own, kernels_delta.hip's k_rows_equal, on a copy of the old row — not a few lines inside
@@ -874,7 +920,7 @@ int ensure_nrt_creq(spx_engine* e, bool force = false);
 
 // what an NRT evaluation of an engine with tall nodes needs before its first launch, from host state alone: the side table, and with
 // LeastNUMANodes no tall node above that strategy's zone limit.  spx_eval and spx_fetch_raw ask before they write anything.
-int nrt_tall_ready(spx_engine* e) {
+int nrt_tall_ready(const spx_engine* e) {
   if (e->h_nrt_tall_nodes.empty()) return SPX_OK;
   if (!e->nrt_tall_ok)
     return fail(e, SPX_ERR_STATE, "NRT: the node table has nodes with more than 8 NUMA zones: call spx_upload_nrt_tall_nodes after spx_upload_nrt_nodes");
@@ -1061,14 +1107,18 @@ int64_t net_cost_bound(const spx_engine* e, int64_t extra_pairs) {
 // the 64-bit sweep (kernels_network_wide.hip) runs when the device holds int64 cost matrices or the bound reaches 2^31
 bool net_wide(const spx_engine* e, int64_t extra_pairs) { return e->net_wide_dev || net_cost_bound(e, extra_pairs) >= (int64_t{1} << 31); }
 
-// Before a NetworkOverhead launch: refuses a snapshot whose bound reaches 2^63, and widens narrow cost matrices on the device (once:
-// they stay int64 until the next topology upload) when the bound asks for the 64-bit sweep.  `when`: which bound, for the message.
-int net_prepare(spx_engine* e, int64_t extra_pairs, const char* when) {
+// Before a NetworkOverhead launch: net_bound_check refuses a snapshot whose bound reaches 2^63 (host state alone), and net_prepare
+// then widens narrow cost matrices on the device (once: they stay int64 until the next topology upload) when the bound asks for the
+// 64-bit sweep.  `when`: which bound, for the message.
+int net_bound_check(const spx_engine* e, int64_t extra_pairs, const char* when) {
   if (net_cost_bound(e, extra_pairs) == std::numeric_limits<int64_t>::max())
     return fail(e, SPX_ERR_ARG, std::string("NetworkOverhead: accumulated cost of a node may reach 2^63 (cost entries x dependency pairs") + when +
                                     "); the reference's own int64 sum would wrap there");
-  if (e->net_wide_dev || !net_wide(e, extra_pairs)) return SPX_OK;
-  int rc;
+  return SPX_OK;
+}
+int net_prepare(spx_engine* e, int64_t extra_pairs, const char* when) {
+  int rc = net_bound_check(e, extra_pairs, when);
+  if (rc || e->net_wide_dev || !net_wide(e, extra_pairs)) return rc;
   if ((rc = upload(e, e->d_net_rcost, e->h_net_rcost.data(), e->h_net_rcost.size() * 8)) || (rc = upload(e, e->d_net_zcost, e->h_net_zcost.data(), e->h_net_zcost.size() * 8)))
     return rc;
   SPX_HIP(e, hipStreamSynchronize(e->stream));

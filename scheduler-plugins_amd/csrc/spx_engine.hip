@@ -242,105 +242,156 @@ int spx_set_plugin_weights(spx_engine* e, const int64_t* weights) {
   return SPX_OK;
 }
 
-int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end) {
-  if (!e) return SPX_ERR_ARG;
-  SPX_HIP(e, hipSetDevice(e->device));
+}  // extern "C"
+
+// ---- spx_eval: eval_rows checks the call (eval_check), readies the tables and the scratch (prepare_*), and issues the launches
+// between ev0 and ev1 (launch_*), one function per plugin.  Nothing is allocated, launched or written before eval_check has passed.
+namespace {
+
+// the plugins of one evaluation's mask
+struct EvalPlugins {
+  uint32_t mask;
+  bool alloc, tlp, lvrb, nrt, net, quota, lroc, peaks, sysched, cosched;
+  bool masked;  // Allocatable's NormalizeScore runs over each pod's feasible nodes as soon as any Filter is in play
+};
+
+EvalPlugins eval_plugins(const spx_engine* e, uint32_t mask) {
+  auto has = [mask](int plugin) { return ((mask >> plugin) & 1u) != 0; };
+  const bool nrt = has(SPX_PLUGIN_NRT), net = has(SPX_PLUGIN_NETOVERHEAD);
+  return EvalPlugins{mask, has(SPX_PLUGIN_ALLOCATABLE), has(SPX_PLUGIN_TLP), has(SPX_PLUGIN_LVRB), nrt, net, has(SPX_PLUGIN_CAPACITY), has(SPX_PLUGIN_LROC),
+                     has(SPX_PLUGIN_PEAKS), has(SPX_PLUGIN_SYSCHED), has(SPX_PLUGIN_COSCHED), nrt || net || e->ext_mask};
+}
+
+// Every SPX_ERR_ARG / SPX_ERR_STATE answer of an evaluation, from host state alone: a call refused here has allocated nothing,
+// launched nothing and written no engine field.  The order is the order in which a call with several faults names them.
+int eval_check(const spx_engine* e, const EvalPlugins& f, int64_t row_begin, int64_t row_end) {
   const uint32_t known = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_TLP) | (1u << SPX_PLUGIN_LVRB) | (1u << SPX_PLUGIN_NRT) |
                          (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY) | (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS) |
                          (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_COSCHED);
-  if (plugin_mask == 0 || (plugin_mask & ~known)) return fail(e, SPX_ERR_ARG, "plugin mask has unsupported bits");
-  const bool R = plugin_mask & (1u << SPX_PLUGIN_LROC);
-  if (R && !(e->tri_nodes && e->lroc_nodes && e->lroc_pods)) return fail(e, SPX_ERR_STATE, "LowRiskOverCommitment node/pod tables not uploaded");
-  const bool K = plugin_mask & (1u << SPX_PLUGIN_PEAKS);
-  if (K && !(e->peaks_nodes && e->peaks_pods)) return fail(e, SPX_ERR_STATE, "Peaks node/pod tables not uploaded");
-  const bool Y = plugin_mask & (1u << SPX_PLUGIN_SYSCHED);
-  if (Y && !(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
-  if (Y && e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
-  if (Y && e->row_indirect) return fail(e, SPX_ERR_STATE, "SySched is not part of the sequential commit loop");
-  const bool G = plugin_mask & (1u << SPX_PLUGIN_COSCHED);
-  if (G && !e->cosched) return fail(e, SPX_ERR_STATE, "Coscheduling tables not uploaded");
-  if (G && e->row_indirect) return fail(e, SPX_ERR_STATE, "Coscheduling is not part of the sequential commit loop");
-  const bool Q = plugin_mask & (1u << SPX_PLUGIN_CAPACITY);
-  if (Q && !e->quota) return fail(e, SPX_ERR_STATE, "CapacityScheduling quota tables not uploaded");
-  if (e->n_nodes <= 0 && plugin_mask != (1u << SPX_PLUGIN_CAPACITY)) return fail(e, SPX_ERR_STATE, "no node table uploaded");
-  const bool A = plugin_mask & (1u << SPX_PLUGIN_ALLOCATABLE);
-  const bool T = plugin_mask & (1u << SPX_PLUGIN_TLP);
-  const bool L = plugin_mask & (1u << SPX_PLUGIN_LVRB);
-  if ((T || L) && !(e->tri_nodes && e->tri_pods)) return fail(e, SPX_ERR_STATE, "trimaran node/pod tables not uploaded");
+  if (f.mask == 0 || (f.mask & ~known)) return fail(e, SPX_ERR_ARG, "plugin mask has unsupported bits");
+  if (f.lroc && !(e->tri_nodes && e->lroc_nodes && e->lroc_pods)) return fail(e, SPX_ERR_STATE, "LowRiskOverCommitment node/pod tables not uploaded");
+  if (f.peaks && !(e->peaks_nodes && e->peaks_pods)) return fail(e, SPX_ERR_STATE, "Peaks node/pod tables not uploaded");
+  if (f.sysched && !(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
+  if (f.sysched && e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
+  if (f.sysched && e->row_indirect) return fail(e, SPX_ERR_STATE, "SySched is not part of the sequential commit loop");
+  if (f.cosched && !e->cosched) return fail(e, SPX_ERR_STATE, "Coscheduling tables not uploaded");
+  if (f.cosched && e->row_indirect) return fail(e, SPX_ERR_STATE, "Coscheduling is not part of the sequential commit loop");
+  if (f.quota && !e->quota) return fail(e, SPX_ERR_STATE, "CapacityScheduling quota tables not uploaded");
+  if (e->n_nodes <= 0 && f.mask != (1u << SPX_PLUGIN_CAPACITY)) return fail(e, SPX_ERR_STATE, "no node table uploaded");
+  if ((f.tlp || f.lvrb) && !(e->tri_nodes && e->tri_pods)) return fail(e, SPX_ERR_STATE, "trimaran node/pod tables not uploaded");
   if (e->n_pods <= 0) {
-    if (T || L) return fail(e, SPX_ERR_STATE, "no pod table uploaded");
+    if (f.tlp || f.lvrb) return fail(e, SPX_ERR_STATE, "no pod table uploaded");
     return fail(e, SPX_ERR_STATE, "n_pods unknown: upload a pod table first");
   }
   if (row_begin < 0 || row_end > e->n_pods || row_begin > row_end) return fail(e, SPX_ERR_ARG, "row range out of bounds");
   int rc;
-  const bool N = plugin_mask & (1u << SPX_PLUGIN_NRT);
-  if (N && e->nrt_wide && !(e->nrtw_slots && e->nrtw_nodes && e->nrtw_pods)) return fail(e, SPX_ERR_STATE, "NRT wide slot/node/pod tables not uploaded");
-  if (N && !e->nrt_wide && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
-  if (N && !e->nrt_wide && !e->nrt_long_ok)
+  if (f.nrt && e->nrt_wide && !(e->nrtw_slots && e->nrtw_nodes && e->nrtw_pods)) return fail(e, SPX_ERR_STATE, "NRT wide slot/node/pod tables not uploaded");
+  if (f.nrt && !e->nrt_wide && !(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
+  if (f.nrt && !e->nrt_wide && !e->nrt_long_ok)
     return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
-  if (N && !e->nrt_wide && (rc = nrt_tall_ready(e))) return rc;
-  if (A && (rc = prepare_alloc(e))) return rc;
-  const bool W = plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD);
-  if (W && !(e->net_nodes && e->net_topo && e->net_pods)) return fail(e, SPX_ERR_STATE, "NetworkOverhead node/topology/pod tables not uploaded");
+  if (f.nrt && !e->nrt_wide && (rc = nrt_tall_ready(e))) return rc;
+  if (f.alloc && (rc = alloc_check(e))) return rc;
+  if (f.net && !(e->net_nodes && e->net_topo && e->net_pods)) return fail(e, SPX_ERR_STATE, "NetworkOverhead node/topology/pod tables not uploaded");
   // the reference accumulates a node's cost in int64 (networkoverhead.go:605-633); the narrow sweeps add in int32 and keep the Filter
   // verdict in the sign bit, which is exact as long as (largest cost entry) x (most pairs of any workload) stays below 2^31; from
   // there on the 64-bit sweep runs (kernels_network_wide.hip), up to the 2^63 at which the reference's own sum could wrap
-  if (W && (rc = net_prepare(e, 0, ""))) return rc;
+  if (f.net && (rc = net_bound_check(e, 0, ""))) return rc;
+  // tables the caller bound: large enough, and (all of them share row_stride when engine-owned) with the engine's row stride
   for (int p = 0; p < 5; ++p)
-    if ((plugin_mask & (1u << p)) && (rc = ensure_score_table(e, p))) return rc;
-  if (R && (rc = ensure_score_table(e, SPX_PLUGIN_LROC))) return rc;
-  if (R && e->score_stride[SPX_PLUGIN_LROC] != e->row_stride)
-    return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-  if (R && (rc = ensure(e, e->d_lroc_tab, static_cast<size_t>(e->row_stride) * spx::kLrocTabCols * sizeof(double)))) return rc;
-  if (K && (rc = ensure_score_table(e, SPX_PLUGIN_PEAKS))) return rc;
-  if (K && e->score_stride[SPX_PLUGIN_PEAKS] != e->row_stride)
-    return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-  if (K && ((rc = ensure(e, e->d_pk_min, static_cast<size_t>(e->n_pods) * 8)) || (rc = ensure(e, e->d_pk_max, static_cast<size_t>(e->n_pods) * 8)) ||
-            (rc = ensure(e, e->d_pk_rowc, static_cast<size_t>(e->n_pods) * 16)) || (rc = ensure(e, e->d_pk_tab, static_cast<size_t>(e->row_stride) * 96))))
-    return rc;
-  if (N && (rc = ensure_status_table(e, SPX_PLUGIN_NRT))) return rc;
-  if (W && (rc = ensure_status_table(e, SPX_PLUGIN_NETOVERHEAD))) return rc;
-  // SySched's raw table: as many distinct sets per chunk as the scratch budget holds (and a launch's grid takes)
-  int64_t sy_per_chunk = 0;
-  if (Y) {
-    if ((rc = ensure_score_table(e, SPX_PLUGIN_SYSCHED))) return rc;
-    if (e->score_stride[SPX_PLUGIN_SYSCHED] != e->row_stride)
-      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-    const size_t row_bytes = static_cast<size_t>(e->row_stride) * sizeof(int32_t);
-    sy_per_chunk = std::min<int64_t>(std::max<int64_t>(1, static_cast<int64_t>(spx::kSyschedRawBudget / row_bytes)), spx::kSyschedMaxChunkSets);
-    if ((rc = ensure(e, e->d_sy_raw, static_cast<size_t>(std::min<int64_t>(sy_per_chunk, e->sy_n_sets)) * row_bytes)) ||
-        (rc = ensure(e, e->d_sy_max, static_cast<size_t>(e->sy_n_sets) * sizeof(int32_t))))
-      return rc;
-  }
+    if ((f.mask & (1u << p)) && (rc = score_table_fits(e, p))) return rc;
+  if (f.lroc && ((rc = score_table_fits(e, SPX_PLUGIN_LROC)) || (rc = score_table_stride(e, SPX_PLUGIN_LROC)))) return rc;
+  if (f.peaks && ((rc = score_table_fits(e, SPX_PLUGIN_PEAKS)) || (rc = score_table_stride(e, SPX_PLUGIN_PEAKS)))) return rc;
+  if (f.nrt && (rc = status_table_fits(e, SPX_PLUGIN_NRT))) return rc;
+  if (f.net && (rc = status_table_fits(e, SPX_PLUGIN_NETOVERHEAD))) return rc;
+  if (f.sysched && ((rc = score_table_fits(e, SPX_PLUGIN_SYSCHED)) || (rc = score_table_stride(e, SPX_PLUGIN_SYSCHED)))) return rc;
+  for (int p = 0; p < 3; ++p)
+    if ((f.mask & (1u << p)) && (rc = score_table_stride(e, p))) return rc;
+  if (f.nrt && (rc = score_table_stride(e, SPX_PLUGIN_NRT))) return rc;
+  if (f.nrt && e->nrt_wide && e->row_indirect)
+    return fail(e, SPX_ERR_STATE, "NRT: the sequential commit loop does not take a wide snapshot (more than 8 resource slots)");
+  if (f.net && (rc = score_table_stride(e, SPX_PLUGIN_NETOVERHEAD))) return rc;
+  if (f.lroc && e->lroc_loop_form >= 0 && row_end - row_begin != 1)
+    return fail(e, SPX_ERR_STATE, "internal: the commit loop evaluates LowRiskOverCommitment one row at a time");
+  if (f.peaks && e->peaks_loop_row && row_end - row_begin != 1) return fail(e, SPX_ERR_STATE, "internal: the commit loop evaluates Peaks one row at a time");
+  return SPX_OK;
+}
 
+// ---- preparation: what has to exist before ev0
+int prepare_tables(spx_engine* e, const EvalPlugins& f) {
+  int rc;
+  if (f.alloc && (rc = prepare_alloc(e))) return rc;
+  if (f.net && (rc = net_prepare(e, 0, ""))) return rc;
+  for (int p = 0; p < SPX_NUM_PLUGINS; ++p)
+    if ((f.mask & (1u << p)) && plugin_has_score(p) && (rc = ensure_score_table(e, p))) return rc;
+  if (f.nrt && (rc = ensure_status_table(e, SPX_PLUGIN_NRT))) return rc;
+  if (f.net && (rc = ensure_status_table(e, SPX_PLUGIN_NETOVERHEAD))) return rc;
+  return SPX_OK;
+}
+
+int prepare_lroc(spx_engine* e) { return ensure(e, e->d_lroc_tab, static_cast<size_t>(e->row_stride) * spx::kLrocTabCols * sizeof(double)); }
+
+int prepare_peaks(spx_engine* e) {
+  int rc;
+  if ((rc = ensure(e, e->d_pk_min, static_cast<size_t>(e->n_pods) * 8)) || (rc = ensure(e, e->d_pk_max, static_cast<size_t>(e->n_pods) * 8)) ||
+      (rc = ensure(e, e->d_pk_rowc, static_cast<size_t>(e->n_pods) * 16)) || (rc = ensure(e, e->d_pk_tab, static_cast<size_t>(e->row_stride) * 96)))
+    return rc;
+  return SPX_OK;
+}
+
+// SySched's raw table: as many distinct sets per chunk as the scratch budget holds (and a launch's grid takes)
+int prepare_sysched(spx_engine* e, int64_t* per_chunk) {
+  const size_t row_bytes = static_cast<size_t>(e->row_stride) * sizeof(int32_t);
+  *per_chunk = std::min<int64_t>(std::max<int64_t>(1, static_cast<int64_t>(spx::kSyschedRawBudget / row_bytes)), spx::kSyschedMaxChunkSets);
+  int rc;
+  if ((rc = ensure(e, e->d_sy_raw, static_cast<size_t>(std::min<int64_t>(*per_chunk, e->sy_n_sets)) * row_bytes)) ||
+      (rc = ensure(e, e->d_sy_max, static_cast<size_t>(e->sy_n_sets) * sizeof(int32_t))))
+    return rc;
+  return SPX_OK;
+}
+
+// the trimaran launch (Allocatable's unmasked broadcast, TLP, LVRB) and what becomes of Allocatable's table in this evaluation
+struct TrimaranStep {
   spx::TrimaranArgs a{};
+  bool alloc_keepable = false;  // the unmasked broadcast goes into an engine-owned table, by a host-side row range
+  bool alloc_kept_now = false;  // ... and these rows already hold it (SPX_OPT_ALLOC_TABLE_KEEP): the sweep leaves Allocatable's stores out
+};
+
+// TargetLoadPacking's float32 node constants and ambiguity table, for spx_eval's sweep and spx_decide's fused one
+int tlp_scratch(spx_engine* e, spx::TrimaranArgs& a) {
+  int rc;
+  if ((rc = ensure(e, e->d_tlp_fast, static_cast<size_t>(spx::round_up(e->row_stride, 1024)) * 4 * sizeof(float)))) return rc;
+  a.tlp_fast = static_cast<float*>(e->d_tlp_fast.p);
+  if (!e->d_tlp_amb.p) e->tlp_amb_built = false;
+  if ((rc = ensure(e, e->d_tlp_amb, static_cast<size_t>(spx::kTlpAmbSize) * 4))) return rc;
+  a.tlp_amb = static_cast<uint32_t*>(e->d_tlp_amb.p);
+  a.tlp_amb_size = spx::kTlpAmbSize;
+  a.tlp_amb_built = &e->tlp_amb_built;
+  a.tlp_amb_geom = e->tlp_amb_geom;
+  return SPX_OK;
+}
+
+int prepare_trimaran(spx_engine* e, const EvalPlugins& f, const EvalCall& call, int64_t row_begin, int64_t row_end, TrimaranStep* t) {
+  spx::TrimaranArgs& a = t->a;
   fill_trimaran(e, a);
   a.row_begin = row_begin;
   a.row_end = row_end;
-  // all three tables share row_stride when engine-owned; bound tables must use it too
-  for (int p = 0; p < 3; ++p)
-    if ((plugin_mask & (1u << p)) && e->score_stride[p] != e->row_stride)
-      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-  // Allocatable's NormalizeScore runs over each pod's feasible nodes as soon as any Filter is in play
-  const bool masked = N || W || e->ext_mask;
-  bool alloc_by_net = false;  // Allocatable's masked table written by the NetworkOverhead sweep (SPX_OPT_NET_ALLOC_FUSED)
-  a.out_alloc = (A && !masked) ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p) : nullptr;
+  a.out_alloc = (f.alloc && !f.masked) ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p) : nullptr;
   // the unmasked table is the broadcast of d_alloc_norm, whatever the pod batch: rows that already hold the broadcast of the row in
   // place are not written again (SPX_OPT_ALLOC_TABLE_KEEP) — the sweeps run their instantiations without Allocatable's stores.
   // Only in an engine-owned table (a bound one is the caller's memory), and not for the commit loop's device-side row.
   const DevBuf& alloc_table = e->score[SPX_PLUGIN_ALLOCATABLE];
-  const bool alloc_keepable = a.out_alloc && !alloc_table.external && !e->row_indirect;
-  bool alloc_kept_now = false;
-  if (alloc_keepable && e->option[SPX_OPT_ALLOC_TABLE_KEEP] && row_end > row_begin) {
+  t->alloc_keepable = a.out_alloc && !alloc_table.external && !e->row_indirect;
+  if (t->alloc_keepable && e->option[SPX_OPT_ALLOC_TABLE_KEEP] && row_end > row_begin) {
     const spx_engine::AllocKept& k = e->alloc_kept;
-    alloc_kept_now = k.buf == alloc_table.p && k.stride == e->score_stride[SPX_PLUGIN_ALLOCATABLE] && k.epoch == e->alloc_epoch && k.end > k.begin &&
-                     row_begin >= k.begin && row_end <= k.end;
-    if (alloc_kept_now) a.out_alloc = nullptr;
+    t->alloc_kept_now = k.buf == alloc_table.p && k.stride == e->score_stride[SPX_PLUGIN_ALLOCATABLE] && k.epoch == e->alloc_epoch && k.end > k.begin &&
+                        row_begin >= k.begin && row_end <= k.end;
+    if (t->alloc_kept_now) a.out_alloc = nullptr;
   }
-  if (A && masked && !e->skip_alloc_masked) alloc_table_dirty(e);  // a masked normalisation is about to write these rows (launch_net or launch_alloc_masked)
-  a.out_tlp = T ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_TLP].p) : nullptr;
-  a.out_lvrb = L ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_LVRB].p) : nullptr;
-  if (L) {
+  if (f.alloc && f.masked && !call.skip_alloc_masked) alloc_table_dirty(e);  // a masked normalisation is about to write these rows (launch_net or launch_alloc_masked)
+  a.out_tlp = f.tlp ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_TLP].p) : nullptr;
+  a.out_lvrb = f.lvrb ? static_cast<uint8_t*>(e->score[SPX_PLUGIN_LVRB].p) : nullptr;
+  int rc;
+  if (f.lvrb) {
     if ((rc = ensure(e, e->d_lv_exact, static_cast<size_t>(e->n_nodes) * 8 * sizeof(double)))) return rc;
     a.lv_exact = static_cast<double*>(e->d_lv_exact.p);
     if (!e->d_lv_exact.p || !e->d_lv_fast.p || !e->d_lv_amb.p) e->lv_amb_built = false;
@@ -351,15 +402,8 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
     a.lv_amb_built = &e->lv_amb_built;
     a.lv_amb_geom = e->lv_amb_geom;
   }
-  if (T) {
-    if ((rc = ensure(e, e->d_tlp_fast, static_cast<size_t>(spx::round_up(e->row_stride, 1024)) * 4 * sizeof(float)))) return rc;
-    a.tlp_fast = static_cast<float*>(e->d_tlp_fast.p);
-    if (!e->d_tlp_amb.p) e->tlp_amb_built = false;
-    if ((rc = ensure(e, e->d_tlp_amb, static_cast<size_t>(spx::kTlpAmbSize) * 4))) return rc;
-    a.tlp_amb = static_cast<uint32_t*>(e->d_tlp_amb.p);
-    a.tlp_amb_size = spx::kTlpAmbSize;
-    a.tlp_amb_built = &e->tlp_amb_built;
-    a.tlp_amb_geom = e->tlp_amb_geom;
+  if (f.tlp) {
+    if ((rc = tlp_scratch(e, a))) return rc;
     // pod classes: a whole-batch evaluation whose order describes the column in place (every writer of d_tlp_pod clears the flag
     // before it writes and rebuilds the order after), when enough of its rows are copies to pay for the scattered row order
     e->tlp_last_form = 0;
@@ -370,226 +414,269 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       if (cls_opt == 2 ? copied > 0 : copied * 100 >= spx::kTlpClassMinCopyPct * e->n_pods) a.tlp_order = static_cast<const int32_t*>(e->d_tlp_order.p);
     }
   }
-  if (!e->hold_ev0) SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
-  if (Q) {
-    if ((rc = ensure(e, e->d_q_status, static_cast<size_t>(e->n_pods)))) return rc;
-    spx::QuotaArgs qa{};
-    qa.row_begin = row_begin;
-    qa.row_end = row_end;
-    qa.row_ptr = e->row_indirect;
-    qa.n_namespaces = e->q_n_namespaces;
-    qa.pod_ns = static_cast<const int32_t*>(e->d_q_pod_ns.p);
-    qa.pod_priority = static_cast<const int32_t*>(e->d_q_pod_prio.p);
-    qa.pod_req = static_cast<const int64_t*>(e->d_q_pod_req.p);
-    qa.pod_req_present = static_cast<const uint8_t*>(e->d_q_pod_reqp.p);
-    qa.has_quota = static_cast<const uint8_t*>(e->d_q_has.p);
-    qa.used = static_cast<const int64_t*>(e->d_q_used.p);
-    qa.max = static_cast<const int64_t*>(e->d_q_max.p);
-    qa.max_present = static_cast<const uint8_t*>(e->d_q_maxp.p);
-    std::memcpy(qa.agg_used, e->q_agg_used, sizeof qa.agg_used);
-    std::memcpy(qa.agg_min, e->q_agg_min, sizeof qa.agg_min);
-    qa.agg_used_present = e->q_agg_used_present;
-    qa.agg_min_present = e->q_agg_min_present;
-    qa.agg_used_dyn = e->q_agg_dyn;
-    qa.other_nominated = static_cast<const int64_t*>(e->d_q_other.p);
-    qa.other_nominated_present = static_cast<const uint8_t*>(e->d_q_otherp.p);
-    qa.nom_ptr = static_cast<const int32_t*>(e->d_q_nom_ptr.p);
-    qa.nom_priority = static_cast<const int32_t*>(e->d_q_nom_prio.p);
-    qa.nom_pending_index = static_cast<const int64_t*>(e->d_q_nom_idx.p);
-    qa.nom_req = static_cast<const int64_t*>(e->d_q_nom_req.p);
-    qa.nom_req_present = static_cast<const uint8_t*>(e->d_q_nom_reqp.p);
-    qa.out_status = static_cast<uint8_t*>(e->d_q_status.p);
-    spx::launch_quota(qa, e->stream);
-    SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+// ---- the launches between ev0 and ev1, in this order
+int launch_quota_rows(spx_engine* e, int64_t row_begin, int64_t row_end) {
+  int rc;
+  if ((rc = ensure(e, e->d_q_status, static_cast<size_t>(e->n_pods)))) return rc;
+  spx::QuotaArgs qa{};
+  qa.row_begin = row_begin;
+  qa.row_end = row_end;
+  qa.row_ptr = e->row_indirect;
+  qa.n_namespaces = e->q_n_namespaces;
+  qa.pod_ns = static_cast<const int32_t*>(e->d_q_pod_ns.p);
+  qa.pod_priority = static_cast<const int32_t*>(e->d_q_pod_prio.p);
+  qa.pod_req = static_cast<const int64_t*>(e->d_q_pod_req.p);
+  qa.pod_req_present = static_cast<const uint8_t*>(e->d_q_pod_reqp.p);
+  qa.has_quota = static_cast<const uint8_t*>(e->d_q_has.p);
+  qa.used = static_cast<const int64_t*>(e->d_q_used.p);
+  qa.max = static_cast<const int64_t*>(e->d_q_max.p);
+  qa.max_present = static_cast<const uint8_t*>(e->d_q_maxp.p);
+  std::memcpy(qa.agg_used, e->q_agg_used, sizeof qa.agg_used);
+  std::memcpy(qa.agg_min, e->q_agg_min, sizeof qa.agg_min);
+  qa.agg_used_present = e->q_agg_used_present;
+  qa.agg_min_present = e->q_agg_min_present;
+  qa.agg_used_dyn = e->q_agg_dyn;
+  qa.other_nominated = static_cast<const int64_t*>(e->d_q_other.p);
+  qa.other_nominated_present = static_cast<const uint8_t*>(e->d_q_otherp.p);
+  qa.nom_ptr = static_cast<const int32_t*>(e->d_q_nom_ptr.p);
+  qa.nom_priority = static_cast<const int32_t*>(e->d_q_nom_prio.p);
+  qa.nom_pending_index = static_cast<const int64_t*>(e->d_q_nom_idx.p);
+  qa.nom_req = static_cast<const int64_t*>(e->d_q_nom_req.p);
+  qa.nom_req_present = static_cast<const uint8_t*>(e->d_q_nom_reqp.p);
+  qa.out_status = static_cast<uint8_t*>(e->d_q_status.p);
+  spx::launch_quota(qa, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+// the PodGroup gate: per snapshot the scan and the groups' verdicts (until the next upload), per call the rows' status bytes
+int launch_cosched_rows(spx_engine* e, int64_t row_begin, int64_t row_end) {
+  spx::CoschedArgs ga{};
+  fill_cosched(e, ga);
+  ga.row_begin = row_begin;
+  ga.row_end = row_end;
+  if (!e->cs_gate_valid) {
+    spx::launch_cosched_gate(ga, e->stream);
+    e->cs_gate_valid = true;
+    e->cs_last_walk = e->cs_n_walk;
+    e->cs_row_begin = e->cs_row_end = 0;
   }
-  if (G) {  // the PodGroup gate: per snapshot the scan and the groups' verdicts (until the next upload), per call the rows' status bytes
-    spx::CoschedArgs ga{};
-    fill_cosched(e, ga);
-    ga.row_begin = row_begin;
-    ga.row_end = row_end;
-    if (!e->cs_gate_valid) {
-      spx::launch_cosched_gate(ga, e->stream);
-      e->cs_gate_valid = true;
-      e->cs_last_walk = e->cs_n_walk;
-      e->cs_row_begin = e->cs_row_end = 0;
-    }
-    spx::launch_cosched_status(ga, e->stream);
-    SPX_HIP(e, hipGetLastError());
-    if (row_end > row_begin) {
-      if (e->cs_row_end > e->cs_row_begin && row_begin <= e->cs_row_end && row_end >= e->cs_row_begin)
-        e->cs_row_begin = std::min(e->cs_row_begin, row_begin), e->cs_row_end = std::max(e->cs_row_end, row_end);
-      else
-        e->cs_row_begin = row_begin, e->cs_row_end = row_end;
+  spx::launch_cosched_status(ga, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  if (row_end > row_begin) {
+    if (e->cs_row_end > e->cs_row_begin && row_begin <= e->cs_row_end && row_end >= e->cs_row_begin)
+      e->cs_row_begin = std::min(e->cs_row_begin, row_begin), e->cs_row_end = std::max(e->cs_row_end, row_end);
+    else
+      e->cs_row_begin = row_begin, e->cs_row_end = row_end;
+  }
+  return SPX_OK;
+}
+
+// What the dense NRT sweep of one evaluation launches: the arguments, whether one representative per pod class is swept and copied
+// to its class, and what d_nrt_fz holds once the fused launch has run (gen 0: matches no later sweep)
+struct NrtDensePlan {
+  spx::NrtArgs na{};
+  bool classes = false;
+  spx_engine::FzKey fz_key;
+};
+
+// LeastAllocated's Score launch in packed float32 (only the split launch of a row range acts on it: launch_nrt_fast)
+int nrt_plan_packed_score(spx_engine* e, spx::NrtArgs& na) {
+  NrtPacked pk;
+  if (!(na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect && nrt_packed_score(e, &pk))) return SPX_OK;
+  if (pk.tab_slot >= 0) {
+    const size_t bytes = (static_cast<size_t>(pk.tab_kmax) + 1) * pk.tab_words * 4;
+    if (!e->d_nrt_pk_tab.p || e->d_nrt_pk_tab.bytes < bytes) e->nrt_pk_tab_built = false;
+    if (int rc = ensure(e, e->d_nrt_pk_tab, bytes)) return rc;
+  }
+  na.pk_mode = 1, na.pk_tab_slot = pk.tab_slot;
+  na.pk_tab = static_cast<uint32_t*>(e->d_nrt_pk_tab.p);
+  na.pk_tab_words = pk.tab_words, na.pk_tab_kmax = pk.tab_kmax, na.pk_tab_inv_unit = pk.tab_inv_unit;
+  na.pk_tab_built = &e->nrt_pk_tab_built;
+  return SPX_OK;
+}
+
+// LeastNUMANodes, batch launch: per evaluated row and node scope a list of the nodes whose cell needs the complete subset
+// search (k_nrt_ln_redo) — room for 3/8 of the nodes per list by default (config #3 lists 13 % of the cells, no row more than 40 %); a
+// list that overflows sends the launch back to the complete sweep
+void nrt_plan_ln_lists(spx_engine* e, spx::NrtArgs& na, int64_t rows) {
+  // The lists are scratch: held to 1 GiB (config #3: 0.42 GB) by shortening them — a shorter list overflows sooner, and an
+  // allocation that fails leaves the launch without lists; either way the complete sweep writes the same table, slower
+  uint32_t per_row = static_cast<uint32_t>(spx::round_up(std::max<int64_t>(64, e->n_nodes * e->option[SPX_OPT_NRT_LN_LIST_PERMILLE] / 1000), 64));
+  constexpr size_t kListWords = (size_t{1} << 30) / sizeof(uint32_t);
+  if (rows > 0) {
+    const size_t room = (kListWords - 2) / (2 * static_cast<size_t>(rows));  // 1 + per_row words per list
+    if (room < 1 + static_cast<size_t>(per_row)) per_row = room > 64 ? static_cast<uint32_t>((room - 1) / 64 * 64) : 0;
+  }
+  const size_t words = 2 + 2 * static_cast<size_t>(rows) * (1 + static_cast<size_t>(per_row));
+  if (rows <= 0 || per_row < 64) return;
+  std::string kept;
+  {
+    std::lock_guard<std::mutex> g(e->err_mu);
+    kept = e->err;
+  }
+  if (ensure(e, e->d_nrt_redo, words * sizeof(uint32_t)) == SPX_OK &&
+      ensure(e, e->d_nrt_lnrec, static_cast<size_t>(e->n_nodes) * (SPX_NRT_MAX_ZONES * (e->nrt_n_res <= 4 ? 4 : 8) * 2 + 16) * sizeof(uint32_t)) == SPX_OK) {
+    na.redo_list = static_cast<uint32_t*>(e->d_nrt_redo.p);
+    na.ln_rec = static_cast<uint32_t*>(e->d_nrt_lnrec.p);
+    na.ln_rows = rows;
+    na.ln_per_row = per_row;
+  } else {
+    (void)hipGetLastError();  // the failed allocation's sticky error
+    std::lock_guard<std::mutex> g(e->err_mu);
+    e->err = kept;
+  }
+}
+
+// the walk's block start reads the windows' sorted quantities: (re)built when the zone tables changed
+int nrt_plan_window_sort(spx_engine* e, spx::NrtArgs& na) {
+  int rc;
+  size_t rank_bytes = 0;
+  const size_t sort_bytes = spx::nrt_window_sort_bytes(e->n_nodes, &rank_bytes);
+  if (!e->d_nrt_wsort.p || e->d_nrt_wsort.bytes < sort_bytes || !e->d_nrt_wrank.p || e->d_nrt_wrank.bytes < rank_bytes) e->nrt_wsort_built = false;
+  if ((rc = ensure(e, e->d_nrt_wsort, sort_bytes)) || (rc = ensure(e, e->d_nrt_wrank, rank_bytes))) return rc;
+  if (!e->nrt_wsort_built) {
+    spx::launch_nrt_window_sort(na, static_cast<double*>(e->d_nrt_wsort.p), static_cast<uint16_t*>(e->d_nrt_wrank.p), e->stream);
+    e->nrt_wsort_built = true;
+  }
+  na.wsort = static_cast<const double*>(e->d_nrt_wsort.p);
+  na.wrank = static_cast<const uint16_t*>(e->d_nrt_wrank.p);
+  return SPX_OK;
+}
+
+// decides the form of the dense sweep over [row_begin, row_end) and readies its scratch and derived tables
+int nrt_dense_plan(spx_engine* e, int64_t row_begin, int64_t row_end, NrtDensePlan* plan) {
+  int rc;
+  if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && (rc = build_ln_tab(e))) return rc;
+  if (e->nrt_params.strategy == SPX_NRT_BALANCED_ALLOCATION) {
+    // room for 1/32 of the cells (config #3 marks 0.7 %); what does not fit is recomputed where it is found.  Inside the
+    // sequential commit loop (row_indirect: one row per launch, graph capture) the list allocated for the first pod is kept.
+    const uint64_t want = std::max<uint64_t>(4096, static_cast<uint64_t>(row_end - row_begin) * static_cast<uint64_t>(e->row_stride) / 32);
+    const uint32_t cap = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 28));
+    if (cap > e->nrt_redo_cap) {
+      if ((rc = ensure(e, e->d_nrt_redo, (2 + 2 * static_cast<size_t>(cap)) * sizeof(uint32_t)))) return rc;
+      e->nrt_redo_cap = cap;
     }
   }
-  if (N && e->nrt_wide) {  // the wide tables: one sparse launch over the row range (kernels_nrt_wide.hip)
-    if (e->score_stride[SPX_PLUGIN_NRT] != e->row_stride)
-      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-    if (e->row_indirect) return fail(e, SPX_ERR_STATE, "NRT: the sequential commit loop does not take a wide snapshot (more than 8 resource slots)");
+  if ((rc = ensure_nrt_creq(e))) return rc;
+  spx::NrtArgs& na = plan->na;
+  fill_nrt(e, na);
+  na.row_begin = row_begin;
+  na.row_end = row_end;
+  na.out_status = static_cast<uint8_t*>(e->status[SPX_PLUGIN_NRT].p);
+  na.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_NRT].p);
+  const bool batch = na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect;  // the float64 formulation, rows given by the host
+  const bool whole = row_begin == 0 && row_end == e->n_pods;
+  // one representative per pod equivalence class when the whole batch is evaluated with the float64 formulation and enough
+  // rows are copies (a partial range may cut a class off from its representative)
+  const bool classes = e->option[SPX_OPT_NRT_POD_CLASSES] && batch && whole && e->nrt_n_dups > 0 && e->nrt_n_dups * 32 >= e->n_pods &&
+                       !(na.strategy == SPX_NRT_LEAST_NUMA_NODES && !na.ln_tab);
+  plan->classes = classes;
+  if ((rc = nrt_plan_packed_score(e, na))) return rc;
+  // the fused Filter + Score launch (kernels_nrt_fused.hip): a whole-batch LeastAllocated sweep in the packed Score's preconditions with unit
+  // weights; it walks the rank stream of the class representatives or, without classes, of every row
+  // (BalancedAllocation, round 6b: the walk carries its float32 Score too — no packed-Score preconditions, its own list of cells for float64)
+  const bool fz_balanced = na.strategy == SPX_NRT_BALANCED_ALLOCATION && batch;
+  bool fused = e->option[SPX_OPT_NRT_FUSED] && e->option[SPX_OPT_NRT_RANK_FILTER] && (na.pk_mode || fz_balanced) && !(na.opts & spx::kOptNrtSingleLaunch) && whole;
+  fused = fused && e->option[SPX_OPT_NRT_RANK_NARROW];  // (its only count layout)
+  for (int i = 0; fused && !fz_balanced && i < e->nrt_n_res; ++i) fused = e->nrt_slot_weight[i] == 0 || e->nrt_slot_weight[i] == 1;
+  if (classes || fused) {
+    if ((rc = nrt_rank_stream(e, classes ? 1 : 2))) return rc;
+  }
+  const bool stream = e->nrt_rk_max_dwords && e->nrt_rk_kind == (classes ? 1 : 2) && e->option[SPX_OPT_NRT_RANK_FILTER];
+  if (classes) {
+    na.row_list = static_cast<const int32_t*>(e->d_nrt_uniq.p);
+    na.n_list = e->nrt_n_uniq;
+  }
+  fused = fused && stream && e->nrt_rk_all_narrow;
+  if (stream && (classes || fused)) {  // the Filter in rank space (its own launch, or inside the fused one)
+    na.rk_stream = static_cast<const uint32_t*>(e->d_nrt_rk.p);
+    na.rk_off = static_cast<const uint32_t*>(e->d_nrt_rk_off.p);
+    na.rk_max_dwords = e->nrt_rk_max_dwords;
+    na.rk_first = static_cast<const uint32_t*>(e->d_nrt_rk_first.p);
+    na.rk_chunks = e->nrt_rk_chunks;
+    na.rk_all_narrow = e->nrt_rk_all_narrow && e->option[SPX_OPT_NRT_FUSED];
+    if (!classes) na.n_list = e->n_pods;
+    if (fused) {
+      if ((rc = ensure(e, e->d_nrt_fz, spx::nrt_fused_item_words(e->nrt_n_res, na.n_list) * sizeof(uint32_t)))) return rc;
+      na.fz_items = static_cast<uint32_t*>(e->d_nrt_fz.p);
+      plan->fz_key = spx_engine::FzKey{e->nrt_items_gen, classes ? 1 : 2, na.pk_tab_slot, e->d_nrt_fz.p};
+      na.fz_pack = !(plan->fz_key == e->nrt_fz_key);
+    }
+  }
+  if (na.strategy == SPX_NRT_LEAST_NUMA_NODES && batch) nrt_plan_ln_lists(e, na, classes ? e->nrt_n_uniq : row_end - row_begin);
+  if (na.rk_stream && na.rk_all_narrow && e->nrt_n_res <= 4 && (rc = nrt_plan_window_sort(e, na))) return rc;
+  return SPX_OK;
+}
+
+// the dense sweep as planned, its copies to the pod classes, then the long rows and the tall nodes' columns
+int nrt_dense_launch(spx_engine* e, const NrtDensePlan& plan, int64_t row_begin, int64_t row_end) {
+  const spx::NrtArgs& na = plan.na;
+  const bool ran_fused = spx::launch_nrt(na, e->stream);
+  // the fused launch may decline (BalancedAllocation's cpu slot not exact in float32, a chunk block too large for LDS): then the
+  // pack did not run either, and the key must not claim d_nrt_fz holds this pod generation's items
+  if (na.fz_items) e->nrt_fz_key = ran_fused ? plan.fz_key : spx_engine::FzKey{};
+  e->last_nrt_filter = ran_fused ? 3 : (na.rk_stream ? 2 : 1);
+  if (plan.classes)
+    spx::launch_rows_expand(static_cast<const int32_t*>(e->d_nrt_dups.p), static_cast<const int32_t*>(e->d_nrt_dups.p) + 2 * e->nrt_n_dups, e->nrt_n_tasks, na.out_status, na.out_score,
+                            e->row_stride, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  int rc;
+  // the long rows overwrite what the sweep above wrote from their pod-level request, before NetworkOverhead and Allocatable's
+  // masked normalisation read the NRT status table (a long row is a class of its own: no copy of it was made above)
+  if ((rc = launch_nrt_long_rows(e, na, row_begin, row_end))) return rc;
+  // then the tall nodes' columns of every row of the range (class copies and long rows included), still ahead of those readers
+  return launch_nrt_tall_rows(e, na, row_begin, row_end);
+}
+
+int launch_nrt_rows(spx_engine* e, int64_t row_begin, int64_t row_end) {
+  int rc;
+  if (e->nrt_wide) {  // the wide tables: one sparse launch over the row range (kernels_nrt_wide.hip)
     if ((rc = launch_nrt_wide_rows(e, row_begin, row_end, nullptr))) return rc;
     e->last_nrt_filter = 4;
     e->nrt_long_last = 0;
     e->nrt_tall_last = 0;
-  } else if (N) {
-    if (e->score_stride[SPX_PLUGIN_NRT] != e->row_stride)
-      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-    if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && (rc = build_ln_tab(e))) return rc;
-    if (e->nrt_params.strategy == SPX_NRT_BALANCED_ALLOCATION) {
-      // room for 1/32 of the cells (config #3 marks 0.7 %); what does not fit is recomputed where it is found.  Inside the
-      // sequential commit loop (row_indirect: one row per launch, graph capture) the list allocated for the first pod is kept.
-      const uint64_t want = std::max<uint64_t>(4096, static_cast<uint64_t>(row_end - row_begin) * static_cast<uint64_t>(e->row_stride) / 32);
-      const uint32_t cap = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 28));
-      if (cap > e->nrt_redo_cap) {
-        if ((rc = ensure(e, e->d_nrt_redo, (2 + 2 * static_cast<size_t>(cap)) * sizeof(uint32_t)))) return rc;
-        e->nrt_redo_cap = cap;
-      }
-    }
-    if ((rc = ensure_nrt_creq(e))) return rc;
-    spx::NrtArgs na{};
-    fill_nrt(e, na);
-    na.row_begin = row_begin;
-    na.row_end = row_end;
-    na.out_status = static_cast<uint8_t*>(e->status[SPX_PLUGIN_NRT].p);
-    na.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_NRT].p);
-    // one representative per pod equivalence class when the whole batch is evaluated with the float64 formulation and enough
-    // rows are copies (a partial range may cut a class off from its representative)
-    const bool classes = e->option[SPX_OPT_NRT_POD_CLASSES] && na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect &&
-                         row_begin == 0 && row_end == e->n_pods && e->nrt_n_dups > 0 && e->nrt_n_dups * 32 >= e->n_pods &&
-                         !(na.strategy == SPX_NRT_LEAST_NUMA_NODES && !na.ln_tab);
-    {  // LeastAllocated's Score launch in packed float32 (only the split launch of a row range acts on it: launch_nrt_fast)
-      NrtPacked pk;
-      if (na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect && nrt_packed_score(e, &pk)) {
-        if (pk.tab_slot >= 0) {
-          const size_t bytes = (static_cast<size_t>(pk.tab_kmax) + 1) * pk.tab_words * 4;
-          if (!e->d_nrt_pk_tab.p || e->d_nrt_pk_tab.bytes < bytes) e->nrt_pk_tab_built = false;
-          if ((rc = ensure(e, e->d_nrt_pk_tab, bytes))) return rc;
-        }
-        na.pk_mode = 1, na.pk_tab_slot = pk.tab_slot;
-        na.pk_tab = static_cast<uint32_t*>(e->d_nrt_pk_tab.p);
-        na.pk_tab_words = pk.tab_words, na.pk_tab_kmax = pk.tab_kmax, na.pk_tab_inv_unit = pk.tab_inv_unit;
-        na.pk_tab_built = &e->nrt_pk_tab_built;
-      }
-    }
-    // the fused Filter + Score launch (kernels_nrt_fused.hip): a whole-batch LeastAllocated sweep in the packed Score's preconditions with unit
-    // weights; it walks the rank stream of the class representatives or, without classes, of every row
-    // (BalancedAllocation, round 6b: the walk carries its float32 Score too — no packed-Score preconditions, its own list of cells for float64)
-    const bool fz_balanced = na.strategy == SPX_NRT_BALANCED_ALLOCATION && na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect;
-    bool fused = e->option[SPX_OPT_NRT_FUSED] && e->option[SPX_OPT_NRT_RANK_FILTER] && (na.pk_mode || fz_balanced) && !(na.opts & spx::kOptNrtSingleLaunch) &&
-                 row_begin == 0 && row_end == e->n_pods;
-    fused = fused && e->option[SPX_OPT_NRT_RANK_NARROW];  // (its only count layout)
-    for (int i = 0; fused && !fz_balanced && i < e->nrt_n_res; ++i) fused = e->nrt_slot_weight[i] == 0 || e->nrt_slot_weight[i] == 1;
-    if (classes || fused) {
-      if ((rc = nrt_rank_stream(e, classes ? 1 : 2))) return rc;
-    }
-    const bool stream = e->nrt_rk_max_dwords && e->nrt_rk_kind == (classes ? 1 : 2) && e->option[SPX_OPT_NRT_RANK_FILTER];
-    spx_engine::FzKey fz_key;  // what d_nrt_fz holds once the fused launch has run (gen 0: matches no later sweep)
-    if (classes) {
-      na.row_list = static_cast<const int32_t*>(e->d_nrt_uniq.p);
-      na.n_list = e->nrt_n_uniq;
-    }
-    fused = fused && stream && e->nrt_rk_all_narrow;
-    if (stream && (classes || fused)) {  // the Filter in rank space (its own launch, or inside the fused one)
-      na.rk_stream = static_cast<const uint32_t*>(e->d_nrt_rk.p);
-      na.rk_off = static_cast<const uint32_t*>(e->d_nrt_rk_off.p);
-      na.rk_max_dwords = e->nrt_rk_max_dwords;
-      na.rk_first = static_cast<const uint32_t*>(e->d_nrt_rk_first.p);
-      na.rk_chunks = e->nrt_rk_chunks;
-      na.rk_all_narrow = e->nrt_rk_all_narrow && e->option[SPX_OPT_NRT_FUSED];
-      if (!classes) na.n_list = e->n_pods;
-      if (fused) {
-        if ((rc = ensure(e, e->d_nrt_fz, spx::nrt_fused_item_words(e->nrt_n_res, na.n_list) * sizeof(uint32_t)))) return rc;
-        na.fz_items = static_cast<uint32_t*>(e->d_nrt_fz.p);
-        fz_key = spx_engine::FzKey{e->nrt_items_gen, classes ? 1 : 2, na.pk_tab_slot, e->d_nrt_fz.p};
-        na.fz_pack = !(fz_key == e->nrt_fz_key);
-      }
-    }
-    if (na.strategy == SPX_NRT_LEAST_NUMA_NODES && na.fast && !(na.opts & spx::kOptNrtGeneric) && !e->row_indirect) {
-      // LeastNUMANodes, batch launch: per evaluated row and node scope a list of the nodes whose cell needs the complete subset
-      // search (k_nrt_ln_redo) — room for 3/8 of the nodes per list by default (config #3 lists 13 % of the cells, no row more than 40 %); a
-      // list that overflows sends the launch back to the complete sweep
-      const int64_t rows = classes ? e->nrt_n_uniq : row_end - row_begin;
-      // The lists are scratch: held to 1 GiB (config #3: 0.42 GB) by shortening them — a shorter list overflows sooner, and an
-      // allocation that fails leaves the launch without lists; either way the complete sweep writes the same table, slower
-      uint32_t per_row = static_cast<uint32_t>(spx::round_up(std::max<int64_t>(64, e->n_nodes * e->option[SPX_OPT_NRT_LN_LIST_PERMILLE] / 1000), 64));
-      constexpr size_t kListWords = (size_t{1} << 30) / sizeof(uint32_t);
-      if (rows > 0) {
-        const size_t room = (kListWords - 2) / (2 * static_cast<size_t>(rows));  // 1 + per_row words per list
-        if (room < 1 + static_cast<size_t>(per_row)) per_row = room > 64 ? static_cast<uint32_t>((room - 1) / 64 * 64) : 0;
-      }
-      const size_t words = 2 + 2 * static_cast<size_t>(rows) * (1 + static_cast<size_t>(per_row));
-      if (rows > 0 && per_row >= 64) {
-        std::string kept;
-        {
-          std::lock_guard<std::mutex> g(e->err_mu);
-          kept = e->err;
-        }
-        if (ensure(e, e->d_nrt_redo, words * sizeof(uint32_t)) == SPX_OK &&
-            ensure(e, e->d_nrt_lnrec, static_cast<size_t>(e->n_nodes) * (SPX_NRT_MAX_ZONES * (e->nrt_n_res <= 4 ? 4 : 8) * 2 + 16) * sizeof(uint32_t)) == SPX_OK) {
-          na.redo_list = static_cast<uint32_t*>(e->d_nrt_redo.p);
-          na.ln_rec = static_cast<uint32_t*>(e->d_nrt_lnrec.p);
-          na.ln_rows = rows;
-          na.ln_per_row = per_row;
-        } else {
-          (void)hipGetLastError();  // the failed allocation's sticky error
-          std::lock_guard<std::mutex> g(e->err_mu);
-          e->err = kept;
-        }
-      }
-    }
-    if (na.rk_stream && na.rk_all_narrow && e->nrt_n_res <= 4) {  // the walk's block start reads the windows' sorted quantities: (re)built when the zone tables changed
-      size_t rank_bytes = 0;
-      const size_t sort_bytes = spx::nrt_window_sort_bytes(e->n_nodes, &rank_bytes);
-      if (!e->d_nrt_wsort.p || e->d_nrt_wsort.bytes < sort_bytes || !e->d_nrt_wrank.p || e->d_nrt_wrank.bytes < rank_bytes) e->nrt_wsort_built = false;
-      if ((rc = ensure(e, e->d_nrt_wsort, sort_bytes)) || (rc = ensure(e, e->d_nrt_wrank, rank_bytes))) return rc;
-      if (!e->nrt_wsort_built) {
-        spx::launch_nrt_window_sort(na, static_cast<double*>(e->d_nrt_wsort.p), static_cast<uint16_t*>(e->d_nrt_wrank.p), e->stream);
-        e->nrt_wsort_built = true;
-      }
-      na.wsort = static_cast<const double*>(e->d_nrt_wsort.p);
-      na.wrank = static_cast<const uint16_t*>(e->d_nrt_wrank.p);
-    }
-    const bool ran_fused = spx::launch_nrt(na, e->stream);
-    // the fused launch may decline (BalancedAllocation's cpu slot not exact in float32, a chunk block too large for LDS): then the
-    // pack did not run either, and the key must not claim d_nrt_fz holds this pod generation's items
-    if (na.fz_items) e->nrt_fz_key = ran_fused ? fz_key : spx_engine::FzKey{};
-    e->last_nrt_filter = ran_fused ? 3 : (na.rk_stream ? 2 : 1);
-    if (classes)
-      spx::launch_rows_expand(static_cast<const int32_t*>(e->d_nrt_dups.p), static_cast<const int32_t*>(e->d_nrt_dups.p) + 2 * e->nrt_n_dups, e->nrt_n_tasks, na.out_status, na.out_score,
-                              e->row_stride, e->stream);
-    SPX_HIP(e, hipGetLastError());
-    // the long rows overwrite what the sweep above wrote from their pod-level request, before NetworkOverhead and Allocatable's
-    // masked normalisation read the NRT status table (a long row is a class of its own: no copy of it was made above)
-    if ((rc = launch_nrt_long_rows(e, na, row_begin, row_end))) return rc;
-    // then the tall nodes' columns of every row of the range (class copies and long rows included), still ahead of those readers
-    if ((rc = launch_nrt_tall_rows(e, na, row_begin, row_end))) return rc;
+    return SPX_OK;
   }
-  if (W) {
-    if (e->score_stride[SPX_PLUGIN_NETOVERHEAD] != e->row_stride)
-      return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-    spx::NetArgs g{};
-    fill_net(e, g);
-    g.row_begin = row_begin;
-    g.row_end = row_end;
-    // upstream scores only nodes that passed every Filter plugin
-    g.other_status[0] = N ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-    g.other_status[1] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
-    g.out_status = static_cast<uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p);
-    g.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_NETOVERHEAD].p);
-    // Allocatable's masked NormalizeScore rides on the network kernel's walks when both are evaluated over a row range (same feasible
-    // set; k_alloc_masked would read the status tables again): launch_net says whether it did
-    if (A && masked && !e->skip_alloc_masked && e->alloc_compact && !e->row_indirect && row_end - row_begin > 1 && e->option[SPX_OPT_NET_ALLOC_FUSED]) {
-      g.alloc_rel = static_cast<const uint32_t*>(e->d_alloc_rel.p);
-      g.out_alloc = static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p);
-    }
-    alloc_by_net = spx::launch_net(g, e->stream);
-    SPX_HIP(e, hipGetLastError());
+  NrtDensePlan plan;
+  if ((rc = nrt_dense_plan(e, row_begin, row_end, &plan))) return rc;
+  return nrt_dense_launch(e, plan, row_begin, row_end);
+}
+
+// NetworkOverhead; *alloc_by_net: Allocatable's masked table was written by this sweep (SPX_OPT_NET_ALLOC_FUSED)
+int launch_net_rows(spx_engine* e, const EvalPlugins& f, const EvalCall& call, int64_t row_begin, int64_t row_end, bool* alloc_by_net) {
+  spx::NetArgs g{};
+  fill_net(e, g);
+  g.row_begin = row_begin;
+  g.row_end = row_end;
+  // upstream scores only nodes that passed every Filter plugin
+  const uint8_t* st[3];
+  feasibility_status(e, f.mask, st);
+  g.other_status[0] = st[0], g.other_status[1] = st[2];
+  g.out_status = static_cast<uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p);
+  g.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_NETOVERHEAD].p);
+  // Allocatable's masked NormalizeScore rides on the network kernel's walks when both are evaluated over a row range (same feasible
+  // set; k_alloc_masked would read the status tables again): launch_net says whether it did
+  if (f.alloc && f.masked && !call.skip_alloc_masked && e->alloc_compact && !e->row_indirect && row_end - row_begin > 1 && e->option[SPX_OPT_NET_ALLOC_FUSED]) {
+    g.alloc_rel = static_cast<const uint32_t*>(e->d_alloc_rel.p);
+    g.out_alloc = static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p);
   }
-  spx::launch_trimaran(a, e->stream);
+  *alloc_by_net = spx::launch_net(g, e->stream);
   SPX_HIP(e, hipGetLastError());
-  e->last_alloc_table = !A ? 0 : masked ? (e->skip_alloc_masked ? 0 : 1) : (alloc_kept_now ? 2 : 1);
-  if (alloc_keepable && a.out_alloc && row_end > row_begin) {
+  return SPX_OK;
+}
+
+int launch_trimaran_rows(spx_engine* e, const EvalPlugins& f, const EvalCall& call, const TrimaranStep& t, int64_t row_begin, int64_t row_end) {
+  spx::launch_trimaran(t.a, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  e->last_alloc_table = !f.alloc ? 0 : f.masked ? (call.skip_alloc_masked ? 0 : 1) : (t.alloc_kept_now ? 2 : 1);
+  if (t.alloc_keepable && t.a.out_alloc && row_end > row_begin) {
     // the launch that broadcasts the row into [row_begin, row_end) is on the stream: these rows join the record when they touch
     // rows written to the same buffer from the same row (eval_info's rule), and replace it otherwise
+    const DevBuf& alloc_table = e->score[SPX_PLUGIN_ALLOCATABLE];
     spx_engine::AllocKept& k = e->alloc_kept;
     const bool same = k.buf == alloc_table.p && k.stride == e->score_stride[SPX_PLUGIN_ALLOCATABLE] && k.epoch == e->alloc_epoch && k.end > k.begin;
     if (same && row_begin <= k.end && row_end >= k.begin) {
@@ -599,134 +686,177 @@ int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row
       k = spx_engine::AllocKept{row_begin, row_end, alloc_table.p, e->score_stride[SPX_PLUGIN_ALLOCATABLE], e->alloc_epoch};
     }
   }
-  if (R) {
-    spx::LrocArgs la{};
-    fill_lroc(e, la);
-    la.row_begin = row_begin;
-    la.row_end = row_end;
-    la.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_LROC].p);
-    if (!e->lroc_tab_ready) {  // per-node riskLoad: once per (node tables, params)
-      spx::launch_lroc_prepare(la, e->stream);
-      SPX_HIP(e, hipGetLastError());
-      e->lroc_tab_ready = true;
-    }
-    // inside the sequential commit loop: one row, a whole workgroup on it, in the form chosen for the batch (kernels_commit_scorers.hip)
-    if (e->lroc_loop_form >= 0) {
-      if (row_end - row_begin != 1) return fail(e, SPX_ERR_STATE, "internal: the commit loop evaluates LowRiskOverCommitment one row at a time");
-      if (e->lroc_loop_form != spx::kLrocFormF32) la.pod_f32 = nullptr;
-      spx::launch_commit_lroc_row(la, e->row_indirect, e->lroc_loop_form, e->stream);
-    } else {
-      e->lroc_last_form = -1;
-      spx::launch_lroc(la, e->stream);
-    }
+  return SPX_OK;
+}
+
+int launch_lroc_rows(spx_engine* e, int64_t row_begin, int64_t row_end) {
+  spx::LrocArgs la{};
+  fill_lroc(e, la);
+  la.row_begin = row_begin;
+  la.row_end = row_end;
+  la.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_LROC].p);
+  if (!e->lroc_tab_ready) {  // per-node riskLoad: once per (node tables, params)
+    spx::launch_lroc_prepare(la, e->stream);
     SPX_HIP(e, hipGetLastError());
+    e->lroc_tab_ready = true;
   }
-  if (K) {  // after the Filter plugins: NormalizeScore runs over each pod's feasible nodes
-    spx::PeaksArgs ka{};
-    fill_peaks(e, ka);
-    ka.row_begin = row_begin;
-    ka.row_end = row_end;
-    ka.other_status[0] = N ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-    ka.other_status[1] = W ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
-    ka.other_status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
-    ka.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_PEAKS].p);
-    // one row per distinct cpu request when the whole batch is swept and nothing narrows a pod's node list (NormalizeScore runs
-    // over the same nodes for every pod then), provided enough rows are copies
-    const bool classes = e->option[SPX_OPT_PEAKS_POD_CLASSES] && !ka.other_status[0] && !ka.other_status[1] && !ka.other_status[2] &&
-                         row_begin == 0 && row_end == e->n_pods && e->pk_n_dups > 0 && e->pk_n_dups * 8 >= e->n_pods;
-    if (classes) {
-      ka.row_list = static_cast<const int32_t*>(e->d_pk_uniq.p);
-      ka.n_list = e->pk_n_uniq;
-    }
-    if (e->pk_negative || e->peaks_loop_row) ka.opts &= ~spx::kOptPeaksEstimate;  // (the float64 passes take whatever the table holds; one row needs no lists)
-    if (ka.opts & spx::kOptPeaksEstimate) {  // the undecided cells' list: sized by the rows this sweep walks
-      size_t seg_bytes = 0, cnt_bytes = 0;
-      ka.est_pods = spx::peaks_est_plan(ka.opts, e->row_stride, classes ? ka.n_list : row_end - row_begin, &seg_bytes, &cnt_bytes);
-      if ((rc = ensure(e, e->d_pk_seg, seg_bytes)) || (rc = ensure(e, e->d_pk_segn, cnt_bytes))) return rc;
-      ka.seg = e->d_pk_seg.p;
-      ka.seg_n = static_cast<int32_t*>(e->d_pk_segn.p);
-    }
-    // inside the sequential commit loop with Filter plugins: the pod's row against its CURRENT status rows, one workgroup, no estimate scratch
-    if (e->peaks_loop_row) {
-      if (row_end - row_begin != 1) return fail(e, SPX_ERR_STATE, "internal: the commit loop evaluates Peaks one row at a time");
-      spx::launch_commit_peaks_row(ka, e->row_indirect, e->stream);
-    } else
-      spx::launch_peaks(ka, e->stream);
-    if (classes)
-      spx::launch_rows_expand(static_cast<const int32_t*>(e->d_pk_dups.p), static_cast<const int32_t*>(e->d_pk_dups.p) + 2 * e->pk_n_dups, e->pk_n_tasks, ka.out_score, nullptr,
-                              e->row_stride, e->stream);
-    SPX_HIP(e, hipGetLastError());
+  // inside the sequential commit loop: one row, a whole workgroup on it, in the form chosen for the batch (kernels_commit_scorers.hip)
+  if (e->lroc_loop_form >= 0) {
+    if (e->lroc_loop_form != spx::kLrocFormF32) la.pod_f32 = nullptr;
+    spx::launch_commit_lroc_row(la, e->row_indirect, e->lroc_loop_form, e->stream);
+  } else {
+    e->lroc_last_form = -1;
+    spx::launch_lroc(la, e->stream);
   }
-  if (Y && row_end > row_begin) {  // after the Filter plugins, as Peaks: NormalizeScore runs over each pod's feasible nodes
-    spx::SyschedArgs ya{};
-    fill_sysched(e, ya);
-    ya.other_status[0] = N ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-    ya.other_status[1] = W ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
-    ya.other_status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
-    ya.row_begin = row_begin;
-    ya.row_end = row_end;
-    ya.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_SYSCHED].p);
-    // nothing narrows a pod's node list and the whole batch is swept: every distinct set's row is normalised once and copied
-    const bool classes = !masked && row_begin == 0 && row_end == e->n_pods;
-    // a single row needs its own set's raw row only
-    int32_t s_lo = 0, s_hi = e->sy_n_sets;
-    if (row_end - row_begin == 1) s_lo = e->h_sy_pod_set[static_cast<size_t>(row_begin)], s_hi = s_lo + 1;
-    SPX_HIP(e, hipMemsetAsync(e->d_sy_max.p, 0, static_cast<size_t>(e->sy_n_sets) * sizeof(int32_t), e->stream));
-    int chunks = 0;
-    for (int64_t s0 = s_lo; s0 < s_hi; s0 += sy_per_chunk, ++chunks) {
-      ya.set_begin = static_cast<int32_t>(s0);
-      ya.set_end = static_cast<int32_t>(std::min<int64_t>(s0 + sy_per_chunk, s_hi));
-      spx::launch_sysched_raw(ya, e->stream);
-      if (classes) spx::launch_sysched_norm(ya, e->stream);
-      else spx::launch_sysched_rows(ya, e->h_sy_first[static_cast<size_t>(ya.set_end)] - e->h_sy_first[static_cast<size_t>(ya.set_begin)], e->stream);
-    }
-    if (classes && e->sy_n_dups > 0)
-      spx::launch_rows_expand(static_cast<const int32_t*>(e->d_sy_dups.p), static_cast<const int32_t*>(e->d_sy_dups.p) + 2 * e->sy_n_dups, e->sy_n_tasks, ya.out_score, nullptr,
-                              e->row_stride, e->stream);
-    SPX_HIP(e, hipGetLastError());
-    e->sy_last_chunks = chunks;
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+// after the Filter plugins: NormalizeScore runs over each pod's feasible nodes
+int launch_peaks_rows(spx_engine* e, const EvalPlugins& f, int64_t row_begin, int64_t row_end) {
+  spx::PeaksArgs ka{};
+  fill_peaks(e, ka);
+  ka.row_begin = row_begin;
+  ka.row_end = row_end;
+  feasibility_status(e, f.mask, ka.other_status);
+  ka.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_PEAKS].p);
+  // one row per distinct cpu request when the whole batch is swept and nothing narrows a pod's node list (NormalizeScore runs
+  // over the same nodes for every pod then), provided enough rows are copies
+  const bool classes = e->option[SPX_OPT_PEAKS_POD_CLASSES] && !f.masked && row_begin == 0 && row_end == e->n_pods && e->pk_n_dups > 0 &&
+                       e->pk_n_dups * 8 >= e->n_pods;
+  if (classes) {
+    ka.row_list = static_cast<const int32_t*>(e->d_pk_uniq.p);
+    ka.n_list = e->pk_n_uniq;
   }
-  if (A && masked && !e->skip_alloc_masked && !alloc_by_net) {
-    spx::ProfileArgs pa{};
-    pa.n_nodes = e->n_nodes;
-    pa.row_stride = e->row_stride;
-    pa.row_begin = row_begin;
-    pa.row_end = row_end;
-    pa.row_ptr = e->row_indirect;
-    pa.status[0] = N ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-    pa.status[1] = W ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
-    pa.status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
-    pa.alloc_raw = static_cast<const int64_t*>(e->d_alloc_raw.p);
-    pa.alloc_rel = static_cast<const uint32_t*>(e->d_alloc_rel.p);
-    pa.out_alloc = static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p);
-    pa.block_per_row = static_cast<int32_t>(e->option[SPX_OPT_ROW_WORKGROUP]);
-    spx::launch_alloc_masked(pa, e->stream);
-    SPX_HIP(e, hipGetLastError());
+  if (e->pk_negative || e->peaks_loop_row) ka.opts &= ~spx::kOptPeaksEstimate;  // (the float64 passes take whatever the table holds; one row needs no lists)
+  if (ka.opts & spx::kOptPeaksEstimate) {  // the undecided cells' list: sized by the rows this sweep walks
+    int rc;
+    size_t seg_bytes = 0, cnt_bytes = 0;
+    ka.est_pods = spx::peaks_est_plan(ka.opts, e->row_stride, classes ? ka.n_list : row_end - row_begin, &seg_bytes, &cnt_bytes);
+    if ((rc = ensure(e, e->d_pk_seg, seg_bytes)) || (rc = ensure(e, e->d_pk_segn, cnt_bytes))) return rc;
+    ka.seg = e->d_pk_seg.p;
+    ka.seg_n = static_cast<int32_t*>(e->d_pk_segn.p);
   }
-  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  // inside the sequential commit loop with Filter plugins: the pod's row against its CURRENT status rows, one workgroup, no estimate scratch
+  if (e->peaks_loop_row)
+    spx::launch_commit_peaks_row(ka, e->row_indirect, e->stream);
+  else
+    spx::launch_peaks(ka, e->stream);
+  if (classes)
+    spx::launch_rows_expand(static_cast<const int32_t*>(e->d_pk_dups.p), static_cast<const int32_t*>(e->d_pk_dups.p) + 2 * e->pk_n_dups, e->pk_n_tasks, ka.out_score, nullptr,
+                            e->row_stride, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+// after the Filter plugins, as Peaks: NormalizeScore runs over each pod's feasible nodes
+int launch_sysched_rows(spx_engine* e, const EvalPlugins& f, int64_t per_chunk, int64_t row_begin, int64_t row_end) {
+  spx::SyschedArgs ya{};
+  fill_sysched(e, ya);
+  feasibility_status(e, f.mask, ya.other_status);
+  ya.row_begin = row_begin;
+  ya.row_end = row_end;
+  ya.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_SYSCHED].p);
+  // nothing narrows a pod's node list and the whole batch is swept: every distinct set's row is normalised once and copied
+  const bool classes = !f.masked && row_begin == 0 && row_end == e->n_pods;
+  // a single row needs its own set's raw row only
+  int32_t s_lo = 0, s_hi = e->sy_n_sets;
+  if (row_end - row_begin == 1) s_lo = e->h_sy_pod_set[static_cast<size_t>(row_begin)], s_hi = s_lo + 1;
+  SPX_HIP(e, hipMemsetAsync(e->d_sy_max.p, 0, static_cast<size_t>(e->sy_n_sets) * sizeof(int32_t), e->stream));
+  int chunks = 0;
+  for (int64_t s0 = s_lo; s0 < s_hi; s0 += per_chunk, ++chunks) {
+    ya.set_begin = static_cast<int32_t>(s0);
+    ya.set_end = static_cast<int32_t>(std::min<int64_t>(s0 + per_chunk, s_hi));
+    spx::launch_sysched_raw(ya, e->stream);
+    if (classes) spx::launch_sysched_norm(ya, e->stream);
+    else spx::launch_sysched_rows(ya, e->h_sy_first[static_cast<size_t>(ya.set_end)] - e->h_sy_first[static_cast<size_t>(ya.set_begin)], e->stream);
+  }
+  if (classes && e->sy_n_dups > 0)
+    spx::launch_rows_expand(static_cast<const int32_t*>(e->d_sy_dups.p), static_cast<const int32_t*>(e->d_sy_dups.p) + 2 * e->sy_n_dups, e->sy_n_tasks, ya.out_score, nullptr,
+                            e->row_stride, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  e->sy_last_chunks = chunks;
+  return SPX_OK;
+}
+
+// Allocatable's NormalizeScore over each pod's feasible nodes, when no other sweep of the evaluation has written it
+int launch_alloc_masked_rows(spx_engine* e, const EvalPlugins& f, int64_t row_begin, int64_t row_end) {
+  spx::ProfileArgs pa{};
+  pa.n_nodes = e->n_nodes;
+  pa.row_stride = e->row_stride;
+  pa.row_begin = row_begin;
+  pa.row_end = row_end;
+  pa.row_ptr = e->row_indirect;
+  feasibility_status(e, f.mask, pa.status);
+  pa.alloc_raw = static_cast<const int64_t*>(e->d_alloc_raw.p);
+  pa.alloc_rel = static_cast<const uint32_t*>(e->d_alloc_rel.p);
+  pa.out_alloc = static_cast<uint8_t*>(e->score[SPX_PLUGIN_ALLOCATABLE].p);
+  pa.block_per_row = static_cast<int32_t>(e->option[SPX_OPT_ROW_WORKGROUP]);
+  spx::launch_alloc_masked(pa, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
+// what the engine remembers of an evaluation whose launches are all on the stream
+void eval_record(spx_engine* e, const EvalPlugins& f, const EvalCall& call, int64_t row_begin, int64_t row_end) {
   e->timed = true;
   e->best_valid = false;
-  e->evaluated |= plugin_mask;
-  const bool alloc_skipped = A && masked && e->skip_alloc_masked;  // spx_decide: the table is not written — nothing to fetch
+  e->evaluated |= f.mask;
+  const bool alloc_skipped = f.alloc && f.masked && call.skip_alloc_masked;  // spx_decide: the table is not written — nothing to fetch
   if (alloc_skipped) {
     e->evaluated &= ~(1u << SPX_PLUGIN_ALLOCATABLE);
     e->eval_info[SPX_PLUGIN_ALLOCATABLE] = spx_engine::EvalInfo{};
   }
-  if (row_end > row_begin) {
-    const uint32_t filters = plugin_mask & kFilterPlugins;
-    for (int p = 0; p < SPX_NUM_PLUGINS; ++p) {
-      if (!((plugin_mask >> p) & 1u) || (alloc_skipped && p == SPX_PLUGIN_ALLOCATABLE)) continue;
-      spx_engine::EvalInfo& i = e->eval_info[p];
-      const bool same_ctx = i.filters == filters && i.ext_gen == e->ext_gen && i.end > i.begin;
-      if (same_ctx && row_begin <= i.end && row_end >= i.begin) {  // overlapping or adjacent: the evaluated rows grow
-        i.begin = std::min(i.begin, row_begin);
-        i.end = std::max(i.end, row_end);
-      } else {
-        i.begin = row_begin, i.end = row_end, i.filters = filters, i.ext_gen = e->ext_gen;
-      }
+  if (row_end <= row_begin) return;
+  const uint32_t filters = f.mask & kFilterPlugins;
+  for (int p = 0; p < SPX_NUM_PLUGINS; ++p) {
+    if (!((f.mask >> p) & 1u) || (alloc_skipped && p == SPX_PLUGIN_ALLOCATABLE)) continue;
+    spx_engine::EvalInfo& i = e->eval_info[p];
+    const bool same_ctx = i.filters == filters && i.ext_gen == e->ext_gen && i.end > i.begin;
+    if (same_ctx && row_begin <= i.end && row_end >= i.begin) {  // overlapping or adjacent: the evaluated rows grow
+      i.begin = std::min(i.begin, row_begin);
+      i.end = std::max(i.end, row_end);
+    } else {
+      i.begin = row_begin, i.end = row_end, i.filters = filters, i.ext_gen = e->ext_gen;
     }
   }
+}
+
+int eval_rows(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end, const EvalCall& call) {
+  SPX_HIP(e, hipSetDevice(e->device));
+  const EvalPlugins f = eval_plugins(e, plugin_mask);
+  int rc;
+  if ((rc = eval_check(e, f, row_begin, row_end))) return rc;
+  if ((rc = prepare_tables(e, f))) return rc;
+  if (f.lroc && (rc = prepare_lroc(e))) return rc;
+  if (f.peaks && (rc = prepare_peaks(e))) return rc;
+  int64_t sy_per_chunk = 0;
+  if (f.sysched && (rc = prepare_sysched(e, &sy_per_chunk))) return rc;
+  TrimaranStep tri;
+  if ((rc = prepare_trimaran(e, f, call, row_begin, row_end, &tri))) return rc;
+  if (!call.hold_ev0) SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  bool alloc_by_net = false;
+  if (f.quota && (rc = launch_quota_rows(e, row_begin, row_end))) return rc;
+  if (f.cosched && (rc = launch_cosched_rows(e, row_begin, row_end))) return rc;
+  if (f.nrt && (rc = launch_nrt_rows(e, row_begin, row_end))) return rc;
+  if (f.net && (rc = launch_net_rows(e, f, call, row_begin, row_end, &alloc_by_net))) return rc;
+  if ((rc = launch_trimaran_rows(e, f, call, tri, row_begin, row_end))) return rc;
+  if (f.lroc && (rc = launch_lroc_rows(e, row_begin, row_end))) return rc;
+  if (f.peaks && (rc = launch_peaks_rows(e, f, row_begin, row_end))) return rc;
+  if (f.sysched && row_end > row_begin && (rc = launch_sysched_rows(e, f, sy_per_chunk, row_begin, row_end))) return rc;
+  if (f.alloc && f.masked && !call.skip_alloc_masked && !alloc_by_net && (rc = launch_alloc_masked_rows(e, f, row_begin, row_end))) return rc;
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  eval_record(e, f, call, row_begin, row_end);
   return SPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spx_eval(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t row_end) {
+  if (!e) return SPX_ERR_ARG;
+  return eval_rows(e, plugin_mask, row_begin, row_end, EvalCall{});
 }
 
 int spx_sync(spx_engine* e) {
@@ -882,32 +1012,29 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
   if (e->n_nodes <= 0) return fail(e, SPX_ERR_STATE, "no node table uploaded");
   int rc;
   const size_t bytes = static_cast<size_t>(e->n_nodes) * sizeof(int64_t);
-  if (plugin == SPX_PLUGIN_ALLOCATABLE) {
+  int64_t* raw = nullptr;  // the scratch row the plugin's launch fills
+  // every plugin but Allocatable, after its state check: the row exists and so does the scratch row
+  auto scratch_row = [&]() -> int {
+    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
+    const int r = ensure(e, e->d_raw_row, bytes);
+    raw = static_cast<int64_t*>(e->d_raw_row.p);
+    return r;
+  };
+  if (plugin == SPX_PLUGIN_ALLOCATABLE) {  // the same row for every pod: no launch
     if ((rc = prepare_alloc(e))) return rc;
-    SPX_HIP(e, hipMemcpyAsync(out, e->d_alloc_raw.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    SPX_HIP(e, hipStreamSynchronize(e->stream));
-    return SPX_OK;
-  }
-  if (plugin == SPX_PLUGIN_NRT && e->nrt_wide) {
-    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
-    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
-    if ((rc = launch_nrt_wide_rows(e, pod_row, pod_row + 1, static_cast<int64_t*>(e->d_raw_row.p)))) return rc;
-    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    SPX_HIP(e, hipStreamSynchronize(e->stream));
-    return SPX_OK;
-  }
-  if (plugin == SPX_PLUGIN_NRT) {  // TopologyMatch has no NormalizeScore (score.go:104-106)
+    raw = static_cast<int64_t*>(e->d_alloc_raw.p);
+  } else if (plugin == SPX_PLUGIN_NRT && e->nrt_wide) {
+    if ((rc = scratch_row()) || (rc = launch_nrt_wide_rows(e, pod_row, pod_row + 1, raw))) return rc;
+  } else if (plugin == SPX_PLUGIN_NRT) {  // TopologyMatch has no NormalizeScore (score.go:104-106)
     if (!(e->nrt_slots && e->nrt_nodes && e->nrt_pods)) return fail(e, SPX_ERR_STATE, "NRT slot/node/pod tables not uploaded");
-    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
-    if ((rc = nrt_tall_ready(e))) return rc;
-    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
+    if ((rc = scratch_row()) || (rc = nrt_tall_ready(e))) return rc;
     if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && (rc = build_ln_tab(e))) return rc;
     if ((rc = ensure_nrt_creq(e))) return rc;
     spx::NrtArgs na{};
     fill_nrt(e, na);
     na.row_begin = pod_row;
     na.row_end = pod_row + 1;
-    na.out_raw = static_cast<int64_t*>(e->d_raw_row.p);
+    na.out_raw = raw;
     spx::launch_nrt(na, e->stream);
     const int64_t swept = e->nrt_long_last;  // (spx_nrt_long_rows reports spx_eval's sweeps, not this row)
     rc = launch_nrt_long_rows(e, na, pod_row, pod_row + 1);
@@ -917,69 +1044,47 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
     rc = launch_nrt_tall_rows(e, na, pod_row, pod_row + 1);
     e->nrt_tall_last = swept_tall;
     if (rc) return rc;
-    SPX_HIP(e, hipGetLastError());
-    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    SPX_HIP(e, hipStreamSynchronize(e->stream));
-    return SPX_OK;
-  }
-  if (plugin == SPX_PLUGIN_NETOVERHEAD) {  // raw accumulated cost / satisfied / violated (PreFilterState maps)
+  } else if (plugin == SPX_PLUGIN_NETOVERHEAD) {  // raw accumulated cost / satisfied / violated (PreFilterState maps)
     if (!(e->net_nodes && e->net_topo && e->net_pods)) return fail(e, SPX_ERR_STATE, "NetworkOverhead tables not uploaded");
-    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
+    if ((rc = scratch_row())) return rc;
     if (which < SPX_NET_RAW_COST || which > SPX_NET_RAW_VIOLATED) return fail(e, SPX_ERR_ARG, "which: 0 cost, 1 satisfied, 2 violated");
-    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
     if ((rc = net_prepare(e, 0, ""))) return rc;
     spx::NetArgs g{};
     fill_net(e, g);
     g.row_begin = pod_row;
     g.row_end = pod_row + 1;
-    g.out_raw = static_cast<int64_t*>(e->d_raw_row.p);
+    g.out_raw = raw;
     g.raw_which = which;
     spx::launch_net(g, e->stream);
-    SPX_HIP(e, hipGetLastError());
-    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    SPX_HIP(e, hipStreamSynchronize(e->stream));
-    return SPX_OK;
-  }
-  if (plugin == SPX_PLUGIN_PEAKS) {  // Peaks.Score before NormalizeScore: the power jump x 1e15
+  } else if (plugin == SPX_PLUGIN_PEAKS) {  // Peaks.Score before NormalizeScore: the power jump x 1e15
     if (!(e->peaks_nodes && e->peaks_pods)) return fail(e, SPX_ERR_STATE, "Peaks node/pod tables not uploaded");
-    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
-    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
+    if ((rc = scratch_row())) return rc;
     spx::PeaksArgs ka{};
     fill_peaks(e, ka);
     ka.row_begin = pod_row;
     ka.row_end = pod_row + 1;
-    ka.out_raw = static_cast<int64_t*>(e->d_raw_row.p);
+    ka.out_raw = raw;
     spx::launch_peaks(ka, e->stream);
-    SPX_HIP(e, hipGetLastError());
-    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    SPX_HIP(e, hipStreamSynchronize(e->stream));
-    return SPX_OK;
-  }
-  if (plugin == SPX_PLUGIN_SYSCHED) {  // SySched.Score before NormalizeScore; math.MaxInt64 for a pod with the empty set
+  } else if (plugin == SPX_PLUGIN_SYSCHED) {  // SySched.Score before NormalizeScore; math.MaxInt64 for a pod with the empty set
     if (!(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
     if (e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
-    if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
-    if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
+    if ((rc = scratch_row())) return rc;
     spx::SyschedArgs ya{};
     fill_sysched(e, ya);
     ya.set_begin = e->h_sy_pod_set[static_cast<size_t>(pod_row)];
     ya.set_end = ya.set_begin + 1;
-    ya.out_raw64 = static_cast<int64_t*>(e->d_raw_row.p);
+    ya.out_raw64 = raw;
     spx::launch_sysched_raw(ya, e->stream);
-    SPX_HIP(e, hipGetLastError());
-    SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    SPX_HIP(e, hipStreamSynchronize(e->stream));
-    return SPX_OK;
+  } else {
+    if (plugin != SPX_PLUGIN_TLP && plugin != SPX_PLUGIN_LVRB) return fail(e, SPX_ERR_ARG, "raw rows: unsupported plugin");
+    if (!(e->tri_nodes && e->tri_pods)) return fail(e, SPX_ERR_STATE, "trimaran node/pod tables not uploaded");
+    if ((rc = scratch_row())) return rc;
+    spx::TrimaranArgs a{};
+    fill_trimaran(e, a);
+    spx::launch_trimaran_raw(a, plugin, pod_row, raw, e->stream);
   }
-  if (plugin != SPX_PLUGIN_TLP && plugin != SPX_PLUGIN_LVRB) return fail(e, SPX_ERR_ARG, "raw rows: unsupported plugin");
-  if (!(e->tri_nodes && e->tri_pods)) return fail(e, SPX_ERR_STATE, "trimaran node/pod tables not uploaded");
-  if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
-  if ((rc = ensure(e, e->d_raw_row, bytes))) return rc;
-  spx::TrimaranArgs a{};
-  fill_trimaran(e, a);
-  spx::launch_trimaran_raw(a, plugin, pod_row, static_cast<int64_t*>(e->d_raw_row.p), e->stream);
   SPX_HIP(e, hipGetLastError());
-  SPX_HIP(e, hipMemcpyAsync(out, e->d_raw_row.p, bytes, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipMemcpyAsync(out, raw, bytes, hipMemcpyDeviceToHost, e->stream));
   SPX_HIP(e, hipStreamSynchronize(e->stream));
   return SPX_OK;
 }
@@ -1113,7 +1218,6 @@ int decide_masked(spx_engine* e, uint32_t eval_mask, uint32_t score_mask, int64_
     return SPX_OK;
   int rc;
   if ((rc = prepare_alloc(e))) return rc;
-  const size_t P = static_cast<size_t>(e->n_pods);
   spx::ProfileArgs pa{};
   pa.n_nodes = e->n_nodes;
   pa.row_stride = e->row_stride;
@@ -1128,26 +1232,21 @@ int decide_masked(spx_engine* e, uint32_t eval_mask, uint32_t score_mask, int64_
     pa.weight[k] = e->plugin_weight[k];
   }
   if (!e->alloc_compact || !spx::decide_masked_ok(pa)) return SPX_OK;
-  if ((rc = ensure(e, e->d_best, P * 20))) return rc;
+  BestRows best;
+  if ((rc = ensure_best(e, &best))) return rc;
   SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
-  e->hold_ev0 = e->skip_alloc_masked = true;
-  rc = spx_eval(e, eval_mask, row_begin, row_end);
-  e->hold_ev0 = e->skip_alloc_masked = false;
-  if (rc) return rc;
+  EvalCall call;
+  call.hold_ev0 = call.skip_alloc_masked = true;
+  if ((rc = eval_rows(e, eval_mask, row_begin, row_end, call))) return rc;
   for (int k = 0; k < SPX_NUM_PLUGINS; ++k)
     if (pa.score[k]) {
       if (!(e->evaluated & (1u << k)) || e->score_stride[k] != e->row_stride)
         return fail(e, SPX_ERR_STATE, "spx_decide: a scoring plugin of the mask has no evaluated table with the engine row stride");
       pa.score[k] = static_cast<const uint8_t*>(e->score[k].p);
     }
-  pa.status[0] = (score_mask & (1u << SPX_PLUGIN_NRT)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-  pa.status[1] = (score_mask & (1u << SPX_PLUGIN_NETOVERHEAD)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
-  pa.status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
+  feasibility_status(e, score_mask, pa.status);
   pa.prefilter = (score_mask & (1u << SPX_PLUGIN_CAPACITY)) ? static_cast<const uint8_t*>(e->d_q_status.p) : nullptr;
-  pa.best_score = static_cast<int64_t*>(e->d_best.p);
-  pa.best_node = reinterpret_cast<int32_t*>(pa.best_score + P);
-  pa.best_ties = pa.best_node + P;
-  pa.best_feasible = pa.best_ties + P;
+  pa.best_score = best.score, pa.best_node = best.node, pa.best_ties = best.ties, pa.best_feasible = best.feasible;
   pa.block_per_row = static_cast<int32_t>(e->option[SPX_OPT_ROW_WORKGROUP]);
   spx::launch_decide_masked(pa, e->stream);
   SPX_HIP(e, hipGetLastError());
@@ -1185,17 +1284,15 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
   if (gate && row_end > row_begin && (!e->cs_gate_valid || row_begin < e->cs_row_begin || row_end > e->cs_row_end))
     return fail(e, SPX_ERR_STATE, "spx_eval_best: Coscheduling's gate has not been evaluated for these rows since its last upload");
   if (gate && e->row_indirect) return fail(e, SPX_ERR_STATE, "Coscheduling is not part of the sequential commit loop");
-  const size_t P = static_cast<size_t>(e->n_pods);
-  if ((rc = ensure(e, e->d_best, P * 20))) return rc;
+  BestRows best;
+  if ((rc = ensure_best(e, &best))) return rc;
   spx::ProfileArgs pa{};
   pa.n_nodes = e->n_nodes;
   pa.row_stride = e->row_stride;
   pa.row_begin = row_begin;
   pa.row_end = row_end;
   pa.row_ptr = e->row_indirect;
-  pa.status[0] = (plugin_mask & (1u << SPX_PLUGIN_NRT)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-  pa.status[1] = (plugin_mask & (1u << SPX_PLUGIN_NETOVERHEAD)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
-  pa.status[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
+  feasibility_status(e, plugin_mask, pa.status);
   pa.prefilter = (plugin_mask & (1u << SPX_PLUGIN_CAPACITY)) ? static_cast<const uint8_t*>(e->d_q_status.p) : nullptr;
   for (int k = 0; k < SPX_NUM_PLUGINS; ++k) {
     const bool has_score = plugin_has_score(k);
@@ -1205,10 +1302,7 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
     }
     pa.weight[k] = e->plugin_weight[k];
   }
-  pa.best_score = static_cast<int64_t*>(e->d_best.p);
-  pa.best_node = reinterpret_cast<int32_t*>(pa.best_score + P);
-  pa.best_ties = pa.best_node + P;
-  pa.best_feasible = pa.best_ties + P;
+  pa.best_score = best.score, pa.best_node = best.node, pa.best_ties = best.ties, pa.best_feasible = best.feasible;
   spx::launch_best(pa, e->stream);
   if (gate) spx::launch_cosched_unschedulable(static_cast<const uint8_t*>(e->d_cs_status.p), row_begin, row_end, pa.best_score, pa.best_node, pa.best_ties, pa.best_feasible, e->stream);
   SPX_HIP(e, hipGetLastError());
@@ -1233,10 +1327,8 @@ extern "C" int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin
   int rc;
   if ((rc = spx_eval(e, C, row_begin, row_end))) return rc;
   if ((rc = decide_profile(e, plugin_mask & ~C, row_begin, row_end))) return rc;
-  const size_t P = static_cast<size_t>(e->n_pods);
-  int64_t* bs = static_cast<int64_t*>(e->d_best.p);
-  int32_t* bn = reinterpret_cast<int32_t*>(bs + P);
-  spx::launch_cosched_unschedulable(static_cast<const uint8_t*>(e->d_cs_status.p), row_begin, row_end, bs, bn, bn + P, bn + 2 * P, e->stream);
+  const BestRows b = best_rows(e);
+  spx::launch_cosched_unschedulable(static_cast<const uint8_t*>(e->d_cs_status.p), row_begin, row_end, b.score, b.node, b.ties, b.feasible, e->stream);
   SPX_HIP(e, hipGetLastError());
   return SPX_OK;
 }
@@ -1270,35 +1362,24 @@ int decide_profile(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64
   if (row_begin < 0 || row_end > e->n_pods || row_begin > row_end) return fail(e, SPX_ERR_ARG, "row range out of bounds");
   const bool use_alloc = plugin_mask & A;
   if (use_alloc && (rc = prepare_alloc(e))) return rc;
-  const size_t P = static_cast<size_t>(e->n_pods);
-  if ((rc = ensure(e, e->d_best, P * 20))) return rc;
-  if ((rc = ensure(e, e->d_tlp_fast, static_cast<size_t>(spx::round_up(e->row_stride, 1024)) * 4 * sizeof(float)))) return rc;
+  BestRows best;
+  if ((rc = ensure_best(e, &best))) return rc;
   if ((rc = ensure(e, e->d_decide, spx::decide_scratch_bytes(e->row_stride, row_end - row_begin)))) return rc;
   spx::DecideLaunch d{};
   fill_trimaran(e, d.t);
   d.t.row_begin = row_begin;
   d.t.row_end = row_end;
-  d.t.tlp_fast = static_cast<float*>(e->d_tlp_fast.p);
-  if (!e->d_tlp_amb.p) e->tlp_amb_built = false;
-  if ((rc = ensure(e, e->d_tlp_amb, static_cast<size_t>(spx::kTlpAmbSize) * 4))) return rc;
-  d.t.tlp_amb = static_cast<uint32_t*>(e->d_tlp_amb.p);
-  d.t.tlp_amb_size = spx::kTlpAmbSize;
-  d.t.tlp_amb_built = &e->tlp_amb_built;
-  d.t.tlp_amb_geom = e->tlp_amb_geom;
+  if ((rc = tlp_scratch(e, d.t))) return rc;
   d.use_alloc = use_alloc;
   d.w_alloc = static_cast<int32_t>(use_alloc ? wa : 0);
   d.w_tlp = static_cast<int32_t>(wt);
   d.scratch = e->d_decide.p;
-  d.best_score = static_cast<int64_t*>(e->d_best.p);
-  d.best_node = reinterpret_cast<int32_t*>(d.best_score + P);
-  d.best_ties = d.best_node + P;
-  d.best_feasible = d.best_ties + P;
+  d.best_score = best.score, d.best_node = best.node, d.best_ties = best.ties, d.best_feasible = best.feasible;
   SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
   if (extra_mask) {
-    e->hold_ev0 = true;
-    rc = spx_eval(e, extra_mask, row_begin, row_end);
-    e->hold_ev0 = false;
-    if (rc) return rc;
+    EvalCall call;
+    call.hold_ev0 = true;
+    if ((rc = eval_rows(e, extra_mask, row_begin, row_end, call))) return rc;
     for (int x = 0; x < 3; ++x)
       if (extra_mask & (1u << kExtra[x])) {
         d.w_extra[d.n_extra] = static_cast<int32_t>(e->plugin_weight[kExtra[x]]);
