@@ -14,6 +14,9 @@
  *                                        pkg/networkaware/networkoverhead/networkoverhead.go:174,326,362,389
  *   TopologicalSort.Less                 pkg/networkaware/topologicalsort/topologicalsort.go:102
  *   CapacityScheduling.PreFilter         pkg/capacityscheduling/capacity_scheduling.go:208
+ *   NodeMetadata.Score / NormalizeScore  pkg/nodemetadata/node_metadata.go:57,150
+ *   PodState.Score / NormalizeScore      pkg/podstate/pod_state.go:42,66
+ *   QOSSort.Less                         pkg/qos/queue_sort.go:46
  *
  * Rules of the boundary (cgo-safe):
  *   - every function returns int: 0 = ok, <0 = error (spx_last_error() gives the text);
@@ -62,12 +65,15 @@ extern "C" {
 #define SPX_PLUGIN_LROC 7  /* trimaran LowRiskOverCommitment */
 #define SPX_PLUGIN_PEAKS 8 /* trimaran Peaks */
 #define SPX_PLUGIN_SYSCHED 9 /* SySched (pkg/sysched) */
-#define SPX_NUM_PLUGINS 10
-/* Coscheduling (pkg/coscheduling): a PreFilter gate per pending pod.  It owns no score table, no status table and no weight, so the
- * id lies outside SPX_NUM_PLUGINS (which sizes those per-plugin arrays, on the host and in the argmax kernels); bit 10 of a plugin
- * mask is accepted by spx_eval, spx_eval_best, spx_decide and spx_fetch_prefilter. */
+/* Coscheduling (pkg/coscheduling): a PreFilter gate per pending pod.  The id lies inside the per-plugin arrays SPX_NUM_PLUGINS sizes
+ * (on the host and in the argmax kernels) but owns no score table and no status table there, and its entry of the weight vector is
+ * ignored; bit 10 of a plugin mask is accepted by spx_eval, spx_eval_best, spx_decide and spx_fetch_prefilter, and the table calls
+ * (spx_fetch_scores, spx_score_table, spx_bind_score_table ...) refuse the id. */
 #define SPX_PLUGIN_COSCHED 10
-#define SPX_NUM_PLUGIN_IDS 11
+#define SPX_PLUGIN_NODEMETA 11 /* NodeMetadata (pkg/nodemetadata) */
+#define SPX_PLUGIN_PODSTATE 12 /* PodState (pkg/podstate) */
+#define SPX_NUM_PLUGINS 13
+#define SPX_NUM_PLUGIN_IDS 13
 
 /* fwk.Status codes (k8s.io/kube-scheduler/framework) */
 #define SPX_STATUS_SUCCESS 0
@@ -745,6 +751,34 @@ typedef struct spx_sort_keys_soa {
   const int32_t* topo_order;
 } spx_sort_keys_soa;
 
+/* NodeMetadata / PodState: one raw int64 Score per node, the same for every pod (node_metadata.go:57-73, pod_state.go:54-66).
+ * NodeMetadata: raw[i] == INT64_MIN is the reference's own invalidScore (node_metadata.go:48: missing key, unparsable value) and is
+ * carried as such.  PodState: terminating pods minus nominated pods of the node, |raw[i]| < 2^31. */
+typedef struct spx_node_column_soa {
+  int64_t n_nodes;
+  const int64_t* raw;
+} spx_node_column_soa;
+
+/* NodeMetadata's MetadataType / ScoringStrategy (apis/config/types.go), for spx_flatten_nodemeta */
+#define SPX_NODEMETA_NUMBER 0
+#define SPX_NODEMETA_TIMESTAMP 1
+#define SPX_NODEMETA_HIGHEST 0
+#define SPX_NODEMETA_LOWEST 1
+#define SPX_NODEMETA_NEWEST 2
+#define SPX_NODEMETA_OLDEST 3
+
+/* QOSSort: the three per-pod values Sort.Less reads (pkg/qos/queue_sort.go:46-58): pod priority, the QoS class in qosOrder's numbering
+ * (:69-73: 1 BestEffort, 2 Burstable, 3 Guaranteed — spx_flatten_pod_qos) and QueuedPodInfo.Timestamp. */
+#define SPX_QOSSORT_BEST_EFFORT 1
+#define SPX_QOSSORT_BURSTABLE 2
+#define SPX_QOSSORT_GUARANTEED 3
+typedef struct spx_qos_sort_keys_soa {
+  int64_t n_pods;
+  const int32_t* priority;
+  const uint8_t* qos;
+  const int64_t* queue_ts;
+} spx_qos_sort_keys_soa;
+
 /* CapacityScheduling.PreFilter: per-pod request vectors and per-namespace nominated lists (CSR, any order) */
 typedef struct spx_quota_soa {
   int64_t n_pods;
@@ -876,6 +910,10 @@ typedef struct spx_net_commit_soa {
  *   spx_fetch_raw(PEAKS)                       Peaks.Score (raw int64: power jump x 1e15)
  *   spx_eval + spx_fetch_scores(SYSCHED)       SySched.Score + NormalizeScore          pkg/sysched/sysched.go:234-279, :281-288
  *   spx_fetch_raw(SYSCHED)                     SySched.Score (raw int64; math.MaxInt64 for a pod with the empty set, :249-251)
+ *   spx_eval + spx_fetch_scores(NODEMETA)      NodeMetadata.Score + NormalizeScore     pkg/nodemetadata/node_metadata.go:57-73, :150-210
+ *   spx_fetch_raw(NODEMETA)                    NodeMetadata.Score (raw int64; math.MinInt64 = invalidScore, :48)   node_metadata.go:80-145
+ *   spx_eval + spx_fetch_scores(PODSTATE)      PodState.Score + NormalizeScore         pkg/podstate/pod_state.go:42-64, :66-91
+ *   spx_fetch_raw(PODSTATE)                    PodState.score (terminating - nominated pods of the node)           pod_state.go:52-64
  *   spx_eval + spx_fetch_status(NRT)           TopologyMatch.Filter                    pkg/noderesourcetopology/filter.go:179-245
  *   spx_eval + spx_fetch_scores(NRT)           TopologyMatch.Score                     pkg/noderesourcetopology/score.go:62-102
  *   spx_eval + spx_fetch_status(NETOVERHEAD)   NetworkOverhead.PreFilter + Filter      pkg/networkaware/networkoverhead/networkoverhead.go:174-298, :326-359
@@ -887,6 +925,10 @@ typedef struct spx_net_commit_soa {
  *   spx_cosched_less                           Coscheduling.Less, GetCreationTimestamp pkg/coscheduling/coscheduling.go:133-145, core.go:368-384
  *   spx_flatten_net_keys + spx_toposort_less   TopologicalSort.Less, FindPodOrder      pkg/networkaware/topologicalsort/topologicalsort.go:102-132, util/util.go:138-153
  *   spx_upload_sort_keys + spx_sort_keys       the activeQ ordering TopologicalSort.Less induces, as one device sort
+ *   spx_flatten_pod_qos + spx_qos_less         QOSSort.Less, compQOS                   pkg/qos/queue_sort.go:46-58, :65-82
+ *   spx_upload_qos_sort_keys + spx_qos_sort    the activeQ ordering QOSSort.Less induces, as one device sort
+ *   spx_flatten_nodemeta / _nodemeta_unix      calculateScore, parseNumericValue, parseTimestampValue              node_metadata.go:80-145
+ *   spx_flatten_podstate                       PodState.score's two counts per node    pod_state.go:52-64
  *   spx_flatten_trimaran_*                     GetNodeMetrics / ScheduledPodsCache / PredictUtilisation / GetResourceRequested
  *                                              pkg/trimaran/collector.go:110-123, handler.go:47-58, targetloadpacking.go:198-205, resourcestats.go:45-146
  *   spx_flatten_nrt_*                          createNUMANodeList / TopologyManagerFromNodeResourceTopology / GetPodEffectiveRequest / OverReserve
@@ -938,6 +980,14 @@ int spx_upload_peaks_pods(spx_engine* e, const spx_peaks_pods_soa* t);
  * whose largest possible score reaches SPX_SYSCHED_MAX_SCORE, a stale bit outside the names */
 int spx_upload_sysched_nodes(spx_engine* e, const spx_sysched_nodes_soa* t);
 int spx_upload_sysched_pods(spx_engine* e, const spx_sysched_pods_soa* t);
+/* NodeMetadata's and PodState's node columns (spx_flatten_nodemeta, spx_flatten_podstate).  n_nodes must equal the engine's node count
+ * once that is known, as for every node table.  There is no row delta: a column is n_nodes x 8 bytes, upload it again.  An upload
+ * clears the plugin's "evaluated" state.  now_unused is reserved (the flattener takes "now"; the column holds finished scores) and
+ * must be 0.  spx_upload_podstate_nodes: SPX_ERR_ARG for a value with |raw| >= 2^31 (these are pod counts; the refusal keeps
+ * `highest = -math.MaxInt64`, pod_state.go:68, out of play).  Neither plugin is carried by spx_commit_sequential or the spx_multi
+ * loaders. */
+int spx_upload_nodemeta_nodes(spx_engine* e, const spx_node_column_soa* t, int64_t now_unused);
+int spx_upload_podstate_nodes(spx_engine* e, const spx_node_column_soa* t);
 /* Coscheduling tables (spx_flatten_cosched_*).  SPX_ERR_ARG: more than SPX_COSCHED_MAX_SLOTS slots, a group / node index out of range,
  * steps that are not strictly ascending present nodes, a negative add-back, or a table spx_cosched_check refuses (the text names the
  * slot).  Every upload marks the gate stale: the next spx_eval with the COSCHED bit scans and gates again. */
@@ -1005,6 +1055,14 @@ int spx_upload_net_commit(spx_engine* e, const spx_net_commit_soa* t);
  * Synchronous; spx_last_eval_ms reports the device time. */
 int spx_upload_sort_keys(spx_engine* e, const spx_sort_keys_soa* t);
 int spx_sort_keys(spx_engine* e, int32_t* perm_out);
+/* QOSSort as one batched sort of the pending queue.  Sort.Less (queue_sort.go:46-58) is a strict weak order: priority descending, QoS
+ * class descending (Guaranteed, Burstable, BestEffort), timestamp ascending.  spx_qos_sort returns perm_out[i] = pod row at queue
+ * position i; rows equal in all three keys keep ascending row order.  Construction: kernels_sort.hip's stable radix passes, twice
+ * (class and timestamp, then priority and the first order's rank), around the key-building kernels of kernels_node_columns.hip.
+ * Independent of spx_upload_sort_keys / spx_sort_keys (whose keys it leaves alone) and of the other pod tables.  SPX_ERR_ARG: n_pods
+ * outside [1, 2^31), a class outside 1..3.  Synchronous; spx_last_eval_ms reports the device time. */
+int spx_upload_qos_sort_keys(spx_engine* e, const spx_qos_sort_keys_soa* t);
+int spx_qos_sort(spx_engine* e, int32_t* perm_out);
 /* CapacityScheduling.PreFilter status per pod (n_pods bytes: 0 Success, SPX_QUOTA_ST_*); valid after spx_eval with the CAPACITY bit */
 int spx_fetch_prefilter(spx_engine* e, int plugin, int64_t row_begin, int64_t row_end, uint8_t* out);
 /* with plugin == SPX_PLUGIN_COSCHED the same call returns PodGroupManager.PreFilter's status per pod (0 Success, SPX_COSCHED_ST_*),
@@ -1302,7 +1360,7 @@ int spx_bind_score_table(spx_engine* e, int plugin, void* dptr, int64_t row_stri
 
 /* per-pod weighted argmax over the evaluated plugins: best[k] node indices and their
  * sum_i weight[i]*score_i (upstream selectHost input); infeasible nodes are skipped.
- * `weights` holds SPX_NUM_PLUGINS entries indexed by plugin id.  Any int64 is a weight, negative ones included (the general
+ * `weights` holds SPX_NUM_PLUGINS entries indexed by plugin id (the entry of SPX_PLUGIN_COSCHED is ignored: the gate scores nothing).  Any int64 is a weight, negative ones included (the general
  * int64 argmax serves what the 32-bit one does not: a negative weight, a weight >= 2^23, sum of weight * 255 >= 2^31), as long
  * as no total can leave int64: with sum of |weight| * 255 over the plugins that own a score table above INT64_MAX the call
  * is refused with SPX_ERR_ARG and the weights in place stay (the largest single weight is 36170086419038336) */
@@ -1317,7 +1375,8 @@ int spx_fetch_best(spx_engine* e, int64_t row_begin, int64_t row_end, int32_t* n
  * writes a score table (the per-row argmax is folded into the sweep: no 1 B/cell/plugin to HBM and back).  Fused for the
  * Filter-less profiles made of TLP, optionally ALLOCATABLE, and any of the Score-only plugins LVRB / LROC / PEAKS, with
  * non-negative plugin weights and no caller feasibility mask.  ALLOCATABLE's and TLP's tables are never written; the
- * (a mask that holds SYSCHED is served by the unfused route: spx_eval + spx_eval_best)
+ * (a mask that holds SYSCHED is served by the unfused route: spx_eval + spx_eval_best; NODEMETA and PODSTATE are summed from their
+ * tables by either route)
  * Score-only plugins' tables ARE evaluated (spx_eval on those plugins, so they can be fetched afterwards) and read once by
  * the fused sweep in place of spx_eval_best's pass over every table.  Any other request is served by running spx_eval and
  * spx_eval_best.  Asynchronous on the engine stream like spx_eval. */
@@ -1342,7 +1401,8 @@ int spx_decide(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t r
  *                      normalised against that pod's own status rows; without one the rows are fixed and swept once up front.
  * plugin_mask is a subset of {ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, LROC, PEAKS}; LROC and PEAKS need their node and
  * pod tables uploaded.  SYSCHED is still rejected (SySched's bind-time bookkeeping — addPod's union into the host set,
- * sysched.go:310-333 — is not carried by the loop).
+ * sysched.go:310-333 — is not carried by the loop).  NODEMETA and PODSTATE are rejected with the same SPX_ERR_ARG: PodState's nominated
+ * count changes when a nominated pod binds, which is commit state the loop does not carry, and NodeMetadata stays out with it.
  * Route: a mask of ALLOCATABLE / TLP / LVRB alone runs the whole chain in one workgroup (about 3 us per pod).  Any other mask runs
  * per pod: one single-row spx_eval + spx_eval_best + the bookkeeping launches on the engine stream (tens of us per pod), the first
  * pod as plain launches, the rest replayed from one captured graph (a linear chain on the engine stream) whose kernels read the
@@ -1715,6 +1775,29 @@ int spx_flatten_cosched_slots(const spx_cosched_objects* o, int32_t* n_slots_out
 int spx_flatten_cosched_nodes(const spx_node_objects* nodes, const spx_cosched_objects* o, int32_t n_slots, const int32_t* slot_res, int64_t* left_base, uint8_t* node_present);
 int spx_flatten_cosched_groups(const spx_node_objects* nodes, const spx_cosched_objects* o, int32_t n_slots, const int32_t* slot_res, int64_t step_cap, int64_t* n_steps_out, int64_t* req, uint32_t* req_mask, int32_t* step_ptr, int32_t* step_node, int64_t* step_add);
 int spx_toposort_less(const spx_pod_objects* pods, const int32_t* topo_order, int64_t n_pairs, const int64_t* a, const int64_t* b, uint8_t* less_out);
+/* NodeMetadata.calculateScore per node (node_metadata.go:80-145) -> spx_node_column_soa.raw.  Node i's label or annotation value
+ * (which of the two is the caller's choice, MetadataSource) is the bytes values[value_ptr[i] .. value_ptr[i+1]); found[i] = the key
+ * exists.  raw_out[i] = INT64_MIN (invalidScore) for !found or a value that does not parse.
+ *   SPX_NODEMETA_NUMBER: strconv.ParseFloat(s, 64)'s grammar exactly — decimal and 0x...p... hexadecimal forms, "inf" / "infinity" /
+ *     "nan" in any case with an optional sign, underscores only after a base prefix, no blanks, a hexadecimal mantissa needs its p
+ *     exponent, a value out of float64's range is an error.  Then int64(v), negated for SPX_NODEMETA_LOWEST (:115-119); NaN, +-Inf
+ *     and |v| >= 2^63 convert to INT64_MIN as on amd64, hence invalid under either strategy.
+ *   SPX_NODEMETA_TIMESTAMP: RFC 3339 as time.Parse(time.RFC3339, s) takes it (the default TimestampFormat, :221-223); age =
+ *     float64(now_unix_nanos - t) / 1e9; -int64(age) for SPX_NODEMETA_NEWEST, int64(age) for SPX_NODEMETA_OLDEST (:134-144).  time.Since
+ *     becomes the explicit now_unix_nanos.  A timestamp outside the years time.Duration can hold saturates as Go's Sub does.
+ * SPX_ERR_ARG: a strategy that does not belong to the type, a value_ptr that is not ascending.
+ * spx_flatten_nodemeta_unix: the same scores from timestamps the caller parsed (any other TimestampFormat is parsed on the Go side):
+ * unix_nanos[i] and valid[i] in place of the strings. */
+int spx_flatten_nodemeta(const char* values, const int64_t* value_ptr, const uint8_t* found, int64_t n_nodes, int type, int strategy, int64_t now_unix_nanos, int64_t* raw_out);
+int spx_flatten_nodemeta_unix(const int64_t* unix_nanos, const uint8_t* valid, int64_t n_nodes, int strategy, int64_t now_unix_nanos, int64_t* raw_out);
+/* PodState.score per node (pod_state.go:52-64): raw_out[n] = assigned pods of node n with a DeletionTimestamp minus pods nominated to
+ * node n — the columns the preemption object tables carry (spx_preempt_objects: assigned pods' node and terminating flag, the
+ * nominated pods' node).  SPX_ERR_ARG: a node index outside [0, n_nodes). */
+int spx_flatten_podstate(int64_t n_nodes, int64_t n_assigned, const int64_t* assigned_node, const uint8_t* assigned_terminating, int64_t n_nominated, const int64_t* nominated_node, int64_t* raw_out);
+/* v1qos.GetPodQOS per pod in QOSSort's numbering (SPX_QOSSORT_*), from the restatement the NRT pod flattener uses */
+int spx_flatten_pod_qos(const spx_pod_objects* pods, uint8_t* qos_out);
+/* QOSSort's Sort.Less (queue_sort.go:46-58) for one pair; 1 = Less(pod 1, pod 2).  Host only. */
+int spx_qos_less(int32_t priority1, int qos1, int64_t ts1, int32_t priority2, int qos2, int64_t ts2);
 /* spx_net_commit_soa columns: *n_entries_out first (NULL arrays), then eff_ptr[P+1], eff_key / eff_max_cost[n_entries] */
 int spx_flatten_net_commit(const spx_pod_objects* pods, const spx_appgroup_objects* ag, int64_t* n_entries_out, int32_t* eff_ptr, int32_t* eff_key, int64_t* eff_max_cost);
 /* pods that joined AppGroup scheduled lists since the flatten: the entries spx_update_net_placed appends (sizes first: NULL arrays) */

@@ -67,7 +67,7 @@ struct spx_engine {
   std::vector<int64_t> alloc_weight{1, 1 << 20};  // defaultResourcesToWeightMap resource_allocation.go:36
   spx_tlp_params tlp{40, 1000, 1.5};             // apis/config/v1/defaults.go:51-55
   spx_lvrb_params lvrb{1.0, 1.0};                // defaults.go:65-67
-  int64_t plugin_weight[SPX_NUM_PLUGINS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+  int64_t plugin_weight[SPX_NUM_PLUGINS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};  // (Coscheduling's entry is never read)
 
   // device tables
   DevBuf d_alloc, d_alloc_w, d_alloc_raw, d_alloc_norm, d_alloc_rel;
@@ -127,6 +127,10 @@ struct spx_engine {
   std::vector<int32_t> h_sy_sptr, h_sy_sbit, h_sy_scnt, h_sy_pod_set, h_sy_first;
   int64_t sy_n_dups = 0, sy_n_tasks = 0;
   int sy_last_chunks = 0;  // spx_kernel_path(SYSCHED)
+
+  // NodeMetadata / PodState: the raw int64 column per node and the scratch row the pod-independent normalisation is broadcast from
+  DevBuf d_nm_raw, d_ps_raw, d_ncol_row;
+  bool nm_nodes = false, ps_nodes = false;
 
   // Coscheduling: the snapshot's left-overs and their scan, the groups' requests / steps / flags, the verdicts and the pods' status.
   // cs_gate_valid: scan and gate hold for the tables in place (any upload clears it); cs_rows: the pod rows whose status is current
@@ -236,7 +240,10 @@ struct spx_engine {
   // TopologicalSort keys
   DevBuf d_sort_prio, d_sort_ts, d_sort_group, d_sort_topo, d_sort_scratch;
   int64_t sort_n = 0;
-  unsigned* h_sort_hist = nullptr;  // pinned
+  unsigned* h_sort_hist = nullptr;  // pinned (scratch of both sorts)
+  // QOSSort keys (independent of TopologicalSort's): priority, class, timestamp as uploaded; the derived columns and the passes' scratch
+  DevBuf d_qos_prio, d_qos_cls, d_qos_ts, d_qos_key, d_qos_none, d_qos_zero, d_qos_rank, d_qos_scratch;
+  int64_t qos_n = 0;
 
   // profile-level state
   DevBuf d_ext_status;  // caller's feasibility mask, stored as a status table (0 = feasible)
@@ -495,9 +502,12 @@ int ensure_score_table(spx_engine* e, int plugin) {
 constexpr uint32_t kFilterPlugins = (1u << SPX_PLUGIN_NRT) | (1u << SPX_PLUGIN_NETOVERHEAD);
 // plugins whose NormalizeScore depends on the feasible set of the cycle
 constexpr uint32_t kNormalizingPlugins =
-    (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_PEAKS) | (1u << SPX_PLUGIN_SYSCHED);
+    (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_PEAKS) | (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_NODEMETA) |
+    (1u << SPX_PLUGIN_PODSTATE);
 // plugins that own a uint8 score table
-constexpr bool plugin_has_score(int k) { return k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS || k == SPX_PLUGIN_SYSCHED; }
+constexpr bool plugin_has_score(int k) {
+  return k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS || k == SPX_PLUGIN_SYSCHED || k == SPX_PLUGIN_NODEMETA || k == SPX_PLUGIN_PODSTATE;
+}
 
 // The status tables that narrow a pod's node list when `mask` is evaluated or summed: {NRT's, NetworkOverhead's, the caller's mask},
 // NULL = not in play (the layout of ProfileArgs.status and the scorers' other_status; NetworkOverhead's own sweep takes [0] and [2])

@@ -75,6 +75,7 @@ int spx_destroy(spx_engine* e) {
                     &e->d_q_usedp, &e->d_q_min, &e->d_q_minp, &e->d_q_agg, &e->d_net_eff_ptr, &e->d_net_eff_key, &e->d_net_eff_cost, &e->d_net_dyn_ptr,
                     &e->d_net_dyn_end, &e->d_net_dyn_node, &e->d_net_dyn_max, &e->d_commit_save, &e->d_row_counter, &e->d_coop_sync, &e->d_coop_node, &e->d_coop_max,
                     &e->d_sort_prio, &e->d_sort_ts, &e->d_sort_group, &e->d_sort_topo, &e->d_sort_scratch,
+                    &e->d_qos_prio, &e->d_qos_cls, &e->d_qos_ts, &e->d_qos_key, &e->d_qos_none, &e->d_qos_zero, &e->d_qos_rank, &e->d_qos_scratch, &e->d_nm_raw, &e->d_ps_raw, &e->d_ncol_row,
                     &e->d_best, &e->d_stats, &e->d_decide, &e->d_lroc_nreq_c, &e->d_lroc_nreq_m, &e->d_lroc_nlim_c, &e->d_lroc_nlim_m,
                     &e->d_lroc_preq_c, &e->d_lroc_preq_m, &e->d_lroc_plim_c, &e->d_lroc_plim_m, &e->d_lroc_tab, &e->d_lroc_podf,
                     &e->d_pk_cap, &e->d_pk_util, &e->d_pk_valid, &e->d_pk_k1, &e->d_pk_k2, &e->d_pk_pod, &e->d_pk_min, &e->d_pk_max, &e->d_pk_rowc, &e->d_pk_tab, &e->d_pk_seg, &e->d_pk_segn,
@@ -251,15 +252,16 @@ namespace {
 // the plugins of one evaluation's mask
 struct EvalPlugins {
   uint32_t mask;
-  bool alloc, tlp, lvrb, nrt, net, quota, lroc, peaks, sysched, cosched;
-  bool masked;  // Allocatable's NormalizeScore runs over each pod's feasible nodes as soon as any Filter is in play
+  bool alloc, tlp, lvrb, nrt, net, quota, lroc, peaks, sysched, cosched, nodemeta, podstate;
+  bool masked;  // Allocatable's (NodeMetadata's, PodState's) NormalizeScore runs over each pod's feasible nodes as soon as any Filter is in play
 };
 
 EvalPlugins eval_plugins(const spx_engine* e, uint32_t mask) {
   auto has = [mask](int plugin) { return ((mask >> plugin) & 1u) != 0; };
   const bool nrt = has(SPX_PLUGIN_NRT), net = has(SPX_PLUGIN_NETOVERHEAD);
   return EvalPlugins{mask, has(SPX_PLUGIN_ALLOCATABLE), has(SPX_PLUGIN_TLP), has(SPX_PLUGIN_LVRB), nrt, net, has(SPX_PLUGIN_CAPACITY), has(SPX_PLUGIN_LROC),
-                     has(SPX_PLUGIN_PEAKS), has(SPX_PLUGIN_SYSCHED), has(SPX_PLUGIN_COSCHED), nrt || net || e->ext_mask};
+                     has(SPX_PLUGIN_PEAKS), has(SPX_PLUGIN_SYSCHED), has(SPX_PLUGIN_COSCHED), has(SPX_PLUGIN_NODEMETA), has(SPX_PLUGIN_PODSTATE),
+                     nrt || net || e->ext_mask};
 }
 
 // Every SPX_ERR_ARG / SPX_ERR_STATE answer of an evaluation, from host state alone: a call refused here has allocated nothing,
@@ -267,13 +269,17 @@ EvalPlugins eval_plugins(const spx_engine* e, uint32_t mask) {
 int eval_check(const spx_engine* e, const EvalPlugins& f, int64_t row_begin, int64_t row_end) {
   const uint32_t known = (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_TLP) | (1u << SPX_PLUGIN_LVRB) | (1u << SPX_PLUGIN_NRT) |
                          (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_CAPACITY) | (1u << SPX_PLUGIN_LROC) | (1u << SPX_PLUGIN_PEAKS) |
-                         (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_COSCHED);
+                         (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_COSCHED) | (1u << SPX_PLUGIN_NODEMETA) | (1u << SPX_PLUGIN_PODSTATE);
   if (f.mask == 0 || (f.mask & ~known)) return fail(e, SPX_ERR_ARG, "plugin mask has unsupported bits");
   if (f.lroc && !(e->tri_nodes && e->lroc_nodes && e->lroc_pods)) return fail(e, SPX_ERR_STATE, "LowRiskOverCommitment node/pod tables not uploaded");
   if (f.peaks && !(e->peaks_nodes && e->peaks_pods)) return fail(e, SPX_ERR_STATE, "Peaks node/pod tables not uploaded");
   if (f.sysched && !(e->sy_nodes && e->sy_pods)) return fail(e, SPX_ERR_STATE, "SySched node/pod tables not uploaded");
   if (f.sysched && e->sy_node_words != e->sy_pod_words) return fail(e, SPX_ERR_STATE, "SySched: the node and pod tables differ in n_words");
   if (f.sysched && e->row_indirect) return fail(e, SPX_ERR_STATE, "SySched is not part of the sequential commit loop");
+  if (f.nodemeta && !e->nm_nodes) return fail(e, SPX_ERR_STATE, "NodeMetadata node column not uploaded");
+  if (f.podstate && !e->ps_nodes) return fail(e, SPX_ERR_STATE, "PodState node column not uploaded");
+  if (f.nodemeta && e->row_indirect) return fail(e, SPX_ERR_STATE, "NodeMetadata is not part of the sequential commit loop");
+  if (f.podstate && e->row_indirect) return fail(e, SPX_ERR_STATE, "PodState is not part of the sequential commit loop");
   if (f.cosched && !e->cosched) return fail(e, SPX_ERR_STATE, "Coscheduling tables not uploaded");
   if (f.cosched && e->row_indirect) return fail(e, SPX_ERR_STATE, "Coscheduling is not part of the sequential commit loop");
   if (f.quota && !e->quota) return fail(e, SPX_ERR_STATE, "CapacityScheduling quota tables not uploaded");
@@ -304,6 +310,8 @@ int eval_check(const spx_engine* e, const EvalPlugins& f, int64_t row_begin, int
   if (f.nrt && (rc = status_table_fits(e, SPX_PLUGIN_NRT))) return rc;
   if (f.net && (rc = status_table_fits(e, SPX_PLUGIN_NETOVERHEAD))) return rc;
   if (f.sysched && ((rc = score_table_fits(e, SPX_PLUGIN_SYSCHED)) || (rc = score_table_stride(e, SPX_PLUGIN_SYSCHED)))) return rc;
+  if (f.nodemeta && ((rc = score_table_fits(e, SPX_PLUGIN_NODEMETA)) || (rc = score_table_stride(e, SPX_PLUGIN_NODEMETA)))) return rc;
+  if (f.podstate && ((rc = score_table_fits(e, SPX_PLUGIN_PODSTATE)) || (rc = score_table_stride(e, SPX_PLUGIN_PODSTATE)))) return rc;
   for (int p = 0; p < 3; ++p)
     if ((f.mask & (1u << p)) && (rc = score_table_stride(e, p))) return rc;
   if (f.nrt && (rc = score_table_stride(e, SPX_PLUGIN_NRT))) return rc;
@@ -797,6 +805,26 @@ int launch_alloc_masked_rows(spx_engine* e, const EvalPlugins& f, int64_t row_be
   return SPX_OK;
 }
 
+// NodeMetadata's or PodState's table, once the status tables of the evaluation are final: the pod-independent row broadcast when
+// nothing narrows a pod's node list, NormalizeScore over each pod's feasible nodes otherwise (kernels_node_columns.hip)
+int launch_node_columns(spx_engine* e, const EvalPlugins& f, int plugin, int64_t row_begin, int64_t row_end) {
+  spx::NodeColArgs ca{};
+  const bool meta = plugin == SPX_PLUGIN_NODEMETA;
+  ca.kind = meta ? spx::kNodeColMeta : spx::kNodeColPodState;
+  ca.n_nodes = e->n_nodes;
+  ca.row_stride = e->row_stride;
+  ca.row_begin = row_begin;
+  ca.row_end = row_end;
+  ca.raw = static_cast<const int64_t*>(meta ? e->d_nm_raw.p : e->d_ps_raw.p);
+  feasibility_status(e, f.mask, ca.status);
+  ca.norm_row = static_cast<uint8_t*>(e->d_ncol_row.p);
+  ca.out_score = static_cast<uint8_t*>(e->score[plugin].p);
+  ca.block_per_row = static_cast<int32_t>(e->option[SPX_OPT_ROW_WORKGROUP]);
+  spx::launch_node_column(ca, e->stream);
+  SPX_HIP(e, hipGetLastError());
+  return SPX_OK;
+}
+
 // what the engine remembers of an evaluation whose launches are all on the stream
 void eval_record(spx_engine* e, const EvalPlugins& f, const EvalCall& call, int64_t row_begin, int64_t row_end) {
   e->timed = true;
@@ -810,7 +838,7 @@ void eval_record(spx_engine* e, const EvalPlugins& f, const EvalCall& call, int6
   if (row_end <= row_begin) return;
   const uint32_t filters = f.mask & kFilterPlugins;
   for (int p = 0; p < SPX_NUM_PLUGINS; ++p) {
-    if (!((f.mask >> p) & 1u) || (alloc_skipped && p == SPX_PLUGIN_ALLOCATABLE)) continue;
+    if (!((f.mask >> p) & 1u) || (alloc_skipped && p == SPX_PLUGIN_ALLOCATABLE) || p == SPX_PLUGIN_COSCHED) continue;  // (the gate keeps its own rows: cs_row_*)
     spx_engine::EvalInfo& i = e->eval_info[p];
     const bool same_ctx = i.filters == filters && i.ext_gen == e->ext_gen && i.end > i.begin;
     if (same_ctx && row_begin <= i.end && row_end >= i.begin) {  // overlapping or adjacent: the evaluated rows grow
@@ -832,6 +860,7 @@ int eval_rows(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t ro
   if (f.peaks && (rc = prepare_peaks(e))) return rc;
   int64_t sy_per_chunk = 0;
   if (f.sysched && (rc = prepare_sysched(e, &sy_per_chunk))) return rc;
+  if ((f.nodemeta || f.podstate) && (rc = ensure(e, e->d_ncol_row, static_cast<size_t>(e->row_stride)))) return rc;
   TrimaranStep tri;
   if ((rc = prepare_trimaran(e, f, call, row_begin, row_end, &tri))) return rc;
   if (!call.hold_ev0) SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
@@ -845,6 +874,8 @@ int eval_rows(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_t ro
   if (f.peaks && (rc = launch_peaks_rows(e, f, row_begin, row_end))) return rc;
   if (f.sysched && row_end > row_begin && (rc = launch_sysched_rows(e, f, sy_per_chunk, row_begin, row_end))) return rc;
   if (f.alloc && f.masked && !call.skip_alloc_masked && !alloc_by_net && (rc = launch_alloc_masked_rows(e, f, row_begin, row_end))) return rc;
+  if (f.nodemeta && (rc = launch_node_columns(e, f, SPX_PLUGIN_NODEMETA, row_begin, row_end))) return rc;
+  if (f.podstate && (rc = launch_node_columns(e, f, SPX_PLUGIN_PODSTATE, row_begin, row_end))) return rc;
   SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
   eval_record(e, f, call, row_begin, row_end);
   return SPX_OK;
@@ -984,7 +1015,7 @@ int reader_copy(spx_engine* e, void* out, const void* src, size_t bytes) {
 
 int spx_fetch_scores(spx_engine* e, int plugin, int64_t pod_row, uint8_t* out) {
   if (!e || !out) return SPX_ERR_ARG;
-  if (plugin < 0 || plugin >= SPX_NUM_PLUGINS || !(e->evaluated & (1u << plugin)))
+  if (plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED || !(e->evaluated & (1u << plugin)))
     return fail(e, SPX_ERR_STATE, "plugin has not been evaluated");
   if (pod_row < 0 || pod_row >= e->n_pods) return fail(e, SPX_ERR_ARG, "pod_row out of range");
   if (int rc = rows_evaluated(e, plugin, pod_row, pod_row + 1)) return rc;
@@ -1056,6 +1087,11 @@ int spx_fetch_raw(spx_engine* e, int plugin, int which, int64_t pod_row, int64_t
     g.out_raw = raw;
     g.raw_which = which;
     spx::launch_net(g, e->stream);
+  } else if (plugin == SPX_PLUGIN_NODEMETA || plugin == SPX_PLUGIN_PODSTATE) {  // the uploaded column, the same for every pod: no launch
+    const bool meta = plugin == SPX_PLUGIN_NODEMETA;
+    if (!(meta ? e->nm_nodes : e->ps_nodes)) return fail(e, SPX_ERR_STATE, meta ? "NodeMetadata node column not uploaded" : "PodState node column not uploaded");
+    if (e->n_pods > 0 && (pod_row < 0 || pod_row >= e->n_pods)) return fail(e, SPX_ERR_ARG, "pod_row out of range");
+    raw = static_cast<int64_t*>(meta ? e->d_nm_raw.p : e->d_ps_raw.p);
   } else if (plugin == SPX_PLUGIN_PEAKS) {  // Peaks.Score before NormalizeScore: the power jump x 1e15
     if (!(e->peaks_nodes && e->peaks_pods)) return fail(e, SPX_ERR_STATE, "Peaks node/pod tables not uploaded");
     if ((rc = scratch_row())) return rc;
@@ -1136,7 +1172,7 @@ int spx_fetch_stats(spx_engine* e, int64_t* reevaluated_cells, int reset) {
 }
 
 int spx_score_table(spx_engine* e, int plugin, void** dptr, int64_t* row_stride, int64_t* n_rows) {
-  if (!e || plugin < 0 || plugin >= SPX_NUM_PLUGINS) return SPX_ERR_ARG;
+  if (!e || plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED) return SPX_ERR_ARG;
   if (e->n_nodes <= 0 || e->n_pods <= 0) return fail(e, SPX_ERR_STATE, "shape unknown: upload node and pod tables first");
   int rc = ensure_score_table(e, plugin);
   if (rc) return rc;
@@ -1147,7 +1183,7 @@ int spx_score_table(spx_engine* e, int plugin, void** dptr, int64_t* row_stride,
 }
 
 int spx_bind_score_table(spx_engine* e, int plugin, void* dptr, int64_t row_stride, int64_t n_rows) {
-  if (!e || plugin < 0 || plugin >= SPX_NUM_PLUGINS) return SPX_ERR_ARG;
+  if (!e || plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED) return SPX_ERR_ARG;
   DevBuf& b = e->score[plugin];
   if (plugin == SPX_PLUGIN_ALLOCATABLE) alloc_table_dirty(e);  // another buffer from here on (a bound one is never kept: the caller owns it)
   if (!dptr) {  // unbind
@@ -1270,14 +1306,14 @@ int spx_eval_best(spx_engine* e, uint32_t plugin_mask, int64_t row_begin, int64_
   // every table in the sum must cover the rows, and the normalising plugins must have been evaluated under exactly the Filter
   // set this argmax uses (their NormalizeScore ran over the nodes that passed those Filters, as upstream's RunScorePlugins does)
   for (int p = 0; p < SPX_NUM_PLUGINS && row_end > row_begin; ++p) {
-    if (!((plugin_mask >> p) & 1u)) continue;
+    if (!((plugin_mask >> p) & 1u) || p == SPX_PLUGIN_COSCHED) continue;  // (the gate's rows are checked below)
     if ((rc = rows_evaluated(e, p, row_begin, row_end))) return rc;
     const spx_engine::EvalInfo& i = e->eval_info[p];
     const bool ctx_matters = ((kNormalizingPlugins >> p) & 1u) != 0;
     uint32_t want = plugin_mask & kFilterPlugins;
     if (p == SPX_PLUGIN_NETOVERHEAD) want &= ~(1u << SPX_PLUGIN_NETOVERHEAD), want |= i.filters & (1u << SPX_PLUGIN_NETOVERHEAD);  // its own Filter is implied
     if (ctx_matters && (i.filters != want || i.ext_gen != e->ext_gen))
-      return fail(e, SPX_ERR_STATE, "spx_eval_best: a normalising plugin (Allocatable / NetworkOverhead / Peaks / SySched) was evaluated under a different Filter set "
+      return fail(e, SPX_ERR_STATE, "spx_eval_best: a normalising plugin (Allocatable / NetworkOverhead / Peaks / SySched / NodeMetadata / PodState) was evaluated under a different Filter set "
                                     "or feasibility mask than this argmax uses; evaluate the whole profile in one spx_eval");
   }
   const bool gate = plugin_mask & (1u << SPX_PLUGIN_COSCHED);

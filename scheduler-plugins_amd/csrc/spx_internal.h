@@ -1208,4 +1208,26 @@ void launch_best(const ProfileArgs& a, hipStream_t s);
 bool decide_masked_ok(const ProfileArgs& a);
 void launch_decide_masked(const ProfileArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- NodeMetadata / PodState (kernels_node_columns.hip)
+// One raw int64 per node; NormalizeScore over the nodes of each pod row that passed the Filters in play.
+enum : int32_t { kNodeColMeta = 0, kNodeColPodState = 1 };
+struct NodeColArgs {
+  int32_t kind;  // kNodeColMeta: INT64_MIN is invalid, valid cells in [1, 100], invalid 0; kNodeColPodState: [0, 100]
+  int64_t n_nodes;
+  int64_t row_stride;
+  int64_t row_begin;
+  int64_t row_end;
+  const int64_t* raw;        // [N]
+  const uint8_t* status[3];  // Filter status tables in play (0 = passed); all NULL: the row is the same for every pod
+  uint8_t* norm_row;         // [row_stride] scratch: the pod-independent row (written and broadcast when no status table is set)
+  uint8_t* out_score;        // the plugin's score table
+  int32_t block_per_row;     // a whole workgroup per row in a batch launch too
+};
+void launch_node_column(const NodeColArgs& a, hipStream_t s);
+
+// QOSSort's key building around kernels_sort.hip's passes: the class as the first sort's int32 "priority" column (with the
+// constant AppGroup / topology columns that sort wants), and the first order's rank as the second sort's int64 "timestamp"
+void launch_qos_class_keys(const uint8_t* qos, int64_t n, int32_t* cls_out, int32_t* none_out, int32_t* zero_out, hipStream_t s);
+void launch_qos_rank_keys(const int32_t* perm, int64_t n, int64_t* rank_out, hipStream_t s);
+
 }  // namespace spx

@@ -472,7 +472,7 @@ int spx_multi_gather_best(spx_multi* m, int64_t n_pods_total, int32_t* node_idx,
 }
 
 int spx_multi_bind_global_table(spx_multi* m, int plugin, int which, int64_t n_pods_total) {
-  if (!m || plugin < 0 || plugin >= SPX_NUM_PLUGINS || (which != 0 && which != 1)) return SPX_ERR_ARG;
+  if (!m || plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED || (which != 0 && which != 1)) return SPX_ERR_ARG;
   if (n_pods_total <= 0) return mfail(m, SPX_ERR_ARG, "n_pods_total must be positive");
   GlobalTable& t = m->table[which][plugin];
   const int64_t per = rows_per_rank(n_pods_total, m->n);
@@ -535,7 +535,7 @@ int spx_multi_bind_global_table(spx_multi* m, int plugin, int which, int64_t n_p
 }
 
 int spx_multi_allgather_table(spx_multi* m, int plugin, int which) {
-  if (!m || plugin < 0 || plugin >= SPX_NUM_PLUGINS || (which != 0 && which != 1)) return SPX_ERR_ARG;
+  if (!m || plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED || (which != 0 && which != 1)) return SPX_ERR_ARG;
   GlobalTable& t = m->table[which][plugin];
   if (t.dptr.empty()) return mfail(m, SPX_ERR_STATE, "no global table bound for this plugin (spx_multi_bind_global_table)");
   // a rank whose shard of the table was not written by its last evaluation (spx_multi_decide on a Filter profile folds Allocatable's
@@ -552,7 +552,7 @@ int spx_multi_allgather_table(spx_multi* m, int plugin, int which) {
 }
 
 int spx_multi_global_table(spx_multi* m, int plugin, int which, int rank, void** dptr, int64_t* row_stride, int64_t* n_rows) {
-  if (!m || plugin < 0 || plugin >= SPX_NUM_PLUGINS || (which != 0 && which != 1) || rank < 0 || rank >= m->n) return SPX_ERR_ARG;
+  if (!m || plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED || (which != 0 && which != 1) || rank < 0 || rank >= m->n) return SPX_ERR_ARG;
   GlobalTable& t = m->table[which][plugin];
   if (t.dptr.empty()) return mfail(m, SPX_ERR_STATE, "no global table bound for this plugin");
   if (dptr) *dptr = t.dptr[static_cast<size_t>(rank)];
@@ -562,7 +562,7 @@ int spx_multi_global_table(spx_multi* m, int plugin, int which, int rank, void**
 }
 
 int spx_multi_fetch_global_rows(spx_multi* m, int plugin, int which, int rank, int64_t row_begin, int64_t row_end, uint8_t* out, int64_t out_stride) {
-  if (!m || !out || plugin < 0 || plugin >= SPX_NUM_PLUGINS || (which != 0 && which != 1) || rank < 0 || rank >= m->n) return SPX_ERR_ARG;
+  if (!m || !out || plugin < 0 || plugin >= SPX_NUM_PLUGINS || plugin == SPX_PLUGIN_COSCHED || (which != 0 && which != 1) || rank < 0 || rank >= m->n) return SPX_ERR_ARG;
   GlobalTable& t = m->table[which][plugin];
   if (t.dptr.empty() || !t.gathered) return mfail(m, SPX_ERR_STATE, "global table not gathered (spx_multi_allgather_table)");
   if (row_begin < 0 || row_end > t.n_pods_total || row_begin > row_end) return mfail(m, SPX_ERR_ARG, "row range out of bounds");

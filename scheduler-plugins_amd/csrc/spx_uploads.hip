@@ -1482,6 +1482,92 @@ int spx_sort_keys(spx_engine* e, int32_t* perm_out) {
   return SPX_OK;
 }
 
+// NodeMetadata's / PodState's raw column: one int64 per node, whole (no row delta: the column is n_nodes x 8 bytes)
+static int upload_node_column(spx_engine* e, const spx_node_column_soa* t, int plugin, DevBuf& col, bool& ready) {
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (!t->raw) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  if (plugin == SPX_PLUGIN_PODSTATE)
+    for (int64_t i = 0; i < t->n_nodes; ++i)
+      if (t->raw[i] >= (int64_t{1} << 31) || t->raw[i] <= -(int64_t{1} << 31))
+        return fail(e, SPX_ERR_ARG, "PodState: a node's terminating minus nominated pod count must lie inside (-2^31, 2^31)");
+  int rc = set_nodes(e, t->n_nodes);
+  if (rc) return rc;
+  ready = false;
+  if ((rc = upload(e, col, t->raw, static_cast<size_t>(t->n_nodes) * sizeof(int64_t)))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  ready = true;
+  e->evaluated &= ~(1u << plugin);
+  e->best_valid = false;
+  return SPX_OK;
+}
+
+int spx_upload_nodemeta_nodes(spx_engine* e, const spx_node_column_soa* t, int64_t now_unused) {
+  if (!e || !t) return SPX_ERR_ARG;
+  if (now_unused != 0) return fail(e, SPX_ERR_ARG, "NodeMetadata: now_unused is reserved and must be 0 (spx_flatten_nodemeta takes the time)");
+  return upload_node_column(e, t, SPX_PLUGIN_NODEMETA, e->d_nm_raw, e->nm_nodes);
+}
+
+int spx_upload_podstate_nodes(spx_engine* e, const spx_node_column_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  return upload_node_column(e, t, SPX_PLUGIN_PODSTATE, e->d_ps_raw, e->ps_nodes);
+}
+
+int spx_upload_qos_sort_keys(spx_engine* e, const spx_qos_sort_keys_soa* t) {
+  if (!e || !t) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (t->n_pods <= 0 || t->n_pods >= (int64_t{1} << 31)) return fail(e, SPX_ERR_ARG, "QOSSort keys: n_pods must be in [1, 2^31)");
+  if (!t->priority || !t->qos || !t->queue_ts) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  const size_t p = static_cast<size_t>(t->n_pods);
+  for (size_t i = 0; i < p; ++i)
+    if (t->qos[i] < SPX_QOSSORT_BEST_EFFORT || t->qos[i] > SPX_QOSSORT_GUARANTEED)
+      return fail(e, SPX_ERR_ARG, "QOSSort keys: qos must be 1 (BestEffort), 2 (Burstable) or 3 (Guaranteed)");
+  int rc;
+  e->qos_n = 0;
+  if ((rc = upload(e, e->d_qos_prio, t->priority, p * 4))) return rc;
+  if ((rc = upload(e, e->d_qos_cls, t->qos, p))) return rc;
+  if ((rc = upload(e, e->d_qos_ts, t->queue_ts, p * 8))) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->qos_n = t->n_pods;
+  return SPX_OK;
+}
+
+int spx_qos_sort(spx_engine* e, int32_t* perm_out) {
+  if (!e || !perm_out) return SPX_ERR_ARG;
+  SPX_HIP(e, hipSetDevice(e->device));
+  if (e->qos_n <= 0) return fail(e, SPX_ERR_STATE, "QOSSort: spx_upload_qos_sort_keys not called");
+  const size_t p = static_cast<size_t>(e->qos_n);
+  int rc;
+  if ((rc = ensure(e, e->d_qos_scratch, spx::sort_scratch_bytes(e->qos_n))) || (rc = ensure(e, e->d_qos_key, p * 4)) || (rc = ensure(e, e->d_qos_none, p * 4)) ||
+      (rc = ensure(e, e->d_qos_zero, p * 4)) || (rc = ensure(e, e->d_qos_rank, p * 8)))
+    return rc;
+  if (!e->h_sort_hist) SPX_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_sort_hist), 16 * 256 * sizeof(unsigned), hipHostMallocDefault));
+  // Less orders by (priority descending, class descending, timestamp ascending).  kernels_sort.hip's passes order int32 descending then
+  // int64 ascending, stably from the row order, so: sort by (class, timestamp); the rank in that order stands for both keys and
+  // is unique; sort by (priority, rank).  No pod belongs to an AppGroup, so that sort's second stage leaves the order as it is.
+  spx::SortArgs a{};
+  a.n = e->qos_n;
+  a.priority = static_cast<const int32_t*>(e->d_qos_key.p);
+  a.queue_ts = static_cast<const int64_t*>(e->d_qos_ts.p);
+  a.appgroup = static_cast<const int32_t*>(e->d_qos_none.p);
+  a.topo_order = static_cast<const int32_t*>(e->d_qos_zero.p);
+  SPX_HIP(e, hipEventRecord(e->ev0, e->stream));
+  spx::launch_qos_class_keys(static_cast<const uint8_t*>(e->d_qos_cls.p), e->qos_n, static_cast<int32_t*>(e->d_qos_key.p), static_cast<int32_t*>(e->d_qos_none.p),
+                             static_cast<int32_t*>(e->d_qos_zero.p), e->stream);
+  hipError_t st = hipSuccess;
+  const int32_t* perm = spx::launch_sort_keys(a, e->d_qos_scratch.p, e->h_sort_hist, e->stream, &st);
+  if (st != hipSuccess || !perm) return fail(e, SPX_ERR_HIP, std::string("spx_qos_sort: ") + hipGetErrorString(st));
+  spx::launch_qos_rank_keys(perm, e->qos_n, static_cast<int64_t*>(e->d_qos_rank.p), e->stream);
+  a.priority = static_cast<const int32_t*>(e->d_qos_prio.p);
+  a.queue_ts = static_cast<const int64_t*>(e->d_qos_rank.p);
+  perm = spx::launch_sort_keys(a, e->d_qos_scratch.p, e->h_sort_hist, e->stream, &st);
+  if (st != hipSuccess || !perm) return fail(e, SPX_ERR_HIP, std::string("spx_qos_sort: ") + hipGetErrorString(st));
+  SPX_HIP(e, hipEventRecord(e->ev1, e->stream));
+  e->timed = true;
+  SPX_HIP(e, hipMemcpyAsync(perm_out, perm, p * 4, hipMemcpyDeviceToHost, e->stream));
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  return SPX_OK;
+}
+
 int spx_upload_quota(spx_engine* e, const spx_quota_soa* t) {
   if (!e || !t) return SPX_ERR_ARG;
   SPX_HIP(e, hipSetDevice(e->device));

@@ -19,8 +19,12 @@ PLUGINS = {
     "TopologicalSort": 6,
 }
 ALLOCATABLE, TLP, LVRB, NRT, NETOVERHEAD, CAPACITY, TOPOSORT, LROC, PEAKS, SYSCHED = range(10)
-NUM_PLUGINS = 10  # SPX_NUM_PLUGINS
-COSCHED = 10  # SPX_PLUGIN_COSCHED: a PreFilter gate without tables or a weight, outside NUM_PLUGINS
+NUM_PLUGINS = 13  # SPX_NUM_PLUGINS
+COSCHED = 10  # SPX_PLUGIN_COSCHED: a PreFilter gate without tables; its entry of the weight vector is ignored
+NODEMETA, PODSTATE = 11, 12  # SPX_PLUGIN_NODEMETA, SPX_PLUGIN_PODSTATE
+NODEMETA_TYPE = {"Number": 0, "Timestamp": 1}  # SPX_NODEMETA_NUMBER / _TIMESTAMP
+NODEMETA_STRATEGY = {"Highest": 0, "Lowest": 1, "Newest": 2, "Oldest": 3}  # SPX_NODEMETA_HIGHEST ...
+INVALID_SCORE = -(1 << 63)  # NodeMetadata's invalidScore (math.MinInt64)
 COSCHED_ST = {"BACKED_OFF": 1, "FEW_SIBLINGS": 2, "GATED": 3, "RESOURCE_GAP": 4}  # SPX_COSCHED_ST_*
 PREEMPT_ST = {"CANDIDATE": 0, "NO_VICTIMS": 1, "NOT_FIT": 2, "QUOTA": 3, "ALL_REPRIEVED": 4, "REMOVE_TWICE": 5, "SKIPPED": 6}  # SPX_PREEMPT_ST_*
 
@@ -861,6 +865,98 @@ class Engine:
         self.n_nodes, self.n_pods = f["N"], P
         self.net_soa = cols
 
+    # ---- NodeMetadata / PodState / QOSSort
+    @staticmethod
+    def _static_lib():
+        from . import lib
+        return lib()
+
+    @staticmethod
+    def _static_fail(rc: int, msg: str):
+        from . import SpxError
+        return SpxError(rc, msg)
+
+    @classmethod
+    def flatten_nodemeta(cls, values: Sequence[Optional[object]], mtype: str = "Number", strategy: str = "Highest", now_unix_nanos: int = 0) -> np.ndarray:
+        """the node's label or annotation strings (None = key not found) -> NodeMetadata's raw int64 column (spx_flatten_nodemeta)"""
+        enc = [b"" if v is None else (v if isinstance(v, bytes) else str(v).encode()) for v in values]
+        ptr = np.zeros(len(enc) + 1, np.int64)
+        np.cumsum([len(b) for b in enc], out=ptr[1:])
+        blob = b"".join(enc) + b"\0"
+        found = np.array([v is not None for v in values], np.uint8)
+        out = np.zeros(len(enc), np.int64)
+        if len(enc) == 0:
+            return out
+        rc = cls._static_lib().spx_flatten_nodemeta(blob, ptr.ctypes.data_as(C.POINTER(C.c_int64)), found.ctypes.data_as(C.POINTER(C.c_uint8)), len(enc),
+                                                    NODEMETA_TYPE[mtype], NODEMETA_STRATEGY[strategy], now_unix_nanos, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        if rc != 0:
+            raise cls._static_fail(rc, "spx_flatten_nodemeta: invalid argument")
+        return out
+
+    @classmethod
+    def flatten_nodemeta_unix(cls, unix_nanos, valid, strategy: str = "Newest", now_unix_nanos: int = 0) -> np.ndarray:
+        """timestamps the caller parsed (any TimestampFormat) -> the raw column (spx_flatten_nodemeta_unix)"""
+        t = np.ascontiguousarray(unix_nanos, dtype=np.int64)
+        v = np.ascontiguousarray(valid, dtype=np.uint8)
+        out = np.zeros(len(t), np.int64)
+        rc = cls._static_lib().spx_flatten_nodemeta_unix(t.ctypes.data_as(C.POINTER(C.c_int64)), v.ctypes.data_as(C.POINTER(C.c_uint8)), len(t),
+                                                         NODEMETA_STRATEGY[strategy], now_unix_nanos, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        if rc != 0:
+            raise cls._static_fail(rc, "spx_flatten_nodemeta_unix: invalid argument")
+        return out
+
+    @classmethod
+    def flatten_podstate(cls, n_nodes: int, assigned_node, assigned_terminating, nominated_node) -> np.ndarray:
+        """terminating minus nominated pods per node (spx_flatten_podstate)"""
+        an = np.ascontiguousarray(assigned_node, dtype=np.int64)
+        at = np.ascontiguousarray(assigned_terminating, dtype=np.uint8)
+        nn = np.ascontiguousarray(nominated_node, dtype=np.int64)
+        out = np.zeros(max(n_nodes, 0), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        rc = cls._static_lib().spx_flatten_podstate(n_nodes, len(an), an.ctypes.data_as(i64p), at.ctypes.data_as(C.POINTER(C.c_uint8)), len(nn),
+                                                    nn.ctypes.data_as(i64p), out.ctypes.data_as(i64p))
+        if rc != 0:
+            raise cls._static_fail(rc, "spx_flatten_podstate: a node index outside [0, n_nodes), or a NULL column")
+        return out
+
+    @classmethod
+    def flatten_pod_qos(cls, pods: Table) -> np.ndarray:
+        """v1qos.GetPodQOS per pod in QOSSort's numbering: 1 BestEffort, 2 Burstable, 3 Guaranteed (spx_flatten_pod_qos)"""
+        out = np.zeros(pods.struct.n_pods, np.uint8)
+        rc = cls._static_lib().spx_flatten_pod_qos(pods.ref(), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc != 0:
+            raise cls._static_fail(rc, "spx_flatten_pod_qos: invalid argument")
+        return out
+
+    @classmethod
+    def qos_less(cls, priority1: int, qos1: int, ts1: int, priority2: int, qos2: int, ts2: int) -> bool:
+        """QOSSort's Less for one pair (spx_qos_less)"""
+        return bool(cls._static_lib().spx_qos_less(priority1, qos1, ts1, priority2, qos2, ts2))
+
+    def upload_nodemeta(self, raw) -> None:
+        """NodeMetadata's raw column, INVALID_SCORE = no valid metadata (spx_upload_nodemeta_nodes)"""
+        raw = np.ascontiguousarray(raw, dtype=np.int64)
+        self._ck(self._lib.spx_upload_nodemeta_nodes(self._h, Table(self._hdr, "spx_node_column_soa", n_nodes=len(raw), raw=raw).ref(), 0))
+        self.n_nodes = len(raw)
+
+    def upload_podstate(self, raw) -> None:
+        """PodState's raw column: terminating minus nominated pods per node (spx_upload_podstate_nodes)"""
+        raw = np.ascontiguousarray(raw, dtype=np.int64)
+        self._ck(self._lib.spx_upload_podstate_nodes(self._h, Table(self._hdr, "spx_node_column_soa", n_nodes=len(raw), raw=raw).ref()))
+        self.n_nodes = len(raw)
+
+    def upload_qos_sort_keys(self, priority, qos, queue_ts) -> None:
+        priority = np.ascontiguousarray(priority, dtype=np.int32)
+        t = Table(self._hdr, "spx_qos_sort_keys_soa", n_pods=len(priority), priority=priority, qos=qos, queue_ts=queue_ts)
+        self._ck(self._lib.spx_upload_qos_sort_keys(self._h, t.ref()))
+        self._qos_n = len(priority)
+
+    def qos_sort(self) -> np.ndarray:
+        """QOSSort as one device sort: the queue order as pod rows (spx_qos_sort)"""
+        perm = np.zeros(getattr(self, "_qos_n", 0) or 1, np.int32)
+        self._ck(self._lib.spx_qos_sort(self._h, perm.ctypes.data_as(C.POINTER(C.c_int32))))
+        return perm[:getattr(self, "_qos_n", 0)]
+
     def sort_queue(self, pods: Table, topo_order: Optional[np.ndarray] = None) -> np.ndarray:
         """TopologicalSort as one device sort: queue order (pod rows) in which every adjacent pair satisfies Less (spx_sort_keys)"""
         topo = np.ascontiguousarray(self.net_soa["topo_order"] if topo_order is None else topo_order, dtype=np.int32)
@@ -1377,6 +1473,7 @@ class Engine:
             return
         mask = np.ascontiguousarray(mask, dtype=np.uint8)
         self._ck(self._lib.spx_upload_feasible_mask(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.shape[0], mask.shape[1]))
+        self.n_pods, self.n_nodes = mask.shape  # (the upload fixes the engine's shape when no table has)
 
     def set_plugin_weights(self, weights: Dict[int, int]) -> None:
         w = np.ones(NUM_PLUGINS, dtype=np.int64)
@@ -1406,7 +1503,7 @@ class Engine:
         """pods in row order, each seeing the commits before it -> (node, weighted score, ties, missing); plugin_mask may hold
         Allocatable / TLP / LVRB / NRT / NetworkOverhead / CapacityScheduling / LowRiskOverCommitment / Peaks (spx_commit_sequential;
         the last two with their tables loaded: a bound pod joins its node's LROC sums, Peaks is normalised per pod over the pod's
-        feasible nodes); SySched is rejected"""
+        feasible nodes); SySched, NodeMetadata and PodState are rejected"""
         row_end = self.n_pods if row_end is None else row_end
         n = row_end - row_begin
         node, score, ties = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32)

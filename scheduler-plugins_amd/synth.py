@@ -767,6 +767,20 @@ def full_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, pods
     return snap
 
 
+def node_column_snapshot(n_nodes: int, seed: int = SEED, invalid_frac: float = 0.1, max_pods: int = 6) -> Dict[str, np.ndarray]:
+    """NodeMetadata's and PodState's raw node columns (spx_node_column_soa.raw) plus a QOSSort queue of n_nodes pods, on a random
+    stream of their own (seed + 311), so that every other generator yields what it always did.  "nodemeta": a numeric label in
+    [-1000, 1000], math.MinInt64 (no valid metadata) on about invalid_frac of the nodes; "podstate": terminating minus nominated pods,
+    each count in [0, max_pods]; "qos": priority / class (1 BestEffort, 2 Burstable, 3 Guaranteed) / queue timestamp columns."""
+    rng = np.random.default_rng(seed + 311)
+    meta = rng.integers(-1000, 1001, n_nodes).astype(np.int64)
+    meta[rng.random(n_nodes) < invalid_frac] = np.iinfo(np.int64).min
+    pod_state = (rng.integers(0, max_pods + 1, n_nodes) - rng.integers(0, max_pods + 1, n_nodes)).astype(np.int64)
+    qos = dict(priority=rng.integers(-2, 3, n_nodes).astype(np.int32) * 1000, qos=rng.integers(1, 4, n_nodes).astype(np.uint8),
+               queue_ts=(1_700_000_000_000_000_000 + rng.integers(0, 50, n_nodes) * 1_000_000).astype(np.int64))
+    return {"nodemeta": meta, "podstate": pod_state, "qos": qos}
+
+
 def sysched_snapshot(hdr: Header, n_nodes: int, n_pods: int, seed: int = SEED, n_profiles: int = 32, stale_frac: float = 0.03,
                      absent_frac: float = 0.03, empty_frac: float = 0.003, n_names: int = 400, core: int = 150, max_residents: int = 12,
                      distinct_pods: bool = False, node_states: Optional[int] = None) -> dict:
