@@ -1,6 +1,13 @@
 // spx_commit.hip — the one-pod-at-a-time loops: spx_upload_net_commit and spx_commit_sequential with its three forms
-// (one-workgroup chain, per-pod launches replayed from a graph, cooperative persistent kernel).  Engine state and shared helpers: spx_engine.h.
+// (one-workgroup chain, per-pod launches replayed from a graph, cooperative persistent kernel).  Engine state and what crosses the units: spx_engine.h; the
+// argument builders and preparations shared with spx_eval: spx_eval_args.hip.
 #include "spx_engine.h"
+
+#include <algorithm>
+#include <cstring>
+#include <limits>
+
+#include "../host/lroc_form.hpp"
 
 extern "C" {
 

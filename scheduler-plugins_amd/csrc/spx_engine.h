@@ -1,45 +1,31 @@
-// spx_engine.h — the engine's state and the helpers its translation units share (round 6: csrc/spx_engine.hip, one file of 3 900 lines
-// in round 5, is now spx_engine.hip (lifecycle, options, parameters, evaluation, fetch), spx_uploads.hip (tables and deltas into HBM),
-// spx_loads.hip (the one-call loaders) and spx_commit.hip (the one-pod-at-a-time loops)).  Not part of the ABI.  The helpers sit in an anonymous namespace:
-// every translation unit gets its own copy of the small ones it uses; the three thread-local error slots exist once (spx_engine.hip).
+// spx_engine.h — the engine's state (struct spx_engine) and the declarations of what crosses its translation units.  Not part of the
+// ABI.  The entry points live in spx_engine.hip (lifecycle, options, parameters, evaluation, fetch), spx_uploads.hip (tables and
+// deltas into HBM), spx_loads.hip (the one-call loaders), spx_commit.hip (the one-pod-at-a-time loops) and spx_preempt.hip (the
+// preemption dry runs and loops).  A helper that two or more of them call is declared below with hidden visibility and defined once:
+// spx_state.hip, spx_eval_args.hip, spx_nrt_rows.hip.  A helper with one user is not here: it sits in that unit's anonymous
+// namespace.  Only functions of a line or two are inline.  The three thread-local error slots exist once (spx_engine.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
-#include <atomic>
-#include <mutex>
-#include <thread>
-
 #include "spx_internal.h"
-#include "../host/lroc_form.hpp"
-#include "../host/nrt_streams.hpp"
-#include "../host/parallel.hpp"
+#include "../host/nrt_streams.hpp"  // (spx_host::NrtQty, a member below)
 
 extern thread_local std::string g_create_error;          // spx_create's failure (no engine to hold it)
 extern thread_local std::string tl_err;                  // this thread's last failure ...
 extern thread_local const spx_engine* tl_err_engine;     // ... and on which engine
-
-namespace {
-
 
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
   bool external = false;
 };
-
-}  // namespace
 
 struct spx_engine {
   int device = 0;
@@ -352,24 +338,17 @@ struct spx_engine {
   int last_alloc_table = 0;  // spx_alloc_table_path
 };
 
+// d_best's four columns, [score int64 P | node int32 P | ties int32 P | feasible int32 P]
+struct BestRows {
+  int64_t* score;
+  int32_t *node, *ties, *feasible;
+};
 
-namespace {
+// A function that crosses the engine's translation units and never leaves libspx.so.  Each is defined once, in the unit its group
+// names; the comments on what it does stand at the definition.
+#define SPX_LOCAL __attribute__((visibility("hidden")))
 
-
-int fail(const spx_engine* e, int code, const std::string& msg) {
-  if (e) {
-    {
-      std::lock_guard<std::mutex> g(e->err_mu);
-      e->err = msg;
-    }
-    tl_err = msg;
-    tl_err_engine = e;
-  } else {
-    g_create_error = msg;
-  }
-  return code;
-}
-
+// a HIP call whose failure ends the calling function with SPX_ERR_HIP and the call's text as the message
 #define SPX_HIP(e, call)                                                                          \
   do {                                                                                            \
     hipError_t _st = (call);                                                                      \
@@ -377,834 +356,65 @@ int fail(const spx_engine* e, int code, const std::string& msg) {
       return fail((e), SPX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st));          \
   } while (0)
 
-int ensure(spx_engine* e, DevBuf& b, size_t bytes) {
-  if (b.external) return fail(e, SPX_ERR_STATE, "internal: resize of an externally bound buffer");
-  if (bytes == 0) bytes = 16;
-  if (b.bytes >= bytes) return SPX_OK;
-  if (b.p) SPX_HIP(e, hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
-  SPX_HIP(e, hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
-  return SPX_OK;
-}
+namespace spx_eng {
 
-int upload(spx_engine* e, DevBuf& b, const void* src, size_t bytes) {
-  if (!src && bytes) return fail(e, SPX_ERR_ARG, "NULL column in table");  // an empty column (e.g. no resource slots) may be NULL
-  int rc = ensure(e, b, bytes);
-  if (rc) return rc;
-  if (bytes) SPX_HIP(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream));
-  return SPX_OK;
-}
+// ---- spx_state.hip: errors, buffers, the snapshot's shape, the tables every evaluation sizes
+SPX_LOCAL int fail(const spx_engine* e, int code, const std::string& msg);
+SPX_LOCAL int ensure(spx_engine* e, DevBuf& b, size_t bytes);
+SPX_LOCAL int upload(spx_engine* e, DevBuf& b, const void* src, size_t bytes);
+SPX_LOCAL int ensure_pinned(spx_engine* e, void*& p, size_t& bytes, size_t want, size_t slack);
+SPX_LOCAL int set_nodes(spx_engine* e, int64_t n);
+SPX_LOCAL int set_pods(spx_engine* e, int64_t p);
+SPX_LOCAL int tlp_build_order(spx_engine* e);
+SPX_LOCAL int score_table_fits(const spx_engine* e, int plugin);
+SPX_LOCAL int ensure_score_table(spx_engine* e, int plugin);
+SPX_LOCAL BestRows best_rows(const spx_engine* e);
+SPX_LOCAL int ensure_best(spx_engine* e, BestRows* out);
+SPX_LOCAL int rows_evaluated(const spx_engine* e, int plugin, int64_t b, int64_t en);
 
-// a pinned host buffer of at least `want` bytes; a buffer that has to grow is allocated with `slack` bytes to spare
-int ensure_pinned(spx_engine* e, void*& p, size_t& bytes, size_t want, size_t slack) {
-  if (bytes >= want) return SPX_OK;
-  if (p) SPX_HIP(e, hipHostFree(p));
-  p = nullptr, bytes = 0;
-  SPX_HIP(e, hipHostMalloc(&p, want + slack, hipHostMallocDefault));
-  bytes = want + slack;
-  return SPX_OK;
-}
+// ---- spx_eval_args.hip: what the evaluation and the commit loops both do before a launch
+SPX_LOCAL int alloc_check(const spx_engine* e);
+SPX_LOCAL int prepare_alloc(spx_engine* e);
+SPX_LOCAL uint32_t launch_opts(const spx_engine* e);
+SPX_LOCAL void fill_lroc(const spx_engine* e, spx::LrocArgs& a);
+SPX_LOCAL void fill_trimaran(const spx_engine* e, spx::TrimaranArgs& a);
+SPX_LOCAL void fill_nrt(const spx_engine* e, spx::NrtArgs& na);
+SPX_LOCAL void fill_net(const spx_engine* e, spx::NetArgs& g);
+SPX_LOCAL int64_t net_cost_bound(const spx_engine* e, int64_t extra_pairs);
+SPX_LOCAL int net_bound_check(const spx_engine* e, int64_t extra_pairs, const char* when);
+SPX_LOCAL int net_prepare(spx_engine* e, int64_t extra_pairs, const char* when);
 
-// every value in [0, 2^52): sums and differences of two such values are exact in float64
-bool all_below_2p52(const int64_t* v, size_t n) {
-  uint64_t acc = 0;
-  for (size_t i = 0; i < n; ++i) acc |= static_cast<uint64_t>(v[i]);
-  return (acc >> 52) == 0;
-}
-// every value in [0, 2^47): such a value, and the difference of two, is the sum of two float32 exactly (k_lroc_fast)
-bool all_below_2p47(const int64_t* v, size_t n) {
-  uint64_t acc = 0;
-  for (size_t i = 0; i < n; ++i) acc |= static_cast<uint64_t>(v[i]);
-  return (acc >> 47) == 0;
-}
-bool none_below(const int64_t* hi, const int64_t* lo, size_t n) {
-  bool ok = true;
-  for (size_t i = 0; i < n; ++i) ok = ok && hi[i] >= lo[i];
-  return ok;
-}
-
-int set_nodes(spx_engine* e, int64_t n) {
-  if (n <= 0) return fail(e, SPX_ERR_ARG, "n_nodes must be positive");
-  if (e->n_nodes != -1 && e->n_nodes != n)
-    return fail(e, SPX_ERR_STATE, "n_nodes differs from tables already uploaded (one snapshot per engine; destroy and re-create to change shape)");
-  e->n_nodes = n;
-  e->row_stride = spx::round_up(n, e->option[SPX_OPT_ROW_ALIGN]);
-  return SPX_OK;
-}
-
-int set_pods(spx_engine* e, int64_t p) {
-  if (p <= 0) return fail(e, SPX_ERR_ARG, "n_pods must be positive");
-  if (e->n_pods != -1 && e->n_pods != p)
-    return fail(e, SPX_ERR_STATE, "n_pods differs from tables already uploaded");
-  e->n_pods = p;
-  return SPX_OK;
-}
-
-// The order of TargetLoadPacking's class form for the pod column in place (n_pods rows of d_tlp_pod, queued on the stream before
-// this call): built on the stream, the count of evaluated rows read back.  The caller has cleared tlp_order_valid before it wrote the
-// column and synchronises the stream afterwards anyway; this synchronises for the one number.
-int tlp_build_order(spx_engine* e) {
-  e->tlp_order_valid = false;
-  if (e->n_pods <= 0 || e->n_pods > std::numeric_limits<int32_t>::max()) return SPX_OK;  // (rows are int32 in the order: such a batch sweeps plain)
-  int rc;
-  const size_t words = spx::tlp_order_scratch_words(spx::kTlpAmbSize, e->n_pods);
-  if ((rc = ensure(e, e->d_tlp_order, static_cast<size_t>(e->n_pods) * sizeof(int32_t))) || (rc = ensure(e, e->d_tlp_order_scratch, words * sizeof(uint32_t))))
-    return rc;
-  uint32_t* scratch = static_cast<uint32_t*>(e->d_tlp_order_scratch.p);
-  // (SPX_OPT_TLP_CHUNK_SCHED is read here: the order in place keeps the schedule it was built with)
-  spx::launch_tlp_order(static_cast<const int64_t*>(e->d_tlp_pod.p), e->n_pods, spx::kTlpAmbSize, e->option[SPX_OPT_TLP_CHUNK_SCHED] != 0,
-                        static_cast<int32_t*>(e->d_tlp_order.p), scratch, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  uint32_t evaluated = 0;
-  SPX_HIP(e, hipMemcpyAsync(&evaluated, scratch + spx::tlp_order_evaluated_word(spx::kTlpAmbSize), sizeof evaluated, hipMemcpyDeviceToHost, e->stream));
-  SPX_HIP(e, hipStreamSynchronize(e->stream));
-  e->tlp_rows_evaluated = evaluated;
-  e->tlp_order_valid = true;
-  return SPX_OK;
-}
+// ---- spx_nrt_rows.hip: NodeResourceTopologyMatch's launches beside the dense sweep
+SPX_LOCAL int launch_nrt_long_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begin, int64_t row_end);
+SPX_LOCAL int nrt_tall_ready(const spx_engine* e);
+SPX_LOCAL int launch_nrt_tall_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begin, int64_t row_end);
+SPX_LOCAL int launch_nrt_wide_rows(spx_engine* e, int64_t row_begin, int64_t row_end, int64_t* out_raw);
+SPX_LOCAL int ensure_nrt_creq(spx_engine* e, bool force = false);
 
 // something other than the unmasked broadcast wrote (or may have written) into Allocatable's score table, or the buffer changed
-void alloc_table_dirty(spx_engine* e) { e->alloc_kept = spx_engine::AllocKept{}; }
+inline void alloc_table_dirty(spx_engine* e) { e->alloc_kept = spx_engine::AllocKept{}; }
 
-// The checks of a plugin's tables that write nothing (spx_eval makes them all before its first allocation): a table the caller bound
-// must hold n_pods x row_stride ...
-int score_table_fits(const spx_engine* e, int plugin) {
-  if (e->score[plugin].external && (e->score_rows[plugin] < e->n_pods || e->score_stride[plugin] < e->row_stride))
-    return fail(e, SPX_ERR_STATE, "bound score table is smaller than n_pods x row_stride");
-  return SPX_OK;
-}
-int status_table_fits(const spx_engine* e, int plugin) {
-  if (e->status[plugin].external && e->status[plugin].bytes < static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride))
-    return fail(e, SPX_ERR_STATE, "bound status table is smaller than n_pods x row_stride");
-  return SPX_OK;
-}
-// ... and use the engine's row stride (an engine-owned table has it by construction: ensure_score_table)
-int score_table_stride(const spx_engine* e, int plugin) {
-  if (e->score[plugin].external && e->score_stride[plugin] != e->row_stride)
-    return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
-  return SPX_OK;
-}
+inline bool forced_reference(const spx_engine* e, int plugin) { return (e->option[SPX_OPT_REFERENCE_KERNELS] >> plugin) & 1; }
 
-int ensure_score_table(spx_engine* e, int plugin) {
-  DevBuf& b = e->score[plugin];
-  if (b.external) return score_table_fits(e, plugin);
-  const size_t had = b.p ? b.bytes : 0;
-  int rc = ensure(e, b, static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride));
-  if (plugin == SPX_PLUGIN_ALLOCATABLE && (rc || b.bytes != had)) alloc_table_dirty(e);  // (a new allocation may come back at the old address)
-  if (rc) return rc;
-  e->score_rows[plugin] = e->n_pods;
-  e->score_stride[plugin] = e->row_stride;
-  return SPX_OK;
-}
-
-constexpr uint32_t kFilterPlugins = (1u << SPX_PLUGIN_NRT) | (1u << SPX_PLUGIN_NETOVERHEAD);
-// plugins whose NormalizeScore depends on the feasible set of the cycle
-constexpr uint32_t kNormalizingPlugins =
-    (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_PEAKS) | (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_NODEMETA) |
-    (1u << SPX_PLUGIN_PODSTATE);
-// plugins that own a uint8 score table
-constexpr bool plugin_has_score(int k) {
-  return k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS || k == SPX_PLUGIN_SYSCHED || k == SPX_PLUGIN_NODEMETA || k == SPX_PLUGIN_PODSTATE;
-}
-
-// The status tables that narrow a pod's node list when `mask` is evaluated or summed: {NRT's, NetworkOverhead's, the caller's mask},
-// NULL = not in play (the layout of ProfileArgs.status and the scorers' other_status; NetworkOverhead's own sweep takes [0] and [2])
-void feasibility_status(const spx_engine* e, uint32_t mask, const uint8_t* out[3]) {
-  out[0] = (mask & (1u << SPX_PLUGIN_NRT)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
-  out[1] = (mask & (1u << SPX_PLUGIN_NETOVERHEAD)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
-  out[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
-}
-
-// d_best's four columns, [score int64 P | node int32 P | ties int32 P | feasible int32 P]
-struct BestRows {
-  int64_t* score;
-  int32_t *node, *ties, *feasible;
-};
-BestRows best_rows(const spx_engine* e) {
-  int64_t* score = static_cast<int64_t*>(e->d_best.p);
-  int32_t* node = reinterpret_cast<int32_t*>(score + e->n_pods);
-  return BestRows{score, node, node + e->n_pods, node + 2 * e->n_pods};
-}
-int ensure_best(spx_engine* e, BestRows* out) {
-  int rc = ensure(e, e->d_best, static_cast<size_t>(e->n_pods) * 20);
-  if (rc == SPX_OK) *out = best_rows(e);
-  return rc;
-}
-
-// What one evaluation is asked for besides its mask and rows (spx_decide's preparatory sweeps; spx_eval itself passes the defaults)
-struct EvalCall {
-  bool hold_ev0 = false;           // the caller has recorded ev0 and times this evaluation together with its own sweep
-  bool skip_alloc_masked = false;  // the caller folds Allocatable's masked normalisation into its argmax kernel: the table is not written
-};
-
-// rows [b, e) of `plugin` hold results of an spx_eval
-int rows_evaluated(const spx_engine* e, int plugin, int64_t b, int64_t en) {
-  const spx_engine::EvalInfo& i = e->eval_info[plugin];
-  if (!(e->evaluated & (1u << plugin)) || b < i.begin || en > i.end)
-    return fail(e, SPX_ERR_STATE, "rows requested have not been evaluated for this plugin (spx_eval covers [" + std::to_string(i.begin) + ", " +
-                                      std::to_string(i.end) + "))");
-  return SPX_OK;
-}
-
-int ensure_status_table(spx_engine* e, int plugin) {
-  DevBuf& b = e->status[plugin];
-  if (b.external) return status_table_fits(e, plugin);
-  return ensure(e, b, static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride));
-}
-
-// what prepare_alloc refuses, from host state alone
-int alloc_check(const spx_engine* e) {
-  if (e->alloc_ready) return SPX_OK;
-  if (!e->d_alloc.p) return fail(e, SPX_ERR_STATE, "Allocatable: spx_upload_alloc_nodes not called");
-  if (e->alloc_n_res != static_cast<int32_t>(e->alloc_res.size()))
-    return fail(e, SPX_ERR_STATE, "Allocatable: uploaded table has a different resource count than the params");
-  return SPX_OK;
-}
-
-int prepare_alloc(spx_engine* e) {
-  if (e->alloc_ready) return SPX_OK;
-  int rc = alloc_check(e);
-  if (rc) return rc;
-  if ((rc = upload(e, e->d_alloc_w, e->alloc_weight.data(), e->alloc_weight.size() * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(e, e->d_alloc_raw, static_cast<size_t>(e->n_nodes) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(e, e->d_alloc_rel, static_cast<size_t>(e->row_stride + 4) * sizeof(uint32_t)))) return rc;
-  // (The comparison is a launch of its own, kernels_delta.hip's k_rows_equal, on a copy of the old row — not a few lines inside
-  // k_alloc_prepare, which has both rows in hand: that kernel lives in kernels_trimaran.hip, whose machine code stamps the counter
-  // profiles of every trimaran workload, and this runs once per node table, off the sweep.)
-  // the row in place (if one was ever computed) is set aside: a recomputation that ends with the same row — a node re-list with
-  // unchanged allocatable — keeps alloc_epoch, and with it the score table that broadcasts the row (SPX_OPT_ALLOC_TABLE_KEEP)
-  const bool had_norm = e->alloc_epoch != 0 && e->d_alloc_norm.p && e->d_alloc_norm.bytes >= static_cast<size_t>(e->row_stride);
-  if ((rc = ensure(e, e->d_alloc_norm, static_cast<size_t>(e->row_stride)))) return rc;
-  if (had_norm) {
-    if ((rc = ensure(e, e->d_alloc_prev, static_cast<size_t>(e->row_stride)))) return rc;
-    SPX_HIP(e, hipMemcpyAsync(e->d_alloc_prev.p, e->d_alloc_norm.p, static_cast<size_t>(e->row_stride), hipMemcpyDeviceToDevice, e->stream));
-  }
-  const uint64_t epoch_before = e->alloc_epoch++;  // a failure below leaves the row unknown: the old epoch comes back only once the rows are known to agree
-  spx::AllocPrepArgs a{};
-  a.n_nodes = e->n_nodes;
-  a.row_stride = e->row_stride;
-  a.n_res = e->alloc_n_res;
-  a.mode = e->alloc_mode;
-  a.alloc = static_cast<const int64_t*>(e->d_alloc.p);
-  a.weight = static_cast<const int64_t*>(e->d_alloc_w.p);
-  a.raw = static_cast<int64_t*>(e->d_alloc_raw.p);
-  a.rel = static_cast<uint32_t*>(e->d_alloc_rel.p);
-  a.norm = static_cast<uint8_t*>(e->d_alloc_norm.p);
-  spx::launch_alloc_prepare(a, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  uint32_t* const flags = static_cast<uint32_t*>(e->d_alloc_rel.p) + e->row_stride;
-  if (had_norm) {
-    spx::launch_rows_equal(a.norm, static_cast<const uint8_t*>(e->d_alloc_prev.p), e->row_stride, flags + 1, e->stream);
-    SPX_HIP(e, hipGetLastError());
-  }
-  // once per node table, in one copy: the flag the kernel leaves behind the offsets, and behind it "the row is the one before"
-  uint32_t back[2] = {0, 0};
-  SPX_HIP(e, hipMemcpyAsync(back, flags, had_norm ? sizeof back : sizeof back[0], hipMemcpyDeviceToHost, e->stream));
-  SPX_HIP(e, hipStreamSynchronize(e->stream));
-  e->alloc_compact = back[0] != 0;
-  if (had_norm && back[1] != 0) e->alloc_epoch = epoch_before;
-  e->alloc_ready = true;
-  return SPX_OK;
-}
-
-bool forced_reference(const spx_engine* e, int plugin) { return (e->option[SPX_OPT_REFERENCE_KERNELS] >> plugin) & 1; }
-
-// the engine's options as the launch-level switches the kernel translation units read
-uint32_t launch_opts(const spx_engine* e) {
-  uint32_t o = 0;
-  if (forced_reference(e, SPX_PLUGIN_TLP) || forced_reference(e, SPX_PLUGIN_LVRB)) o |= spx::kOptTrimaranExact;
-  if (forced_reference(e, SPX_PLUGIN_NRT)) o |= spx::kOptNrtGeneric;
-  if (forced_reference(e, SPX_PLUGIN_NETOVERHEAD)) o |= spx::kOptNetGeneric;
-  if (e->option[SPX_OPT_NRT_SINGLE_LAUNCH]) o |= spx::kOptNrtSingleLaunch;
-  if (e->option[SPX_OPT_COMMIT_FROM_MEMORY]) o |= spx::kOptCommitFromMemory;
-  if (e->option[SPX_OPT_PEAKS_TILE] / 10 == 8) o |= spx::kOptPeaksWideA;
-  if (e->option[SPX_OPT_PEAKS_TILE] % 10 == 8) o |= spx::kOptPeaksWideB;
-  if (!e->option[SPX_OPT_TLP_AMB_TABLE]) o |= spx::kOptTlpNoAmbTable;
-  if (e->option[SPX_OPT_PEAKS_ESTIMATE]) o |= spx::kOptPeaksEstimate;
-  if (e->option[SPX_OPT_PEAKS_ESTIMATE] == 8) o |= spx::kOptPeaksEst8;
-  return o;
-}
-
-bool lroc_exact53(const spx_engine* e) {
+inline bool lroc_exact53(const spx_engine* e) {
   return e->lroc_nodes_exact && e->lroc_pods_exact && e->lv_alloc_exact && !forced_reference(e, SPX_PLUGIN_LROC);
 }
 // the float32 sweep (k_lroc_fast) may run: exact columns, below 2^47, every limit at least its request (SetMaxLimits, resourcestats.go:227-231)
-bool lroc_f32_ok(const spx_engine* e) {
+inline bool lroc_f32_ok(const spx_engine* e) {
   return lroc_exact53(e) && e->lroc_nodes_f32 && e->lroc_pods_f32 && e->lv_alloc_f32 && !e->option[SPX_OPT_LROC_FLOAT64];
 }
 
-void fill_lroc(const spx_engine* e, spx::LrocArgs& a) {
-  a.n_nodes = e->n_nodes;
-  a.row_stride = e->row_stride;
-  a.alloc_cpu_milli = static_cast<const int64_t*>(e->d_lv_acpu.p);
-  a.alloc_mem = static_cast<const int64_t*>(e->d_lv_amem.p);
-  a.cpu_avg = static_cast<const double*>(e->d_lv_cavg.p);
-  a.cpu_std = static_cast<const double*>(e->d_lv_cstd.p);
-  a.mem_avg = static_cast<const double*>(e->d_lv_mavg.p);
-  a.mem_std = static_cast<const double*>(e->d_lv_mstd.p);
-  a.flags = static_cast<const uint8_t*>(e->d_lv_flags.p);
-  a.node_req_cpu = static_cast<const int64_t*>(e->d_lroc_nreq_c.p);
-  a.node_req_mem = static_cast<const int64_t*>(e->d_lroc_nreq_m.p);
-  a.node_lim_cpu = static_cast<const int64_t*>(e->d_lroc_nlim_c.p);
-  a.node_lim_mem = static_cast<const int64_t*>(e->d_lroc_nlim_m.p);
-  a.pod_req_cpu = static_cast<const int64_t*>(e->d_lroc_preq_c.p);
-  a.pod_req_mem = static_cast<const int64_t*>(e->d_lroc_preq_m.p);
-  a.pod_lim_cpu = static_cast<const int64_t*>(e->d_lroc_plim_c.p);
-  a.pod_lim_mem = static_cast<const int64_t*>(e->d_lroc_plim_m.p);
-  a.sqrt_window = std::sqrt(static_cast<double>(e->lroc.smoothing_window_size));  // math.Pow(x, 0.5) = Sqrt(x)
-  a.w_cpu = e->lroc.risk_limit_weight_cpu;
-  a.w_mem = e->lroc.risk_limit_weight_mem;
-  a.node_tab = static_cast<double*>(e->d_lroc_tab.p);
-  a.exact53 = lroc_exact53(e) ? 1 : 0;
-  a.pod_f32 = lroc_f32_ok(e) ? static_cast<const float*>(e->d_lroc_podf.p) : nullptr;
-  a.n_pods_total = e->n_pods;
-  a.stats = static_cast<unsigned long long*>(e->d_stats.p);
-}
-
-void fill_peaks(const spx_engine* e, spx::PeaksArgs& a) {
-  a.opts = launch_opts(e);
-  a.n_nodes = e->n_nodes;
-  a.row_stride = e->row_stride;
-  a.cap_cpu_milli = static_cast<const int64_t*>(e->d_pk_cap.p);
-  a.cpu_util = static_cast<const double*>(e->d_pk_util.p);
-  a.valid = static_cast<const uint8_t*>(e->d_pk_valid.p);
-  a.k1 = static_cast<const double*>(e->d_pk_k1.p);
-  a.k2 = static_cast<const double*>(e->d_pk_k2.p);
-  a.pod_cpu_milli = static_cast<const int64_t*>(e->d_pk_pod.p);
-  a.row_min = static_cast<int64_t*>(e->d_pk_min.p);
-  a.row_max = static_cast<int64_t*>(e->d_pk_max.p);
-  a.row_c = static_cast<float*>(e->d_pk_rowc.p);
-  a.node_tab = static_cast<double*>(e->d_pk_tab.p);
-}
-
-void fill_sysched(const spx_engine* e, spx::SyschedArgs& a) {
-  a.n_nodes = e->n_nodes;
-  a.row_stride = e->row_stride;
-  a.n_words = e->sy_node_words;
-  a.host_bits = static_cast<const uint64_t*>(e->d_sy_host.p);
-  a.present = static_cast<const uint8_t*>(e->d_sy_present.p);
-  a.n_resident = static_cast<const int32_t*>(e->d_sy_k.p);
-  a.resident_missing = static_cast<const int32_t*>(e->d_sy_a.p);
-  a.stale_ptr = static_cast<const int32_t*>(e->d_sy_sptr.p);
-  a.stale_bit = static_cast<const int32_t*>(e->d_sy_sbit.p);
-  a.stale_count = static_cast<const int32_t*>(e->d_sy_scnt.p);
-  a.set_bits = static_cast<const uint64_t*>(e->d_sy_sets.p);
-  a.set_empty = static_cast<const uint8_t*>(e->d_sy_empty.p);
-  a.pod_set = static_cast<const int32_t*>(e->d_sy_pod_set.p);
-  a.order = static_cast<const int32_t*>(e->d_sy_order.p);
-  a.set_first = static_cast<const int32_t*>(e->d_sy_first.p);
-  a.raw = static_cast<int32_t*>(e->d_sy_raw.p);
-  a.set_max = static_cast<int32_t*>(e->d_sy_max.p);
-}
-
-void fill_cosched(const spx_engine* e, spx::CoschedArgs& a) {
-  a.n_nodes = e->n_nodes;
-  a.n_slots = e->cs_n_slots;
-  a.n_groups = e->cs_n_groups;
-  a.n_walk = e->cs_n_walk;
-  a.left_base = static_cast<const int64_t*>(e->d_cs_left.p);
-  a.node_present = static_cast<const uint8_t*>(e->d_cs_present.p);
-  a.prefix = static_cast<int64_t*>(e->d_cs_prefix.p);
-  a.slot_max = static_cast<int64_t*>(e->d_cs_smax.p);
-  a.slot_total = static_cast<int64_t*>(e->d_cs_stotal.p);
-  a.any_present = static_cast<int32_t*>(e->d_cs_any.p);
-  a.req = static_cast<const int64_t*>(e->d_cs_req.p);
-  a.req_mask = static_cast<const uint32_t*>(e->d_cs_mask.p);
-  a.step_ptr = static_cast<const int32_t*>(e->d_cs_sptr.p);
-  a.step_node = static_cast<const int32_t*>(e->d_cs_snode.p);
-  a.step_cum = static_cast<const int64_t*>(e->d_cs_scum.p);
-  a.walk_group = static_cast<const int32_t*>(e->d_cs_walk.p);
-  a.pass_mask = static_cast<uint32_t*>(e->d_cs_pass.p);
-  a.open_mask = static_cast<uint32_t*>(e->d_cs_open.p);
-  a.gap = static_cast<int64_t*>(e->d_cs_gap.p);
-  a.g_exists = static_cast<const uint8_t*>(e->d_cs_exists.p);
-  a.min_member = static_cast<const int32_t*>(e->d_cs_minm.p);
-  a.has_min_resources = static_cast<const uint8_t*>(e->d_cs_hasres.p);
-  a.backed_off = static_cast<const uint8_t*>(e->d_cs_backoff.p);
-  a.permitted = static_cast<const uint8_t*>(e->d_cs_permit.p);
-  a.listed = static_cast<const int32_t*>(e->d_cs_listed.p);
-  a.gated = static_cast<const int32_t*>(e->d_cs_gated.p);
-  a.pod_group = static_cast<const int32_t*>(e->d_cs_pod_group.p);
-  a.out_status = static_cast<uint8_t*>(e->d_cs_status.p);
-}
-
-void fill_trimaran(const spx_engine* e, spx::TrimaranArgs& a) {
-  a.opts = launch_opts(e);
-  a.row_ptr = e->row_indirect;
-  a.n_nodes = e->n_nodes;
-  a.row_stride = e->row_stride;
-  a.alloc_norm = static_cast<const uint8_t*>(e->d_alloc_norm.p);
-  a.cap_cpu_milli = static_cast<const int64_t*>(e->d_cap_cpu.p);
-  a.tlp_cpu_util = static_cast<const double*>(e->d_tlp_util.p);
-  a.tlp_missing_milli = static_cast<const int64_t*>(e->d_tlp_missing.p);
-  a.tlp_valid = static_cast<const uint8_t*>(e->d_tlp_valid.p);
-  a.tlp_pod_milli = static_cast<const int64_t*>(e->d_tlp_pod.p);
-  a.tlp_target = static_cast<double>(e->tlp.target_utilization);
-  a.lv_alloc_cpu_milli = static_cast<const int64_t*>(e->d_lv_acpu.p);
-  a.lv_alloc_mem = static_cast<const int64_t*>(e->d_lv_amem.p);
-  a.lv_cpu_avg = static_cast<const double*>(e->d_lv_cavg.p);
-  a.lv_cpu_std = static_cast<const double*>(e->d_lv_cstd.p);
-  a.lv_mem_avg = static_cast<const double*>(e->d_lv_mavg.p);
-  a.lv_mem_std = static_cast<const double*>(e->d_lv_mstd.p);
-  a.lv_flags = static_cast<const uint8_t*>(e->d_lv_flags.p);
-  a.lv_req_cpu_milli = static_cast<const int64_t*>(e->d_lv_rcpu.p);
-  a.lv_req_mem = static_cast<const int64_t*>(e->d_lv_rmem.p);
-  a.lv_margin = e->lvrb.safe_variance_margin;
-  a.lv_sensitivity = e->lvrb.safe_variance_sensitivity;
-  a.stats = static_cast<unsigned long long*>(e->d_stats.p);
-}
-
-// The packed float32 form of LeastAllocated's Score launch (nrt_fast_device.h, score_least_packed) needs every weighted slot to be
-// "small" — with 2^s the largest power of two dividing all its capacities and requests, capacity / 2^s <= 32768 and request / 2^s < 2^24 —
-// or, one slot at most and not cpu, to go through k_nrt_pk_tab_build's table indexed by request / unit, unit = the largest power of
-// two dividing all its requests.  false = the float64 form.
-struct NrtPacked {
-  uint32_t small_slots = 0;
-  int32_t tab_slot = -1;
-  uint32_t tab_kmax = 0, tab_words = 0;
-  double tab_inv_unit = 1.0;
-};
-constexpr int64_t kNrtSmallCap = 32768;
-bool nrt_packed_score(const spx_engine* e, NrtPacked* out) {
-  *out = NrtPacked{};
-  // (MostAllocated: the same float32 products serve x = 100 v / c as serve 100 - x; only the fused walk consumes the answer for that strategy)
-  if (!e->option[SPX_OPT_NRT_PACKED_SCORE] || !e->nrt_nodes || !e->nrt_pods || e->in_commit_loop ||
-      (e->nrt_params.strategy != SPX_NRT_LEAST_ALLOCATED && !(e->nrt_params.strategy == SPX_NRT_MOST_ALLOCATED && e->option[SPX_OPT_NRT_FUSED])))
-    return false;
-  int64_t wsum = 0;
-  for (int i = 0; i < e->nrt_n_res && i < SPX_NRT_MAX_RES; ++i) {
-    if (e->nrt_slot_weight[i] < 0) return false;
-    wsum += e->nrt_slot_weight[i];
-  }
-  if (wsum > spx::kNrtPkMaxWeightSum) return false;
-  auto low_zeros = [](uint64_t bits) { return bits ? __builtin_ctzll(bits) : 63; };
-  for (int i = 0; i < e->nrt_n_res && i < SPX_NRT_MAX_RES; ++i) {
-    if (e->nrt_slot_weight[i] == 0) continue;  // contributes 0 whatever its resource score
-    const uint64_t pod_bits = e->nrt_qty_pods.bits[i];
-    if (pod_bits == 0) {  // no request but zeros: the resource score is 100 or 0 in both forms
-      out->small_slots |= 1u << i;
-      continue;
-    }
-    const int s = low_zeros(pod_bits | e->nrt_qty_nodes.bits[i]);
-    if ((e->nrt_qty_nodes.most[i] >> s) <= kNrtSmallCap && (e->nrt_qty_pods.most[i] >> s) < (int64_t{1} << 24)) {
-      out->small_slots |= 1u << i;
-      continue;
-    }
-    const int su = low_zeros(pod_bits);
-    const int64_t kmax = e->nrt_qty_pods.most[i] >> su;
-    const size_t words = static_cast<size_t>((e->n_nodes + 255) / 256 + 31) / 32;
-    if (out->tab_slot >= 0 || i == e->nrt_cpu_slot || kmax > spx::kNrtPkTabMaxK || (static_cast<size_t>(kmax) + 1) * words * 4 > spx::kNrtPkTabMaxBytes)
-      return false;
-    out->tab_slot = i, out->tab_kmax = static_cast<uint32_t>(kmax), out->tab_words = static_cast<uint32_t>(words);
-    out->tab_inv_unit = std::ldexp(1.0, -su);
-  }
-  return true;
-}
-
-void fill_nrt(const spx_engine* e, spx::NrtArgs& na) {
-  na.opts = launch_opts(e);
-  na.row_ptr = e->row_indirect;
-  na.n_nodes = e->n_nodes;
-  na.n_pods = e->n_pods;
-  na.row_stride = e->row_stride;
-  na.n_res = e->nrt_n_res;
-  na.strategy = e->nrt_params.strategy;
-  std::memcpy(na.slot_flags, e->nrt_slot_flags, sizeof na.slot_flags);
-  std::memcpy(na.slot_weight, e->nrt_slot_weight, sizeof na.slot_weight);
-  na.flags = static_cast<const uint8_t*>(e->d_nrt_flags.p);
-  na.max_numa = static_cast<const int32_t*>(e->d_nrt_max_numa.p);
-  na.n_zones = static_cast<const uint8_t*>(e->d_nrt_nz.p);
-  na.zone_id = static_cast<const uint8_t*>(e->d_nrt_zid.p);
-  na.zone_present = static_cast<const uint8_t*>(e->d_nrt_zp.p);
-  na.zone_avail = static_cast<const int64_t*>(e->d_nrt_avail.p);
-  na.zone_cost = static_cast<const int32_t*>(e->d_nrt_cost.p);
-  na.min_avg = static_cast<const float*>(e->d_nrt_minavg.p);
-  na.node_present = static_cast<const uint8_t*>(e->d_nrt_np.p);
-  na.qos = static_cast<const uint8_t*>(e->d_nrt_qos.p);
-  na.non_native = static_cast<const uint8_t*>(e->d_nrt_nn.p);
-  na.n_ctr = static_cast<const uint8_t*>(e->d_nrt_nctr.p);
-  na.ctr_kind = static_cast<const uint8_t*>(e->d_nrt_ckind.p);
-  na.ctr_present = static_cast<const uint8_t*>(e->d_nrt_cpres.p);
-  na.ctr_req = static_cast<const int64_t*>(e->d_nrt_creq.p);
-  na.pod_present = static_cast<const uint8_t*>(e->d_nrt_ppres.p);
-  na.pod_req = static_cast<const int64_t*>(e->d_nrt_preq.p);
-  na.fast = e->nrt_fast_slots && e->nrt_fast_nodes && e->nrt_fast_pods;
-  na.cpu_slot = e->nrt_cpu_slot;
-  for (int i = 0; i < SPX_NRT_MAX_RES; ++i) na.slot_weight_f[i] = static_cast<double>(e->nrt_slot_weight[i]);
-  na.f_av = static_cast<const double*>(e->d_nrt_fav.p);
-  na.f_rc = static_cast<const double*>(e->d_nrt_frc.p);
-  na.f_rcv = static_cast<const double*>(e->d_nrt_frcv.p);
-  na.f_cpu = static_cast<const double*>(e->d_nrt_fcpu.p);
-  na.f_braw = static_cast<const double*>(e->d_nrt_fbraw.p);
-  na.f_rep = static_cast<const uint8_t*>(e->d_nrt_frep.p);
-  na.pod_items = static_cast<const uint32_t*>(e->d_nrt_items.p);
-  na.perm = static_cast<const int32_t*>(e->d_nrt_perm.p);
-  na.stats = static_cast<unsigned long long*>(e->d_stats.p);
-  na.exact32_slots = ~(e->nrt_big_nodes | e->nrt_big_pods);
-  na.pk_mode = 0, na.pk_tab_slot = -1;  // (spx_eval's NRT section turns the packed Score on)
-  // inside the per-pod commit loop k_commit_apply subtracts requests from the zone table: "every quantity is a float32 value" is
-  // not closed under subtraction (2^30 and 1 are, 2^30 - 1 is not) and the masks above describe the uploaded tables, so
-  // BalancedAllocation's float32 "request > capacity" test gives way to the undecided -> float64 redo route there
-  if (e->in_commit_loop) na.exact32_slots = 0;
-  na.redo_list = static_cast<uint32_t*>(e->d_nrt_redo.p);
-  na.redo_cap = e->nrt_redo_cap;
-  na.ln_tab = (e->nrt_ln_ok && e->nrt_ln_built) ? static_cast<const uint32_t*>(e->d_nrt_ln.p) : nullptr;
-  na.ln_const = na.ln_tab ? na.ln_tab + static_cast<size_t>(spx::make_ln_layout().rows) * static_cast<size_t>(e->n_nodes) : nullptr;
-}
-
-// the long rows of [row_begin, row_end) (kernels_nrt_long.hip) after the dense sweep `na` wrote their cells as those of an empty pod
-// (no containers, no request): their status and score rows are overwritten (or, with na.out_raw, the raw row).  Inside the sequential commit loop
-// (row_indirect) the launch reads the row from the device and leaves at once when it is not long.  No launch without long rows.
-int launch_nrt_long_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begin, int64_t row_end) {
-  e->nrt_long_last = 0;
-  const std::vector<int32_t>& rows = e->h_nrt_long_rows;
-  if (rows.empty()) return SPX_OK;
-  if (!e->nrt_long_ok) return fail(e, SPX_ERR_STATE, "NRT: the pod batch has pods with more than 8 containers: call spx_upload_nrt_long_pods after spx_upload_nrt_pods");
-  const int64_t k0 = std::lower_bound(rows.begin(), rows.end(), row_begin) - rows.begin();
-  const int64_t k1 = std::lower_bound(rows.begin(), rows.end(), row_end) - rows.begin();
-  if (k1 <= k0 && !e->row_indirect) return SPX_OK;
-  spx::NrtLongArgs l{};
-  l.n_nodes = na.n_nodes;
-  l.n_pods = na.n_pods;
-  l.row_stride = na.row_stride;
-  l.n_res = na.n_res;
-  l.strategy = na.strategy;
-  std::memcpy(l.slot_flags, na.slot_flags, sizeof l.slot_flags);
-  std::memcpy(l.slot_weight, na.slot_weight, sizeof l.slot_weight);
-  l.flags = na.flags, l.max_numa = na.max_numa, l.n_zones = na.n_zones, l.zone_id = na.zone_id, l.zone_present = na.zone_present;
-  l.zone_avail = na.zone_avail, l.zone_cost = na.zone_cost, l.min_avg = na.min_avg, l.node_present = na.node_present;
-  l.qos = na.qos, l.non_native = na.non_native, l.pod_present = na.pod_present, l.pod_req = na.pod_req;
-  l.pod_row = static_cast<const int32_t*>(e->d_nrtl_row.p);
-  l.ctr_ptr = static_cast<const int32_t*>(e->d_nrtl_ptr.p);
-  l.ctr_kind = static_cast<const uint8_t*>(e->d_nrtl_kind.p);
-  l.ctr_present = static_cast<const uint8_t*>(e->d_nrtl_pres.p);
-  l.ctr_req = static_cast<const int64_t*>(e->d_nrtl_req.p);
-  l.long_begin = k0;
-  l.long_end = k1;
-  if (e->row_indirect) {
-    l.row_ptr = e->row_indirect;
-    l.long_of_row = static_cast<const int32_t*>(e->d_nrtl_map.p);
-  }
-  l.out_status = na.out_status;
-  l.out_score = na.out_score;
-  l.out_raw = na.out_raw;
-  spx::launch_nrt_long(l, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  e->nrt_long_last = k1 - k0;
-  return SPX_OK;
-}
-
-// combin.Combinations(n, k) for n = 9 .. 16 as 16-bit masks over list positions, size-major then lexicographic (the 16-bit sibling
-// of nrt_combinations; 131 064 masks, built once on the host and uploaded: the 64 KB constant segment does not hold them)
-struct NrtTallCombos {
-  std::vector<uint16_t> mask;
-  uint32_t start[8][SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA + 1];
-};
-inline NrtTallCombos make_nrt_tall_combos() {
-  NrtTallCombos t;
-  for (int n = 9; n <= SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA; ++n) {
-    for (int k = 1; k <= SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA; ++k) {
-      t.start[n - 9][k - 1] = static_cast<uint32_t>(t.mask.size());
-      if (k > n) continue;
-      int c[SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA];
-      for (int i = 0; i < k; ++i) c[i] = i;
-      while (true) {
-        unsigned m = 0;
-        for (int i = 0; i < k; ++i) m |= 1u << c[i];
-        t.mask.push_back(static_cast<uint16_t>(m));
-        int i = k - 1;
-        while (i >= 0 && c[i] == n - k + i) --i;
-        if (i < 0) break;
-        ++c[i];
-        for (int j = i + 1; j < k; ++j) c[j] = c[j - 1] + 1;
-      }
-    }
-    t.start[n - 9][SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA] = static_cast<uint32_t>(t.mask.size());
-  }
-  return t;
-}
-
-int ensure_nrt_creq(spx_engine* e, bool force = false);
-
-// what an NRT evaluation of an engine with tall nodes needs before its first launch, from host state alone: the side table, and with
-// LeastNUMANodes no tall node above that strategy's zone limit.  spx_eval and spx_fetch_raw ask before they write anything.
-int nrt_tall_ready(const spx_engine* e) {
-  if (e->h_nrt_tall_nodes.empty()) return SPX_OK;
-  if (!e->nrt_tall_ok)
-    return fail(e, SPX_ERR_STATE, "NRT: the node table has nodes with more than 8 NUMA zones: call spx_upload_nrt_tall_nodes after spx_upload_nrt_nodes");
-  if (e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && e->nrt_tall_ln_node >= 0) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "NRT: LeastNUMANodes takes nodes of up to %d NUMA zones; node %d lists %d", SPX_NRT_TALL_MAX_ZONES_LEAST_NUMA,
-                  e->nrt_tall_ln_node, e->nrt_tall_ln_zones);
-    return fail(e, SPX_ERR_STATE, buf);
-  }
-  return SPX_OK;
-}
-
-// the tall nodes' columns of rows [row_begin, row_end) (kernels_nrt_tall.hip) after the dense sweep `na` and the long rows wrote them as
-// those of a node without an NRT object: status and score are overwritten (or, with na.out_raw, the raw row's entries).  It runs for
-// every row of the range — class copies, short and long rows — in reference arithmetic, whatever form the dense sweep took.  No launch
-// and no allocation without tall nodes.
-int launch_nrt_tall_rows(spx_engine* e, const spx::NrtArgs& na, int64_t row_begin, int64_t row_end) {
-  e->nrt_tall_last = 0;
-  const std::vector<int32_t>& tall = e->h_nrt_tall_nodes;
-  if (tall.empty()) return SPX_OK;
-  if (e->row_indirect) return fail(e, SPX_ERR_STATE, "NRT: the sequential commit loop does not take nodes with more than 8 NUMA zones");
-  int rc;
-  if ((rc = nrt_tall_ready(e))) return rc;  // (the callers checked before their first launch; a direct call must not get past it either)
-  if (row_end <= row_begin) return SPX_OK;
-  spx::NrtTallArgs t{};
-  t.n_nodes = na.n_nodes, t.n_pods = na.n_pods, t.row_stride = na.row_stride, t.n_res = na.n_res, t.strategy = na.strategy;
-  std::memcpy(t.slot_flags, na.slot_flags, sizeof t.slot_flags);
-  std::memcpy(t.slot_weight, na.slot_weight, sizeof t.slot_weight);
-  t.n_tall = static_cast<int32_t>(tall.size());
-  t.zone_stride = e->nrt_tall_stride;
-  t.node_idx = static_cast<const int32_t*>(e->d_nrtt_idx.p);
-  t.flags = static_cast<const uint8_t*>(e->d_nrtt_flags.p);
-  t.max_numa = static_cast<const int32_t*>(e->d_nrtt_max.p);
-  t.node_present = static_cast<const uint8_t*>(e->d_nrtt_np.p);
-  t.n_zones = static_cast<const uint8_t*>(e->d_nrtt_nz.p);
-  t.zone_id = static_cast<const uint8_t*>(e->d_nrtt_zid.p);
-  t.zone_present = static_cast<const uint8_t*>(e->d_nrtt_zp.p);
-  t.zone_avail = static_cast<const int64_t*>(e->d_nrtt_avail.p);
-  t.zone_cost = static_cast<const int32_t*>(e->d_nrtt_cost.p);
-  t.min_avg = static_cast<const float*>(e->d_nrtt_minavg.p);
-  // the per-container request column: a batch the float64 formulation takes does not ship it, and the dense sweep that just ran did
-  // not need it (ensure_nrt_creq) — this kernel reads it whatever form the dense sweep took, so it is rebuilt from the record stream here
-  if ((rc = ensure_nrt_creq(e, true))) return rc;
-  t.qos = na.qos, t.non_native = na.non_native, t.n_ctr = na.n_ctr, t.ctr_kind = na.ctr_kind, t.ctr_present = na.ctr_present;
-  t.ctr_req = static_cast<const int64_t*>(e->d_nrt_creq.p);
-  t.pod_present = na.pod_present, t.pod_req = na.pod_req;
-  if (!e->h_nrt_long_rows.empty()) {
-    t.long_of_row = static_cast<const int32_t*>(e->d_nrtl_map.p);
-    t.long_ptr = static_cast<const int32_t*>(e->d_nrtl_ptr.p);
-    t.long_kind = static_cast<const uint8_t*>(e->d_nrtl_kind.p);
-    t.long_present = static_cast<const uint8_t*>(e->d_nrtl_pres.p);
-    t.long_req = static_cast<const int64_t*>(e->d_nrtl_req.p);
-  }
-  t.row_begin = row_begin, t.row_end = row_end;
-  if (na.strategy == SPX_NRT_LEAST_NUMA_NODES) {
-    if (!e->nrt_tall_combos) {
-      const NrtTallCombos c = make_nrt_tall_combos();
-      if ((rc = upload(e, e->d_nrtt_cmask, c.mask.data(), c.mask.size() * sizeof(uint16_t))) || (rc = upload(e, e->d_nrtt_cstart, c.start, sizeof c.start))) return rc;
-      SPX_HIP(e, hipStreamSynchronize(e->stream));  // (a local table)
-      e->nrt_tall_combos = true;
-    }
-    t.combo_mask = static_cast<const uint16_t*>(e->d_nrtt_cmask.p);
-    t.combo_start = static_cast<const uint32_t*>(e->d_nrtt_cstart.p);
-  }
-  t.n_waves = spx::nrt_tall_waves(row_end - row_begin, t.n_tall, t.zone_stride, t.n_res);
-  if ((rc = ensure(e, e->d_nrtt_work, static_cast<size_t>(spx::nrt_tall_work_bytes(t.zone_stride, t.n_res, t.n_waves))))) return rc;
-  t.work = static_cast<int64_t*>(e->d_nrtt_work.p);
-  t.out_status = na.out_status, t.out_score = na.out_score, t.out_raw = na.out_raw;
-  spx::launch_nrt_tall(t, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  e->nrt_tall_last = static_cast<int64_t>(tall.size());
-  return SPX_OK;
-}
-
-// NodeResourceTopologyMatch over the wide tables, rows [row_begin, row_end) into the status / score tables (or, with out_raw, the one
-// row's raw scores).  Replaces the whole dense machinery: no pod classes, rank stream, fused walk, redo lists or long rows.
-int launch_nrt_wide_rows(spx_engine* e, int64_t row_begin, int64_t row_end, int64_t* out_raw) {
-  if (!(e->nrtw_slots && e->nrtw_nodes && e->nrtw_pods)) return fail(e, SPX_ERR_STATE, "NRT wide slot/node/pod tables not uploaded");
-  spx::NrtWideArgs w{};
-  w.n_nodes = e->n_nodes;
-  w.n_pods = e->n_pods;
-  w.row_stride = e->row_stride;
-  w.n_res = e->nrtw_n_res;
-  w.strategy = e->nrt_params.strategy;
-  w.slot_flags = static_cast<const uint8_t*>(e->d_nrtw_sflags.p);
-  w.slot_weight = static_cast<const int64_t*>(e->d_nrtw_sweight.p);
-  w.flags = static_cast<const uint8_t*>(e->d_nrtw_flags.p);
-  w.max_numa = static_cast<const int32_t*>(e->d_nrtw_max_numa.p);
-  w.n_zones = static_cast<const uint8_t*>(e->d_nrtw_nz.p);
-  w.zone_id = static_cast<const uint8_t*>(e->d_nrtw_zid.p);
-  w.zone_present = static_cast<const uint32_t*>(e->d_nrtw_zp.p);
-  w.zone_avail = static_cast<const int64_t*>(e->d_nrtw_avail.p);
-  w.zone_cost = static_cast<const int32_t*>(e->d_nrtw_cost.p);
-  w.min_avg = static_cast<const float*>(e->d_nrtw_minavg.p);
-  w.node_present = static_cast<const uint32_t*>(e->d_nrtw_np.p);
-  w.qos = static_cast<const uint8_t*>(e->d_nrtw_qos.p);
-  w.non_native = static_cast<const uint8_t*>(e->d_nrtw_nn.p);
-  w.req_ptr = static_cast<const int32_t*>(e->d_nrtw_rptr.p);
-  w.req_slot = static_cast<const uint8_t*>(e->d_nrtw_rslot.p);
-  w.req_qty = static_cast<const int64_t*>(e->d_nrtw_rqty.p);
-  w.ctr_ptr = static_cast<const int32_t*>(e->d_nrtw_cptr.p);
-  w.ctr_kind = static_cast<const uint8_t*>(e->d_nrtw_ckind.p);
-  w.ent_ptr = static_cast<const int32_t*>(e->d_nrtw_eptr.p);
-  w.ent_slot = static_cast<const uint8_t*>(e->d_nrtw_eslot.p);
-  w.ent_qty = static_cast<const int64_t*>(e->d_nrtw_eqty.p);
-  w.row_begin = row_begin;
-  w.row_end = row_end;
-  w.out_status = static_cast<uint8_t*>(e->status[SPX_PLUGIN_NRT].p);
-  w.out_score = static_cast<uint8_t*>(e->score[SPX_PLUGIN_NRT].p);
-  w.out_raw = out_raw;
-  spx::launch_nrt_wide(w, e->stream);
-  SPX_HIP(e, hipGetLastError());
-  return SPX_OK;
-}
-
-// the reference-arithmetic NRT kernel's request column, when the coming launch may take that kernel and the batch did not ship it
-// (`force`: whatever form the dense sweep takes — the tall nodes' kernel reads the column in every case)
-int ensure_nrt_creq(spx_engine* e, bool force) {
-  const bool fast = e->nrt_fast_slots && e->nrt_fast_nodes && e->nrt_fast_pods && !forced_reference(e, SPX_PLUGIN_NRT) &&
-                    !(e->nrt_params.strategy == SPX_NRT_LEAST_NUMA_NODES && !(e->nrt_ln_ok && e->nrt_ln_built));
-  if ((fast && !force) || e->nrt_creq_valid) return SPX_OK;
-  const size_t bytes = static_cast<size_t>(e->n_pods) * SPX_NRT_MAX_CTRS * static_cast<size_t>(e->nrt_n_res) * sizeof(int64_t);
-  int rc = ensure(e, e->d_nrt_creq, bytes);
-  if (rc) return rc;
-  spx::launch_nrt_creq_from_items(static_cast<const uint32_t*>(e->d_nrt_items.p), e->nrt_n_res, e->n_pods, static_cast<int64_t*>(e->d_nrt_creq.p), e->stream);
-  SPX_HIP(e, hipGetLastError());
-  e->nrt_creq_valid = true;
-  return SPX_OK;
-}
-
-using spx_host::kNrtFastLimit;
-using spx_host::kNrtWeightLimit;
-using spx_host::nrt_biased_rcp;
-using spx_host::nrt_exact_f32;
-using spx_host::nrt_fast_qty;
-using spx_host::nrt_value_of;
-using spx_host::nrt_build_classes;
-using spx_host::nrt_build_items;
-using spx_host::nrt_build_rank_stream;
-
-void fill_net(const spx_engine* e, spx::NetArgs& g) {
-  g.opts = launch_opts(e);
-  g.row_ptr = e->row_indirect;
-  g.n_nodes = e->n_nodes;
-  g.row_stride = e->row_stride;
-  g.n_regions = e->net_n_regions;
-  g.n_zones = e->net_n_zones;
-  g.n_classes = e->net_n_classes;
-  g.region = static_cast<const int32_t*>(e->d_net_region.p);
-  g.zone = static_cast<const int32_t*>(e->d_net_zone.p);
-  g.node_class = static_cast<const int32_t*>(e->d_net_class.p);
-  g.node_class16 = e->net_class16 ? static_cast<const uint16_t*>(e->d_net_class16.p) : nullptr;
-  g.cls_size = static_cast<const int32_t*>(e->d_net_cls_size.p);
-  g.cls_region = static_cast<const int32_t*>(e->d_net_cls_region.p);
-  g.cls_zone = static_cast<const int32_t*>(e->d_net_cls_zone.p);
-  if (e->net_wide_dev) {
-    g.cost_wide = 1;
-    g.region_cost64 = static_cast<const int64_t*>(e->d_net_rcost.p);
-    g.zone_cost64 = static_cast<const int64_t*>(e->d_net_zcost.p);
-  } else {
-    g.region_cost = static_cast<const int32_t*>(e->d_net_rcost.p);
-    g.zone_cost = static_cast<const int32_t*>(e->d_net_zcost.p);
-  }
-  g.pod_key = static_cast<const int32_t*>(e->d_net_pod_key.p);
-  g.key_flag = static_cast<const uint8_t*>(e->d_net_key_flag.p);
-  g.pair_ptr = static_cast<const int32_t*>(e->d_net_pair_ptr.p);
-  g.pair_node = static_cast<const int32_t*>(e->d_net_pair_node.p);
-  g.pair_max = static_cast<const int64_t*>(e->d_net_pair_max.p);
-  if (e->net_dyn_active) {  // sequential commit: lists with slack that grow as pods are bound
-    g.pair_ptr = static_cast<const int32_t*>(e->d_net_dyn_ptr.p);
-    g.pair_end = static_cast<const int32_t*>(e->d_net_dyn_end.p);
-    g.pair_node = static_cast<const int32_t*>(e->d_net_dyn_node.p);
-    g.pair_max = static_cast<const int64_t*>(e->d_net_dyn_max.p);
-  }
-}
-
-// NetworkOverhead: the bound of a node's accumulated cost, (largest cost entry) x (most pairs of any workload key, `extra_pairs`
-// more once a batch is bound), INT64_MAX when the product does not fit int64
-int64_t net_cost_bound(const spx_engine* e, int64_t extra_pairs) {
-  int64_t b;
-  return __builtin_mul_overflow(e->net_max_cost, std::max<int64_t>(e->net_max_pairs + extra_pairs, 1), &b) ? std::numeric_limits<int64_t>::max() : b;
-}
-
 // the 64-bit sweep (kernels_network_wide.hip) runs when the device holds int64 cost matrices or the bound reaches 2^31
-bool net_wide(const spx_engine* e, int64_t extra_pairs) { return e->net_wide_dev || net_cost_bound(e, extra_pairs) >= (int64_t{1} << 31); }
+inline bool net_wide(const spx_engine* e, int64_t extra_pairs) { return e->net_wide_dev || net_cost_bound(e, extra_pairs) >= (int64_t{1} << 31); }
 
-// Before a NetworkOverhead launch: net_bound_check refuses a snapshot whose bound reaches 2^63 (host state alone), and net_prepare
-// then widens narrow cost matrices on the device (once: they stay int64 until the next topology upload) when the bound asks for the
-// 64-bit sweep.  `when`: which bound, for the message.
-int net_bound_check(const spx_engine* e, int64_t extra_pairs, const char* when) {
-  if (net_cost_bound(e, extra_pairs) == std::numeric_limits<int64_t>::max())
-    return fail(e, SPX_ERR_ARG, std::string("NetworkOverhead: accumulated cost of a node may reach 2^63 (cost entries x dependency pairs") + when +
-                                    "); the reference's own int64 sum would wrap there");
-  return SPX_OK;
-}
-int net_prepare(spx_engine* e, int64_t extra_pairs, const char* when) {
-  int rc = net_bound_check(e, extra_pairs, when);
-  if (rc || e->net_wide_dev || !net_wide(e, extra_pairs)) return rc;
-  if ((rc = upload(e, e->d_net_rcost, e->h_net_rcost.data(), e->h_net_rcost.size() * 8)) || (rc = upload(e, e->d_net_zcost, e->h_net_zcost.data(), e->h_net_zcost.size() * 8)))
-    return rc;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));
-  e->net_wide_dev = true;
-  return SPX_OK;
-}
+}  // namespace spx_eng
 
-// the cost matrices of either width onto the device (one pair of buffers: an upload of one width replaces the other), their int64
-// host copy and the largest entry
-template <typename T>
-int upload_net_costs(spx_engine* e, int32_t n_regions, int32_t n_zones, const T* region_cost, const T* zone_cost) {
-  if (n_regions < 0 || n_zones < 0) return fail(e, SPX_ERR_ARG, "negative topology size");
-  const size_t rr = static_cast<size_t>(n_regions) * n_regions, zz = static_cast<size_t>(n_zones) * n_zones;
-  int rc;
-  if ((rc = upload(e, e->d_net_rcost, region_cost ? static_cast<const void*>(region_cost) : static_cast<const void*>(&rc), rr * sizeof(T)))) return rc;
-  if ((rc = upload(e, e->d_net_zcost, zone_cost ? static_cast<const void*>(zone_cost) : static_cast<const void*>(&rc), zz * sizeof(T)))) return rc;
-  e->net_n_regions = n_regions;
-  e->net_n_zones = n_zones;
-  e->net_wide_dev = sizeof(T) == 8;
-  e->h_net_rcost.assign(region_cost ? region_cost : nullptr, region_cost ? region_cost + rr : nullptr);
-  e->h_net_zcost.assign(zone_cost ? zone_cost : nullptr, zone_cost ? zone_cost + zz : nullptr);
-  e->h_net_rcost.resize(rr, -1), e->h_net_zcost.resize(zz, -1);  // (a NULL column: net_prepare widens to "no entry", full size)
-  e->net_max_cost = SPX_NET_MAX_COST;
-  for (const int64_t c : e->h_net_rcost) e->net_max_cost = std::max(e->net_max_cost, c);
-  for (const int64_t c : e->h_net_zcost) e->net_max_cost = std::max(e->net_max_cost, c);
-  SPX_HIP(e, hipStreamSynchronize(e->stream));
-  e->net_topo = true;
-  return SPX_OK;
-}
+using namespace spx_eng;  // (the call sites say fail, ensure, upload, ...)
 
-// host [N][inner] -> device [inner][N] so that lane = node reads coalesce
-template <typename T>
-int upload_transposed(spx_engine* e, DevBuf& b, const T* src, int64_t n, int64_t inner) {
-  if (!src) return fail(e, SPX_ERR_ARG, "NULL column in table");
-  std::vector<T> tmp(static_cast<size_t>(n) * static_cast<size_t>(inner));
-  spx_host::parallel_rows(n, [&](int64_t row0, int64_t row1) {
-    for (int64_t i = row0; i < row1; ++i)
-      for (int64_t k = 0; k < inner; ++k) tmp[static_cast<size_t>(k) * n + i] = src[static_cast<size_t>(i) * inner + k];
-  }, 2048);
-  int rc = upload(e, b, tmp.data(), tmp.size() * sizeof(T));
-  if (rc) return rc;
-  SPX_HIP(e, hipStreamSynchronize(e->stream));  // tmp dies at scope exit
-  return SPX_OK;
-}
-
-// The (row, representative) pairs of a pod batch's equivalence classes as launch_rows_expand reads them: sorted by representative (then row), and
-// behind them the copy tasks — (first pair, count <= kRowsExpandFan) per run of pairs with one representative — so that a workgroup reads a
-// representative's row once for up to eight copies.  Returns the task count; `dups` = [pairs | tasks].
-inline int64_t expand_tasks(std::vector<int32_t>& dups, int64_t n_rows) {
-  const size_t n = dups.size() / 2;
-  // counting sort by representative (the pairs arrive in ascending order of the copied row, and stay so inside a representative's run)
-  std::vector<int32_t> at(static_cast<size_t>(n_rows) + 1, 0), sorted(2 * n);
-  for (size_t i = 0; i < n; ++i) ++at[static_cast<size_t>(dups[2 * i + 1]) + 1];
-  for (int64_t r = 0; r < n_rows; ++r) at[static_cast<size_t>(r) + 1] += at[static_cast<size_t>(r)];
-  for (size_t i = 0; i < n; ++i) {
-    const size_t k = static_cast<size_t>(at[static_cast<size_t>(dups[2 * i + 1])]++);
-    sorted[2 * k] = dups[2 * i], sorted[2 * k + 1] = dups[2 * i + 1];
-  }
-  dups.swap(sorted);
-  int64_t tasks = 0;
-  for (size_t i = 0; i < n;) {
-    size_t j = i;
-    while (j < n && j - i < static_cast<size_t>(spx::kRowsExpandFan) && dups[2 * j + 1] == dups[2 * i + 1]) ++j;
-    dups.push_back(static_cast<int32_t>(i)), dups.push_back(static_cast<int32_t>(j - i));
-    ++tasks;
-    i = j;
-  }
-  return tasks;
-}
-
-}  // namespace
-
-// defined in spx_uploads.hip, used by the evaluation and the commit loops (not exported)
 extern "C" {
-__attribute__((visibility("hidden"))) int build_ln_tab(spx_engine* e);
-__attribute__((visibility("hidden"))) int nrt_rank_stream(spx_engine* e, int kind);
-// defined with spx_decide (spx_engine.hip), also the commit loops' per-pod step
-__attribute__((visibility("hidden"))) int decide_masked(spx_engine* e, uint32_t eval_mask, uint32_t score_mask, int64_t row_begin, int64_t row_end, bool* done);
+// ---- spx_uploads.hip: derived NRT tables the evaluation and the commit loops ask for
+SPX_LOCAL int build_ln_tab(spx_engine* e);
+SPX_LOCAL int nrt_rank_stream(spx_engine* e, int kind);
+// ---- spx_engine.hip: defined with spx_decide, also the commit loops' per-pod step
+SPX_LOCAL int decide_masked(spx_engine* e, uint32_t eval_mask, uint32_t score_mask, int64_t row_begin, int64_t row_end, bool* done);
 }

@@ -1,14 +1,184 @@
 // spx_engine.hip — the C-ABI engine of libspx.so: lifecycle, options and parameters, the evaluation (spx_eval, spx_decide, spx_eval_best)
 // and the fetch calls.  Tables and deltas into HBM: spx_uploads.hip; the one-call loaders: spx_loads.hip; the one-pod-at-a-time loops:
-// spx_commit.hip; shared state and helpers: spx_engine.h.  See include/spx.h for the contract.
+// spx_commit.hip; the preemption runs: spx_preempt.hip.  State and what crosses the units: spx_engine.h (defined in spx_state.hip,
+// spx_eval_args.hip, spx_nrt_rows.hip); the helpers only this file calls open it, in the first namespace below.  See include/spx.h
+// for the contract.
 //
 // There is deliberately no CPU fallback: spx_create() fails with SPX_ERR_NOGPU when no HIP device
 // is usable, and every compute entry point needs an engine.
 #include "spx_engine.h"
 
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+
 thread_local std::string g_create_error;
 thread_local std::string tl_err;
 thread_local const spx_engine* tl_err_engine = nullptr;
+
+// ---- this file's own helpers: the plugin sets, the bound-table checks, the argument builders and the packed Score's preconditions
+namespace {
+
+constexpr uint32_t kFilterPlugins = (1u << SPX_PLUGIN_NRT) | (1u << SPX_PLUGIN_NETOVERHEAD);
+// plugins whose NormalizeScore depends on the feasible set of the cycle
+constexpr uint32_t kNormalizingPlugins =
+    (1u << SPX_PLUGIN_ALLOCATABLE) | (1u << SPX_PLUGIN_NETOVERHEAD) | (1u << SPX_PLUGIN_PEAKS) | (1u << SPX_PLUGIN_SYSCHED) | (1u << SPX_PLUGIN_NODEMETA) |
+    (1u << SPX_PLUGIN_PODSTATE);
+// plugins that own a uint8 score table
+constexpr bool plugin_has_score(int k) {
+  return k <= SPX_PLUGIN_NETOVERHEAD || k == SPX_PLUGIN_LROC || k == SPX_PLUGIN_PEAKS || k == SPX_PLUGIN_SYSCHED || k == SPX_PLUGIN_NODEMETA || k == SPX_PLUGIN_PODSTATE;
+}
+
+// The checks of a plugin's tables that write nothing (spx_eval makes them all before its first allocation): a table the caller bound
+// must hold n_pods x row_stride (a score table: score_table_fits, spx_state.hip) ...
+int status_table_fits(const spx_engine* e, int plugin) {
+  if (e->status[plugin].external && e->status[plugin].bytes < static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride))
+    return fail(e, SPX_ERR_STATE, "bound status table is smaller than n_pods x row_stride");
+  return SPX_OK;
+}
+// ... and use the engine's row stride (an engine-owned table has it by construction: ensure_score_table)
+int score_table_stride(const spx_engine* e, int plugin) {
+  if (e->score[plugin].external && e->score_stride[plugin] != e->row_stride)
+    return fail(e, SPX_ERR_STATE, "bound score table must use the engine row stride (spx_score_table reports it)");
+  return SPX_OK;
+}
+
+int ensure_status_table(spx_engine* e, int plugin) {
+  DevBuf& b = e->status[plugin];
+  if (b.external) return status_table_fits(e, plugin);
+  return ensure(e, b, static_cast<size_t>(e->n_pods) * static_cast<size_t>(e->row_stride));
+}
+
+// The status tables that narrow a pod's node list when `mask` is evaluated or summed: {NRT's, NetworkOverhead's, the caller's mask},
+// NULL = not in play (the layout of ProfileArgs.status and the scorers' other_status; NetworkOverhead's own sweep takes [0] and [2])
+void feasibility_status(const spx_engine* e, uint32_t mask, const uint8_t* out[3]) {
+  out[0] = (mask & (1u << SPX_PLUGIN_NRT)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NRT].p) : nullptr;
+  out[1] = (mask & (1u << SPX_PLUGIN_NETOVERHEAD)) ? static_cast<const uint8_t*>(e->status[SPX_PLUGIN_NETOVERHEAD].p) : nullptr;
+  out[2] = e->ext_mask ? static_cast<const uint8_t*>(e->d_ext_status.p) : nullptr;
+}
+
+// What one evaluation is asked for besides its mask and rows (spx_decide's preparatory sweeps; spx_eval itself passes the defaults)
+struct EvalCall {
+  bool hold_ev0 = false;           // the caller has recorded ev0 and times this evaluation together with its own sweep
+  bool skip_alloc_masked = false;  // the caller folds Allocatable's masked normalisation into its argmax kernel: the table is not written
+};
+
+void fill_peaks(const spx_engine* e, spx::PeaksArgs& a) {
+  a.opts = launch_opts(e);
+  a.n_nodes = e->n_nodes;
+  a.row_stride = e->row_stride;
+  a.cap_cpu_milli = static_cast<const int64_t*>(e->d_pk_cap.p);
+  a.cpu_util = static_cast<const double*>(e->d_pk_util.p);
+  a.valid = static_cast<const uint8_t*>(e->d_pk_valid.p);
+  a.k1 = static_cast<const double*>(e->d_pk_k1.p);
+  a.k2 = static_cast<const double*>(e->d_pk_k2.p);
+  a.pod_cpu_milli = static_cast<const int64_t*>(e->d_pk_pod.p);
+  a.row_min = static_cast<int64_t*>(e->d_pk_min.p);
+  a.row_max = static_cast<int64_t*>(e->d_pk_max.p);
+  a.row_c = static_cast<float*>(e->d_pk_rowc.p);
+  a.node_tab = static_cast<double*>(e->d_pk_tab.p);
+}
+
+void fill_sysched(const spx_engine* e, spx::SyschedArgs& a) {
+  a.n_nodes = e->n_nodes;
+  a.row_stride = e->row_stride;
+  a.n_words = e->sy_node_words;
+  a.host_bits = static_cast<const uint64_t*>(e->d_sy_host.p);
+  a.present = static_cast<const uint8_t*>(e->d_sy_present.p);
+  a.n_resident = static_cast<const int32_t*>(e->d_sy_k.p);
+  a.resident_missing = static_cast<const int32_t*>(e->d_sy_a.p);
+  a.stale_ptr = static_cast<const int32_t*>(e->d_sy_sptr.p);
+  a.stale_bit = static_cast<const int32_t*>(e->d_sy_sbit.p);
+  a.stale_count = static_cast<const int32_t*>(e->d_sy_scnt.p);
+  a.set_bits = static_cast<const uint64_t*>(e->d_sy_sets.p);
+  a.set_empty = static_cast<const uint8_t*>(e->d_sy_empty.p);
+  a.pod_set = static_cast<const int32_t*>(e->d_sy_pod_set.p);
+  a.order = static_cast<const int32_t*>(e->d_sy_order.p);
+  a.set_first = static_cast<const int32_t*>(e->d_sy_first.p);
+  a.raw = static_cast<int32_t*>(e->d_sy_raw.p);
+  a.set_max = static_cast<int32_t*>(e->d_sy_max.p);
+}
+
+void fill_cosched(const spx_engine* e, spx::CoschedArgs& a) {
+  a.n_nodes = e->n_nodes;
+  a.n_slots = e->cs_n_slots;
+  a.n_groups = e->cs_n_groups;
+  a.n_walk = e->cs_n_walk;
+  a.left_base = static_cast<const int64_t*>(e->d_cs_left.p);
+  a.node_present = static_cast<const uint8_t*>(e->d_cs_present.p);
+  a.prefix = static_cast<int64_t*>(e->d_cs_prefix.p);
+  a.slot_max = static_cast<int64_t*>(e->d_cs_smax.p);
+  a.slot_total = static_cast<int64_t*>(e->d_cs_stotal.p);
+  a.any_present = static_cast<int32_t*>(e->d_cs_any.p);
+  a.req = static_cast<const int64_t*>(e->d_cs_req.p);
+  a.req_mask = static_cast<const uint32_t*>(e->d_cs_mask.p);
+  a.step_ptr = static_cast<const int32_t*>(e->d_cs_sptr.p);
+  a.step_node = static_cast<const int32_t*>(e->d_cs_snode.p);
+  a.step_cum = static_cast<const int64_t*>(e->d_cs_scum.p);
+  a.walk_group = static_cast<const int32_t*>(e->d_cs_walk.p);
+  a.pass_mask = static_cast<uint32_t*>(e->d_cs_pass.p);
+  a.open_mask = static_cast<uint32_t*>(e->d_cs_open.p);
+  a.gap = static_cast<int64_t*>(e->d_cs_gap.p);
+  a.g_exists = static_cast<const uint8_t*>(e->d_cs_exists.p);
+  a.min_member = static_cast<const int32_t*>(e->d_cs_minm.p);
+  a.has_min_resources = static_cast<const uint8_t*>(e->d_cs_hasres.p);
+  a.backed_off = static_cast<const uint8_t*>(e->d_cs_backoff.p);
+  a.permitted = static_cast<const uint8_t*>(e->d_cs_permit.p);
+  a.listed = static_cast<const int32_t*>(e->d_cs_listed.p);
+  a.gated = static_cast<const int32_t*>(e->d_cs_gated.p);
+  a.pod_group = static_cast<const int32_t*>(e->d_cs_pod_group.p);
+  a.out_status = static_cast<uint8_t*>(e->d_cs_status.p);
+}
+
+// The packed float32 form of LeastAllocated's Score launch (nrt_fast_device.h, score_least_packed) needs every weighted slot to be
+// "small" — with 2^s the largest power of two dividing all its capacities and requests, capacity / 2^s <= 32768 and request / 2^s < 2^24 —
+// or, one slot at most and not cpu, to go through k_nrt_pk_tab_build's table indexed by request / unit, unit = the largest power of
+// two dividing all its requests.  false = the float64 form.
+struct NrtPacked {
+  uint32_t small_slots = 0;
+  int32_t tab_slot = -1;
+  uint32_t tab_kmax = 0, tab_words = 0;
+  double tab_inv_unit = 1.0;
+};
+constexpr int64_t kNrtSmallCap = 32768;
+bool nrt_packed_score(const spx_engine* e, NrtPacked* out) {
+  *out = NrtPacked{};
+  // (MostAllocated: the same float32 products serve x = 100 v / c as serve 100 - x; only the fused walk consumes the answer for that strategy)
+  if (!e->option[SPX_OPT_NRT_PACKED_SCORE] || !e->nrt_nodes || !e->nrt_pods || e->in_commit_loop ||
+      (e->nrt_params.strategy != SPX_NRT_LEAST_ALLOCATED && !(e->nrt_params.strategy == SPX_NRT_MOST_ALLOCATED && e->option[SPX_OPT_NRT_FUSED])))
+    return false;
+  int64_t wsum = 0;
+  for (int i = 0; i < e->nrt_n_res && i < SPX_NRT_MAX_RES; ++i) {
+    if (e->nrt_slot_weight[i] < 0) return false;
+    wsum += e->nrt_slot_weight[i];
+  }
+  if (wsum > spx::kNrtPkMaxWeightSum) return false;
+  auto low_zeros = [](uint64_t bits) { return bits ? __builtin_ctzll(bits) : 63; };
+  for (int i = 0; i < e->nrt_n_res && i < SPX_NRT_MAX_RES; ++i) {
+    if (e->nrt_slot_weight[i] == 0) continue;  // contributes 0 whatever its resource score
+    const uint64_t pod_bits = e->nrt_qty_pods.bits[i];
+    if (pod_bits == 0) {  // no request but zeros: the resource score is 100 or 0 in both forms
+      out->small_slots |= 1u << i;
+      continue;
+    }
+    const int s = low_zeros(pod_bits | e->nrt_qty_nodes.bits[i]);
+    if ((e->nrt_qty_nodes.most[i] >> s) <= kNrtSmallCap && (e->nrt_qty_pods.most[i] >> s) < (int64_t{1} << 24)) {
+      out->small_slots |= 1u << i;
+      continue;
+    }
+    const int su = low_zeros(pod_bits);
+    const int64_t kmax = e->nrt_qty_pods.most[i] >> su;
+    const size_t words = static_cast<size_t>((e->n_nodes + 255) / 256 + 31) / 32;
+    if (out->tab_slot >= 0 || i == e->nrt_cpu_slot || kmax > spx::kNrtPkTabMaxK || (static_cast<size_t>(kmax) + 1) * words * 4 > spx::kNrtPkTabMaxBytes)
+      return false;
+    out->tab_slot = i, out->tab_kmax = static_cast<uint32_t>(kmax), out->tab_words = static_cast<uint32_t>(words);
+    out->tab_inv_unit = std::ldexp(1.0, -su);
+  }
+  return true;
+}
+
+}  // namespace
 
 extern "C" {
 

@@ -1,6 +1,12 @@
 // spx_loads.hip — the one-call loaders: spx_load_* / spx_load_profile turn object tables into SoA columns (the host flatteners) and hand
-// them to the spx_upload_* functions of spx_uploads.hip.  Engine state and shared helpers: spx_engine.h.
+// them to the spx_upload_* functions of spx_uploads.hip.  Engine state and what crosses the units: spx_engine.h.
 #include "spx_engine.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <thread>
 
 extern "C" {
 

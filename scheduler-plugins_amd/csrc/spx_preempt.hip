@@ -4,8 +4,13 @@
 // spx_fetch_preempt_*): table checks and uploads, the launches of kernels_preempt.hip, kernels_preempt_seq.hip, kernels_ptol.hip,
 // kernels_ptol_seq.hip, kernels_ptol_nrt.hip, kernels_preempt_nrt.hip, kernels_ptol_nrt_seq.hip and kernels_preempt_nrt_seq.hip, and the
 // fetches, which serve whichever of the eight ran last.
-// State: spx_engine.h.
+// State: spx_engine.h; of the shared helpers it takes fail, ensure, upload, set_nodes and set_pods (spx_state.hip).
 #include "spx_engine.h"
+
+#include <algorithm>
+#include <cstring>
+#include <type_traits>
+#include <unordered_map>
 
 namespace {
 

@@ -1,11 +1,110 @@
 // spx_uploads.hip — tables into HBM: spx_upload_* (SoA columns), spx_update_* (snapshot deltas) and the derived host-built streams of the
 // NRT sweeps (host/nrt_streams.cc).  A full node table and a delta of its rows take one road: the helpers of the first namespace below.
-// The one-call loaders (object tables -> SoA -> these functions): spx_loads.hip.  Engine state and shared helpers: spx_engine.h.
+// The one-call loaders (object tables -> SoA -> these functions): spx_loads.hip.  Engine state and what crosses the units:
+// spx_engine.h.  The first namespace below opens with the helpers only the uploads call: the exactness scans, the transposed and
+// the cost-matrix uploads, the copy tasks of the pod classes.
 #include "spx_engine.h"
 
+#include <algorithm>
 #include <array>
+#include <cstring>
+#include <mutex>
+#include <utility>
+
+#include "../host/parallel.hpp"
 
 namespace {
+
+using spx_host::kNrtWeightLimit;
+using spx_host::nrt_biased_rcp;
+using spx_host::nrt_exact_f32;
+using spx_host::nrt_fast_qty;
+using spx_host::nrt_value_of;
+using spx_host::nrt_build_classes;
+using spx_host::nrt_build_items;
+using spx_host::nrt_build_rank_stream;
+
+// every value in [0, 2^52): sums and differences of two such values are exact in float64
+bool all_below_2p52(const int64_t* v, size_t n) {
+  uint64_t acc = 0;
+  for (size_t i = 0; i < n; ++i) acc |= static_cast<uint64_t>(v[i]);
+  return (acc >> 52) == 0;
+}
+// every value in [0, 2^47): such a value, and the difference of two, is the sum of two float32 exactly (k_lroc_fast)
+bool all_below_2p47(const int64_t* v, size_t n) {
+  uint64_t acc = 0;
+  for (size_t i = 0; i < n; ++i) acc |= static_cast<uint64_t>(v[i]);
+  return (acc >> 47) == 0;
+}
+bool none_below(const int64_t* hi, const int64_t* lo, size_t n) {
+  bool ok = true;
+  for (size_t i = 0; i < n; ++i) ok = ok && hi[i] >= lo[i];
+  return ok;
+}
+
+// the cost matrices of either width onto the device (one pair of buffers: an upload of one width replaces the other), their int64
+// host copy and the largest entry
+template <typename T>
+int upload_net_costs(spx_engine* e, int32_t n_regions, int32_t n_zones, const T* region_cost, const T* zone_cost) {
+  if (n_regions < 0 || n_zones < 0) return fail(e, SPX_ERR_ARG, "negative topology size");
+  const size_t rr = static_cast<size_t>(n_regions) * n_regions, zz = static_cast<size_t>(n_zones) * n_zones;
+  int rc;
+  if ((rc = upload(e, e->d_net_rcost, region_cost ? static_cast<const void*>(region_cost) : static_cast<const void*>(&rc), rr * sizeof(T)))) return rc;
+  if ((rc = upload(e, e->d_net_zcost, zone_cost ? static_cast<const void*>(zone_cost) : static_cast<const void*>(&rc), zz * sizeof(T)))) return rc;
+  e->net_n_regions = n_regions;
+  e->net_n_zones = n_zones;
+  e->net_wide_dev = sizeof(T) == 8;
+  e->h_net_rcost.assign(region_cost ? region_cost : nullptr, region_cost ? region_cost + rr : nullptr);
+  e->h_net_zcost.assign(zone_cost ? zone_cost : nullptr, zone_cost ? zone_cost + zz : nullptr);
+  e->h_net_rcost.resize(rr, -1), e->h_net_zcost.resize(zz, -1);  // (a NULL column: net_prepare widens to "no entry", full size)
+  e->net_max_cost = SPX_NET_MAX_COST;
+  for (const int64_t c : e->h_net_rcost) e->net_max_cost = std::max(e->net_max_cost, c);
+  for (const int64_t c : e->h_net_zcost) e->net_max_cost = std::max(e->net_max_cost, c);
+  SPX_HIP(e, hipStreamSynchronize(e->stream));
+  e->net_topo = true;
+  return SPX_OK;
+}
+
+// host [N][inner] -> device [inner][N] so that lane = node reads coalesce
+template <typename T>
+int upload_transposed(spx_engine* e, DevBuf& b, const T* src, int64_t n, int64_t inner) {
+  if (!src) return fail(e, SPX_ERR_ARG, "NULL column in table");
+  std::vector<T> tmp(static_cast<size_t>(n) * static_cast<size_t>(inner));
+  spx_host::parallel_rows(n, [&](int64_t row0, int64_t row1) {
+    for (int64_t i = row0; i < row1; ++i)
+      for (int64_t k = 0; k < inner; ++k) tmp[static_cast<size_t>(k) * n + i] = src[static_cast<size_t>(i) * inner + k];
+  }, 2048);
+  int rc = upload(e, b, tmp.data(), tmp.size() * sizeof(T));
+  if (rc) return rc;
+  SPX_HIP(e, hipStreamSynchronize(e->stream));  // tmp dies at scope exit
+  return SPX_OK;
+}
+
+// The (row, representative) pairs of a pod batch's equivalence classes as launch_rows_expand reads them: sorted by representative (then row), and
+// behind them the copy tasks — (first pair, count <= kRowsExpandFan) per run of pairs with one representative — so that a workgroup reads a
+// representative's row once for up to eight copies.  Returns the task count; `dups` = [pairs | tasks].
+int64_t expand_tasks(std::vector<int32_t>& dups, int64_t n_rows) {
+  const size_t n = dups.size() / 2;
+  // counting sort by representative (the pairs arrive in ascending order of the copied row, and stay so inside a representative's run)
+  std::vector<int32_t> at(static_cast<size_t>(n_rows) + 1, 0), sorted(2 * n);
+  for (size_t i = 0; i < n; ++i) ++at[static_cast<size_t>(dups[2 * i + 1]) + 1];
+  for (int64_t r = 0; r < n_rows; ++r) at[static_cast<size_t>(r) + 1] += at[static_cast<size_t>(r)];
+  for (size_t i = 0; i < n; ++i) {
+    const size_t k = static_cast<size_t>(at[static_cast<size_t>(dups[2 * i + 1])]++);
+    sorted[2 * k] = dups[2 * i], sorted[2 * k + 1] = dups[2 * i + 1];
+  }
+  dups.swap(sorted);
+  int64_t tasks = 0;
+  for (size_t i = 0; i < n;) {
+    size_t j = i;
+    while (j < n && j - i < static_cast<size_t>(spx::kRowsExpandFan) && dups[2 * j + 1] == dups[2 * i + 1]) ++j;
+    dups.push_back(static_cast<int32_t>(i)), dups.push_back(static_cast<int32_t>(j - i));
+    ++tasks;
+    i = j;
+  }
+  return tasks;
+}
+
 // one pinned blob for a delta's columns: [idx int32 n] then each column, 16-byte aligned; uploaded with one DMA
 struct DeltaBlob {
   spx_engine* e;

@@ -20,6 +20,44 @@ def test_library_exports_every_declared_symbol():
     assert lib.spx_abi_version() == 1
 
 
+def test_engine_helpers_are_hidden_and_defined_once():
+    """What csrc/spx_engine.h declares with SPX_LOCAL crosses the engine's translation units and stops there: no dynamic symbol of
+    libspx.so demangles to one of those functions, and exactly one object of the build defines each.  The names are read from the
+    header.  (The library and its objects come from `python __graft_entry__.py build`; nothing here builds them.)"""
+    import pathlib
+    import subprocess
+
+    spx.lib()
+    pkg = pathlib.Path(spx.PKG_DIR)
+    src = re.sub(r"//[^\n]*", "", (pkg / "csrc" / "spx_engine.h").read_text())
+    assert "namespace {" not in src, "spx_engine.h has an anonymous namespace again"
+    # each declaration under its qualified name: the header's named namespaces are flat, `namespace X {` ... `}  // namespace X`
+    spans = [(m.start(), m.end(), m.group(1)) for m in re.finditer(r"^namespace (\w+) \{.*?^\}", src, flags=re.M | re.S)]
+    names = []
+    for m in re.finditer(r"^SPX_LOCAL\s[^;(]*?(\w+)\s*\(", src, flags=re.M):
+        ns = [n for a, b, n in spans if a < m.start() < b]
+        names.append("::".join(ns + [m.group(1)]))
+    assert len(names) >= 25 and len(set(names)) == len(names), names
+    assert {"spx_eng::fail", "spx_eng::upload", "spx_eng::net_prepare", "spx_eng::launch_nrt_tall_rows", "decide_masked"} <= set(names)
+
+    def defined(path, *flags):
+        """the functions `path` defines, demangled, without their parameter lists"""
+        out = subprocess.run(["nm", "-C", "--defined-only", *flags, str(path)], check=True, stdout=subprocess.PIPE, text=True).stdout
+        syms = [line.split(None, 2) for line in out.splitlines()]
+        return {s[2].split("(")[0] for s in syms if len(s) == 3 and s[1] in "TtWw"}
+
+    exported = defined(spx.LIB_PATH, "-D")
+    assert "spx_eval" in exported and len(exported) >= 25  # (the reading of nm's output works)
+    assert not exported & set(names), sorted(exported & set(names))
+    objects = sorted((pkg / "_obj").glob("*.o"))
+    assert objects
+    homes = {n: [] for n in names}
+    for obj in objects:
+        for n in defined(obj) & set(names):
+            homes[n].append(obj.name)
+    assert all(len(h) == 1 for h in homes.values()), {n: h for n, h in homes.items() if len(h) != 1}
+
+
 def test_no_torch_types_in_signatures():
     # plain pointers and sizes only: every argument / return type is a ctypes scalar, a pointer to one, or a pointer to a
     # struct declared in spx.h (ctypes caches POINTER(T) classes under whichever module created them first, so the
